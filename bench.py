@@ -9,11 +9,15 @@ of every frame against its successor.  Workload = BASELINE.json configs[1] (KITT
 
 Launch contract: `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver starts it under
 torch.distributed.run with one rank per GPU (backend nccl == RCCL) - and a bare `python bench.py --gpus N` (no WORLD_SIZE in
-the environment) re-executes itself that way, or exits non-zero when the node has fewer than N GPUs: `n_gpus` of the JSON
-line is always what ran (`launch_plan`).  Frames / sequences shard over the ranks with no data-path collective; the only
+the environment) starts itself that way as a child process, or exits non-zero when the node has fewer than N GPUs: `n_gpus` of
+the JSON line is always what ran (`launch_plan`).  Frames / sequences shard over the ranks with no data-path collective; the only
 communication is the gather of the variable-length keypoint/descriptor/depth records to rank 0 (weak scaling), by default
 through the library's own C-ABI entry points over RCCL (`--transport abi`: rgbl_gather_*, csrc/gather.hip), or through
 torch.distributed (`--transport torch`).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` writes what the last timed step
+computed as .npy files (`dump_outputs`).  `--full` adds everything else the line can carry: the parity spot check against
+the CPU oracle, the sparse up-sampling leg, the per-kernel roofline leg, the CPU baselines and the `extra` workloads.
 """
 import argparse
 import ctypes as C
@@ -39,6 +43,8 @@ WORKLOADS = {
 }
 LEVELS, SCALE, INI_TH, MIN_TH = 8, 1.2, 12, 7
 PROF_STEPS = 12    # serialised steps of the per-kernel timing leg (profiles/summarize_rocprof.py divides its counter totals by them)
+DUMP_FRAMES, DUMP_SEED = 64, 20240   # --dump-outputs: at most this many frames of the last step, drawn with this seed
+DUMP_BYTES = 48 << 20                # ... and at most this many bytes of per-keypoint arrays (capacity-based bound)
 
 
 def level_sizes(w, h):
@@ -759,6 +765,58 @@ def extra_workloads(lib, dev, torch, copy_ceiling=None):
     return out
 
 
+def synth_frames(seq, indices):
+    """seq.frame(t) for t in `indices` as one [n, h, w] uint8 array.  Every frame draws its noise from a generator of its own
+    and numpy releases the GIL while it fills the arrays, so a few threads build the batch several times faster, and the
+    frames are the same whatever the number of threads."""
+    from concurrent.futures import ThreadPoolExecutor
+    out = np.empty((len(indices), seq.h, seq.w), np.uint8)
+
+    def fill(i):
+        out[i] = seq.frame(indices[i])
+    try:
+        workers = len(os.sched_getaffinity(0))
+    except AttributeError:
+        workers = os.cpu_count() or 1
+    with ThreadPoolExecutor(max(1, min(8, workers))) as ex:
+        list(ex.map(fill, range(len(indices))))
+    return out
+
+
+def dump_frames(B, cap):
+    """The frames of a step whose per-keypoint outputs --dump-outputs writes: all of them, or a fixed seeded sample of
+    DUMP_FRAMES (fewer when cap keypoints per frame would pass DUMP_BYTES), ascending."""
+    k = min(B, DUMP_FRAMES, max(1, DUMP_BYTES // (cap * 4 * (7 + 32 + 5))))
+    if k == B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=k, replace=False))
+
+
+def dump_outputs(out_dir, n, mono, kp, desc, depth, uright, bi, bd, sd, frames):
+    """--dump-outputs: what one step hands its caller, as float32 .npy files in out_dir.  n and mono ([frames of the step])
+    are written whole; the per-keypoint arrays only for `frames`, each frame's first n rows, concatenated in that order:
+      keypoints  [M, 7]   x, y, size, angle, response, octave, class_id (the two int32 fields by value)
+      descriptors [M, 32] the 32 descriptor bytes by value
+      depth, uright, match_index, match_distance, match_second_distance  [M]
+    kp .. sd are host copies of the pipeline's output set (pipeline.OutSet), rows `frames` only.  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = kp.shape[1]
+    cnt = np.clip(np.asarray(n)[frames], 0, cap)
+    rows = lambda a: np.concatenate([a[i, :c] for i, c in enumerate(cnt)])
+    kp = np.ascontiguousarray(kp, np.float32)
+    kp_i = kp.view(np.int32)
+    kp_rows = rows(np.concatenate([kp[..., :5], kp_i[..., 5:7].astype(np.float32)], axis=-1))
+    arrays = {"n": np.asarray(n), "mono": np.asarray(mono), "frames": np.asarray(frames), "keypoints": kp_rows,
+              "descriptors": rows(desc), "depth": rows(depth), "uright": rows(uright), "match_index": rows(bi),
+              "match_distance": rows(bd), "match_second_distance": rows(sd)}
+    shapes = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -786,6 +844,13 @@ def main():
                          "of world x batch frames cut into contiguous chunks (sharding.frame_chunk), every rank also extracts the "
                          "frame behind its chunk (a one-frame halo, recomputed, never communicated) so that its last frame is "
                          "matched against its true successor - SURVEY 8(e) 'single long sequence'")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can carry: the parity spot check against the "
+                         "CPU oracle, the sparse up-sampling leg, the serialised per-kernel leg with the roofline object, the CPU "
+                         "baselines and the extra workloads (--no-cpu-baseline / --no-extras leave parts out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; the per-keypoint arrays of a "
+                         "fixed, seeded sample of frames: dump_outputs)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_worker:
@@ -799,8 +864,10 @@ def main():
     if plan[0] == "error":
         raise SystemExit("bench.py: " + plan[1])
     if plan[0] == "exec":
+        # a fresh child process, not an exec of this one: the device query above may already have initialised HIP here
         sys.stdout.flush()
-        os.execv(plan[1][0], plan[1])
+        import subprocess
+        raise SystemExit(subprocess.call(plan[1]))
     world = plan[1]
 
     from orb_slam3_rgbl_amd import _lib as L
@@ -841,10 +908,10 @@ def main():
         seq = synth.Sequence(0, w, h, n_frames=total, constant_density=not os.environ.get("RGBL_BENCH_SPARSE"))
         first, last, _ = sharding.frame_chunk(total, world, rank)
         assert last - first == B
-        frames = np.stack([seq.frame((first + i) % total) for i in range(B + 1)])
+        frames = synth_frames(seq, [(first + i) % total for i in range(B + 1)])
     else:
         seq = synth.Sequence(sharding.sequences_of_rank(world, world, rank)[0], w, h, n_frames=B, constant_density=not os.environ.get("RGBL_BENCH_SPARSE"))
-        frames = np.stack([seq.frame(i) for i in range(B)])
+        frames = synth_frames(seq, list(range(B)))
     n_scans = min(B, 8)
     scans = [synth.lidar_scan(rank * 1000 + i, n_az=n_az) for i in range(n_scans)]
     n_points = scans[0].shape[1]
@@ -918,9 +985,16 @@ def main():
                                                                last.bd, last.sd)
     k_mean = float(d_n.float().mean().item())
 
+    # ---- what the last timed step handed its caller (the --full legs below run further steps on the same output sets)
+    if args.dump_outputs and rank == 0:
+        sel = dump_frames(B, cap)
+        idx = torch.from_numpy(sel).to(dev)
+        host = [t.index_select(0, idx).cpu().numpy() for t in (d_kp, d_desc, d_depth, d_uright, d_bi, d_bd, d_sd)]
+        dump_outputs(args.dump_outputs, d_n.cpu().numpy(), last.mono.cpu().numpy(), *host, frames=sel)
+
     # ---- parity spot check of what the timed pipeline produced (four frames against the CPU oracle)
     spot = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import oracle_py as O
         orc = O.Extractor(nfeatures, SCALE, LEVELS, INI_TH, MIN_TH)
         spot = spot_check(O, orc, O.make_depth_params(proj), frames, cloud, last, sorted({0, B // 3, 2 * B // 3, B - 1}), w, h)
@@ -928,7 +1002,7 @@ def main():
     # ---- opt-in variant, reported beside the headline only: no dense ProcessedDepthMap (rgbl_depth_set_sparse), the keypoints'
     # depths come out of the index maps directly.  Same inputs; depth / uRight must not change by a bit.
     sparse_leg = None
-    if world == 1 and not args.no_extras and not args.serial:
+    if args.full and world == 1 and not args.no_extras and not args.serial:
         ref_depth, ref_ur = d_depth.clone(), d_uright.clone()
         for ln in pipe.lanes:
             ln.dm.SetSparseUpsampling(True)
@@ -952,7 +1026,7 @@ def main():
     cpu = None
     kernels = {}
     copy_ceiling = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # per-kernel timing leg: one stream for everything, so that the HIP-event brackets around each launch are not
         # stretched by other kernels running concurrently
         prof_steps = PROF_STEPS
@@ -1029,7 +1103,7 @@ def main():
             "roofline": roofline,
             "cpu_baseline": cpu,
         }
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             out["extra"] = extra_workloads(lib, dev, torch, copy_ceiling)
             out["extra"]["sparse_upsampling"] = sparse_leg
             # BASELINE configs[2] (SearchForTriangulation) and the matcher calls of one tracked frame: per-call latency through the

@@ -82,7 +82,7 @@ def traffic(out_dir, steps, warmup, frames_per_step, out, tag="bench", extra_arg
             d["dispatches_per_step"] = n / n_steps
     json.dump({"frames_per_step": int(frames_per_step), "steps_profiled": n_steps,
                "bytes_per_counter_unit": factors, "factor_used": {"FETCH_SIZE": f_fetch, "WRITE_SIZE": f_write},
-               "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE|SQ_INSTS_VALU -- python bench.py --serial --no-cpu-baseline --no-extras --steps %s --warmup %s %s" % (steps, warmup, extra_args),
+               "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE|SQ_INSTS_VALU -- python bench.py --full --serial --no-cpu-baseline --no-extras --steps %s --warmup %s %s" % (steps, warmup, extra_args),
                "kernels": kernels}, open(out, "w"), indent=1, sort_keys=True)
 
 

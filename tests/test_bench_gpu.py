@@ -10,11 +10,13 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*args):
+def run_bench(*args, full=True):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "64",
-                          "--no-extras", "--no-cpu-baseline"] + list(args), capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "64"]
+    if full:    # the parity spot check and the roofline object of the line come from the --full legs
+        cmd += ["--full", "--no-extras", "--no-cpu-baseline"]
+    res = subprocess.run(cmd + list(args), capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-3000:]
     lines = res.stdout.strip().splitlines()
     return json.loads(lines[-1]), lines      # the line is the last thing on stdout (RCCL's banner is flushed in front of it)
@@ -87,3 +89,50 @@ def test_serialised_kernel_table_is_stable(gpu_lib):
     # written); what the table reports - the median - sits within 15 % of the fastest step
     print("k_hamming_fp4 per-step stats: fresh", a["k_hamming_fp4"], "after load", b["k_hamming_fp4"])
     assert a["k_hamming_fp4"]["median"] <= 1.15 * a["k_hamming_fp4"]["min"], a["k_hamming_fp4"]
+
+
+@pytest.mark.gpu
+def test_plain_line_and_the_dumped_outputs_of_its_last_step(gpu_lib, tmp_path):
+    """A plain run: --steps timed steps, ms_per_step behind value, none of the --full legs.  --dump-outputs writes the last
+    step's outputs: n / mono of every frame and the records of a seeded sample, one sampled frame checked against the oracle."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import oracle_py as O
+    from orb_slam3_rgbl_amd import frontend as F
+    from orb_slam3_rgbl_amd import sharding, synth
+    d, _ = run_bench("--dump-outputs", str(tmp_path), full=False)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"]
+    assert abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["parity_spot_check"] is None and d["roofline"] is None and d["cpu_baseline"] is None and "extra" not in d
+    a = {p.stem: np.load(str(p)) for p in tmp_path.iterdir()}
+    assert set(a) == {"n", "mono", "frames", "keypoints", "descriptors", "depth", "uright", "match_index", "match_distance",
+                      "match_second_distance"}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 20
+    n, sel = a["n"].astype(int), a["frames"].astype(int)
+    assert len(n) == 64 and abs(n.mean() - d["config"]["keypoints_per_frame"]) < 1e-3 and np.array_equal(sel, np.arange(64))
+    m = int(n[sel].sum())
+    assert a["keypoints"].shape == (m, 7) and a["descriptors"].shape == (m, 32)
+    assert all(a[k].shape == (m,) for k in ("depth", "uright", "match_index", "match_distance", "match_second_distance"))
+    # frame 5 of the step against the CPU oracle: the same input the bench builds
+    w, h, nf, n_az, _ = bench.WORKLOADS["kitti"]
+    seq = synth.Sequence(sharding.sequences_of_rank(1, 1, 0)[0], w, h, n_frames=64, constant_density=True)
+    fi, o = 5, int(n[:5].sum())
+    rows = slice(o, o + n[fi])
+    orc = O.Extractor(nf, bench.SCALE, bench.LEVELS, bench.INI_TH, bench.MIN_TH)
+    okps, odesc, omono = orc(seq.frame(fi))
+    assert n[fi] == len(okps) and a["mono"][fi] == omono
+    for j, f in enumerate(("x", "y", "size", "angle", "response", "octave", "class_id")):
+        assert np.array_equal(a["keypoints"][rows, j], okps[f].astype(np.float32)), f
+    assert np.array_equal(a["descriptors"][rows], odesc.astype(np.float32))
+    proj = F.projection_matrix(synth.KITTI_K, synth.KITTI_TR, gpu_lib)
+    od, our, _, _ = O.depth(O.make_depth_params(proj), synth.lidar_scan(fi % 8, n_az=n_az), w, h,
+                            np.stack([okps["x"], okps["y"]], 1), okps["x"], want_maps=False)
+    assert np.array_equal(a["depth"][rows].view(np.uint32), od.view(np.uint32))
+    assert np.array_equal(a["uright"][rows].view(np.uint32), our.view(np.uint32))
+    obi, obd, osd = O.hamming_bf(odesc, orc(seq.frame(fi + 1))[1])
+    assert np.array_equal(a["match_index"][rows], obi.astype(np.float32))
+    assert np.array_equal(a["match_distance"][rows], obd.astype(np.float32))
+    assert np.array_equal(a["match_second_distance"][rows], osd.astype(np.float32))

@@ -760,15 +760,14 @@ def test_reference_compute_stereo_matches_on_a_real_stereo_pair(refframe):
 # The two other RGB-L settings files the reference ships (Examples/RGB-L/KITTI04-12.yaml, KITTIxx-03.yaml: KITTI sequences
 # 03 - 12) still carry the stale key LiDAR.MethodInverseDilation.KernelSize; DepthModule.cc:566-582 asks for KernelSize_u /
 # KernelSize_v, so ParseUpsamplingParameters fails, CalculateDepthFromPcd returns at once (:52-55) and every keypoint of those
-# sequences keeps mvDepth = -1: as shipped, the reference runs them as monocular frames.  Read in place, not copied.
-SHIPPED = "/root/reference/Examples/RGB-L"
+# sequences keeps mvDepth = -1: as shipped, the reference runs them as monocular frames.  The three files are stored verbatim
+# in tests/golden/rgbl_settings.
+SHIPPED = os.path.join(ROOT, "tests", "golden", "rgbl_settings")
 
 
 @pytest.mark.parametrize("name,fx", [("KITTI04-12.yaml", 707.0912), ("KITTIxx-03.yaml", 721.5377)])
 def test_reference_disables_upsampling_on_its_other_shipped_settings(refdepth, name, fx):
     path = os.path.join(SHIPPED, name)
-    if not os.path.exists(path):
-        pytest.skip("the reference's Examples/RGB-L is not on this host")
     R = RefDepth(refdepth, path)
     assert R.parsed == (True, False)
     # K * Tr is still built, with this file's intrinsics, as the restated oracle builds it

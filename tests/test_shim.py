@@ -42,13 +42,11 @@ def test_shim_depthmodule_parse_outcomes(emu_lib, tmp_path):
 
 @pytest.mark.parametrize("name,expect", [("KITTI00-02.yaml", 3), ("KITTI04-12.yaml", 1), ("KITTIxx-03.yaml", 1)])
 def test_shim_depthmodule_on_the_references_shipped_settings(emu_lib, name, expect):
-    """The three settings files of Examples/RGB-L, read in place: the drop-in parser must end where the reference's own parser
-    ends (tests/test_reference_build.py::test_reference_disables_upsampling_on_its_other_shipped_settings) - the files for
-    sequences 03 - 12 carry a stale key, up-sampling stays disabled (DepthModule.cc:566-582)."""
+    """The three settings files of Examples/RGB-L (verbatim copies in tests/golden/rgbl_settings): the drop-in parser must end
+    where the reference's own parser ends (tests/test_reference_build.py::test_reference_disables_upsampling_on_its_other_shipped_settings)
+    - the files for sequences 03 - 12 carry a stale key, up-sampling stays disabled (DepthModule.cc:566-582)."""
     import subprocess
-    path = os.path.join("/root/reference/Examples/RGB-L", name)
-    if not os.path.exists(path):
-        pytest.skip("the reference's Examples/RGB-L is not on this host")
+    path = os.path.join(ROOT, "tests", "golden", "rgbl_settings", name)
     exe = os.path.join(ROOT, "tests", "_build", "shim_test_emu")
     shim_driver.build(os.path.join(ROOT, "tests", "_build"), "rgbl_frontend_emu", exe)
     res = subprocess.run([exe, "--parse", path], capture_output=True, text=True, timeout=120)

@@ -14,7 +14,7 @@ cp orb_slam3_rgbl_amd/librgbl_frontend.so /tmp/lib_asbuilt.so
 for setting in "$@"; do
   spec="$setting"; sf=0
   case "$spec" in sf:*) sf=1; spec="${spec#sf:}";; esac
-  args=""; case "$spec" in *" -- "*) args="${spec#* -- }"; spec="${spec%% -- *}";; esac
+  args="--full"; case "$spec" in *" -- "*) args="--full ${spec#* -- }"; spec="${spec%% -- *}";; esac
   lib="${spec%%,*}"; envs=""; [ "$spec" != "$lib" ] && envs=$(echo "${spec#*,}" | tr ',' ' ')
   if [ -z "$lib" ] || [ "$lib" = "-" ]; then cp /tmp/lib_asbuilt.so orb_slam3_rgbl_amd/librgbl_frontend.so; else cp "$lib" orb_slam3_rgbl_amd/librgbl_frontend.so; fi
   if [ $sf = 1 ]; then

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out; REPO=$PWD
 ( time timeout 540 python -m pytest tests -m gpu -q -n 4 ) > $OUT/tests.log 2>&1
 tail -3 $OUT/tests.log
-timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 python - <<'PY'
 import json
 try:
@@ -22,7 +22,7 @@ except Exception as e:
 PY
 cp $OUT/bench.json $OUT/r06_bench_line.json
 cd /tmp
-timeout 150 rocprofv3 --kernel-trace --stats -d $OUT/prof_stats -o r06 -- python $REPO/bench.py --serial --no-cpu-baseline --no-extras --steps 10 --warmup 3 > $OUT/prof_stats.log 2>&1
+timeout 150 rocprofv3 --kernel-trace --stats -d $OUT/prof_stats -o r06 -- python $REPO/bench.py --full --serial --no-cpu-baseline --no-extras --steps 10 --warmup 3 > $OUT/prof_stats.log 2>&1
 timeout 150 rocprofv3 --kernel-trace --stats -d $OUT/prof_single -o r06 -- python $REPO/tools/host_api_latency.py > $OUT/prof_single.log 2>&1
 cd $REPO
 db=$(find $OUT/prof_stats -name "*.db" | head -1); [ -n "$db" ] && python profiles/summarize_rocprof.py stats $db $OUT/r06_kernel_stats.csv

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out; export TMPDIR=/tmp; OUT=$PWD/gpurun_out
 ( time timeout 600 python -m pytest tests -m gpu -q -n 4 -x ) > $OUT/tests.log 2>&1
 tail -15 $OUT/tests.log
-timeout 400 python bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+timeout 400 python bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 python - <<'PY'
 import json
 try:

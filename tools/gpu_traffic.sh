@@ -12,8 +12,8 @@ for c in FETCH_SIZE WRITE_SIZE; do
   timeout 120 rocprofv3 --pmc $c -d $OUT/prof_calib_$c -o p -- /tmp/hbm_calib > $OUT/prof_calib_$c.log 2>&1
 done
 for c in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU SQ_ACTIVE_INST_VALU; do
-  timeout 150 rocprofv3 --pmc $c -d $OUT/prof_bench_$c -o p -- python $REPO/bench.py --serial --no-cpu-baseline --no-extras --steps $STEPS --warmup $WARM > $OUT/prof_bench_$c.log 2>&1
-  timeout 150 rocprofv3 --pmc $c -d $OUT/prof_4k_$c -o p -- python $REPO/bench.py --workload 4k --serial --no-cpu-baseline --no-extras --steps $STEPS --warmup $WARM > $OUT/prof_4k_$c.log 2>&1
+  timeout 150 rocprofv3 --pmc $c -d $OUT/prof_bench_$c -o p -- python $REPO/bench.py --full --serial --no-cpu-baseline --no-extras --steps $STEPS --warmup $WARM > $OUT/prof_bench_$c.log 2>&1
+  timeout 150 rocprofv3 --pmc $c -d $OUT/prof_4k_$c -o p -- python $REPO/bench.py --full --workload 4k --serial --no-cpu-baseline --no-extras --steps $STEPS --warmup $WARM > $OUT/prof_4k_$c.log 2>&1
 done
 cd $REPO
 python profiles/summarize_rocprof.py traffic $OUT $STEPS $WARM $(python -c "import bench; print(bench.WORKLOADS['kitti'][4])") $OUT/r06_pmc_traffic.json bench
