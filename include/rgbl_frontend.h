@@ -360,6 +360,14 @@ int rgbl_depth_project_batch_device(rgbl_depth* h, const float* d_cloud, int bat
  * (16-byte aligned, scan_stride a multiple of 4) */
 int rgbl_depth_project_xyzi_batch_device(rgbl_depth* h, const float* d_xyzi, int batch, int n, size_t scan_stride, int w,
                                          int h_, float* d_processed);
+/* projection half for a batch of .bin scans of different lengths (KITTI scans hold ~115 k - 130 k points each), packed back
+ * to back: scan b = records [d_offsets[b], d_offsets[b+1]) of d_xyzi (float4 x, y, z, reflectance; 16-byte aligned).
+ * d_offsets: int64[batch + 1], device memory.  max_n >= every scan's count and <= cfg.max_points; it sizes the grid.  Point
+ * indices stay local to their scan: "last point wins" (DepthModule.cc:123-137) holds per scan, every up-sampling method and
+ * sparse handles work as with the fixed-n calls, an empty scan gives an empty depth map.  A scan longer than max_n is never
+ * truncated silently: rgbl_depth_sync returns RGBL_ERR_OVERFLOW.  Enqueued on the handle's stream. */
+int rgbl_depth_project_xyzi_varlen_batch_device(rgbl_depth* h, const float* d_xyzi, const int64_t* d_offsets, int batch,
+                                                int max_n, int w, int h_, float* d_processed);
 int rgbl_depth_gather_batch_device(rgbl_depth* h, int batch, int w, int h_, const rgbl_keypoint* d_kp,
                                    const int32_t* d_n, int kp_cap, const float* d_kpun_x, float* d_depth,
                                    float* d_uright);
@@ -755,6 +763,86 @@ int rgbl_bow_descend_batch_device(rgbl_vocabulary* v, void* hip_stream, const ui
 /* F12 with the reference's fp32 evaluation order (Pinhole.cpp:109-112); K = {fx, fy, cx, cy}. Host. */
 void rgbl_fundamental(const float K1[4], const float K2[4], const float R12[9], const float t12[3],
                       float F12[9]);
+
+/* ------------------------------------------------------------------------------------------------
+ * Host-fed batches      Frame::Frame(imGray, PointCloud, ...) (src/Frame.cc:289-377) + Tracking::GrabImageRGBL
+ *                       (src/Tracking.cc:1563-1582) for batches of frames that arrive in host memory, one after another,
+ *                       the way Examples/RGB-L/rgbl_kitti.cc:87-94, 151-185 reads them (colour PNG + velodyne .bin scan)
+ * ----------------------------------------------------------------------------------------------
+ * A feeder sits on an existing extractor handle and depth handle (it keeps no configuration of theirs) and streams batches
+ * through `slots` page-locked slots, in ring order:
+ *
+ *   rgbl_feeder_acquire(f, &slot);                        the next slot; its previous batch must have been collected
+ *   for b in 0 .. batch - 1:
+ *     rgbl_feeder_scan(f, slot, b, n_b, &xyzi);           reserves n_b .bin records (a .bin file's size / 16) for frame b
+ *     rgbl_feeder_image(f, slot, b, &px);                 w x h x channels bytes, row stride w * channels
+ *     ... fread / decode straight into xyzi and px        (any thread, any frame, once its scan is reserved)
+ *   rgbl_feeder_submit(f, slot, batch);                   queues the batch and returns at once
+ *   ... acquire / fill / submit the next slots ...
+ *   rgbl_feeder_collect(f, slot, &res);                   waits for that batch only; host pointers to its results
+ *
+ * Slot memory: one page-locked block (hipHostMalloc) per slot holding max_batch images, max_points_batch packed scan records,
+ *   the scan offsets and the page-locked copies of the results.  Nothing is copied twice on the host.
+ * Scan reservation: in frame order b = 0, 1, ... from one thread (the scans are packed back to back); over-reserving
+ *   (more than max_points in one scan, more than max_points_batch in the batch, b out of order) returns RGBL_ERR_CAPACITY
+ *   resp. RGBL_ERR_INVALID.  After that any thread may fill any frame of the slot.  An empty scan (n = 0) is valid.
+ * Submit: on the feeder's own copy stream one host-to-device copy each of the images, of the scan records in use and of the
+ *   offsets, each behind the last readers of the slot's device buffers (events).  Then, ordered by events: cv::cvtColor
+ *   (Tracking.cc:1567-1580; channels 1 extracts straight from the slot) and ORBextractor::operator() on the extractor's
+ *   stream, UndistortKeyPoints (Frame.cc:837-845, only when n_dist > 0 and dist[0] != 0), the projection of the scans
+ *   (rgbl_depth_project_xyzi_varlen_batch_device) on the depth stream next to the extraction, the keypoint gather
+ *   (DepthModule.cc:82-104) and the copy of the results into the slot's page-locked block - also on the depth stream: the
+ *   copy stream carries only the NEXT batches' inputs, which would otherwise wait for this batch's kernels.
+ * Results (rgbl_feeder_results): the layout of rgbl_extract_batch with cap = rgbl_extractor_max_keypoints(ex): frame b's
+ *   keypoints at kp + b * cap, descriptors at desc + b * cap * 32, mvDepth / mvuRight at depth / uright + b * cap, mvKeysUn
+ *   (x, y) at kpun_xy + b * cap * 2 (NULL without undistortion: mvKeysUn = mvKeys), n / mono: batch ints.  Valid until the
+ *   slot is acquired again.
+ * Errors: RGBL_ERR_INVALID for acquiring a slot whose batch was submitted and not collected (or is still being filled),
+ *   collecting a slot that holds no submitted batch (collecting twice), submitting a batch whose scans were not all reserved
+ *   or that is longer than max_batch, and for a configuration that does not fit its handles.  Deferred device errors surface
+ *   in collect (the results are filled all the same): RGBL_ERR_OVERFLOW / RGBL_ERR_CAPACITY of the extractor, as
+ *   rgbl_extractor_sync reports them, and RGBL_ERR_OVERFLOW for a scan the projection could not hold.  They belong to the
+ *   collected batch: the flags are taken and cleared on the device right behind that batch's own extraction and projection.
+ *   A submit that fails after it has queued part of the batch leaves the slot failed: collect waits for what was queued and
+ *   returns that error (no results); the slot can then be acquired again.
+ * A feeder drives its handles' streams: while it lives, the handles serve no other caller.  Nothing of a handle changes when
+ * no feeder drives it. */
+typedef struct rgbl_feeder rgbl_feeder;
+typedef struct {
+  int channels, blue_first;        /* 1 gray, 3 / 4 interleaved; blue_first = settings Camera.RGB == 0 (BGR, as cv::imread) */
+  int max_batch;                   /* frames per batch, <= both handles' max_batch */
+  int max_points;                  /* points per scan, <= the depth handle's max_points */
+  long long max_points_batch;      /* points per batch (packed scan records per slot); 0 = max_batch * max_points */
+  int slots;                       /* batches in flight, >= 2 */
+  float K[4];                      /* fx, fy, cx, cy (undistortion only) */
+  float dist[5];                   /* k1, k2, p1, p2[, k3] */
+  int n_dist;                      /* 0, 4 or 5; 0 or dist[0] == 0: no undistortion (Frame.cc:839) */
+} rgbl_feeder_cfg;
+typedef struct {
+  int batch, cap;
+  const rgbl_keypoint* kp;         /* batch x cap */
+  const uint8_t* desc;             /* batch x cap x 32 */
+  const int32_t* n;                /* batch */
+  const int32_t* mono;             /* batch: ORBextractor::operator()'s return value */
+  const float* depth;              /* batch x cap: mvDepth (-1 = none) */
+  const float* uright;             /* batch x cap: mvuRight */
+  const float* kpun_xy;            /* batch x cap x 2: mvKeysUn, NULL without undistortion */
+} rgbl_feeder_results;
+int rgbl_feeder_create(const rgbl_feeder_cfg* cfg, rgbl_extractor* ex, rgbl_depth* dm, rgbl_feeder** out);
+void rgbl_feeder_destroy(rgbl_feeder* f);  /* waits for the batches in flight */
+int rgbl_feeder_acquire(rgbl_feeder* f, int* slot);
+int rgbl_feeder_image(rgbl_feeder* f, int slot, int b, uint8_t** px);
+int rgbl_feeder_scan(rgbl_feeder* f, int slot, int b, int n, float** xyzi);
+int rgbl_feeder_submit(rgbl_feeder* f, int slot, int batch);
+int rgbl_feeder_collect(rgbl_feeder* f, int slot, rgbl_feeder_results* out);
+/* The same arrays on the device, for work that goes on there (Hamming matchers, rgbl_gather_pack, rgbl_device_frame_capture):
+ * *done_event (a HIP event) fires when they are complete; wait for it with rgbl_event_wait.  Valid from submit until the slot's
+ * next batch is submitted; the slot must still be collected before it is acquired again.  The feeder does not know the device
+ * work a caller queues on its own streams: that work must have COMPLETED (rgbl_*_sync, or an event the caller waits for on the
+ * host) before the caller acquires the slot again, because the next submit overwrites these arrays. */
+int rgbl_feeder_device_outputs(rgbl_feeder* f, int slot, rgbl_feeder_results* out, void** done_event);
+/* Page-locked bytes the feeder holds (all slots). */
+long long rgbl_feeder_pinned_bytes(const rgbl_feeder* f);
 
 /* ------------------------------------------------------------------------------------------------
  * Environment switches.  Every one of them is read ONCE, when the handle it concerns is created (never on a launch path:

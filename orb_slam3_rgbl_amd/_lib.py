@@ -111,6 +111,19 @@ class InitializationInput(C.Structure):
                 ("check_orientation", C.c_int)]
 
 
+class FeederCfg(C.Structure):
+    """rgbl_feeder_cfg (host-fed batches, orb_slam3_rgbl_amd/feed.py)."""
+    _fields_ = [("channels", C.c_int), ("blue_first", C.c_int), ("max_batch", C.c_int), ("max_points", C.c_int),
+                ("max_points_batch", C.c_longlong), ("slots", C.c_int), ("K", C.c_float * 4), ("dist", C.c_float * 5),
+                ("n_dist", C.c_int)]
+
+
+class FeederResults(C.Structure):
+    """rgbl_feeder_results: host (rgbl_feeder_collect) or device (rgbl_feeder_device_outputs) pointers of one batch."""
+    _fields_ = [("batch", C.c_int), ("cap", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("n", C.c_void_p),
+                ("mono", C.c_void_p), ("depth", C.c_void_p), ("uright", C.c_void_p), ("kpun_xy", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol of include/rgbl_frontend.h
 _V, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -146,6 +159,7 @@ SYMBOLS = {
     "rgbl_structuring_element": (_I, [_I, _I, _I, _V]),
     "rgbl_depth_compute_xyzi": (_I, [_V, _V, _I, _I, _I, _V, _V, _I, _V, _V, _V, _V]),
     "rgbl_depth_project_xyzi_batch_device": (_I, [_V, _V, _I, _I, _Z, _I, _I, _V]),
+    "rgbl_depth_project_xyzi_varlen_batch_device": (_I, [_V, _V, _V, _I, _I, _I, _I, _V]),
     "rgbl_depth_compute": (_I, [_V, _V, _I, _I, _I, _I, _V, _V, _I, _V, _V, _V, _V]),
     "rgbl_depth_prefetch": (_I, [_V, _V, _I, _I, _I, _I]),
     "rgbl_depth_prefetch_xyzi": (_I, [_V, _V, _I, _I, _I]),
@@ -231,6 +245,15 @@ SYMBOLS = {
     "rgbl_device_frame_size": (_I, [_V]),
     "rgbl_device_frame_set_grid": (_I, [_V, _V]),
     "rgbl_device_frame_download": (_I, [_V, _V, _V, _V, _V]),
+    "rgbl_feeder_create": (_I, [C.POINTER(FeederCfg), _V, _V, C.POINTER(_V)]),
+    "rgbl_feeder_destroy": (None, [_V]),
+    "rgbl_feeder_acquire": (_I, [_V, C.POINTER(_I)]),
+    "rgbl_feeder_image": (_I, [_V, _I, _I, C.POINTER(_V)]),
+    "rgbl_feeder_scan": (_I, [_V, _I, _I, _I, C.POINTER(_V)]),
+    "rgbl_feeder_submit": (_I, [_V, _I, _I]),
+    "rgbl_feeder_collect": (_I, [_V, _I, C.POINTER(FeederResults)]),
+    "rgbl_feeder_device_outputs": (_I, [_V, _I, C.POINTER(FeederResults), C.POINTER(_V)]),
+    "rgbl_feeder_pinned_bytes": (C.c_longlong, [_V]),
     "rgbl_bow_transform_frame": (_I, [_V, _V, _I, _V, _V, _I, C.POINTER(_I), _V, _V, _V, _I, C.POINTER(_I)]),
 }
 

@@ -136,6 +136,11 @@ struct rgbl_device_frame {
 };
 // where the last host-pointer call of a handle left its results on the device (extractor.hip / depth.hip; not exported C ABI)
 int rgbl_internal_depth_uright(rgbl_depth* d, const float** d_uright, int* k, hipStream_t* stream);
+int rgbl_internal_depth_info(rgbl_depth* d, int* w, int* h, int* max_points, int* max_batch, int** d_err);
+int rgbl_internal_depth_gather_xy(rgbl_depth* d, int batch, const rgbl_keypoint* d_kp, const int32_t* d_n, int kp_cap,
+                                  const float* d_kpun_xy, float* d_depth, float* d_uright);
+int rgbl_internal_extractor_info(rgbl_extractor* e, int* w, int* h, int* max_batch, int* device, int** d_err);
+int rgbl_internal_extractor_take_flags(rgbl_extractor* e, int* d_dst);
 
 namespace rgbl {
 

@@ -74,15 +74,39 @@ constexpr int kIdxBits = 20;
 constexpr int kProjectPts = 4;  // points per work-item of k_project_index
 constexpr uint32_t kIdxMask = (1u << kIdxBits) - 1u;
 
-template <bool kXyzi>
-__global__ __launch_bounds__(256) void k_project_index(ProjParams P, const float* __restrict__ cloud, size_t cloud_stride,
+// Scans: where scan f lies.  size_t (the fixed-n calls) = floats between scans; VarlenScans = scans of different lengths packed
+// back to back (rgbl_depth_project_xyzi_varlen_batch_device): scan f is the records [offsets[f], offsets[f + 1]) of `cloud`,
+// `n` = max_n sizes the grid and work-items past their own scan's end exit.  Indices stay local to the scan (tag | i + 1,
+// pt_depth[f * pt_stride + i]), so the dilation and the sparse gather read them unchanged.  A scan longer than max_n (or a
+// decreasing offset) raises *err and is projected up to max_n only: rgbl_depth_sync reports it.  The fixed-n kernels keep
+// their argument layout, and with it their code.
+struct VarlenScans { const int64_t* offsets; int* err; };
+
+template <bool kXyzi, class Scans>
+__device__ __forceinline__ const float* scan_of(const float* cloud, Scans scans, int f, int* n, bool first) {
+  if constexpr (std::is_same<Scans, size_t>::value) {
+    return cloud + (size_t)f * scans;
+  } else {
+    static_assert(kXyzi, "variable-length scans come in the .bin layout");
+    const int max_n = *n;
+    const int64_t b0 = scans.offsets[f], cnt = scans.offsets[f + 1] - b0;
+    if ((cnt > max_n || cnt < 0) && first && scans.err) *scans.err = 1;
+    *n = cnt < 0 ? 0 : (cnt > max_n ? max_n : (int)cnt);
+    return cloud + 4 * (size_t)b0;
+  }
+}
+
+template <bool kXyzi, class Scans = size_t>
+__global__ __launch_bounds__(256) void k_project_index(ProjParams P, const float* __restrict__ cloud, Scans scans,
                                                        int n, int ld, int w, int h, uint32_t* __restrict__ idx_map,
                                                        size_t map_stride, float* __restrict__ pt_depth, size_t pt_stride,
                                                        uint32_t tag) {
+  constexpr bool kVarlen = !std::is_same<Scans, size_t>::value;
   // kProjectPts points per work-item, all of them requested before the first is used
   const int f = xcd_frame();
-  const float* C = cloud + (size_t)f * cloud_stride;
+  const float* C = scan_of<kXyzi>(cloud, scans, f, &n, xcd_item() == 0 && threadIdx.x == 0);
   const int i0 = xcd_item() * (256 * kProjectPts) + threadIdx.x;
+  if (kVarlen && i0 >= n) return;  // past this scan's end (an empty scan included: no record to clamp the loads to)
   CloudPoint c[kProjectPts];
 #pragma unroll
   for (int j = 0; j < kProjectPts; ++j) c[j] = load_point<kXyzi>(C, ld, imin(i0 + 256 * j, n - 1));
@@ -99,15 +123,16 @@ __global__ __launch_bounds__(256) void k_project_index(ProjParams P, const float
   }
 }
 
-template <bool kXyzi>
-__global__ __launch_bounds__(256) void k_project_write(ProjParams P, const float* __restrict__ cloud, size_t cloud_stride,
+template <bool kXyzi, class Scans = size_t>
+__global__ __launch_bounds__(256) void k_project_write(ProjParams P, const float* __restrict__ cloud, Scans scans,
                                                        int n, int ld, int w, int h, const uint32_t* __restrict__ idx_map,
                                                        float* __restrict__ raw, size_t map_stride) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
   const int f = blockIdx.y;
+  const float* C = scan_of<kXyzi>(cloud, scans, f, &n, false);  // k_project_index has raised the flag already
+  if (i >= n) return;
   float d;
-  const int pix = project_point<kXyzi>(P, cloud + (size_t)f * cloud_stride, ld, i, w, h, &d);
+  const int pix = project_point<kXyzi>(P, C, ld, i, w, h, &d);
   if (pix >= 0 && idx_map[(size_t)f * map_stride + pix] == (uint32_t)(i + 1)) raw[(size_t)f * map_stride + pix] = d;
 }
 
@@ -443,6 +468,10 @@ struct rgbl_depth {
   // last projection left behind (dense == false: index maps of generation `tag`, the gather evaluates the dilation per keypoint)
   bool sparse = false;
   struct { bool dense = true; bool indexed = false; uint32_t tag = 0; int batch = 0; } maps;
+  // rgbl_depth_project_xyzi_varlen_batch_device: a scan longer than its call's max_n raises *d_err; rgbl_depth_sync reads it back
+  // once such a call was queued (varlen_queued), so handles that never take variable-length scans synchronise as before
+  int* d_err = nullptr;
+  bool varlen_queued = false;
 };
 
 namespace {
@@ -501,8 +530,10 @@ int enqueue_upsample(rgbl_depth* e, int batch, int w, int h) {
 }
 
 // Part 1 (independent of the keypoints): projection + ordered scatter + dense up-sampling.
+// d_offsets != NULL: variable-length .bin scans (k_project_*<true, true>), n = max_n sizes the grid.
 int enqueue_maps(rgbl_depth* e, const float* d_cloud, int batch, int n, int ld, size_t cloud_stride, int w, int h,
-                 float* d_processed_out, bool xyzi = false, bool need_raw = true, bool want_dense = true) {
+                 float* d_processed_out, bool xyzi = false, bool need_raw = true, bool want_dense = true,
+                 const int64_t* d_offsets = nullptr) {
   hipStream_t s = e->stream;
   const size_t ms = e->map_stride;
   // Whatever a prefetch left in the maps is overwritten from here on: EVERY entry point that projects - the host ones, the
@@ -536,12 +567,15 @@ int enqueue_maps(rgbl_depth* e, const float* d_cloud, int batch, int n, int ld, 
   if (n > 0) {
     e->timer.begin("k_project_index", s);
     const dim3 pgrid((n + 255) / 256, batch), igrid = xcd_grid(e->xcd_map, (n + 256 * kProjectPts - 1) / (256 * kProjectPts), batch);
-    if (xyzi) hipLaunchKernelGGL(k_project_index<true>, igrid, dim3(256), 0, s, e->proj, d_cloud, cloud_stride, n, ld, w, h, e->d_idx, ms, pt_depth, pt_stride, tag);
+    const VarlenScans varlen{d_offsets, e->d_err};
+    if (d_offsets) hipLaunchKernelGGL((k_project_index<true, VarlenScans>), igrid, dim3(256), 0, s, e->proj, d_cloud, varlen, n, ld, w, h, e->d_idx, ms, pt_depth, pt_stride, tag);
+    else if (xyzi) hipLaunchKernelGGL(k_project_index<true>, igrid, dim3(256), 0, s, e->proj, d_cloud, cloud_stride, n, ld, w, h, e->d_idx, ms, pt_depth, pt_stride, tag);
     else hipLaunchKernelGGL(k_project_index<false>, igrid, dim3(256), 0, s, e->proj, d_cloud, cloud_stride, n, ld, w, h, e->d_idx, ms, pt_depth, pt_stride, tag);
     e->timer.end(s);
     if (!indexed) {
       e->timer.begin("k_project_write", s);
-      if (xyzi) hipLaunchKernelGGL(k_project_write<true>, pgrid, dim3(256), 0, s, e->proj, d_cloud, cloud_stride, n, ld, w, h, e->d_idx, e->d_raw, ms);
+      if (d_offsets) hipLaunchKernelGGL((k_project_write<true, VarlenScans>), pgrid, dim3(256), 0, s, e->proj, d_cloud, varlen, n, ld, w, h, e->d_idx, e->d_raw, ms);
+      else if (xyzi) hipLaunchKernelGGL(k_project_write<true>, pgrid, dim3(256), 0, s, e->proj, d_cloud, cloud_stride, n, ld, w, h, e->d_idx, e->d_raw, ms);
       else hipLaunchKernelGGL(k_project_write<false>, pgrid, dim3(256), 0, s, e->proj, d_cloud, cloud_stride, n, ld, w, h, e->d_idx, e->d_raw, ms);
       e->timer.end(s);
     }
@@ -679,6 +713,8 @@ int rgbl_depth_create(const rgbl_depth_cfg* cfg, int device, rgbl_depth** out) {
   if (rc == RGBL_OK) rc = dalloc(e, &e->d_cloud, (size_t)4 * cfg->max_points);
   if (rc == RGBL_OK) rc = dalloc(e, &e->d_ptdepth, B * (size_t)cfg->max_points);
   if (rc == RGBL_OK) rc = dalloc(e, &e->d_kp, (size_t)5 * cfg->max_keypoints);
+  if (rc == RGBL_OK) rc = dalloc(e, &e->d_err, 1);
+  if (rc == RGBL_OK && hipMemset(e->d_err, 0, sizeof(int)) != hipSuccess) { set_error("hipMemset failed"); rc = RGBL_ERR_HIP; }
   if (rc == RGBL_OK) {
     e->d_kpun = e->d_kp + (size_t)2 * cfg->max_keypoints;
     e->d_depth = e->d_kpun + cfg->max_keypoints;
@@ -837,6 +873,19 @@ int rgbl_depth_project_xyzi_batch_device(rgbl_depth* e, const float* d_xyzi, int
   return enqueue_maps(e, d_xyzi, batch, n, n, scan_stride, w, h, d_processed, true, false, d_processed != nullptr);
 }
 
+int rgbl_depth_project_xyzi_varlen_batch_device(rgbl_depth* e, const float* d_xyzi, const int64_t* d_offsets, int batch, int max_n,
+                                                int w, int h, float* d_processed) {
+  if (!e || !d_xyzi || !d_offsets) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  if (w != e->cfg.width || h != e->cfg.height || batch < 1 || batch > e->cfg.max_batch || max_n < 0 || max_n > e->cfg.max_points ||
+      ((uintptr_t)d_xyzi & 15)) {
+    set_error("varlen xyzi batch: batch <= %d, max_n <= %d points, scans 16-byte aligned", e->cfg.max_batch, e->cfg.max_points);
+    return RGBL_ERR_INVALID;
+  }
+  RGBL_HIP(hipSetDevice(e->device));
+  e->varlen_queued = true;
+  return enqueue_maps(e, d_xyzi, batch, max_n, max_n, 0, w, h, d_processed, true, false, d_processed != nullptr, d_offsets);
+}
+
 int rgbl_depth_project_batch_device(rgbl_depth* e, const float* d_cloud, int batch, int n, int ld, size_t cloud_stride, int w,
                                     int h, float* d_processed) {
   if (!e || !d_cloud) { set_error("null argument"); return RGBL_ERR_INVALID; }
@@ -879,6 +928,16 @@ int rgbl_depth_sync(rgbl_depth* e) {
   RGBL_HIP(hipSetDevice(e->device));
   RGBL_HIP(hipStreamSynchronize(e->stream));
   e->timer.collect();
+  if (e->varlen_queued) {
+    e->varlen_queued = false;
+    int flag = 0;
+    RGBL_HIP(hipMemcpy(&flag, e->d_err, sizeof(int), hipMemcpyDeviceToHost));
+    if (flag) {
+      RGBL_HIP(hipMemset(e->d_err, 0, sizeof(int)));
+      set_error("a scan of a variable-length batch held more points than the call's max_n (projected up to max_n only)");
+      return RGBL_ERR_OVERFLOW;
+    }
+  }
   return RGBL_OK;
 }
 int rgbl_depth_set_stream(rgbl_depth* e, void* hip_stream) {
@@ -925,4 +984,20 @@ int rgbl_internal_depth_uright(rgbl_depth* d, const float** d_uright, int* k, hi
   if (!d) { set_error("null depth handle"); return RGBL_ERR_INVALID; }
   *d_uright = d->d_uright; *k = d->last_k; *stream = d->stream;
   return RGBL_OK;
+}
+
+// feed.hip: the size of a handle, its overflow flag (copied out and cleared behind every fed batch, so a batch reports its own
+// scans) and the keypoint gather with mvKeysUn as (x, y) pairs - the layout rgbl_undistort_keypoints_batch_device writes
+int rgbl_internal_depth_info(rgbl_depth* d, int* w, int* h, int* max_points, int* max_batch, int** d_err) {
+  if (!d) { set_error("null depth handle"); return RGBL_ERR_INVALID; }
+  *w = d->cfg.width; *h = d->cfg.height; *max_points = d->cfg.max_points; *max_batch = d->cfg.max_batch; *d_err = d->d_err;
+  return RGBL_OK;
+}
+int rgbl_internal_depth_gather_xy(rgbl_depth* e, int batch, const rgbl_keypoint* d_kp, const int32_t* d_n, int kp_cap,
+                                  const float* d_kpun_xy, float* d_depth, float* d_uright) {
+  RGBL_HIP(hipSetDevice(e->device));
+  const float* kp = reinterpret_cast<const float*>(d_kp);
+  const int kstride = (int)(sizeof(rgbl_keypoint) / sizeof(float));
+  return enqueue_keypoints(e, batch, e->cfg.width, e->cfg.height, kp, kstride, (size_t)kp_cap * kstride, d_kpun_xy, 2,
+                           (size_t)kp_cap * 2, d_n, 0, kp_cap, d_depth, d_uright, (size_t)kp_cap);
 }

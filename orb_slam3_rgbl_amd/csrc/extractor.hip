@@ -1605,6 +1605,23 @@ void rgbl_test_block_sort(uint64_t* key, uint32_t* val, int n) {
 
 }  // extern "C"
 
+// feed.hip (not part of the C ABI): the size of a handle and its device flag word, which rgbl_extractor_sync reads back
+int rgbl_internal_extractor_info(rgbl_extractor* e, int* w, int* h, int* max_batch, int* device, int** d_err) {
+  if (!e) { rgbl::set_error("null extractor handle"); return RGBL_ERR_INVALID; }
+  *w = e->cfg.width; *h = e->cfg.height; *max_batch = e->cfg.max_batch; *device = e->device; *d_err = e->d_err;
+  return RGBL_OK;
+}
+// feed.hip: ties the device flags to one fed batch.  Queued on the handle's stream behind that batch's extraction: the flag word
+// goes to d_dst (device memory) and is cleared, together with the per-level candidate counters a failed extraction leaves behind
+// (what check_device_flags clears on the host) - zero is their state between extractions, so clearing them costs nothing else.
+int rgbl_internal_extractor_take_flags(rgbl_extractor* e, int* d_dst) {
+  if (!e || !d_dst) { rgbl::set_error("null argument"); return RGBL_ERR_INVALID; }
+  RGBL_HIP(hipMemcpyAsync(d_dst, e->d_err, sizeof(int), hipMemcpyDeviceToDevice, e->stream));
+  RGBL_HIP(hipMemsetAsync(e->d_err, 0, sizeof(int), e->stream));
+  RGBL_HIP(hipMemsetAsync(e->d_levelcnt, 0, sizeof(uint32_t) * (size_t)e->cfg.max_batch * e->L, e->stream));
+  return RGBL_OK;
+}
+
 #ifdef RGBL_EMU
 // test hooks (emulation build only)
 extern "C" void rgbl_test_sincosf(float x, float* s, float* c) { *s = rgbl::glibc_sinf(x); *c = rgbl::glibc_cosf(x); }
