@@ -454,7 +454,8 @@ int rgbl_device_frame_upload(rgbl_device_frame* f, int n, const uint8_t* desc, c
  * dist[0] == 0, as upstream.  Enqueued on the extractor's stream behind that extraction; returns without waiting. */
 int rgbl_device_frame_capture(rgbl_device_frame* f, rgbl_extractor* ex, int frame, int n, rgbl_depth* depth, const float K[4],
                               const float* dist, int n_dist);
-/* mFeatVec as CSR (the node ids stay with the caller: the merge walk of two FeatureVectors is host work).  Synchronous. */
+/* mFeatVec as CSR (the node ids stay with the caller: the merge walk of two FeatureVectors is host work).  Call again after
+ * upload / capture (they invalidate it).  Synchronous. */
 int rgbl_device_frame_set_feature_vector(rgbl_device_frame* f, int n_nodes, const int32_t* node_off, const int32_t* node_feat);
 /* Frame::AssignFeaturesToGrid (src/Frame.cc:475-506) for the frame's keypoints, kept with the frame: grid = Frame::mnMinX, mnMinY,
  * mnMaxX, mnMaxY, mfGridElementWidthInv, mfGridElementHeightInv.  A projection search whose input names this frame and the same six

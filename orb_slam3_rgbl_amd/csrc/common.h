@@ -122,7 +122,7 @@ struct rgbl_device_frame {
   int32_t* d_oct = nullptr;
   float* d_ur = nullptr;
   // Frame::AssignFeaturesToGrid, kept with the frame (rgbl_device_frame_set_grid): the projection searches skip their grid build
-  uint32_t* d_cell_start = nullptr;   // 64 x 48 + 1
+  uint32_t* d_cell_start = nullptr;   // 64 x 48 + 1, at the start of ONE block with the two below
   uint16_t* d_cell_items = nullptr;   // cap
   int32_t* d_grid_scratch = nullptr;  // cap (what k_proj_grid initialises besides the grid)
   float grid[6] = {0, 0, 0, 0, 0, 0};

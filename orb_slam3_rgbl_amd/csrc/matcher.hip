@@ -1766,16 +1766,6 @@ int ensure_arena(rgbl_matcher* m, size_t bytes) {
 // (k_hamming_mfma) instead of the block-scaled FP4 one (k_hamming_fp4, the default): read when the handle is created.
 inline bool bf_on_matrix_cores(const rgbl_matcher* m) { return m->bf_matrix; }
 inline bool bf_on_fp4(const rgbl_matcher* m) { return m->bf_fp4; }
-struct Arena {
-  uint8_t* base; size_t off = 0;
-  template <class T> T* take(size_t count) {
-    off = (off + 255) / 256 * 256;
-    T* p = reinterpret_cast<T*>(base + off);
-    off += count * sizeof(T);
-    return p;
-  }
-};
-inline size_t pad256(size_t b) { return (b + 255) / 256 * 256 + 256; }
 int ensure_pin(rgbl_matcher* m, size_t bytes) {
   if (bytes <= m->pin_size) return RGBL_OK;
   if (m->h_pin) { (void)hipHostFree(m->h_pin); m->h_pin = nullptr; m->pin_size = 0; }
@@ -1788,44 +1778,58 @@ int ensure_pin(rgbl_matcher* m, size_t bytes) {
 // uploads is copied into the mirror at the offsets its device copies have and goes up with ONE hipMemcpyAsync (round 5
 // queued one per array, 8 - 17 per call, from pageable memory); the result arrays are taken back to back and come back
 // with one.  Arrays of a frame that is resident on the device (rgbl_device_frame) are not staged at all.
+// begin() runs the call's layout - its put / put_fill / stage / result / scratch calls - twice: a measuring pass that copies,
+// waits for and launches nothing, then, with the arena and mirror grown to that size, the carving pass.
 struct HostCall {
-  rgbl_matcher* m = nullptr;
-  hipStream_t s = nullptr;
-  Arena A{nullptr};
-  size_t up_end = 0, res_begin = ~(size_t)0, res_end = 0;
-  int begin(rgbl_matcher* mm, size_t need) {
-    m = mm; s = mm->stream;
-    RGBL_TRY(ensure_arena(m, need));
-    RGBL_TRY(ensure_pin(m, need));
-    A = Arena{m->d_buf};
-    return RGBL_OK;
-  }
-  size_t off_of(const void* d) const { return (size_t)(reinterpret_cast<const uint8_t*>(d) - m->d_buf); }
-  template <class E> int put(const E** dst, const E* src, size_t count) {
-    E* p = A.take<E>(count);
-    *dst = p;
-    if (count) memcpy(m->h_pin + off_of(p), src, count * sizeof(E));
-    up_end = A.off;
-    return RGBL_OK;
-  }
-  template <class E> E* put_fill(size_t count, int byte) {   // an array the device starts from (e.g. all -1) travels with the upload
-    E* p = A.take<E>(count);
-    if (count) memset(m->h_pin + off_of(p), byte, count * sizeof(E));
-    up_end = A.off;
-    return p;
-  }
-  int upload() {
+  rgbl_matcher* m;
+  hipStream_t s;
+  bool carving = false;
+  size_t off = 0, up_end = 0, res_begin = ~(size_t)0, res_end = 0;
+  explicit HostCall(rgbl_matcher* mm) : m(mm), s(mm->stream) {}
+  template <class Layout> int begin(Layout&& layout) {   // ... and the call's ONE upload
+    RGBL_TRY(layout());
+    const size_t measured = off;
+    RGBL_TRY(ensure_arena(m, measured));
+    RGBL_TRY(ensure_pin(m, measured));
+    carving = true;
+    off = up_end = 0;
+    RGBL_TRY(layout());
+    if (off != measured) { set_error("staging layout: %zu bytes measured, %zu carved", measured, off); return RGBL_ERR_INVALID; }
     if (up_end) RGBL_HIP(hipMemcpyAsync(m->d_buf, m->h_pin, up_end, hipMemcpyHostToDevice, s));
     return RGBL_OK;
   }
-  template <class E> E* stage(size_t count) { E* p = A.take<E>(count); up_end = A.off; return p; }   // the caller fills mirror(p)
-  template <class E> E* mirror(E* d) { return reinterpret_cast<E*>(m->h_pin + off_of(d)); }
-  template <class E> E* scratch(size_t count) { return A.take<E>(count); }
+  template <class E> E* take(size_t count) {   // every array starts 256-byte aligned; nullptr while measuring
+    off = (off + 255) / 256 * 256;
+    E* p = carving ? reinterpret_cast<E*>(m->d_buf + off) : nullptr;
+    off += count * sizeof(E);
+    return p;
+  }
+  size_t off_of(const void* d) const { return (size_t)(reinterpret_cast<const uint8_t*>(d) - m->d_buf); }
+  template <class E> void put(const E** dst, const E* src, size_t count) {
+    E* p = take<E>(count);
+    *dst = p;
+    if (carving && count) memcpy(m->h_pin + off_of(p), src, count * sizeof(E));
+    up_end = off;
+  }
+  template <class E> E* put_fill(size_t count, int byte) {   // an array the device starts from (e.g. all -1) travels with the upload
+    E* p = take<E>(count);
+    if (carving && count) memset(m->h_pin + off_of(p), byte, count * sizeof(E));
+    up_end = off;
+    return p;
+  }
+  template <class E, class Fill> E* stage(size_t count, Fill fill) {   // fill(mirror) writes the upload itself
+    E* p = take<E>(count);
+    if (carving) fill(reinterpret_cast<E*>(m->h_pin + off_of(p)));
+    up_end = off;
+    return p;
+  }
+  template <class E> E* scratch(size_t count) { return take<E>(count); }
   template <class E> void mark_result(E* p, size_t count) {
+    if (!carving) return;
     res_begin = std::min(res_begin, off_of(p));
     res_end = std::max(res_end, off_of(p) + count * sizeof(E));
   }
-  template <class E> E* result(size_t count) { E* p = A.take<E>(count); mark_result(p, count); return p; }
+  template <class E> E* result(size_t count) { E* p = take<E>(count); mark_result(p, count); return p; }
   int fetch() {   // the call's only wait
     if (res_end > res_begin) RGBL_HIP(hipMemcpyAsync(m->h_pin + res_begin, m->d_buf + res_begin, res_end - res_begin, hipMemcpyDeviceToHost, s));
     RGBL_HIP(hipStreamSynchronize(s));
@@ -1836,8 +1840,77 @@ struct HostCall {
   // a frame's resident arrays: the stream waits for whatever filled them last
   int use(const rgbl_device_frame* f, int n) {
     if (f->device != m->device || f->n != n) { set_error("device frame: %d features on device %d, the call says %d on device %d", f->n, f->device, n, m->device); return RGBL_ERR_INVALID; }
-    RGBL_HIP(hipStreamWaitEvent(s, f->ready, 0));
+    if (carving) RGBL_HIP(hipStreamWaitEvent(s, f->ready, 0));
     return RGBL_OK;
+  }
+};
+
+// A frame's per-feature arrays that the call reads (a null destination: not read): the resident copy when the frame has one
+// (dev), else staged with the rest of the call's upload.
+int put_features(HostCall& hc, const rgbl_device_frame* dev, int n, const uint8_t* desc, const float* xy, const int32_t* oct,
+                 const float* ur, const uint8_t** d_desc, const float** d_xy, const int32_t** d_oct, const float** d_ur) {
+  if (dev) {
+    RGBL_TRY(hc.use(dev, n));
+    if (d_desc) *d_desc = dev->d_desc;
+    if (d_xy) *d_xy = dev->d_xy;
+    if (d_oct) *d_oct = dev->d_oct;
+    if (d_ur) *d_ur = dev->d_ur;
+    return RGBL_OK;
+  }
+  if (d_desc) hc.put(d_desc, desc, (size_t)n * 32);
+  if (d_xy) hc.put(d_xy, xy, (size_t)n * 2);
+  if (d_oct) hc.put(d_oct, oct, (size_t)n);
+  if (d_ur) hc.put(d_ur, ur, (size_t)n);
+  return RGBL_OK;
+}
+
+// A key frame's FeatureVector (CSR): the resident copy when its frame holds one of the same shape
+// (rgbl_device_frame_set_feature_vector since the last upload / capture), else staged.
+void put_feature_vector(HostCall& hc, const rgbl_keyframe_view* v, const int32_t** d_off, const int32_t** d_feat) {
+  const int nf = v->node_off[v->n_nodes];
+  if (v->device && v->device->n_nodes == v->n_nodes && v->device->nf == nf) {
+    *d_off = v->device->d_fv; *d_feat = v->device->d_fv + v->n_nodes + 1;
+    return;
+  }
+  hc.put(d_off, v->node_off, (size_t)v->n_nodes + 1);
+  hc.put(d_feat, v->node_feat, (size_t)nf);
+}
+
+// The vocabulary nodes two sorted FeatureVectors share, in the order of the reference's merge walk
+// (ORBmatcher.cc:243-246, 388-401; 963-968, 1103-1116).
+void shared_nodes(const rgbl_keyframe_view* a, const rgbl_keyframe_view* b, std::vector<int32_t>& pa, std::vector<int32_t>& pb) {
+  pa.clear(); pb.clear();
+  for (int i = 0, j = 0; i < a->n_nodes && j < b->n_nodes;) {
+    if (a->node_id[i] == b->node_id[j]) { pa.push_back(i++); pb.push_back(j++); }
+    else if (a->node_id[i] < b->node_id[j]) ++i;
+    else ++j;
+  }
+}
+
+// The rotation-consistency check (e.g. ORBmatcher.cc:1083-1096, 1119-1136): add() bins an item by angle_a - angle_b in the
+// order the caller visits it; drop_outliers() hands every item outside the bins ComputeThreeMaxima keeps (:2012-2053) to drop.
+struct RotationFilter {
+  std::vector<int> hist[30];
+  void add(int item, float angle_a, float angle_b) {
+    float rot = angle_a - angle_b;
+    if (rot < 0.0) rot += 360.0f;
+    int bin = (int)roundf(rot * (1.0f / 30));
+    if (bin == 30) bin = 0;
+    if (bin >= 0 && bin < 30) hist[bin].push_back(item);
+  }
+  template <class Drop> void drop_outliers(Drop drop) const {
+    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+    for (int i = 0; i < 30; ++i) {
+      const int sz = (int)hist[i].size();
+      if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
+      else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
+      else if (sz > max3) { max3 = sz; i3 = i; }
+    }
+    if (max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+    else if (max3 < 0.1f * (float)max1) { i3 = -1; }
+    for (int i = 0; i < 30; ++i)
+      if (i != i1 && i != i2 && i != i3)
+        for (int item : hist[i]) drop(item);
   }
 };
 }  // namespace
@@ -1974,9 +2047,7 @@ void rgbl_device_frame_destroy(rgbl_device_frame* f) {
   if (f->stream) { (void)hipStreamSynchronize(f->stream); (void)hipStreamDestroy(f->stream); }
   if (f->block) (void)hipFree(f->block);
   if (f->d_fv) (void)hipFree(f->d_fv);
-  if (f->d_cell_start) (void)hipFree(f->d_cell_start);
-  if (f->d_cell_items) (void)hipFree(f->d_cell_items);
-  if (f->d_grid_scratch) (void)hipFree(f->d_grid_scratch);
+  if (f->d_cell_start) (void)hipFree(f->d_cell_start);   // the grid's block
   if (f->h_pin) (void)hipHostFree(f->h_pin);
   delete f;
 }
@@ -2007,7 +2078,7 @@ int rgbl_device_frame_upload(rgbl_device_frame* f, int n, const uint8_t* desc, c
   RGBL_HIP(hipEventRecord(f->ready, f->stream));
   RGBL_HIP(hipStreamSynchronize(f->stream));   // the mirror is reused by the next upload; the caller's arrays are free at once anyway
   f->n = n;
-  f->has_grid = false;   // new keypoints: rgbl_device_frame_set_grid again
+  f->has_grid = false; f->n_nodes = -1; f->nf = 0;   // new keypoints: rgbl_device_frame_set_grid / _set_feature_vector again
   return RGBL_OK;
 }
 
@@ -2038,10 +2109,14 @@ int rgbl_device_frame_set_feature_vector(rgbl_device_frame* f, int n_nodes, cons
 int rgbl_device_frame_set_grid(rgbl_device_frame* f, const float grid[6]) {
   if (!f || !grid) { set_error("device frame: null argument"); return RGBL_ERR_INVALID; }
   RGBL_HIP(hipSetDevice(f->device));
-  if (!f->d_cell_start) {
-    RGBL_HIP(hipMalloc(&f->d_cell_start, sizeof(uint32_t) * (kGridCells + 1)));
-    RGBL_HIP(hipMalloc(&f->d_cell_items, sizeof(uint16_t) * (size_t)f->cap));
-    RGBL_HIP(hipMalloc(&f->d_grid_scratch, sizeof(int32_t) * (size_t)f->cap));
+  if (!f->d_cell_start) {   // one block: cell_start [kGridCells + 1] | cell_items [cap] | scratch [cap], 256-byte aligned
+    const size_t items = (sizeof(uint32_t) * (kGridCells + 1) + 255) / 256 * 256;
+    const size_t scratch = items + (sizeof(uint16_t) * (size_t)f->cap + 255) / 256 * 256;
+    uint8_t* block = nullptr;
+    RGBL_HIP(hipMalloc(&block, scratch + sizeof(int32_t) * (size_t)f->cap));
+    f->d_cell_start = reinterpret_cast<uint32_t*>(block);
+    f->d_cell_items = reinterpret_cast<uint16_t*>(block + items);
+    f->d_grid_scratch = reinterpret_cast<int32_t*>(block + scratch);
   }
   ProjDev P;
   memset(&P, 0, sizeof(P));
@@ -2165,21 +2240,26 @@ int rgbl_hamming_bf(rgbl_matcher* m, const uint8_t* desc_a, int na, const uint8_
   int splits = 1;
   if (bf_on_matrix_cores(m) && bf_on_fp4(m) && m->bf_split)
     splits = std::max(1, std::min(std::min(16, stages / 4), 128 / std::max(qblocks, 1)));
-  HostCall hc;
-  RGBL_TRY(hc.begin(m, pad256((size_t)2 * cap * 32) + pad256(8) + 3 * pad256((size_t)na * 4) + pad256((size_t)splits * na * 8)));
+  HostCall hc(m);
   hipStream_t s = hc.s;
-  // both descriptor sets and the counts in one block, ONE request up; the three result arrays come back with one
-  uint8_t* d_desc = hc.stage<uint8_t>((size_t)2 * cap * 32);
-  memcpy(hc.mirror(d_desc), desc_a, (size_t)na * 32);
-  if (nb > 0) memcpy(hc.mirror(d_desc) + (size_t)cap * 32, desc_b, (size_t)nb * 32);
   const int32_t counts[2] = {na, nb};
+  const uint8_t* d_desc = nullptr;
   const int32_t* d_n = nullptr;
-  RGBL_TRY(hc.put(&d_n, counts, 2));
-  RGBL_TRY(hc.upload());
-  int32_t* d_bi = hc.result<int32_t>(na);
-  int32_t* d_bd = hc.result<int32_t>(na);
-  int32_t* d_sd = hc.result<int32_t>(na);
-  uint32_t* d_partial = hc.scratch<uint32_t>((size_t)splits * na * 2);
+  int32_t *d_bi = nullptr, *d_bd = nullptr, *d_sd = nullptr;
+  uint32_t* d_partial = nullptr;
+  RGBL_TRY(hc.begin([&]() -> int {
+    // both descriptor sets and the counts in one block, ONE request up; the three result arrays come back with one
+    d_desc = hc.stage<uint8_t>((size_t)2 * cap * 32, [&](uint8_t* h) {
+      memcpy(h, desc_a, (size_t)na * 32);
+      if (nb > 0) memcpy(h + (size_t)cap * 32, desc_b, (size_t)nb * 32);
+    });
+    hc.put(&d_n, counts, 2);
+    d_bi = hc.result<int32_t>(na);
+    d_bd = hc.result<int32_t>(na);
+    d_sd = hc.result<int32_t>(na);
+    d_partial = hc.scratch<uint32_t>((size_t)splits * na * 2);
+    return RGBL_OK;
+  }));
   // pair_a/pair_b == NULL selects the fixed pair (frame 0 -> frame 1)
   if (bf_on_matrix_cores(m)) {
     m->timer.begin(bf_on_fp4(m) ? "k_hamming_fp4" : "k_hamming_mfma", s);
@@ -2276,62 +2356,30 @@ int rgbl_search_triangulation(rgbl_matcher* m, const rgbl_keyframe_view* k1, con
   *out_nmatches = 0;
   const int n1 = k1->n, n2 = k2->n;
   for (int i = 0; i < n1; ++i) matches12[i] = -1;
-  // merge walk of the two sorted FeatureVectors (ORBmatcher.cc:963-968, 1103-1116)
   std::vector<int32_t> pa, pb;
-  for (int a = 0, b = 0; a < k1->n_nodes && b < k2->n_nodes;) {
-    if (k1->node_id[a] == k2->node_id[b]) { pa.push_back(a++); pb.push_back(b++); }
-    else if (k1->node_id[a] < k2->node_id[b]) ++a;
-    else ++b;
-  }
+  shared_nodes(k1, k2, pa, pb);
   const int npairs = (int)pa.size();
   if (npairs > 0 && n1 > 0 && n2 > 0) {
     RGBL_HIP(hipSetDevice(m->device));
-  StreamDrain drain(m->stream);  // error returns included
-    const int nf1 = k1->node_off[k1->n_nodes], nf2 = k2->node_off[k2->n_nodes];
-    size_t need = pad256((size_t)n1 * 32) + pad256((size_t)n2 * 32) + pad256((size_t)n1 * 8) + pad256((size_t)n2 * 8) +
-                  pad256((size_t)n2 * 4) + pad256((size_t)n1 * 4) + pad256((size_t)n2 * 4) + pad256(n1) + pad256(n2) +
-                  pad256((size_t)(k1->n_nodes + 1) * 4) + pad256((size_t)nf1 * 4) + pad256((size_t)(k2->n_nodes + 1) * 4) +
-                  pad256((size_t)nf2 * 4) + 2 * pad256((size_t)npairs * 4) + 2 * pad256((size_t)prm->n_levels * 4) +
-                  pad256((size_t)n1 * 4);
-    HostCall hc;
-    RGBL_TRY(hc.begin(m, need));
+    StreamDrain drain(m->stream);  // error returns included
+    HostCall hc(m);
     hipStream_t s = hc.s;
     TriDev T;
-    const rgbl_keyframe_view* kv[2] = {k1, k2};
-    const uint8_t** desc[2] = {&T.desc1, &T.desc2};
-    const float** xy[2] = {&T.xy1, &T.xy2};
-    const float** ur[2] = {&T.ur1, &T.ur2};
-    const int32_t **off[2] = {&T.off1, &T.off2}, **feat[2] = {&T.feat1, &T.feat2};
-    const int32_t* oct1_unused = nullptr;
-    const int32_t** oct[2] = {&oct1_unused, &T.oct2};
-    for (int k = 0; k < 2; ++k) {
-      const rgbl_keyframe_view* v = kv[k];
-      const int nf = v->node_off[v->n_nodes];
-      if (const rgbl_device_frame* f = v->device) {
-        RGBL_TRY(hc.use(f, v->n));
-        *desc[k] = f->d_desc; *xy[k] = f->d_xy; *oct[k] = f->d_oct; *ur[k] = f->d_ur;
-      } else {
-        RGBL_TRY(hc.put(desc[k], v->desc, (size_t)v->n * 32));
-        RGBL_TRY(hc.put(xy[k], v->kp_xy, (size_t)v->n * 2));
-        if (k == 1) RGBL_TRY(hc.put(oct[k], v->kp_octave, (size_t)v->n));
-        RGBL_TRY(hc.put(ur[k], v->uright, (size_t)v->n));
-      }
-      if (v->device && v->device->n_nodes == v->n_nodes && v->device->nf == nf) {
-        *off[k] = v->device->d_fv; *feat[k] = v->device->d_fv + v->n_nodes + 1;
-      } else {
-        RGBL_TRY(hc.put(off[k], v->node_off, (size_t)v->n_nodes + 1));
-        RGBL_TRY(hc.put(feat[k], v->node_feat, (size_t)nf));
-      }
-    }
-    RGBL_TRY(hc.put(&T.mp1, k1->has_mappoint, (size_t)n1));
-    RGBL_TRY(hc.put(&T.mp2, k2->has_mappoint, (size_t)n2));
-    RGBL_TRY(hc.put(&T.pair_n1, pa.data(), (size_t)npairs));
-    RGBL_TRY(hc.put(&T.pair_n2, pb.data(), (size_t)npairs));
-    RGBL_TRY(hc.put(&T.scale2, prm->scale_factors2, (size_t)prm->n_levels));
-    RGBL_TRY(hc.put(&T.sigma2, prm->level_sigma2_2, (size_t)prm->n_levels));
-    T.matches12 = hc.put_fill<int32_t>(n1, 0xff);   // all -1: travels with the upload
-    hc.mark_result(T.matches12, n1);
-    RGBL_TRY(hc.upload());
+    RGBL_TRY(hc.begin([&]() -> int {
+      RGBL_TRY(put_features(hc, k1->device, n1, k1->desc, k1->kp_xy, nullptr, k1->uright, &T.desc1, &T.xy1, nullptr, &T.ur1));
+      put_feature_vector(hc, k1, &T.off1, &T.feat1);
+      RGBL_TRY(put_features(hc, k2->device, n2, k2->desc, k2->kp_xy, k2->kp_octave, k2->uright, &T.desc2, &T.xy2, &T.oct2, &T.ur2));
+      put_feature_vector(hc, k2, &T.off2, &T.feat2);
+      hc.put(&T.mp1, k1->has_mappoint, (size_t)n1);
+      hc.put(&T.mp2, k2->has_mappoint, (size_t)n2);
+      hc.put(&T.pair_n1, pa.data(), (size_t)npairs);
+      hc.put(&T.pair_n2, pb.data(), (size_t)npairs);
+      hc.put(&T.scale2, prm->scale_factors2, (size_t)prm->n_levels);
+      hc.put(&T.sigma2, prm->level_sigma2_2, (size_t)prm->n_levels);
+      T.matches12 = hc.put_fill<int32_t>(n1, 0xff);   // all -1: travels with the upload
+      hc.mark_result(T.matches12, n1);
+      return RGBL_OK;
+    }));
     memcpy(T.F, prm->F12, sizeof(T.F));
     T.ep[0] = prm->epipole[0];
     T.ep[1] = prm->epipole[1];
@@ -2347,50 +2395,17 @@ int rgbl_search_triangulation(rgbl_matcher* m, const rgbl_keyframe_view* k1, con
   int nmatches = 0;
   for (int i = 0; i < n1; ++i) nmatches += matches12[i] >= 0;
   if (prm->check_orientation) {
-    // rotation-consistency histogram (ORBmatcher.cc:1083-1096, 1119-1136) + ComputeThreeMaxima (:2012-2053).
-    // Bins are filled in the order the reference visits idx1: node by node, bucket order.
-    std::vector<int> hist[30];
-    const float factor = 1.0f / 30;
+    // ORBmatcher.cc:1083-1096, 1119-1136: bins filled in the order the reference visits idx1, node by node, bucket order
+    RotationFilter rf;
     for (int p = 0; p < npairs; ++p)
       for (int q = k1->node_off[pa[p]]; q < k1->node_off[pa[p] + 1]; ++q) {
         const int idx1 = k1->node_feat[q];
-        if (matches12[idx1] < 0) continue;
-        float rot = k1->kp_angle[idx1] - k2->kp_angle[matches12[idx1]];
-        if (rot < 0.0) rot += 360.0f;
-        int bin = (int)roundf(rot * factor);
-        if (bin == 30) bin = 0;
-        if (bin >= 0 && bin < 30) hist[bin].push_back(idx1);
+        if (matches12[idx1] >= 0) rf.add(idx1, k1->kp_angle[idx1], k2->kp_angle[matches12[idx1]]);
       }
-    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-    for (int i = 0; i < 30; ++i) {
-      const int sz = (int)hist[i].size();
-      if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-      else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-      else if (sz > max3) { max3 = sz; i3 = i; }
-    }
-    if (max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-    else if (max3 < 0.1f * (float)max1) { i3 = -1; }
-    for (int i = 0; i < 30; ++i) {
-      if (i == i1 || i == i2 || i == i3) continue;
-      for (int idx1 : hist[i]) { matches12[idx1] = -1; --nmatches; }
-    }
+    rf.drop_outliers([&](int idx1) { matches12[idx1] = -1; --nmatches; });
   }
   *out_nmatches = nmatches;
   return RGBL_OK;
-}
-
-// rotation-consistency bins that survive: ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:2012-2053)
-static void three_maxima(const std::vector<int>* hist, int L, int& i1, int& i2, int& i3) {
-  int max1 = 0, max2 = 0, max3 = 0;
-  i1 = i2 = i3 = -1;
-  for (int i = 0; i < L; ++i) {
-    const int sz = (int)hist[i].size();
-    if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-    else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-    else if (sz > max3) { max3 = sz; i3 = i; }
-  }
-  if (max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-  else if (max3 < 0.1f * (float)max1) { i3 = -1; }
 }
 
 // what the two greedy, best-only projection matchers (Frame-to-Frame and key-frame-to-Frame) hand to the kernels
@@ -2408,23 +2423,6 @@ struct ProjHost {
   const rgbl_device_frame* dev2;  // nullable: the second frame's xy / octave / uright / descriptors resident on the device
 };
 
-// the second frame's per-feature arrays: from the resident copy, or staged with the rest of the call's upload
-int put_frame2(HostCall& hc, ProjDev& P, const rgbl_device_frame* dev2, int n2, const float* xy2, const int32_t* oct2, const float* ur2,
-               bool want_ur, const uint8_t* desc2) {
-  if (dev2) {
-    RGBL_TRY(hc.use(dev2, n2));
-    P.xy2 = dev2->d_xy; P.oct2 = dev2->d_oct; P.desc2 = dev2->d_desc;
-    if (want_ur) P.ur2 = dev2->d_ur;
-    return RGBL_OK;
-  }
-
-  RGBL_TRY(hc.put(&P.xy2, xy2, (size_t)n2 * 2));
-  RGBL_TRY(hc.put(&P.oct2, oct2, (size_t)n2));
-  if (want_ur) RGBL_TRY(hc.put(&P.ur2, ur2, (size_t)n2));
-  RGBL_TRY(hc.put(&P.desc2, desc2, (size_t)n2 * 32));
-  return RGBL_OK;
-}
-
 // Frame::AssignFeaturesToGrid for the call: the resident frame's own grid when it has one for these image bounds
 // (rgbl_device_frame_set_grid), else k_proj_grid on the call's scratch.  P.grid, P.xy2, P.blocked2 must be set.
 void grid_for_call(rgbl_matcher* m, hipStream_t s, ProjDev& P, const rgbl_device_frame* dev2) {
@@ -2440,6 +2438,42 @@ void grid_for_call(rgbl_matcher* m, hipStream_t s, ProjDev& P, const rgbl_device
   m->timer.end(s);
 }
 
+// The greedy, best-only searches (SearchByProjection in three forms, SearchLocalPoints, SearchForInitialization): candidates
+// per point, then ONE block that settles them in point order, in LDS when both sets fit.  greedy_layout() carves the result
+// (P.choice) and the scratch inside the call's layout; greedy_search() launches.
+struct GreedyKernels {
+  void (*candidates)(ProjDev);
+  void (*resolve_lds)(ProjDev);
+  void (*resolve_global)(ProjDev);
+  const char *candidates_name, *resolve_name;
+};
+
+void greedy_layout(HostCall& hc, ProjDev& P) {
+  P.choice = hc.result<int32_t>(P.n1);
+  P.cell_start = hc.scratch<uint32_t>(kGridCells + 1);
+  P.cell_items = hc.scratch<uint16_t>(P.n2);
+  P.taken_by = hc.scratch<int32_t>(P.n2);
+  P.min_unres = hc.scratch<int32_t>(P.n2);
+  P.win = hc.scratch<float4>(P.n1);
+  P.rng = hc.scratch<int4>(P.n1);
+  P.clist = hc.scratch<uint32_t>((size_t)P.n1 * kProjCand);
+  P.cref = hc.scratch<uint32_t>(P.n1);
+  P.state = hc.scratch<uint8_t>(P.n1);
+}
+
+int greedy_search(rgbl_matcher* m, hipStream_t s, ProjDev& P, const rgbl_device_frame* dev2, const GreedyKernels& K) {
+  grid_for_call(m, s, P, dev2);
+  m->timer.begin(K.candidates_name, s);
+  hipLaunchKernelGGL(K.candidates, dim3((P.n1 + kPointsPerBlock - 1) / kPointsPerBlock), dim3(256), 0, s, P);
+  m->timer.end(s);
+  m->timer.begin(K.resolve_name, s);
+  const bool lds = P.n2 <= kResolveLdsN2 && P.n1 <= kResolveLdsN1;
+  hipLaunchKernelGGL(lds ? K.resolve_lds : K.resolve_global, dim3(1), dim3(kResolveBS), 0, s, P);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  return RGBL_OK;
+}
+
 int projection_core(rgbl_matcher* m, const ProjHost& in, int32_t* match2, int* out_nmatches) {
   *out_nmatches = 0;
   const int n1 = in.n1, n2 = in.n2;
@@ -2450,35 +2484,24 @@ int projection_core(rgbl_matcher* m, const ProjHost& in, int32_t* match2, int* o
     if (in.valid1[i] && (in.oct1[i] < 0 || in.oct1[i] >= in.n_levels)) { set_error("octave out of range"); return RGBL_ERR_INVALID; }
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
-  size_t need = pad256(n1) * 2 + pad256((size_t)n1 * 12) + pad256((size_t)n1 * 32) + pad256((size_t)n1 * 4) + pad256((size_t)n2 * 8) +
-                pad256((size_t)n2 * 4) * 2 + pad256((size_t)n2 * 32) + pad256((size_t)n2 * 2) + pad256((size_t)n2 * 4) * 3 + pad256(n2) +
-                pad256((size_t)n1 * 16) * 2 + pad256(n1) * 2 + pad256((size_t)n1 * 4) + pad256((size_t)n1 * kProjCand * 4) + pad256((size_t)n1 * 4) + 256 +
-                pad256((size_t)(kGridCells + 1) * 4);
-  HostCall hc;
-  RGBL_TRY(hc.begin(m, need));
+  HostCall hc(m);
   hipStream_t s = hc.s;
   ProjDev P;
   P.n1 = n1; P.n2 = n2;
   P.proj1 = nullptr; P.level1 = nullptr; P.viewcos1 = nullptr; P.blocked2 = nullptr; P.ur2 = nullptr; P.nnratio = 0.f;
-  RGBL_TRY(hc.put(&P.valid1, in.valid1, (size_t)n1));
-  if (in.obs1) RGBL_TRY(hc.put(&P.obs1, in.obs1, (size_t)n1));
-  else P.obs1 = hc.put_fill<uint8_t>(n1, 1);   // every point blocks
-  RGBL_TRY(hc.put(&P.wpos1, in.wpos1, (size_t)n1 * 3));
-  RGBL_TRY(hc.put(&P.mpdesc1, in.mpdesc1, (size_t)n1 * 32));
-  RGBL_TRY(hc.put(&P.oct1, in.oct1, (size_t)n1));
-  RGBL_TRY(put_frame2(hc, P, in.dev2, n2, in.xy2, in.oct2, in.ur2, in.ur2 != nullptr || (in.dev2 && in.want_ur2), in.desc2));
-  if (in.blocked2) RGBL_TRY(hc.put(&P.blocked2, in.blocked2, (size_t)n2));
-  RGBL_TRY(hc.upload());
-  P.choice = hc.result<int32_t>(n1);
-  P.cell_start = hc.scratch<uint32_t>(kGridCells + 1);
-  P.cell_items = hc.scratch<uint16_t>(n2);
-  P.taken_by = hc.scratch<int32_t>(n2);
-  P.min_unres = hc.scratch<int32_t>(n2);
-  P.win = hc.scratch<float4>(n1);
-  P.rng = hc.scratch<int4>(n1);
-  P.clist = hc.scratch<uint32_t>((size_t)n1 * kProjCand);
-  P.cref = hc.scratch<uint32_t>(n1);
-  P.state = hc.scratch<uint8_t>(n1);
+  const bool want_ur = in.ur2 != nullptr || (in.dev2 && in.want_ur2);
+  RGBL_TRY(hc.begin([&]() -> int {
+    hc.put(&P.valid1, in.valid1, (size_t)n1);
+    if (in.obs1) hc.put(&P.obs1, in.obs1, (size_t)n1);
+    else P.obs1 = hc.put_fill<uint8_t>(n1, 1);   // every point blocks
+    hc.put(&P.wpos1, in.wpos1, (size_t)n1 * 3);
+    hc.put(&P.mpdesc1, in.mpdesc1, (size_t)n1 * 32);
+    hc.put(&P.oct1, in.oct1, (size_t)n1);
+    RGBL_TRY(put_features(hc, in.dev2, n2, in.desc2, in.xy2, in.oct2, in.ur2, &P.desc2, &P.xy2, &P.oct2, want_ur ? &P.ur2 : nullptr));
+    if (in.blocked2) hc.put(&P.blocked2, in.blocked2, (size_t)n2);
+    greedy_layout(hc, P);
+    return RGBL_OK;
+  }));
   memcpy(P.grid, in.grid, sizeof(P.grid));
   memcpy(P.q, in.Tcw_q, sizeof(P.q));
   memcpy(P.t, in.Tcw_t, sizeof(P.t));
@@ -2489,43 +2512,22 @@ int projection_core(rgbl_matcher* m, const ProjHost& in, int32_t* match2, int* o
   P.forward = in.forward; P.backward = in.backward;
   P.skip_behind = in.skip_behind; P.max_dist = in.max_dist;
   P.sim3_mode = in.sim3_mode;
-  grid_for_call(m, s, P, in.dev2);
-  m->timer.begin("k_proj_candidates", s);
-  hipLaunchKernelGGL(k_proj_candidates, dim3((n1 + kPointsPerBlock - 1) / kPointsPerBlock), dim3(256), 0, s, P);
-  m->timer.end(s);
-  m->timer.begin("k_proj_resolve", s);
-  if (n2 <= kResolveLdsN2 && n1 <= kResolveLdsN1) hipLaunchKernelGGL(k_proj_resolve<true>, dim3(1), dim3(kResolveBS), 0, s, P);
-  else hipLaunchKernelGGL(k_proj_resolve<false>, dim3(1), dim3(kResolveBS), 0, s, P);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(greedy_search(m, s, P, in.dev2, {k_proj_candidates, k_proj_resolve<true>, k_proj_resolve<false>, "k_proj_candidates", "k_proj_resolve"}));
   RGBL_TRY(hc.fetch());
   const int32_t* choice = hc.host(P.choice);
   // what the loop leaves in CurrentFrame.mvpMapPoints (a later point overwrites an unobserved earlier one), the match
   // count, and the rotation-consistency pass (ORBmatcher.cc:1768-1790, 1860-1884 / 1961-2006)
   int nmatches = 0;
-  std::vector<int> hist[30];
-  const float factor = 1.0f / 30;
+  RotationFilter rf;
   for (int i = 0; i < n1; ++i) {
     const int c = choice[i];
     if (c < 0) continue;
     match2[c] = i;
     ++nmatches;
-    if (in.check_orientation) {
-      float rot = in.angle1[i] - in.angle2[c];
-      if (rot < 0.0) rot += 360.0f;
-      int bin = (int)roundf(rot * factor);
-      if (bin == 30) bin = 0;
-      if (bin >= 0 && bin < 30) hist[bin].push_back(c);
-    }
+    if (in.check_orientation) rf.add(c, in.angle1[i], in.angle2[c]);
   }
-  if (in.check_orientation) {
-    int i1, i2, i3;
-    three_maxima(hist, 30, i1, i2, i3);
-    for (int i = 0; i < 30; ++i) {
-      if (i == i1 || i == i2 || i == i3) continue;
-      for (int c : hist[i]) { match2[c] = -1; --nmatches; }  // a feature chosen twice is un-counted twice, as in the reference
-    }
-  }
+  // a feature chosen twice is un-counted twice, as in the reference
+  if (in.check_orientation) rf.drop_outliers([&](int c) { match2[c] = -1; --nmatches; });
   *out_nmatches = nmatches;
   return RGBL_OK;
 }
@@ -2597,15 +2599,17 @@ int rgbl_distinctive_descriptors(rgbl_matcher* m, const uint8_t* desc, const int
   if (off[0] != 0 || (total > 0 && !desc)) { set_error("offsets start at 0; descriptors missing"); return RGBL_ERR_INVALID; }
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
-  HostCall hc;
-  RGBL_TRY(hc.begin(m, pad256((size_t)total * 32) + pad256((size_t)(n_points + 1) * 4) + pad256((size_t)n_points * 4)));
+  HostCall hc(m);
   hipStream_t s = hc.s;
   const uint8_t* d_desc = nullptr;
   const int32_t* d_off = nullptr;
-  if (total > 0) RGBL_TRY(hc.put(&d_desc, desc, (size_t)total * 32));
-  RGBL_TRY(hc.put(&d_off, off, (size_t)n_points + 1));
-  RGBL_TRY(hc.upload());
-  int32_t* d_best = hc.result<int32_t>(n_points);
+  int32_t* d_best = nullptr;
+  RGBL_TRY(hc.begin([&]() -> int {
+    if (total > 0) hc.put(&d_desc, desc, (size_t)total * 32);
+    hc.put(&d_off, off, (size_t)n_points + 1);
+    d_best = hc.result<int32_t>(n_points);
+    return RGBL_OK;
+  }));
   m->timer.begin("k_distinctive", s);
   hipLaunchKernelGGL(k_distinctive, dim3(n_points), dim3(64), 0, s, d_desc, d_off, d_best);
   m->timer.end(s);
@@ -2628,24 +2632,23 @@ static int fuse_core(rgbl_matcher* m, const rgbl_fuse_input* in, int cam_frame, 
     if (in->valid1[i] && (in->level1[i] < 0 || in->level1[i] >= in->n_levels)) { set_error("predicted level out of range"); return RGBL_ERR_INVALID; }
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
-  size_t need = pad256(n1) + pad256((size_t)n1 * 12) + pad256((size_t)n1 * 32) + pad256((size_t)n1 * 4) + pad256((size_t)n2 * 8) +
-                pad256((size_t)n2 * 4) * 2 + pad256((size_t)n2 * 32) + pad256((size_t)n2 * 2) + pad256((size_t)n2 * 4) * 2 +
-                pad256((size_t)n1 * 8) + pad256((size_t)(kGridCells + 1) * 4);
-  HostCall hc;
-  RGBL_TRY(hc.begin(m, need));
+  HostCall hc(m);
   hipStream_t s = hc.s;
   ProjDev P{};
   P.n1 = n1; P.n2 = n2;
-  RGBL_TRY(hc.put(&P.valid1, in->valid1, (size_t)n1));
-  RGBL_TRY(hc.put(&P.wpos1, in->world_pos1, (size_t)n1 * 3));
-  RGBL_TRY(hc.put(&P.mpdesc1, in->mp_desc1, (size_t)n1 * 32));
-  RGBL_TRY(hc.put(&P.oct1, in->level1, (size_t)n1));
-  RGBL_TRY(put_frame2(hc, P, in->device2, n2, in->kp2_xy, in->kp2_octave, in->uright2, want_ur2 != 0, in->desc2));
-  RGBL_TRY(hc.upload());
-  P.cand = hc.result<unsigned long long>(n1);
-  P.cell_start = hc.scratch<uint32_t>(kGridCells + 1);
-  P.cell_items = hc.scratch<uint16_t>(n2);
-  P.taken_by = hc.scratch<int32_t>(n2);  // written by k_proj_grid, not used by the fuse search
+  RGBL_TRY(hc.begin([&]() -> int {
+    hc.put(&P.valid1, in->valid1, (size_t)n1);
+    hc.put(&P.wpos1, in->world_pos1, (size_t)n1 * 3);
+    hc.put(&P.mpdesc1, in->mp_desc1, (size_t)n1 * 32);
+    hc.put(&P.oct1, in->level1, (size_t)n1);
+    RGBL_TRY(put_features(hc, in->device2, n2, in->desc2, in->kp2_xy, in->kp2_octave, in->uright2, &P.desc2, &P.xy2, &P.oct2,
+                          want_ur2 ? &P.ur2 : nullptr));
+    P.cand = hc.result<unsigned long long>(n1);
+    P.cell_start = hc.scratch<uint32_t>(kGridCells + 1);
+    P.cell_items = hc.scratch<uint16_t>(n2);
+    P.taken_by = hc.scratch<int32_t>(n2);  // written by k_proj_grid, not used by the fuse search
+    return RGBL_OK;
+  }));
   memcpy(P.grid, in->grid, sizeof(P.grid));
   memcpy(P.q, in->Tcw_q, sizeof(P.q));
   memcpy(P.t, in->Tcw_t, sizeof(P.t));
@@ -2743,48 +2746,28 @@ int rgbl_search_local_points(rgbl_matcher* m, const rgbl_local_points_input* in,
     if (in->valid1[i] && (in->level1[i] < 0 || in->level1[i] >= in->n_levels)) { set_error("predicted level out of range"); return RGBL_ERR_INVALID; }
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
-  size_t need = pad256(n1) * 2 + pad256((size_t)n1 * 12) + pad256((size_t)n1 * 32) + pad256((size_t)n1 * 4) * 2 + pad256((size_t)n2 * 8) +
-                pad256((size_t)n2 * 4) * 2 + pad256((size_t)n2 * 32) + pad256(n2) + pad256((size_t)n2 * 2) + pad256((size_t)n2 * 4) * 2 +
-                pad256((size_t)n1 * 16) * 2 + pad256(n1) * 2 + pad256((size_t)n1 * 4) + pad256((size_t)n1 * kProjCand * 4) + pad256((size_t)n1 * 4) + 256 +
-                pad256((size_t)(kGridCells + 1) * 4);
-  HostCall hc;
-  RGBL_TRY(hc.begin(m, need));
+  HostCall hc(m);
   hipStream_t s = hc.s;
   ProjDev P;
   memset(&P, 0, sizeof(P));
   P.n1 = n1; P.n2 = n2;
-  RGBL_TRY(hc.put(&P.valid1, in->valid1, (size_t)n1));
-  RGBL_TRY(hc.put(&P.obs1, in->mp_observed1, (size_t)n1));
-  RGBL_TRY(hc.put(&P.proj1, in->proj1, (size_t)n1 * 3));
-  RGBL_TRY(hc.put(&P.mpdesc1, in->mp_desc1, (size_t)n1 * 32));
-  RGBL_TRY(hc.put(&P.level1, in->level1, (size_t)n1));
-  RGBL_TRY(hc.put(&P.viewcos1, in->view_cos1, (size_t)n1));
-  RGBL_TRY(put_frame2(hc, P, in->device2, n2, in->kp2_xy, in->kp2_octave, in->uright2, true, in->desc2));
-  if (in->blocked2) RGBL_TRY(hc.put(&P.blocked2, in->blocked2, (size_t)n2));
-  RGBL_TRY(hc.upload());
-  P.choice = hc.result<int32_t>(n1);
-  P.cell_start = hc.scratch<uint32_t>(kGridCells + 1);
-  P.cell_items = hc.scratch<uint16_t>(n2);
-  P.taken_by = hc.scratch<int32_t>(n2);
-  P.min_unres = hc.scratch<int32_t>(n2);
-  P.win = hc.scratch<float4>(n1);
-  P.rng = hc.scratch<int4>(n1);
-  P.clist = hc.scratch<uint32_t>((size_t)n1 * kProjCand);
-  P.cref = hc.scratch<uint32_t>(n1);
-  P.state = hc.scratch<uint8_t>(n1);
+  RGBL_TRY(hc.begin([&]() -> int {
+    hc.put(&P.valid1, in->valid1, (size_t)n1);
+    hc.put(&P.obs1, in->mp_observed1, (size_t)n1);
+    hc.put(&P.proj1, in->proj1, (size_t)n1 * 3);
+    hc.put(&P.mpdesc1, in->mp_desc1, (size_t)n1 * 32);
+    hc.put(&P.level1, in->level1, (size_t)n1);
+    hc.put(&P.viewcos1, in->view_cos1, (size_t)n1);
+    RGBL_TRY(put_features(hc, in->device2, n2, in->desc2, in->kp2_xy, in->kp2_octave, in->uright2, &P.desc2, &P.xy2, &P.oct2, &P.ur2));
+    if (in->blocked2) hc.put(&P.blocked2, in->blocked2, (size_t)n2);
+    greedy_layout(hc, P);
+    return RGBL_OK;
+  }));
   memcpy(P.grid, in->grid, sizeof(P.grid));
   P.th = in->th;
   P.nnratio = in->nnratio;
   for (int l = 0; l < kProjMaxLevels; ++l) P.scale[l] = l < in->n_levels ? in->scale_factors[l] : 1.f;
-  grid_for_call(m, s, P, in->device2);
-  m->timer.begin("k_local_candidates", s);
-  hipLaunchKernelGGL(k_local_candidates, dim3((n1 + kPointsPerBlock - 1) / kPointsPerBlock), dim3(256), 0, s, P);
-  m->timer.end(s);
-  m->timer.begin("k_local_resolve", s);
-  if (n2 <= kResolveLdsN2 && n1 <= kResolveLdsN1) hipLaunchKernelGGL(k_local_resolve<true>, dim3(1), dim3(kResolveBS), 0, s, P);
-  else hipLaunchKernelGGL(k_local_resolve<false>, dim3(1), dim3(kResolveBS), 0, s, P);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(greedy_search(m, s, P, in->device2, {k_local_candidates, k_local_resolve<true>, k_local_resolve<false>, "k_local_candidates", "k_local_resolve"}));
   RGBL_TRY(hc.fetch());
   const int32_t* choice = hc.host(P.choice);
   int nmatches = 0;
@@ -2808,31 +2791,20 @@ int rgbl_search_for_initialization(rgbl_matcher* m, const rgbl_initialization_in
     if (in->kp1_octave[i] < 0) { set_error("negative octave"); return RGBL_ERR_INVALID; }
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
-  size_t need = pad256((size_t)n1 * 8) + pad256((size_t)n1 * 32) + pad256((size_t)n1 * 4) + pad256((size_t)n2 * 8) + pad256((size_t)n2 * 4) +
-                pad256((size_t)n2 * 32) + pad256((size_t)n2 * 2) + pad256((size_t)n2 * 4) * 3 + pad256((size_t)n1 * 16) * 2 + pad256(n1) * 2 +
-                pad256((size_t)n1 * 4) + pad256((size_t)n1 * kProjCand * 4) + pad256((size_t)n1 * 4) + 256 + pad256((size_t)(kGridCells + 1) * 4);
-  HostCall hc;
-  RGBL_TRY(hc.begin(m, need));
+  HostCall hc(m);
   hipStream_t s = hc.s;
   ProjDev P;
   memset(&P, 0, sizeof(P));
   P.n1 = n1; P.n2 = n2;
-  RGBL_TRY(hc.put(&P.proj1, (const float*)prev_matched, (size_t)n1 * 2));
-  RGBL_TRY(hc.put(&P.mpdesc1, in->desc1, (size_t)n1 * 32));
-  RGBL_TRY(hc.put(&P.oct1, in->kp1_octave, (size_t)n1));
-  RGBL_TRY(put_frame2(hc, P, nullptr, n2, in->kp2_xy, in->kp2_octave, nullptr, false, in->desc2));
-  RGBL_TRY(hc.upload());
-  P.choice = hc.result<int32_t>(n1);
-  P.owner = hc.result<int32_t>(n2);
-  P.cell_start = hc.scratch<uint32_t>(kGridCells + 1);
-  P.cell_items = hc.scratch<uint16_t>(n2);
-  P.taken_by = hc.scratch<int32_t>(n2);
-  P.min_unres = hc.scratch<int32_t>(n2);
-  P.win = hc.scratch<float4>(n1);
-  P.rng = hc.scratch<int4>(n1);
-  P.clist = hc.scratch<uint32_t>((size_t)n1 * kProjCand);
-  P.cref = hc.scratch<uint32_t>(n1);
-  P.state = hc.scratch<uint8_t>(n1);
+  RGBL_TRY(hc.begin([&]() -> int {
+    hc.put(&P.proj1, (const float*)prev_matched, (size_t)n1 * 2);
+    hc.put(&P.mpdesc1, in->desc1, (size_t)n1 * 32);
+    hc.put(&P.oct1, in->kp1_octave, (size_t)n1);
+    RGBL_TRY(put_features(hc, nullptr, n2, in->desc2, in->kp2_xy, in->kp2_octave, nullptr, &P.desc2, &P.xy2, &P.oct2, nullptr));
+    P.owner = hc.result<int32_t>(n2);   // next to P.choice: one copy back
+    greedy_layout(hc, P);
+    return RGBL_OK;
+  }));
   memcpy(P.grid, in->grid, sizeof(P.grid));
   P.th = (float)in->window_size;  // GetFeaturesInArea takes r as const float&
   P.nnratio = in->nnratio;
@@ -2841,41 +2813,19 @@ int rgbl_search_for_initialization(rgbl_matcher* m, const rgbl_initialization_in
   int v = 51;
   while (v <= 256 && !((float)v * in->nnratio > 50.0f)) ++v;
   P.max_dist = v - 1;
-  grid_for_call(m, s, P, nullptr);
-  m->timer.begin("k_init_candidates", s);
-  hipLaunchKernelGGL(k_init_candidates, dim3((n1 + kPointsPerBlock - 1) / kPointsPerBlock), dim3(256), 0, s, P);
-  m->timer.end(s);
-  m->timer.begin("k_init_resolve", s);
-  if (n2 <= kResolveLdsN2 && n1 <= kResolveLdsN1) hipLaunchKernelGGL(k_init_resolve<true>, dim3(1), dim3(kResolveBS), 0, s, P);
-  else hipLaunchKernelGGL(k_init_resolve<false>, dim3(1), dim3(kResolveBS), 0, s, P);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(greedy_search(m, s, P, nullptr, {k_init_candidates, k_init_resolve<true>, k_init_resolve<false>, "k_init_candidates", "k_init_resolve"}));
   RGBL_TRY(hc.fetch());
   const int32_t *choice = hc.host(P.choice), *owner = hc.host(P.owner);
   // a feature whose match was taken over later stays in the rotation histogram (pushed at match time, :720-730) but
   // holds no match any more (:708-712); nmatches always equals the number of entries >= 0
-  std::vector<int> hist[30];
-  const float factor = 1.0f / 30;
+  RotationFilter rf;
   for (int i = 0; i < n1; ++i) {
     const int c = choice[i];
     if (c < 0) continue;
     if (owner[c] == i) matches12[i] = c;
-    if (in->check_orientation) {
-      float rot = in->kp1_angle[i] - in->kp2_angle[c];
-      if (rot < 0.0) rot += 360.0f;
-      int bin = (int)roundf(rot * factor);
-      if (bin == 30) bin = 0;
-      if (bin >= 0 && bin < 30) hist[bin].push_back(i);
-    }
+    if (in->check_orientation) rf.add(i, in->kp1_angle[i], in->kp2_angle[c]);
   }
-  if (in->check_orientation) {
-    int i1, i2, i3;
-    three_maxima(hist, 30, i1, i2, i3);
-    for (int b = 0; b < 30; ++b) {
-      if (b == i1 || b == i2 || b == i3) continue;
-      for (int i : hist[b]) matches12[i] = -1;
-    }
-  }
+  if (in->check_orientation) rf.drop_outliers([&](int i) { matches12[i] = -1; });
   int nmatches = 0;
   for (int i = 0; i < n1; ++i)
     if (matches12[i] >= 0) {  // "Update prev matched" (:757-760)
@@ -3142,13 +3092,7 @@ static int bow_core(rgbl_matcher* m, const rgbl_keyframe_view* kf, const rgbl_ke
   const int n1 = kf->n, n2 = fr->n;
   match1.assign(n1, -1);
   match2.assign(n2, -1);
-  // merge walk of the two sorted FeatureVectors (ORBmatcher.cc:243-246, 388-401)
-  pa.clear(); pb.clear();
-  for (int a = 0, b = 0; a < kf->n_nodes && b < fr->n_nodes;) {
-    if (kf->node_id[a] == fr->node_id[b]) { pa.push_back(a++); pb.push_back(b++); }
-    else if (kf->node_id[a] < fr->node_id[b]) ++a;
-    else ++b;
-  }
+  shared_nodes(kf, fr, pa, pb);
   const int npairs = (int)pa.size();
   if (npairs == 0 || n1 == 0 || n2 == 0) return RGBL_OK;
   for (int p = 0; p < npairs; ++p)
@@ -3158,43 +3102,25 @@ static int bow_core(rgbl_matcher* m, const rgbl_keyframe_view* kf, const rgbl_ke
     }
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
-  const int nf1 = kf->node_off[kf->n_nodes], nf2 = fr->node_off[fr->n_nodes];
-  size_t need = pad256((size_t)n1 * 32) + pad256((size_t)n2 * 32) + pad256(n1) + pad256(n2) + pad256((size_t)(kf->n_nodes + 1) * 4) +
-                pad256((size_t)nf1 * 4) + pad256((size_t)(fr->n_nodes + 1) * 4) + pad256((size_t)nf2 * 4) +
-                2 * pad256((size_t)npairs * 4) + pad256((size_t)n1 * 4) + pad256((size_t)n2 * 4);
-  HostCall hc;
-  RGBL_TRY(hc.begin(m, need));
+  HostCall hc(m);
   hipStream_t s = hc.s;
   BowDev T;
   T.valid2 = nullptr;
-  const rgbl_keyframe_view* kv[2] = {kf, fr};
-  const uint8_t** desc[2] = {&T.desc1, &T.desc2};
-  const int32_t **off[2] = {&T.off1, &T.off2}, **feat[2] = {&T.feat1, &T.feat2};
-  for (int k = 0; k < 2; ++k) {
-    const rgbl_keyframe_view* v = kv[k];
-    const int nf = v->node_off[v->n_nodes];
-    if (const rgbl_device_frame* f = v->device) {
-      RGBL_TRY(hc.use(f, v->n));
-      *desc[k] = f->d_desc;
-    } else {
-      RGBL_TRY(hc.put(desc[k], v->desc, (size_t)v->n * 32));
-    }
-    if (v->device && v->device->n_nodes == v->n_nodes && v->device->nf == nf) {
-      *off[k] = v->device->d_fv; *feat[k] = v->device->d_fv + v->n_nodes + 1;
-    } else {
-      RGBL_TRY(hc.put(off[k], v->node_off, (size_t)v->n_nodes + 1));
-      RGBL_TRY(hc.put(feat[k], v->node_feat, (size_t)nf));
-    }
-  }
-  RGBL_TRY(hc.put(&T.valid1, kf->has_mappoint, (size_t)n1));
-  if (second_needs_mp) RGBL_TRY(hc.put(&T.valid2, fr->has_mappoint, (size_t)n2));
-  RGBL_TRY(hc.put(&T.pair_n1, pa.data(), (size_t)npairs));
-  RGBL_TRY(hc.put(&T.pair_n2, pb.data(), (size_t)npairs));
-  T.match1 = hc.put_fill<int32_t>(n1, 0xff);   // all -1: travel with the upload
-  T.match2 = hc.put_fill<int32_t>(n2, 0xff);
-  hc.mark_result(T.match1, n1);
-  hc.mark_result(T.match2, n2);
-  RGBL_TRY(hc.upload());
+  RGBL_TRY(hc.begin([&]() -> int {
+    RGBL_TRY(put_features(hc, kf->device, n1, kf->desc, nullptr, nullptr, nullptr, &T.desc1, nullptr, nullptr, nullptr));
+    put_feature_vector(hc, kf, &T.off1, &T.feat1);
+    RGBL_TRY(put_features(hc, fr->device, n2, fr->desc, nullptr, nullptr, nullptr, &T.desc2, nullptr, nullptr, nullptr));
+    put_feature_vector(hc, fr, &T.off2, &T.feat2);
+    hc.put(&T.valid1, kf->has_mappoint, (size_t)n1);
+    if (second_needs_mp) hc.put(&T.valid2, fr->has_mappoint, (size_t)n2);
+    hc.put(&T.pair_n1, pa.data(), (size_t)npairs);
+    hc.put(&T.pair_n2, pb.data(), (size_t)npairs);
+    T.match1 = hc.put_fill<int32_t>(n1, 0xff);   // all -1: travel with the upload
+    T.match2 = hc.put_fill<int32_t>(n2, 0xff);
+    hc.mark_result(T.match1, n1);
+    hc.mark_result(T.match2, n2);
+    return RGBL_OK;
+  }));
   T.nnratio = nnratio;
   T.max_best = max_best;
   T.n_left2 = n_left2;
@@ -3235,23 +3161,10 @@ int rgbl_search_by_bow_rig(rgbl_matcher* m, const rgbl_keyframe_view* kf, const 
   int nmatches = 0;
   for (int i = 0; i < n2; ++i) { match_f[i] = match2[i]; nmatches += match_f[i] >= 0; }
   if (check_orientation) {
-    std::vector<int> hist[30];
-    const float factor = 1.0f / 30;
-    for (int idx2 = 0; idx2 < n2; ++idx2) {
-      const int idx1 = match2[idx2];
-      if (idx1 < 0) continue;
-      float rot = kf->kp_angle[idx1] - fr->kp_angle[idx2];
-      if (rot < 0.0) rot += 360.0f;
-      int bin = (int)roundf(rot * factor);
-      if (bin == 30) bin = 0;
-      if (bin >= 0 && bin < 30) hist[bin].push_back(idx2);
-    }
-    int i1, i2, i3;
-    three_maxima(hist, 30, i1, i2, i3);
-    for (int i = 0; i < 30; ++i) {
-      if (i == i1 || i == i2 || i == i3) continue;
-      for (int idx2 : hist[i]) { match_f[idx2] = -1; --nmatches; }
-    }
+    RotationFilter rf;
+    for (int idx2 = 0; idx2 < n2; ++idx2)
+      if (match2[idx2] >= 0) rf.add(idx2, kf->kp_angle[match2[idx2]], fr->kp_angle[idx2]);
+    rf.drop_outliers([&](int idx2) { match_f[idx2] = -1; --nmatches; });
   }
   *out_nmatches = nmatches;
   return RGBL_OK;
@@ -3271,25 +3184,13 @@ int rgbl_search_by_bow_keyframes(rgbl_matcher* m, const rgbl_keyframe_view* kf1,
   int nmatches = 0;
   for (int i = 0; i < n1; ++i) { match12[i] = match1[i]; nmatches += match12[i] >= 0; }
   if (check_orientation) {
-    std::vector<int> hist[30];
-    const float factor = 1.0f / 30;
+    RotationFilter rf;
     for (int p = 0; p < npairs; ++p)
       for (int q = kf1->node_off[pa[p]]; q < kf1->node_off[pa[p] + 1]; ++q) {
         const int idx1 = kf1->node_feat[q];
-        const int idx2 = match1[idx1];
-        if (idx2 < 0) continue;
-        float rot = kf1->kp_angle[idx1] - kf2->kp_angle[idx2];
-        if (rot < 0.0) rot += 360.0f;
-        int bin = (int)roundf(rot * factor);
-        if (bin == 30) bin = 0;
-        if (bin >= 0 && bin < 30) hist[bin].push_back(idx1);
+        if (match1[idx1] >= 0) rf.add(idx1, kf1->kp_angle[idx1], kf2->kp_angle[match1[idx1]]);
       }
-    int i1, i2, i3;
-    three_maxima(hist, 30, i1, i2, i3);
-    for (int i = 0; i < 30; ++i) {
-      if (i == i1 || i == i2 || i == i3) continue;
-      for (int idx1 : hist[i]) { match12[idx1] = -1; --nmatches; }
-    }
+    rf.drop_outliers([&](int idx1) { match12[idx1] = -1; --nmatches; });
   }
   *out_nmatches = nmatches;
   return RGBL_OK;

@@ -1372,6 +1372,21 @@ def check_device_frames(lib, n=900, seed=17, w=640, h=360, nfeatures=700):
         got = mt.SearchByBoWKeyFrames(dict(hollow(a), device=d1), dict(hollow(b), device=d2))
         assert got[1] == want[1] and np.array_equal(got[0], want[0]), "SearchByBoW(KF, KF) on resident frames"
         mt.close()
+    # a refill drops the FeatureVector: the previous one, of the very same shape, must not be read
+    for d, kf in ((d1, kf1), (d2, kf2)):
+        d.set_feature_vector(kf["node_off"], rng.permutation(kf["node_feat"]))
+        d.upload(kf["desc"], kf["xy"], kf["octave"], kf["uright"])
+    mt = F.ORBmatcher(0.7, True, lib=lib)
+    want = O.search_by_bow(a, b, 0.7, True)
+    got = mt.SearchByBoW(dict(hollow(a), device=d1), dict(hollow(b), device=d2))
+    assert got[1] == want[1] and np.array_equal(got[0], want[0]), "SearchByBoW on refilled frames"
+    mt.close()
+    mt = F.ORBmatcher(0.6, True, lib=lib)
+    Fm = mt.fundamental(K, K, R, t)
+    want = O.search_triangulation(kf1, kf2, Fm, ep, sf, s2, False, False, True)
+    _, nm, m12 = mt.SearchForTriangulation(dict(hollow(kf1), device=d1), dict(hollow(kf2), device=d2), Fm, ep, sf, s2, False, False)
+    assert nm == want[1] and np.array_equal(m12, want[0]), "triangulation on refilled frames"
+    mt.close()
     d1.close()
     d2.close()
     # the projection searches: the CurrentFrame / key frame resident, the map points from the host
@@ -1476,6 +1491,16 @@ def check_device_frames(lib, n=900, seed=17, w=640, h=360, nfeatures=700):
     for g, x in zip(got, want):
         assert np.array_equal(g.view(np.uint64) if g.dtype == np.float64 else g, x.view(np.uint64) if x.dtype == np.float64 else x)
     V.close()
+    # a capture drops the FeatureVector as well
+    fv = dict(node_id=want[2].astype(np.int32), node_off=want[3], node_feat=want[4].astype(np.int32))
+    cap.set_feature_vector(fv["node_off"], rng.permutation(fv["node_feat"]))
+    cap.capture(ex, len(kps), dm)
+    fr = dict(frame, has_mp=np.ones(len(kps), np.uint8), **fv)
+    mt = F.ORBmatcher(0.7, True, lib=lib)
+    want = O.search_by_bow(fr, fr, 0.7, True)
+    got = mt.SearchByBoW(fr, dict(hollow(fr), device=cap))
+    assert got[1] == want[1] and np.array_equal(got[0], want[0]) and want[1] > 50, "SearchByBoW on a recaptured frame"
+    mt.close()
     cap.close()
     dm.close()
     ex.close()
