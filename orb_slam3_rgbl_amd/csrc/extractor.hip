@@ -6,7 +6,8 @@
 // HBM layout (all buffers are per handle, sized for max_batch frames; frame f at base + f*frame_stride):
 //   pyr    : levels 1..L-1 of the 8-bit pyramid, each level padded to a 64-byte pitch (level 0 is read
 //            straight from the caller's image, it is never copied)
-//   blur   : levels 0..L-1 of the Gaussian working images, same pitches
+//   blur   : levels 0..L-1 of the Gaussian working images, same pitches and level offsets, stored in tiles of 32 px x 4 rows
+//            (one 128-byte line each; extractor_kernels.h: blur_offset) - levels take whole strips of four rows in both buffers
 //   cells  : one candidate counter per FAST detection cell + cell_cap packed candidates per cell
 //   keys   : two ping-pong arrays of packed keys per level for the quad-tree partitions
 //   nodes  : quad-tree node lists (ping-pong), split counts, expandable lists, sort scratch
@@ -212,7 +213,7 @@ int build_geometry(rgbl_extractor* e) {
     g.h = round_even_f((float)c.height * e->inv_scale[l]);
     g.pitch = (int)align_up(g.w, 64);
     g.img_off = (uint32_t)img_off;
-    img_off += (size_t)g.pitch * g.h;
+    img_off += (size_t)g.pitch * blur_rows(g.h);   // whole strips of the tiled blurred level (extractor_kernels.h: blur_offset)
     g.quota = e->per_level[l];
     g.scale = e->scale[l];
     g.patch_size = (int)(31 * e->scale[l]);
@@ -685,6 +686,11 @@ int enqueue_extract(rgbl_extractor* e, const uint8_t* d_imgs, int batch, int str
   // described on the auxiliary stream next to those quad-trees; the main stream takes the other levels and the frame totals.
   const bool split_desc = !e->timer.enabled && batch >= 8 && L > 1 && e->geom[1].koff > 0;
   const int slot_split = split_desc ? e->geom[1].koff : 0;
+#ifdef RGBL_ORIENT_STAMPS   // phase clocks of k_orient_brief, summed over the waves into the debug block (extractor_kernels.h)
+#define RGBL_OB_DBG_ARG , e->d_dbg
+#else
+#define RGBL_OB_DBG_ARG
+#endif
   auto launch_desc = [&](hipStream_t st, int slot_begin, int slot_end, int write_total) {
     if (slot_end <= slot_begin) return;
     e->timer.begin("k_orient_brief", st);
@@ -692,7 +698,7 @@ int enqueue_extract(rgbl_extractor* e, const uint8_t* d_imgs, int batch, int str
     hipLaunchKernelGGL(k_orient_brief<256>, xcd_grid(e->xcd_map, (slot_end - slot_begin + 4 * kKpPerWave - 1) / (4 * kKpPerWave), batch), dim3(256), 0, st, e->d_geom, L, e->umax,
                        e->d_pattern, d_imgs, stride, frame_stride, e->d_pyr, e->pyr_frame, e->d_blur, e->pyr_frame,
                        e->d_kpkey, e->d_kpcount, (size_t)e->kp_frame, kp_dst, desc_dst, lapping ? e->out_cap : cap, d_n,
-                       lapping ? (int32_t*)nullptr : d_mono, e->d_err, slot_begin, slot_end, write_total);
+                       lapping ? (int32_t*)nullptr : d_mono, e->d_err, slot_begin, slot_end, write_total RGBL_OB_DBG_ARG);
     e->timer.end(st);
   };
   if (split_desc) {
@@ -1257,8 +1263,18 @@ int rgbl_extractor_get_level(rgbl_extractor* e, int frame, int level, int blurre
   const LevelGeom& g = e->geom[level];
   const uint8_t* src;
   int pitch;
-  if (blurred) { src = e->d_blur + (size_t)frame * e->pyr_frame + g.img_off; pitch = g.pitch; }
-  else if (level == 0) { src = e->last_img0 + (size_t)frame * e->last_frame0; pitch = e->last_pitch0; }
+  if (blurred) {
+    // the blurred levels are tiled (extractor_kernels.h: blur_offset): one linear transfer of the level's strips, rows rebuilt on the host
+    std::vector<uint8_t> tmp((size_t)g.pitch * blur_rows(g.h));
+    RGBL_HIP(hipStreamSynchronize(e->stream));
+    RGBL_HIP(hipMemcpyAsync(tmp.data(), e->d_blur + (size_t)frame * e->pyr_frame + g.img_off, tmp.size(), hipMemcpyDeviceToHost, e->stream));
+    RGBL_HIP(hipStreamSynchronize(e->stream));
+    for (int y = 0; y < g.h; ++y)
+      for (int x = 0; x < g.w; x += kBlurTileW)
+        memcpy(dst + (size_t)y * dst_stride + x, tmp.data() + blur_offset(x, y, g.pitch), std::min(kBlurTileW, g.w - x));
+    return RGBL_OK;
+  }
+  if (level == 0) { src = e->last_img0 + (size_t)frame * e->last_frame0; pitch = e->last_pitch0; }
   else { src = e->d_pyr + (size_t)frame * e->pyr_frame + g.img_off; pitch = g.pitch; }
   const int border = (with_border && !blurred) ? 19 : 0;
   RGBL_HIP(hipStreamSynchronize(e->stream));

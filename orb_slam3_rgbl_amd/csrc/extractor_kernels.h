@@ -27,7 +27,8 @@ struct ResizeTab {  // one output column / row of cv::resize's fixed-point table
 
 struct LevelGeom {
   int w, h, pitch;            // level size; pitch of the pyramid / blur buffers (bytes)
-  uint32_t img_off;           // byte offset of this level inside one frame's pyramid (and blur) buffer
+  uint32_t img_off;           // byte offset of this level inside one frame's pyramid (and blur) buffer: a level takes
+                              // pitch * blur_rows(h) bytes of both, so the two share offsets and frame stride
   int quota;                  // mnFeaturesPerLevel[level]
   int kcap, koff;             // keypoint slots of this level inside one frame's keypoint arrays
   int n_cols, n_rows, w_cell, h_cell, max_bx, max_by;
@@ -46,6 +47,25 @@ struct LevelGeom {
 };
 
 struct UMax { int v[16]; };
+
+// Layout of the blurred working images (written by k_gauss7, read by k_orient_brief and by the debug accessor
+// rgbl_extractor_get_level, by nothing else).  A level is cut into tiles of kBlurTileW x kBlurTileH pixels; a tile is ONE
+// 128-byte cache line holding its four rows one after the other (32 bytes each), the tiles of a strip of four rows lie
+// side by side (a strip takes 4 * pitch bytes - the pitch is a multiple of 64, hence of the tile width), the strips follow
+// each other.  The 37 x 40-byte neighbourhood of a keypoint then lies in ~22 lines instead of the ~49 of row-major
+// rows (one L1 tag look-up each, which is what paces k_orient_brief).  Rows inside a tile rather than 4 x 4 blocks: an
+// aligned 8- or 16-byte piece of a pixel row never straddles a tile, so the reader fetches pieces of rows and its LDS patch
+// stays row-major.  The last strip of a level is padded to four rows (blur_rows); the padding is never written or read.
+// (Tiles of 16 px x 8 rows - set the two constants - touch 19 instead of 22 lines per neighbourhood by count and measured
+// level with these: docs/history/r07_measured.md.)
+constexpr int kBlurTileWLog = 5, kBlurTileHLog = 2;
+constexpr int kBlurTileW = 1 << kBlurTileWLog, kBlurTileH = 1 << kBlurTileHLog;
+static_assert(kBlurTileW * kBlurTileH == 128 && kBlurTileW >= 16 && kBlurTileH >= 4, "one line per tile; k_gauss7 stores 16-byte row pieces of 4-row blocks");
+__host__ __device__ inline uint32_t blur_rows(int h) { return (uint32_t)(h + kBlurTileH - 1) & ~(uint32_t)(kBlurTileH - 1); }
+__host__ __device__ inline uint32_t blur_offset(int x, int y, int pitch) {  // byte of pixel (x, y) inside its level
+  return (uint32_t)(y >> kBlurTileHLog) * (uint32_t)(kBlurTileH * pitch) + ((uint32_t)(x >> kBlurTileWLog) << 7) +
+         ((uint32_t)(y & (kBlurTileH - 1)) << kBlurTileWLog) + (uint32_t)(x & (kBlurTileW - 1));
+}
 
 struct QNode {  // quad-tree node, 16 bytes
   uint16_t x0, x1, y0, y1;
@@ -770,6 +790,16 @@ struct BlurTiles { int tile_off[kMaxLevels + 1]; int tiles_x[kMaxLevels]; };
 struct GaussTile { uint16_t x0, y0, w, h, pitch; uint8_t l, pad; uint32_t img_off; };  // one output tile, prepared by the host
 static_assert(sizeof(GaussTile) == 16, "one s_load_dwordx4 per tile");
 
+// The value of the lane whose number differs in bit 0 (kBit = 1) or bit 1 (kBit = 2): a DPP move inside the group of four lanes
+template <int kBit>
+__device__ __forceinline__ uint32_t quad_xchg(uint32_t v) {
+#ifdef RGBL_EMU
+  return (uint32_t)__shfl_xor((int)v, kBit);
+#else
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kBit == 1 ? 0xB1 : 0x4E, 0xF, 0xF, false);   // quad_perm [1,0,3,2] / [2,3,0,1]
+#endif
+}
+
 template <int BS>
 __global__ __launch_bounds__(BS) void k_gauss7(const GaussTile* __restrict__ tiles,
                                                     const uint8_t* __restrict__ img0, int pitch0, size_t frame0,
@@ -850,8 +880,8 @@ __global__ __launch_bounds__(BS) void k_gauss7(const GaussTile* __restrict__ til
   __syncthreads();
   for (int item = tid; item < 256; item += BS) {  // 32 column groups x 8 row groups
   const int cg = item & 31, rg = item >> 5;
-  const int x = x0 + 4 * cg;
-  if (x >= W) continue;
+  // (no work-item leaves early: the four lanes of a group exchange their words below.  Column groups right of the level
+  // compute on whatever the LDS holds there and store nothing.)
   uint32_t pv[5][4];  // row pairs 2 rg .. 2 rg + 4 = the tile rows 4 rg .. 4 rg + 9
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
@@ -860,14 +890,12 @@ __global__ __launch_bounds__(BS) void k_gauss7(const GaussTile* __restrict__ til
   }
   const uint32_t kE0 = 18u | (34u << 16), kE1 = 48u | (56u << 16), kE2 = 48u | (34u << 16), kE3 = 18u;
   const uint32_t kO0 = 18u << 16, kO1 = 34u | (48u << 16), kO2 = 56u | (48u << 16), kO3 = 34u | (18u << 16);
-  // the row pitch is a multiple of 64 and x a multiple of 4: a full word always fits the row (what lands in the padding right
-  // of the last column is never read), so no byte-wise tail; acc < 2^24 and its byte 2 is the pixel: one v_perm_b32 per pixel
-  uint8_t* D = blur + (size_t)f * blur_frame + T.img_off + (__umul24((uint32_t)(y0 + 4 * rg), (uint32_t)T.pitch) + (uint32_t)x);
+  // acc < 2^24 and its byte 2 is the pixel: one v_perm_b32 per pixel
+  uint32_t out[4];   // [o]: the four pixels of row 4 rg + o
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
-    if (y0 + 4 * rg + o >= H) break;
     const int b = o >> 1;  // first row pair of the window
-    uint32_t out = 0;
+    out[o] = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       uint32_t acc = 32768u;
@@ -878,10 +906,30 @@ __global__ __launch_bounds__(BS) void k_gauss7(const GaussTile* __restrict__ til
         acc = udot2(pv[b][i], kO0, acc); acc = udot2(pv[b + 1][i], kO1, acc);
         acc = udot2(pv[b + 2][i], kO2, acc); acc = udot2(pv[b + 3][i], kO3, acc);
       }
-      out = i == 0 ? acc >> 16 : perm_bytes(acc, out, i == 1 ? 0x0c0c0600u : i == 2 ? 0x0c060100u : 0x06020100u);
+      out[o] = i == 0 ? acc >> 16 : perm_bytes(acc, out[o], i == 1 ? 0x0c0c0600u : i == 2 ? 0x0c060100u : 0x06020100u);
     }
-    *reinterpret_cast<uint32_t*>(D + __umul24((uint32_t)o, (uint32_t)T.pitch)) = out;
   }
+  // Tiled layout (blur_offset): the 4 x 4 blocks of four neighbouring lanes are 16 columns of the four rows of ONE tile.
+  // The lanes transpose their 4 x 4 words (two exchange steps) so that lane q of the group holds the 16 bytes of row q and
+  // stores them with one 128-bit store: the eight lanes of a tile write its whole 128-byte line with ONE instruction.
+  // (Every lane storing its own four words puts 32 bytes into each of 8 lines per instruction, four times: k_gauss7, which
+  // is paced by its memory requests, went from 1.02 to 1.10 ms per 1024 KITTI frames.)
+  const int q = cg & 3;
+#pragma unroll
+  for (int o = 0; o < 4; o += 2) {
+    const uint32_t got = quad_xchg<1>((q & 1) ? out[o] : out[o + 1]);
+    if (q & 1) out[o] = got; else out[o + 1] = got;
+  }
+#pragma unroll
+  for (int o = 0; o < 2; ++o) {
+    const uint32_t got = quad_xchg<2>((q & 2) ? out[o] : out[o + 2]);
+    if (q & 2) out[o] = got; else out[o + 2] = got;
+  }
+  // the row pitch is a multiple of 64: the 16 bytes always fit the row (what lands in the padding right of the last column is
+  // never looked at)
+  const int x = x0 + 16 * (cg >> 2), y = y0 + 4 * rg + q;
+  if (x < W && y < H)
+    *reinterpret_cast<uint4*>(blur + (size_t)f * blur_frame + T.img_off + blur_offset(x, y, T.pitch)) = make_uint4(out[0], out[1], out[2], out[3]);
   }
 }
 
@@ -1747,7 +1795,8 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
 // grid = (ceil(kp_frame / (4 * kKpPerWave)), B), block = 256 (128: 144.4 k, 512: 143.5 k against 146.5 k frames/s).
 // 8 since the end of round 6 (4 before: 10 registers of patch words per keypoint in flight; 2 / 4 / 6 / 8 / 12 / 16 on the KITTI step, twice each
 // on one box: 142.1 / 144.9 / 146.3 / 146.3 / 144.2 / 141.6 k frames/s, the kernel 1.38 / 1.26 / 1.25 / 1.23 / 1.21 / 1.35 ms; single frames
-// unchanged: 0.308 -> 0.309 ms through the drop-in classes).
+// unchanged: 0.308 -> 0.309 ms through the drop-in classes).  With the tiled blurred levels (4 + 8 registers of patch words per keypoint, 127
+// VGPRs = 4 waves per SIMD as before) 8 stays ahead of 6: the kernel 1.05 against 1.11 ms.
 constexpr int kKpPerWave = 8;
 
 __device__ __forceinline__ int bcast_i(int v, int k) {  // value of lane k, wave-uniform (k is a constant after unrolling)
@@ -1762,6 +1811,20 @@ __device__ __forceinline__ float bcast_f(float v, int k) { return __int_as_float
 // (Round 5: more resident waves do not help here - amdgpu_waves_per_eu(6) gives 71 VGPRs / 7 waves per SIMD instead of 82 / 5 and
 // the kernel takes 0.65 instead of 0.63 ms per 512 frames, (8) spills: 0.81 ms.  What paces it is the number of cache lines its
 // patch gathers touch - ~90 per keypoint, one L1 tag look-up each - not the latency those waves could hide.)
+// Hence the tiled blurred levels (blur_offset): ~61 lines per keypoint, the kernel 1.23 -> 1.05 ms per 1024 KITTI frames while its
+// vector instructions grew by a quarter (the tile arithmetic of the piece addresses).  The blurred patches by LDS-DMA straight
+// into LDS (16-byte pieces, 64-byte patch rows, no patch registers: 57 VGPRs) lost: the patches of all of a wave's keypoints must
+// then sit in LDS at once, 2 / 3 / 4 / 5 keypoints per wave ran 1.22 / 1.29 / 1.27 / 1.38 ms (docs/history/r07_measured.md).
+// -DRGBL_ORIENT_STAMPS (never in the shipped library): every wave that has keypoints adds the device-clock ticks of its phases
+// to dbg[0..5] and 1 to dbg[7] (tools/orient_stamps.py): 0 slot search + pattern + patch requests issued, 1 wait for the first
+// raw patch + its moments, 2 the other moments, 3 barriers + angle / sin / cos, 4 pass 2, 5 keypoint record.
+#ifdef RGBL_ORIENT_STAMPS
+#define RGBL_OB_DBG_PARAM , unsigned long long* __restrict__ dbg
+#define RGBL_OB_STAMP(k) const unsigned long long ob_t##k = rgbl_clock()
+#else
+#define RGBL_OB_DBG_PARAM
+#define RGBL_OB_STAMP(k) do { } while (0)
+#endif
 template <int BS>
 __global__ __launch_bounds__(BS) void k_orient_brief(const LevelGeom* __restrict__ geom, int n_levels, UMax umax,
                                                       const int8_t* __restrict__ pattern,
@@ -1773,11 +1836,15 @@ __global__ __launch_bounds__(BS) void k_orient_brief(const LevelGeom* __restrict
                                                       rgbl_keypoint* __restrict__ out_kp,
                                                       uint8_t* __restrict__ out_desc, int cap,
                                                       int32_t* __restrict__ out_n, int32_t* __restrict__ out_mono,
-                                                      int* __restrict__ err, int slot_begin, int slot_end, int write_total) {
+                                                      int* __restrict__ err, int slot_begin, int slot_end, int write_total RGBL_OB_DBG_PARAM) {
+  RGBL_OB_STAMP(0);
   // The launch covers the keypoint slots slot_begin .. slot_end - 1 (slots are laid out level after level): level 0's
   // keypoints can be described while the quad-trees of the upper levels still run; write_total: this launch sees the final
   // counts of ALL levels and writes the frame's keypoint count.
-  __shared__ unsigned long long s_patch_q[BS / 64][37 * 5];  // blurred 37x37 neighbourhood, 40-byte rows
+  // blurred 37x37 neighbourhood, row-major, kPatchPitch bytes per row: the six aligned 8-byte pieces that cover the 40
+  // bytes x - 18 .. x + 21 from wherever the row starts inside its first piece
+  constexpr int kPatchPieces = 6, kPatchPitch = 8 * kPatchPieces, kPatchLoads = (37 * kPatchPieces + 63) / 64;
+  __shared__ unsigned long long s_patch_q[BS / 64][37 * kPatchPieces];
   const int lane = lane_id(), wave = wave_id();
   const int bx = xcd_item(), f = xcd_frame();  // grid = xcd_grid(keypoint groups, B): an XCD's L2 keeps its frames' levels
   const int* cnts = kp_count + (size_t)f * n_levels;
@@ -1813,13 +1880,14 @@ __global__ __launch_bounds__(BS) void k_orient_brief(const LevelGeom* __restrict
   }
 
   // ---- all patch words of all keypoints are requested first (one exposed memory latency per wave instead of one per
-  //      keypoint and pass): 4 + 6 registers per keypoint.  Keypoints sit >= 19 px inside the level, so x-15..x+16 and
-  //      x-18..x+21 stay inside the row pitch.
+  //      keypoint and pass): 4 + 8 registers per keypoint.  Keypoints sit >= 19 px inside the level, so x-15..x+16 stays
+  //      inside the row pitch; the blurred pieces reach up to column x + 29 <= w + 9, which can be past the pitch: such a
+  //      piece lands in the first tile of the next strip (or in the slack behind the buffer) and is never looked at.
   // Wide loads: a patch row of 32 bytes is two lanes x 16 bytes (one global_load_dwordx4 per keypoint instead of four dword
-  // loads), a blurred row of 40 bytes five lanes x 8 bytes (three dwordx2 loads instead of six dword loads) - the kernel is
-  // bound by the number of vector-memory instructions its patches take, not by their bytes.
+  // loads), a blurred row six lanes x 8 aligned bytes (four dwordx2 loads).  The blurred level is tiled (blur_offset):
+  // the pieces of four consecutive rows share their 128-byte lines, ~22 lines per keypoint instead of ~49.
   uint32_t rawreg[kKpPerWave][4];
-  unsigned long long blreg[kKpPerWave][3];
+  unsigned long long blreg[kKpPerWave][kPatchLoads];
 #pragma unroll
   for (int k = 0; k < kKpPerWave; ++k) {
     if (!((vmask >> k) & 1)) continue;  // wave-uniform
@@ -1838,17 +1906,19 @@ __global__ __launch_bounds__(BS) void k_orient_brief(const LevelGeom* __restrict
     if (!((vmask >> k) & 1)) continue;
     const int lk = bcast_i(l, k), x = bcast_i(kx, k), y = bcast_i(ky, k);
     const LevelGeom& g = geom[lk];
-    const uint8_t* bl = blur + (size_t)f * blur_frame + g.img_off + (size_t)(y - 18) * g.pitch + (x - 18);
+    const uint8_t* bl = blur + (size_t)f * blur_frame + g.img_off;
+    const int xa = (x - 18) & ~7, pitch = g.pitch;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < kPatchLoads; ++j) {
       const int i = lane + 64 * j;
-      const int r = i / 5, c = i - r * 5;
+      const int r = i / kPatchPieces, c = i - r * kPatchPieces;
       unsigned long long v = 0ull;
-      if (i < 37 * 5) __builtin_memcpy(&v, bl + (__umul24((uint32_t)r, (uint32_t)g.pitch) + (uint32_t)(8 * c)), 8);
+      if (i < 37 * kPatchPieces) __builtin_memcpy(&v, bl + blur_offset(xa + 8 * c, y - 18 + r, pitch), 8);
       blreg[k][j] = v;
     }
   }
 
+  RGBL_OB_STAMP(1);
   // what depends on the lane only: its row v and half, the bytes of its 16 that lie inside the circle (|u| <= umax[|v|];
   // u = 16 does not exist), the weights u + 15 resp. u of the bytes
   uint32_t ic_mask[4] = {0u, 0u, 0u, 0u}, ic_coef[4];
@@ -1883,7 +1953,11 @@ __global__ __launch_bounds__(BS) void k_orient_brief(const LevelGeom* __restrict
     m10 = wave_sum_uniform(m10);
     m01 = wave_sum_uniform(m01);
     if (lane == k) { my_m10 = m10; my_m01 = m01; }
+#ifdef RGBL_ORIENT_STAMPS
+    if (k == __builtin_ctzll(vmask | (1ull << 63)) && lane == 0) atomicAdd(&dbg[1], rgbl_clock() - ob_t1);
+#endif
   }
+  RGBL_OB_STAMP(2);
 
   // ---- once per keypoint: orientation and the steering coefficients (fastAtan2, glibc's sinf / cosf in double precision:
   //      ~150 vector instructions that only need one lane per keypoint).  The first wave does it for the keypoints of ALL the
@@ -1901,6 +1975,7 @@ __global__ __launch_bounds__(BS) void k_orient_brief(const LevelGeom* __restrict
   __syncthreads();
   const int mine = wave * kKpPerWave + (lane < kKpPerWave ? lane : 0);
   const float angle = s_angle[mine], ca = s_cos[mine], sb = s_sin[mine];
+  RGBL_OB_STAMP(3);
 
   // ---- pass 2, keypoint after keypoint: steered BRIEF-256 on the blurred level through a 37x37 LDS patch
   const uint8_t* patch = reinterpret_cast<const uint8_t*>(s_patch_q[wave]);
@@ -1909,27 +1984,28 @@ __global__ __launch_bounds__(BS) void k_orient_brief(const LevelGeom* __restrict
     if (!((vmask >> k) & 1)) continue;  // wave-uniform
     const int dk = bcast_i(dense, k);
     const float a = bcast_f(ca, k), b = bcast_f(sb, k);
+    const int centre = 18 * kPatchPitch + 18 + ((bcast_i(kx, k) - 18) & 7);  // the keypoint's byte in the patch
     wave_sync();
 #pragma unroll
-    for (int j = 0; j < 3; ++j)
-      if (lane + 64 * j < 37 * 5) s_patch_q[wave][lane + 64 * j] = blreg[k][j];
+    for (int j = 0; j < kPatchLoads; ++j)
+      if (lane + 64 * j < 37 * kPatchPieces) s_patch_q[wave][lane + 64 * j] = blreg[k][j];
     wave_sync();
     // Two points of a pair side by side in packed fp32 (v_pk_mul_f32 / v_pk_add_f32: two IEEE operations per instruction,
     // no contraction): x a - y b and x b + y a as in computeOrbDescriptor (ORBextractor.cc:118-119).  cvRound = adding
     // 1.5 * 2^23 (round-half-even lands in the mantissa; |coordinate| < 2^22); the two biased integers go straight into
     // one 24-bit multiply-add, the biases leave with one constant.
     const f32x2 av = {a, a}, bv = {b, b}, magic = {12582912.0f, 12582912.0f};
-    constexpr int kBias = 0x400000 * 40 + 0x4B400000;  // (low 24 bits of the biased row) * 40 + the biased column
+    constexpr int kBias = 0x400000 * kPatchPitch + 0x4B400000;  // (low 24 bits of the biased row) * pitch + the biased column
     unsigned long long bits[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const f32x2 rx = px[q] * av - py[q] * bv;
       const f32x2 ry = px[q] * bv + py[q] * av;
       const f32x2 cx = rx + magic, cy = ry + magic;
-      const int i0 = __mul24(__float_as_int(cy[0]), 40) + __float_as_int(cx[0]) - kBias;
-      const int i1 = __mul24(__float_as_int(cy[1]), 40) + __float_as_int(cx[1]) - kBias;
-      const int t0 = patch[18 * 40 + 18 + i0];
-      const int t1 = patch[18 * 40 + 18 + i1];
+      const int i0 = __mul24(__float_as_int(cy[0]), kPatchPitch) + __float_as_int(cx[0]) - kBias;
+      const int i1 = __mul24(__float_as_int(cy[1]), kPatchPitch) + __float_as_int(cx[1]) - kBias;
+      const int t0 = patch[centre + i0];
+      const int t1 = patch[centre + i1];
       bits[q] = __ballot(t0 < t1);
     }
     if (lane < 4) {
@@ -1937,6 +2013,7 @@ __global__ __launch_bounds__(BS) void k_orient_brief(const LevelGeom* __restrict
       d[lane] = bits[lane];
     }
   }
+  RGBL_OB_STAMP(4);
   if (valid) {
     const LevelGeom& g = geom[l];
     rgbl_keypoint kp;
@@ -1949,7 +2026,14 @@ __global__ __launch_bounds__(BS) void k_orient_brief(const LevelGeom* __restrict
     kp.class_id = -1;
     out_kp[(size_t)f * cap + dense] = kp;
   }
+#ifdef RGBL_ORIENT_STAMPS
+  if (vmask && lane == 0) {   // (dbg[1] is a part of dbg[2]'s interval: the read-out subtracts it)
+    atomicAdd(&dbg[0], ob_t1 - ob_t0); atomicAdd(&dbg[2], ob_t2 - ob_t1); atomicAdd(&dbg[3], ob_t3 - ob_t2);
+    atomicAdd(&dbg[4], ob_t4 - ob_t3); atomicAdd(&dbg[5], rgbl_clock() - ob_t4); atomicAdd(&dbg[7], 1ull);
+  }
+#endif
 }
+#undef RGBL_OB_STAMP
 
 // vLappingArea packing (ORBextractor.cc:1153-1162): keypoints with lap0 <= x <= lap1 fill the arrays from
 // the back (in reverse order), all others from the front.  One workgroup per frame.
