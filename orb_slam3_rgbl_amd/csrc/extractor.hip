@@ -46,55 +46,73 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 
 using namespace rgbl;
 
-struct rgbl_extractor {
-  rgbl_extractor_cfg cfg;
-  int device = 0;
-  int L = 0;
-  hipStream_t stream = nullptr, own_stream = nullptr;
-  hipStream_t aux_stream = nullptr;  // the Gaussian working images only depend on the pyramid: they overlap FAST + quad-tree
-  hipStream_t lvl_stream = nullptr;  // single frames: FAST + quad-tree of the levels 1 - 2 start behind their own resizes (RGBL_LEVEL_SPLIT=0: off)
-  int level_split = 3;               // ... the main stream keeps the levels from this one on
-  hipEvent_t ev_pyr = nullptr, ev_blur = nullptr, ev_start = nullptr, ev_fast0 = nullptr, ev_desc0 = nullptr, ev_r = nullptr, ev_fb = nullptr;
-  int split_pyr = 0;  // batches: the pyramid levels k .. L - 1 and their FAST cells leave the main chain (default L / 2 from 6 levels on; RGBL_SPLIT_PYR=k, 0 = off)
+// ---- launch plan: WHAT runs WHERE and AFTER WHAT, as data (build_plan writes it down, enqueue_extract executes it) ----
+enum StreamId : uint8_t { kMain = 0, kAux, kLvl, kNumStreams };   // the handle's stream (or the caller's), auxiliary, level
+enum StepKind : uint8_t { kResize = 0, kFast, kGauss, kOctree, kDesc, kPermute, kRecord, kWait };
+// Launch steps cover the pyramid levels [begin, end): kResize builds them one after the other, kFast is their detection cells
+// (with k_compact_cells behind them where that is on), kGauss their blurred images, kOctree their quad-trees, kDesc the
+// descriptors of their keypoint slots (flag: this launch also writes the frame totals); kPermute is the lapping-area pass.
+// kRecord marks the point the stream has reached, kWait makes the stream wait for a mark: separate steps, a mark is often
+// recorded several launches before it is waited for.
+struct Step { uint8_t kind, stream, mark, flag; int32_t begin, end; };
+constexpr int kMaxMarks = 6;   // the most a schedule uses
+
+// ---- tuning switches (include/rgbl_frontend.h lists them): read_switches reads every one ONCE, when the handle is created
+struct Switches {
+  bool graph = true;            // RGBL_GRAPH=0: no hipGraph replay on the host-pointer path
   bool gauss_wg256 = false;     // RGBL_GAUSS_BS=256: four-wave workgroups for k_gauss7 (two waves measured faster)
   bool octree_stamps = false;   // RGBL_OCTREE_STAMPS: the quad-tree kernel leaves phase time stamps (tools/octree_stamps.py)
   bool octree_no_hist = false;  // RGBL_OCTREE_HIST=0: breadth-first rounds as passes over the keys instead of on the count pyramid
-  KernelTimer timer;
-  // hipGraph of the host-pointer path (all device pointers of that path are the handle's own buffers, so one captured
-  // launch sequence can be replayed): key = (batch, row stride, lapping area, stream)
-#ifndef RGBL_EMU
-  hipGraphExec_t graph_exec = nullptr;
-#endif
-  int graph_batch = 0, graph_stride = 0, graph_lap0 = 0, graph_lap1 = 0;
-  hipStream_t graph_stream = nullptr;
-  bool graph_ok = true;  // RGBL_GRAPH=0 or a failed capture switch the replay off
-  int octree_wg = 0;  // 0 = choose per launch; RGBL_OCTREE_WG=256|512 pins the quad-tree workgroup width (tuning / tests)
-  bool octree_ldskeys = true;  // single frames: k_octree keeps the candidate lists in LDS (RGBL_OCTREE_LDSKEYS=0 switches it off)
+  bool octree_ldskeys = true;   // RGBL_OCTREE_LDSKEYS=0: single frames do not keep k_octree's candidate lists in LDS
+  int level_split = 3;          // RGBL_LEVEL_SPLIT=k: single frames, FAST + quad-tree of the levels 1 .. k - 1 on the level stream (0 = off)
+  int octree_wg = 0;            // RGBL_OCTREE_WG=256|512 pins the quad-tree workgroup width (tuning / tests); 0 = chosen per launch
+  int compact_min_batch = 8;    // batches of at least this many frames: FAST cells write their own slots, k_compact_cells
+                                // builds the dense lists (RGBL_COMPACT=0: never, =1: always)
+  bool xcd_map = true;          // RGBL_XCD_MAP=0: no XCD-aware workgroup -> (item, frame) mapping of the pixel kernels (common.h: xcd_grid)
+  int fast_waves = 0;           // RGBL_FAST_BS=64 / 128: 1 / 2 waves per detection cell of k_fast_cells; 0 = by batch size
+  int split_pyr_raw = -1;       // RGBL_SPLIT_PYR=k; -1 = not set
+  int octree_ncap_raw = -1;     // RGBL_OCTREE_NCAP=0 | 2048; -1 = not set
+  bool dense_raw = true;        // RGBL_DENSE=0: candidates stay in their cells' slots
+  // resolved from the raw values once the geometry is known (resolve_switches)
+  int split_pyr = 0;    // batches: the pyramid levels k .. L - 1 and their FAST cells leave the main chain (default L / 2 from 6 levels on; 0 = off)
   int octree_ncap = 0;  // LDS node capacity of the label-based quad-tree kernel (512 / 2048); 0 = key-moving kernel on global lists
-  int max_cell = 0, max_cell_w = 0;  // largest detection-cell side / width over the levels: select the k_fast_cells instantiation
-  int fast_waves = 0;  // waves per detection cell of k_fast_cells: 0 = by batch size, RGBL_FAST_BS=64 / 128 force 1 / 2
-  bool xcd_map = true;  // XCD-aware workgroup -> (item, frame) mapping of the pixel kernels (common.h: xcd_item_frame); RGBL_XCD_MAP=0 switches it off
+  bool dense = false;   // k_fast_cells writes a level's candidates as one list (label-based quad-tree kernel, separate pixel kernels)
+};
+
+struct rgbl_extractor {
+  rgbl_extractor_cfg cfg;
+  int device = 0;
+  Switches sw;
+  // ---- streams and timing
+  hipStream_t stream = nullptr;   // the main stream of a call: own[kMain] or the caller's (rgbl_extractor_set_stream)
+  // own[kAux]: the Gaussian working images only depend on the pyramid, they overlap FAST + quad-tree; own[kLvl]: single
+  // frames, FAST + quad-tree of the levels 1 - 2 start behind their own resizes
+  hipStream_t own[kNumStreams] = {};
+  hipEvent_t marks[kMaxMarks] = {};   // Step::mark -> event
+  KernelTimer timer;
+  // ---- geometry
+  int L = 0;
   std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
   std::vector<int> per_level;
   UMax umax;
   std::vector<LevelGeom> geom;
   BlurTiles blur_tiles;
+  int max_cell = 0, max_cell_w = 0;  // largest detection-cell side / width over the levels: select the k_fast_cells instantiation
   int cells_frame = 0, kp_frame = 0;
   size_t pyr_frame = 0, slots_frame = 0, keys_frame = 0, nodes_frame = 0, img_frame = 0;
   int img_pitch = 0;
-  // device memory
+  std::vector<int> group_off;        // [L + 1] first cell group of every level
+  // ---- tables (device)
   LevelGeom* d_geom = nullptr;
-  FastCell* d_cells = nullptr;  // one record per detection cell of a frame (k_fast_cells)
-  CellGroup* d_groups = nullptr;          // groups of up to 256 consecutive cells of one level (k_compact_cells)
-  std::vector<int> group_off;             // [L + 1] first group of every level
-  int compact_min_batch = 8;              // batches of at least this many frames: FAST cells write their own slots, k_compact_cells
-                                          // builds the dense lists (RGBL_COMPACT=0: never, =1: always)
-  GaussTile* d_gtiles = nullptr;  // one record per Gaussian output tile of a frame (k_gauss7)
+  FastCell* d_cells = nullptr;       // one record per detection cell of a frame (k_fast_cells)
+  CellGroup* d_groups = nullptr;     // groups of up to 256 consecutive cells of one level (k_compact_cells)
+  GaussTile* d_gtiles = nullptr;     // one record per Gaussian output tile of a frame (k_gauss7)
   ResizeTab *d_xtab = nullptr, *d_ytab = nullptr;
   ResizeGroup* d_xgroups = nullptr;  // k_resize_linear: one record per 4 output columns (index xtab_off / 4 + group)
   int32_t* d_xsxa = nullptr;         // first source byte of the group's 8-byte window, -1 = byte path
   uint8_t* d_rootx = nullptr;
   int8_t* d_pattern = nullptr;
+  // ---- device buffers
   uint8_t *d_img = nullptr, *d_pyr = nullptr, *d_blur = nullptr;
   uint32_t *d_cellcnt = nullptr, *d_slots = nullptr, *d_keys_a = nullptr, *d_keys_b = nullptr;
   QNode *d_list_a = nullptr, *d_list_b = nullptr;
@@ -104,34 +122,44 @@ struct rgbl_extractor {
   uint8_t* d_divided = nullptr;
   uint32_t* d_kpkey = nullptr;
   int* d_kpcount = nullptr;
-  uint8_t* h_pinned = nullptr;      // page-locked result block of the host-pointer path: counts, flags, keypoints, descriptors of small batches
+  uint32_t* d_levelcnt = nullptr;    // [B][L] candidates per level, counted by k_fast_cells' cells (dense candidate lists)
+  unsigned long long* d_dbg = nullptr;
+  rgbl_keypoint* d_tmp_kp = nullptr;   // the lapping permutation's source (and rgbl_undistort_points' staging)
+  uint8_t* d_tmp_desc = nullptr;
+  std::vector<void*> allocs;
+  // ---- host-path staging
+  uint8_t* d_stage = nullptr;        // the result block (stage_layout): error flags | counts | monoIndex | keypoints | descriptors
+  int* d_err = nullptr;              // ... and pointers to its parts
+  int32_t *d_out_n = nullptr, *d_out_mono = nullptr;
+  rgbl_keypoint* d_out_kp = nullptr;
+  uint8_t* d_out_desc = nullptr;
+  int out_cap = 0;
+  uint8_t* h_pinned = nullptr;       // page-locked result block of small batches, same layout
   size_t h_pinned_bytes = 0;
-  uint32_t* d_levelcnt = nullptr;  // [B][L] candidates per level, counted by k_fast_cells' cells (dense candidate lists)
-  bool dense = false;              // k_fast_cells writes a level's candidates as one list (label-based quad-tree kernel, separate pixel kernels)
-  bool dense_dirty = false;        // an enqueue failed between the FAST and the quad-tree launches: the counters may hold leftovers
-  int* d_err = nullptr;            // (the first word of d_stage)
-  uint8_t* d_stage = nullptr;      // error flags | d_out_n | d_out_mono | d_out_kp | d_out_desc, the layout of h_pinned
-  int32_t* d_stereo_sad = nullptr;  // ComputeStereoMatches scratch (grow-only)
+  void* d_color = nullptr;           // staging of one host colour frame (rgbl_extract_color), allocated on first use
+  size_t color_bytes = 0;
+  int32_t* d_stereo_sad = nullptr;   // ComputeStereoMatches scratch (grow-only)
   size_t stereo_sad_count = 0;
   void* d_stereo_stage = nullptr;
-  void* d_color = nullptr;  // staging of one host colour frame (rgbl_extract_color), allocated on first use
-  size_t color_bytes = 0;
   size_t stereo_stage_bytes = 0;
   uint8_t* h_stereo_stage = nullptr;   // page-locked mirror of d_stereo_stage (rgbl_stereo_matches: one request per direction)
-  unsigned long long* d_dbg = nullptr;
-  // staging for the host entry points and for the lapping permutation
-  rgbl_keypoint *d_out_kp = nullptr, *d_tmp_kp = nullptr;
-  uint8_t *d_out_desc = nullptr, *d_tmp_desc = nullptr;
-  int32_t *d_out_n = nullptr, *d_out_mono = nullptr;
-  int out_cap = 0;
+  // hipGraph of the host-pointer path (all device pointers of that path are the handle's own buffers, so one captured
+  // launch sequence can be replayed): key = (batch, row stride, lapping area, stream)
+#ifndef RGBL_EMU
+  hipGraphExec_t graph_exec = nullptr;
+#endif
+  int graph_batch = 0, graph_stride = 0, graph_lap0 = 0, graph_lap1 = 0;
+  hipStream_t graph_stream = nullptr;
+  bool graph_ok = true;  // RGBL_GRAPH=0 or a failed capture switch the replay off
+  // ---- last-call state
+  bool dense_dirty = false;          // an enqueue failed between the FAST and the quad-tree launches: the counters may hold leftovers
   // rgbl_extract_begin: an extraction of one frame whose results are on their way into the page-locked block
   struct { bool active = false; const uint8_t* img = nullptr; int w = 0, h = 0, stride = 0, lap0 = 0, lap1 = 0; } pending;
-  // last call (for get_level / get_candidates)
+  // for get_level / get_candidates
   const uint8_t* last_img0 = nullptr;
   int last_pitch0 = 0;
   size_t last_frame0 = 0;
   int last_batch = 0;
-  std::vector<void*> allocs;
 };
 
 namespace {
@@ -161,6 +189,23 @@ void build_resize_tab(int ssize, int dsize, bool clamp_x, std::vector<ResizeTab>
     t.a1 = (int16_t)round_even_f(f * 2048);
     tab.push_back(t);
   }
+}
+
+// Every RGBL_* variable the extractor honours (depth.hip and matcher.hip read their own); called once per handle.
+void read_switches(Switches* w) {
+  if (const char* v = getenv("RGBL_GRAPH")) w->graph = atoi(v) != 0;
+  if (const char* v = getenv("RGBL_GAUSS_BS")) w->gauss_wg256 = atoi(v) == 256;
+  if (getenv("RGBL_OCTREE_STAMPS")) w->octree_stamps = true;
+  if (const char* v = getenv("RGBL_OCTREE_HIST")) w->octree_no_hist = v[0] == '0';
+  if (const char* v = getenv("RGBL_OCTREE_LDSKEYS")) w->octree_ldskeys = atoi(v) != 0;
+  if (const char* v = getenv("RGBL_LEVEL_SPLIT")) w->level_split = atoi(v);
+  if (const char* v = getenv("RGBL_OCTREE_WG")) { const int wg = atoi(v); if (wg == kOctNarrow || wg == kOctWide) w->octree_wg = wg; }
+  if (const char* v = getenv("RGBL_COMPACT")) w->compact_min_batch = atoi(v) ? 1 : 0x7fffffff;
+  if (const char* v = getenv("RGBL_XCD_MAP")) w->xcd_map = v[0] != '0';
+  if (const char* v = getenv("RGBL_FAST_BS")) w->fast_waves = atoi(v) == 64 ? 1 : atoi(v) == 128 ? 2 : 0;
+  if (const char* v = getenv("RGBL_SPLIT_PYR")) w->split_pyr_raw = std::max(atoi(v), 0);   // anything below 2 means off
+  if (const char* v = getenv("RGBL_OCTREE_NCAP")) w->octree_ncap_raw = atoi(v);
+  if (const char* v = getenv("RGBL_DENSE")) w->dense_raw = v[0] != '0';
 }
 
 int build_geometry(rgbl_extractor* e) {
@@ -282,6 +327,23 @@ int build_geometry(rgbl_extractor* e) {
   return RGBL_OK;
 }
 
+// the switches whose value depends on the geometry
+void resolve_switches(rgbl_extractor* e) {
+  Switches& w = e->sw;
+  // 8 levels: the levels 4 - 7 (a fifth of the pixels) leave the main chain (round 5: the default)
+  w.split_pyr = w.split_pyr_raw >= 0 ? w.split_pyr_raw : (e->L >= 6 ? e->L / 2 : 0);
+  // quad-tree kernel: the smallest LDS node capacity that holds every level's list (RGBL_OCTREE_NCAP=0 forces the
+  // key-moving kernel on global lists, 2048 the large instantiation - tests)
+  uint32_t node_cap = 0, key_cap = 0;
+  for (int l = 0; l < e->L; ++l) { node_cap = std::max(node_cap, e->geom[l].node_cap); key_cap = std::max(key_cap, e->geom[l].key_cap); }
+  w.octree_ncap = node_cap <= 512 ? 512 : (node_cap <= 2048 ? 2048 : 0);
+  if (key_cap >= (1u << 24)) w.octree_ncap = 0;  // candidate indices travel in 24 bits of its best-key word
+  const int want = w.octree_ncap_raw;
+  if (want == 0 || (want == 2048 && node_cap <= 2048 && w.octree_ncap != 0)) w.octree_ncap = want;
+  // dense candidate lists need the label-based quad-tree kernel (order-free) and the per-cell FAST kernel (RGBL_DENSE=0: cell slots)
+  w.dense = w.octree_ncap != 0 && w.dense_raw;
+}
+
 int upload_tables(rgbl_extractor* e) {
   const int L = e->L;
   std::vector<ResizeTab> xt, yt;
@@ -364,7 +426,6 @@ int upload_tables(rgbl_extractor* e) {
     e->group_off[L] = (int)groups.size();
     RGBL_TRY(dev_alloc(e, &e->d_groups, groups.size()));
     RGBL_HIP(hipMemcpy(e->d_groups, groups.data(), sizeof(CellGroup) * groups.size(), hipMemcpyHostToDevice));
-    if (const char* v = getenv("RGBL_COMPACT")) e->compact_min_batch = atoi(v) ? 1 : 0x7fffffff;
   }
   RGBL_TRY(dev_alloc(e, &e->d_geom, L));
   RGBL_TRY(dev_alloc(e, &e->d_xtab, xt.size() + 8));
@@ -402,16 +463,25 @@ int upload_tables(rgbl_extractor* e) {
   if (!yt.empty()) RGBL_HIP(hipMemcpy(e->d_ytab, yt.data(), sizeof(ResizeTab) * yt.size(), hipMemcpyHostToDevice));
   RGBL_HIP(hipMemcpy(e->d_rootx, rootx.data(), rootx.size(), hipMemcpyHostToDevice));
   RGBL_HIP(hipMemcpy(e->d_pattern, kBriefPattern, 1024, hipMemcpyHostToDevice));
-  if (const char* v = getenv("RGBL_XCD_MAP")) e->xcd_map = v[0] != '0';
-  e->split_pyr = L >= 6 ? L / 2 : 0;   // 8 levels: the levels 4 - 7 (a fifth of the pixels) leave the main chain (round 5: the default)
-  if (const char* v = getenv("RGBL_SPLIT_PYR")) e->split_pyr = atoi(v);
-  if (const char* v = getenv("RGBL_FAST_BS")) e->fast_waves = atoi(v) == 64 ? 1 : atoi(v) == 128 ? 2 : 0;
   return RGBL_OK;
 }
 
-// layout of the host-pointer path's result block (device and page-locked): head | keypoints | descriptors, every part 256-byte aligned
-static inline size_t stage_head(const rgbl_extractor* e) { return (256 + 2 * sizeof(int32_t) * (size_t)e->cfg.max_batch + 255) / 256 * 256; }
-static inline size_t stage_kp_bytes(const rgbl_extractor* e, int batch) { return ((size_t)batch * e->out_cap * sizeof(rgbl_keypoint) + 255) / 256 * 256; }
+// The host-pointer path's results live in ONE device block laid out like the page-locked block they are copied into:
+//   error flags (256 B) | counts [max_batch] | monoIndex [max_batch] | keypoints [batch x out_cap] | descriptors [batch x out_cap x 32]
+// so that a call that fills the whole handle (one frame per call above all) brings everything back with ONE copy - round 4
+// queued five (flag, counts, monoIndex, keypoints, descriptors: three copy kernels and two DMA transfers of ~5 us each at
+// the very end of a frame's critical path).  Head and keypoint ranges are rounded up to 256 bytes, so that the descriptors -
+// written with 16-byte and 8-byte stores by k_lapping_permute / k_orient_brief - start 256-byte aligned.
+struct StageLayout { size_t counts, mono, kp, desc, bytes; };   // byte offsets of the parts (the flags are at 0) and the block's size
+StageLayout stage_layout(const rgbl_extractor* e, int batch) {
+  StageLayout s;
+  s.counts = 256;
+  s.mono = s.counts + sizeof(int32_t) * (size_t)e->cfg.max_batch;
+  s.kp = align_up(s.mono + sizeof(int32_t) * (size_t)e->cfg.max_batch, 256);
+  s.desc = s.kp + align_up((size_t)batch * e->out_cap * sizeof(rgbl_keypoint), 256);
+  s.bytes = s.desc + (size_t)batch * e->out_cap * 32;
+  return s;
+}
 
 int alloc_scratch(rgbl_extractor* e) {
   const size_t B = (size_t)e->cfg.max_batch;
@@ -422,7 +492,7 @@ int alloc_scratch(rgbl_extractor* e) {
   RGBL_TRY(dev_alloc(e, &e->d_slots, B * e->slots_frame));
   RGBL_TRY(dev_alloc(e, &e->d_keys_a, B * e->keys_frame));
   RGBL_TRY(dev_alloc(e, &e->d_keys_b, B * e->keys_frame));
-  if (e->octree_ncap == 0) {  // global node lists of the key-moving quad-tree kernel
+  if (e->sw.octree_ncap == 0) {  // global node lists of the key-moving quad-tree kernel
     RGBL_TRY(dev_alloc(e, &e->d_list_a, B * e->nodes_frame));
     RGBL_TRY(dev_alloc(e, &e->d_list_b, B * e->nodes_frame));
     RGBL_TRY(dev_alloc(e, &e->d_div, B * e->nodes_frame));
@@ -439,31 +509,159 @@ int alloc_scratch(rgbl_extractor* e) {
   RGBL_TRY(dev_alloc(e, &e->d_dbg, B * (size_t)e->L * 16));
   RGBL_HIP(hipMemset(e->d_dbg, 0, B * (size_t)e->L * 16 * sizeof(unsigned long long)));
   e->out_cap = e->kp_frame;
-  // The host-pointer path's results live in ONE device block laid out like the page-locked block they are copied into:
-  //   error flags (256 B) | counts [B] | monoIndex [B] | keypoints [B x out_cap] | descriptors [B x out_cap x 32]
-  // so that a call that fills the whole handle (one frame per call above all) brings everything back with ONE copy - round 4
-  // queued five (flag, counts, monoIndex, keypoints, descriptors: three copy kernels and two DMA transfers of ~5 us each at
-  // the very end of a frame's critical path).
-  {
-    // head and keypoint ranges are rounded up to 256 bytes (in this block and in the page-locked one alike), so that the
-    // descriptors - written with 16-byte and 8-byte stores by k_lapping_permute / k_orient_brief - start 256-byte aligned
-    const size_t head = stage_head(e), kp_bytes = stage_kp_bytes(e, (int)B);
-    uint8_t* blk = nullptr;
-    RGBL_TRY(dev_alloc(e, &blk, head + kp_bytes + B * (size_t)e->out_cap * 32));
-    e->d_stage = blk;
-    e->d_err = reinterpret_cast<int*>(blk);
-    e->d_out_n = reinterpret_cast<int32_t*>(blk + 256);
-    e->d_out_mono = e->d_out_n + B;
-    e->d_out_kp = reinterpret_cast<rgbl_keypoint*>(blk + head);
-    e->d_out_desc = blk + head + kp_bytes;
-    RGBL_HIP(hipMemset(blk, 0, head));
-  }
+  const StageLayout lay = stage_layout(e, (int)B);
+  RGBL_TRY(dev_alloc(e, &e->d_stage, lay.bytes));
+  e->d_err = reinterpret_cast<int*>(e->d_stage);
+  e->d_out_n = reinterpret_cast<int32_t*>(e->d_stage + lay.counts);
+  e->d_out_mono = reinterpret_cast<int32_t*>(e->d_stage + lay.mono);
+  e->d_out_kp = reinterpret_cast<rgbl_keypoint*>(e->d_stage + lay.kp);
+  e->d_out_desc = e->d_stage + lay.desc;
+  RGBL_HIP(hipMemset(e->d_stage, 0, lay.kp));
   RGBL_TRY(dev_alloc(e, &e->d_tmp_kp, B * (size_t)e->out_cap));
   RGBL_TRY(dev_alloc(e, &e->d_tmp_desc, B * (size_t)e->out_cap * 32));
   // results of up to 4 frames per call come back through one page-locked block (run_staged)
-  e->h_pinned_bytes = stage_head(e) + stage_kp_bytes(e, (int)std::min<size_t>(B, 4)) + std::min<size_t>(B, 4) * (size_t)e->out_cap * 32;
+  e->h_pinned_bytes = stage_layout(e, (int)std::min<size_t>(B, 4)).bytes;
   if (hipHostMalloc(reinterpret_cast<void**>(&e->h_pinned), e->h_pinned_bytes, hipHostMallocDefault) != hipSuccess) { e->h_pinned = nullptr; e->h_pinned_bytes = 0; (void)hipGetLastError(); }
   return RGBL_OK;
+}
+
+// ---- the schedules ---------------------------------------------------------------------------------------------------
+// Written down by hand, one builder per schedule; enqueue_extract issues the steps in exactly this order (a captured graph
+// dispatches in capture order, the orders below are measured ones).  tests/test_extract_plan.py checks that every schedule
+// orders what the kernels' reads and writes need ordered.
+struct Plan {
+  std::vector<Step> steps;
+  int marks = 0;
+  void launch(StepKind k, StreamId st, int begin, int end, int flag = 0) {
+    if (end > begin) steps.push_back(Step{(uint8_t)k, (uint8_t)st, 0, (uint8_t)flag, begin, end});
+  }
+  void resize(StreamId st, int b, int e) { launch(kResize, st, b, e); }
+  void fast(StreamId st, int b, int e) { launch(kFast, st, b, e); }
+  void gauss(StreamId st, int b, int e) { launch(kGauss, st, b, e); }
+  void octree(StreamId st, int b, int e) { launch(kOctree, st, b, e); }
+  int record(StreamId st) { steps.push_back(Step{kRecord, (uint8_t)st, (uint8_t)marks, 0, 0, 0}); return marks++; }   // returns the new mark
+  void wait(StreamId st, int mark) { steps.push_back(Step{kWait, (uint8_t)st, (uint8_t)mark, 0, 0, 0}); }
+};
+
+// While per-kernel timing is on, everything stays on one stream so that the event brackets are not contended:
+// 1. pyramid: level l from level l - 1 (ORBextractor.cc:1170-1195), 4. Gaussian working images (ORBextractor.cc:1132-1133),
+// 2. FAST per detection cell (ORBextractor.cc:806-872), 3. quad-tree distribution (ORBextractor.cc:555-779)
+void plan_serial(Plan& p, int L) {
+  p.resize(kMain, 1, L);
+  p.gauss(kMain, 0, L);
+  p.fast(kMain, 0, L);
+  p.octree(kMain, 0, L);
+}
+
+// Level 0 of the pyramid is the input image itself: its FAST cells (a third of all pixels) and its Gaussian do not wait for
+// the resize chain - seven short dependent launches that leave most of the chip idle - but run next to it on the auxiliary
+// stream; so do the Gaussian working images of the upper levels (they only depend on the pyramid) next to FAST and quad-tree.
+void plan_overlap(Plan& p, int L) {
+  const int start = p.record(kMain);
+  p.wait(kAux, start);
+  p.fast(kAux, 0, 1);
+  // level 0's Gaussian in front of its quad-tree launch: the quad-tree workgroups (37 KB of LDS each) only get placed as the
+  // FAST cells of the upper levels drain anyway, the Gaussian fills the time until then (125.7 -> 126.8 k frames/s; the
+  // quad-tree launch on the main stream in front of the upper levels' FAST cells instead: 122.3 k)
+  p.gauss(kAux, 0, 1);
+  p.octree(kAux, 0, 1);
+  const int level0 = p.record(kAux);
+  p.resize(kMain, 1, L);
+  const int pyr = p.record(kMain);
+  p.wait(kAux, pyr);
+  p.gauss(kAux, 1, L);
+  const int blur = p.record(kAux);
+  p.fast(kMain, 1, L);
+  p.octree(kMain, 1, L);   // level 0 went with its FAST cells above
+  p.wait(kMain, level0);
+  p.wait(kMain, blur);     // orientation + descriptors need the blurred levels
+}
+
+// Batches (RGBL_SPLIT_PYR=k; default k = L / 2): the small levels k .. L - 1 - their resizes are the tail of a chain of
+// dependent launches, their FAST cells a fifth of the pixels - are produced on the auxiliary stream behind level 0's FAST
+// cells, so that the main stream's FAST launch (levels 1 .. k - 1) starts after k - 1 resizes instead of L - 1.
+// Round 3: k = 4 144.7 k, k = 3 144.3 k, k = 5 143.0 k against 142.9 - 143.3 k frames/s, left off.  Round 5, three A/B
+// calls on the KITTI step: k = 4 +1.8 ... +2.7 % (145.4 / 146.3 / 144.4 k against 142.8 / 142.9 / 140.6 k), k = 3 and 5
+// nothing; the small levels' quad-trees on the auxiliary stream as well: -2 %.  The default since.
+void plan_batch_split(Plan& p, int L, int k) {
+  const int start = p.record(kMain);
+  p.wait(kAux, start);
+  p.fast(kAux, 0, 1);
+  p.resize(kMain, 1, k);
+  const int first_resizes = p.record(kMain);
+  p.wait(kAux, first_resizes);
+  p.resize(kAux, k, L);
+  p.fast(kAux, k, L);
+  const int small_fast = p.record(kAux);
+  p.gauss(kAux, 0, 1);
+  p.octree(kAux, 0, 1);
+  const int level0 = p.record(kAux);
+  p.gauss(kAux, 1, L);
+  const int blur = p.record(kAux);
+  p.fast(kMain, 1, k);
+  p.wait(kMain, small_fast);
+  p.octree(kMain, 1, L);
+  p.wait(kMain, level0);
+  p.wait(kMain, blur);
+}
+
+// A single frame is a race of dependent chains, and the longest one sets its latency.  Until round 4: main stream =
+// 7 resizes -> FAST of ALL upper levels -> their quad-trees (the level-1 problem: 53 us) -> descriptors.  Level 1 exists
+// after ONE resize: the levels 1 .. k - 1 (RGBL_LEVEL_SPLIT=k, default 3) take a third stream - FAST and quad-tree behind
+// their own resizes - while the main stream finishes the pyramid and handles the small levels k .. L - 1; level 0 stays on
+// the auxiliary stream.  Critical path 29 + 14 + 55 us -> max(level 0: 14 + quad-tree, levels 1 - 2: 8 + 12 + quad-tree, rest: 29 + 8 + 32).
+void plan_level_split(Plan& p, int L, int k) {
+  // The captured graph dispatches its nodes in the order of capture, a few us apiece: level 0 first (it needs nothing but the
+  // image), the Gaussian of the upper levels - read by the descriptors only - LAST, behind FAST and quad-tree of the small
+  // levels (captured in front of them it delayed that branch, the last to finish: 0.332 -> 0.315 ms per frame on one box,
+  // no change on a faster one; capturing the longest branch first cost 60 us: 0.31 -> 0.38 ms).
+  const int start = p.record(kMain);
+  p.wait(kAux, start);
+  p.fast(kAux, 0, 1);
+  p.gauss(kAux, 0, 1);
+  p.octree(kAux, 0, 1);
+  const int level0 = p.record(kAux);
+  p.resize(kMain, 1, k);
+  const int first_resizes = p.record(kMain);
+  p.wait(kLvl, first_resizes);
+  p.fast(kLvl, 1, k);
+  p.octree(kLvl, 1, k);
+  const int first_levels = p.record(kLvl);
+  p.resize(kMain, k, L);
+  const int pyr = p.record(kMain);
+  p.fast(kMain, k, L);
+  p.octree(kMain, k, L);
+  p.wait(kAux, pyr);
+  p.gauss(kAux, 1, L);
+  const int blur = p.record(kAux);
+  p.wait(kMain, first_levels);
+  p.wait(kMain, level0);
+  p.wait(kMain, blur);
+}
+
+// The plan of one extraction of `batch` frames: `serial` = per-kernel timing is on, `lapping` = the call has a lapping area.
+Plan build_plan(const rgbl_extractor* e, int batch, bool serial, bool lapping) {
+  const int L = e->L;
+  Plan p;
+  p.steps.reserve(32);
+  if (serial) plan_serial(p, L);
+  else if (batch >= 8 && e->sw.split_pyr >= 2 && e->sw.split_pyr < L) plan_batch_split(p, L, e->sw.split_pyr);
+  else if (batch < 8 && e->sw.level_split >= 2 && e->sw.level_split < L) plan_level_split(p, L, e->sw.level_split);
+  else plan_overlap(p, L);
+  // 5. orientation + descriptors + packing (ORBextractor.cc:894-895, 1136-1165).  Batches: level 0's keypoints (its quad-tree
+  // and its Gaussian are done long before the upper levels' quad-trees; the auxiliary stream has them and every level's
+  // Gaussian behind it at this point) are described on the auxiliary stream next to those quad-trees; the main stream takes
+  // the other levels and the frame totals.
+  if (!serial && batch >= 8 && L > 1) {
+    p.launch(kDesc, kAux, 0, 1);
+    const int desc0 = p.record(kAux);
+    p.launch(kDesc, kMain, 1, L, 1);
+    p.wait(kMain, desc0);
+  } else {
+    p.launch(kDesc, kMain, 0, L, 1);
+  }
+  if (lapping) p.launch(kPermute, kMain, 0, L);
+  return p;
 }
 
 // Enqueues the whole extraction of `batch` frames on e->stream. All pointers are device pointers.
@@ -473,8 +671,8 @@ int enqueue_extract(rgbl_extractor* e, const uint8_t* d_imgs, int batch, int str
   const int L = e->L;
   hipStream_t s = e->stream;
   e->last_img0 = d_imgs; e->last_pitch0 = stride; e->last_frame0 = frame_stride; e->last_batch = batch;
-  if (e->dense && e->dense_dirty) RGBL_HIP(hipMemsetAsync(e->d_levelcnt, 0, sizeof(uint32_t) * (size_t)e->cfg.max_batch * L, s));
-  e->dense_dirty = e->dense;  // cleared at the end of a complete enqueue: the quad-tree workgroups leave the counters at zero
+  if (e->sw.dense && e->dense_dirty) RGBL_HIP(hipMemsetAsync(e->d_levelcnt, 0, sizeof(uint32_t) * (size_t)e->cfg.max_batch * L, s));
+  e->dense_dirty = e->sw.dense;  // cleared at the end of a complete enqueue: the quad-tree workgroups leave the counters at zero
 
   // cells of at most kCellSmall px (every level of the usual image sizes) take the small-LDS instantiation: two waves per
   // cell (a cell is a chain of short phases; 16 workgroups of two waves per CU overlap better than 8 of four), tile pitch 48
@@ -484,24 +682,24 @@ int enqueue_extract(rgbl_extractor* e, const uint8_t* d_imgs, int batch, int str
   // Batches: ONE wave per cell - no second wave's fixed work (6.0e8 instead of 6.7e8 vector instructions per 512-frame step),
   // the kernel's own time is the same (fewer waves to hide the LDS round trips) but what runs beside it gains; a single
   // frame is latency-bound and keeps two waves per cell (half the trips per wave).  RGBL_FAST_BS=64 / 128 overrides.
-  const bool one_wave = e->fast_waves ? e->fast_waves == 1 : batch >= 8;
+  const bool one_wave = e->sw.fast_waves ? e->sw.fast_waves == 1 : batch >= 8;
   if (one_wave && e->max_cell <= kCellSmall && e->max_cell_w <= 41) { fast = k_fast_cells<kCellSmall, 64, 48>; fast_bs = 64; }
   // Batches: the cells write their own slots (no reservation on the level's counter: on a 4K frame all resident cells of a
   // XCD hammered ONE address) and k_compact_cells builds the dense lists behind them, one atomic per 256 cells.  A single
   // frame keeps the reservation inside the FAST kernel: no contention to speak of, and one launch less on its critical path.
-  const bool compact = e->dense && batch >= e->compact_min_batch;
+  const bool compact = e->sw.dense && batch >= e->sw.compact_min_batch;
   auto level_at = [&](int cell) { for (int l = 0; l < L; ++l) if ((int)e->geom[l].cell_off == cell) return l; return L; };
   auto launch_fast = [&](hipStream_t st, int cell_begin, int cell_end) {
     if (cell_end <= cell_begin) return;
     e->timer.begin("k_fast_cells", st);
-    hipLaunchKernelGGL(fast, xcd_grid(e->xcd_map, cell_end - cell_begin, batch), dim3(fast_bs), 0, st, e->d_cells, d_imgs, stride, frame_stride,
+    hipLaunchKernelGGL(fast, xcd_grid(e->sw.xcd_map, cell_end - cell_begin, batch), dim3(fast_bs), 0, st, e->d_cells, d_imgs, stride, frame_stride,
                        e->d_pyr, e->pyr_frame, e->cfg.ini_th_fast, e->cfg.min_th_fast, e->d_cellcnt, (size_t)e->cells_frame,
-                       e->d_slots, e->slots_frame, cell_begin, e->d_geom, L, e->d_keys_a, e->keys_frame, (e->dense && !compact) ? e->d_levelcnt : nullptr);
+                       e->d_slots, e->slots_frame, cell_begin, e->d_geom, L, e->d_keys_a, e->keys_frame, (e->sw.dense && !compact) ? e->d_levelcnt : nullptr);
     e->timer.end(st);
     if (compact) {
       const int g0 = e->group_off[level_at(cell_begin)], g1 = e->group_off[level_at(cell_end)];   // the ranges are whole levels
       e->timer.begin("k_compact_cells", st);
-      hipLaunchKernelGGL(k_compact_cells, xcd_grid(e->xcd_map, g1 - g0, batch), dim3(256), 0, st, e->d_groups, e->d_cells, e->d_cellcnt,
+      hipLaunchKernelGGL(k_compact_cells, xcd_grid(e->sw.xcd_map, g1 - g0, batch), dim3(256), 0, st, e->d_groups, e->d_cells, e->d_cellcnt,
                          (size_t)e->cells_frame, e->d_slots, e->slots_frame, e->d_geom, L, e->d_keys_a, e->keys_frame, e->d_levelcnt, g0);
       e->timer.end(st);
     }
@@ -510,8 +708,8 @@ int enqueue_extract(rgbl_extractor* e, const uint8_t* d_imgs, int batch, int str
     if (tile_end <= tile_begin) return;
     e->timer.begin("k_gauss7", st);
     // two passes with a barrier in between: 16 workgroups of two waves per CU interleave better than 8 of four (0.63 -> 0.54 ms)
-    const bool g128 = !e->gauss_wg256;
-    hipLaunchKernelGGL(g128 ? k_gauss7<128> : k_gauss7<256>, xcd_grid(e->xcd_map, tile_end - tile_begin, batch), dim3(g128 ? 128 : 256), 0, st, e->d_gtiles,
+    const bool g128 = !e->sw.gauss_wg256;
+    hipLaunchKernelGGL(g128 ? k_gauss7<128> : k_gauss7<256>, xcd_grid(e->sw.xcd_map, tile_end - tile_begin, batch), dim3(g128 ? 128 : 256), 0, st, e->d_gtiles,
                        d_imgs, stride, frame_stride, e->d_pyr, e->pyr_frame, e->d_blur, e->pyr_frame, tile_begin);
     e->timer.end(st);
   };
@@ -525,167 +723,53 @@ int enqueue_extract(rgbl_extractor* e, const uint8_t* d_imgs, int batch, int str
   ob.divided = e->d_divided; ob.nodes_frame = e->nodes_frame;
   ob.rootx = e->d_rootx;
   ob.kp_key = e->d_kpkey; ob.kp_count = e->d_kpcount; ob.kp_frame = (size_t)e->kp_frame;
-  ob.level_cnt = e->dense ? e->d_levelcnt : nullptr;
+  ob.level_cnt = e->sw.dense ? e->d_levelcnt : nullptr;
   ob.level_cnt_last = e->d_levelcnt + (size_t)e->cfg.max_batch * L;
   ob.err = e->d_err;
-  ob.dbg = e->octree_stamps ? e->d_dbg : nullptr;
-  ob.no_hist = e->octree_no_hist ? 1 : 0;
+  ob.dbg = e->sw.octree_stamps ? e->d_dbg : nullptr;
+  ob.no_hist = e->sw.octree_no_hist ? 1 : 0;
   // narrow workgroups leave room for more (level, frame) problems per CU; small batches, which cannot fill the chip anyway,
   // take the wide group (shorter passes over the keys).  Node lists of up to 512 / 2048 entries live in LDS
   // (octree_labels.h); beyond that - more than ~9 000 features - the key-moving kernel on global lists takes over.
-  const bool narrow = e->octree_wg ? e->octree_wg == kOctNarrow : (long)L * batch >= 1024;
+  const bool narrow = e->sw.octree_wg ? e->sw.octree_wg == kOctNarrow : (long)L * batch >= 1024;
   auto launch_octree = [&](hipStream_t st, int level_begin, int level_end) {
     if (level_end <= level_begin) return;
     e->timer.begin("k_octree", st);
     const dim3 grid(level_end - level_begin, batch);
-    if (e->octree_ncap == 0) {
+    if (e->sw.octree_ncap == 0) {
       if (narrow) hipLaunchKernelGGL(k_octree_moving<kOctNarrow>, grid, dim3(kOctNarrow), 0, st, e->d_geom, L, ob, level_begin);
       else hipLaunchKernelGGL(k_octree_moving<kOctWide>, grid, dim3(kOctWide), 0, st, e->d_geom, L, ob, level_begin);
-    } else if (e->octree_ncap == 512) {
+    } else if (e->sw.octree_ncap == 512) {
       // a handful of problems (a single frame): candidate lists in LDS, 1024 work-items each (octree_labels.h: KEYCAP)
-      if (e->octree_ldskeys && !e->octree_wg && (long)(level_end - level_begin) * batch <= 64)
+      if (e->sw.octree_ldskeys && !e->sw.octree_wg && (long)(level_end - level_begin) * batch <= 64)
         hipLaunchKernelGGL((k_octree<1024, 512, kOctKeysLds>), grid, dim3(1024), 0, st, e->d_geom, L, ob, level_begin);
       else if (narrow) hipLaunchKernelGGL((k_octree<kOctNarrow, 512>), grid, dim3(kOctNarrow), 0, st, e->d_geom, L, ob, level_begin);
       else hipLaunchKernelGGL((k_octree<kOctWide, 512>), grid, dim3(kOctWide), 0, st, e->d_geom, L, ob, level_begin);
     } else {
       // 2048 nodes = 147 KB of LDS: ONE workgroup per CU whatever its width, so it takes all 16 wave slots of the CU - a 4K
       // level-0 problem is ~160 k candidates per pass (round 4: 512 -> 1024 work-items; RGBL_OCTREE_WG=256 / 512 still pin the others)
-      if (e->octree_wg == kOctNarrow) hipLaunchKernelGGL((k_octree<kOctNarrow, 2048>), grid, dim3(kOctNarrow), 0, st, e->d_geom, L, ob, level_begin);
-      else if (e->octree_wg == kOctWide) hipLaunchKernelGGL((k_octree<kOctWide, 2048>), grid, dim3(kOctWide), 0, st, e->d_geom, L, ob, level_begin);
+      if (e->sw.octree_wg == kOctNarrow) hipLaunchKernelGGL((k_octree<kOctNarrow, 2048>), grid, dim3(kOctNarrow), 0, st, e->d_geom, L, ob, level_begin);
+      else if (e->sw.octree_wg == kOctWide) hipLaunchKernelGGL((k_octree<kOctWide, 2048>), grid, dim3(kOctWide), 0, st, e->d_geom, L, ob, level_begin);
       else hipLaunchKernelGGL((k_octree<1024, 2048>), grid, dim3(1024), 0, st, e->d_geom, L, ob, level_begin);
     }
     e->timer.end(st);
   };
-  {
-    // Level 0 of the pyramid is the input image itself: its FAST cells (a third of all pixels) and its Gaussian do not
-    // wait for the resize chain - seven short dependent launches that leave most of the chip idle - but run next to it
-    // on the auxiliary stream.  (While per-kernel timing is on, everything stays on one stream so that the event
-    // brackets are not contended.)
-    const bool overlap = !e->timer.enabled;
-    hipStream_t bs = overlap ? e->aux_stream : s;
-    const int cells0 = L > 1 ? e->geom[1].cell_off : e->cells_frame, tiles0 = e->blur_tiles.tile_off[1];
-    // 1. pyramid: level l from level l-1 (ORBextractor.cc:1170-1195)
-    auto launch_resize = [&](hipStream_t st, int l) {
-      const LevelGeom& g = e->geom[l];
-      const LevelGeom& p = e->geom[l - 1];
-      const uint8_t* src = (l == 1) ? d_imgs : e->d_pyr + p.img_off;
-      const int spitch = (l == 1) ? stride : p.pitch;
-      const size_t sframe = (l == 1) ? frame_stride : e->pyr_frame;
-      e->timer.begin("k_resize_linear", st);
-      const int rtx = (g.w + 4 * kResizeLanes - 1) / (4 * kResizeLanes), rty = (g.h + 4 * kResizeRows - 1) / (4 * kResizeRows);
-      hipLaunchKernelGGL(k_resize_linear, xcd_grid(e->xcd_map, rtx * rty, batch), dim3(kResizeWG), 0, st, src, spitch, sframe, p.w, p.h, e->d_pyr + g.img_off, g.pitch, e->pyr_frame, g.w, g.h,
-                       e->d_xtab + g.xtab_off, e->d_xgroups + g.xtab_off / 4, e->d_xsxa + g.xtab_off / 4, e->d_ytab + g.ytab_off, rtx);
-      e->timer.end(st);
-    };
-    const int sp = (overlap && batch >= 8 && e->split_pyr >= 2 && e->split_pyr < L) ? e->split_pyr : 0;
-    if (sp) {
-      // Batches (RGBL_SPLIT_PYR=k; default k = L / 2): the small levels k .. L - 1 - their resizes are the tail of a chain of
-      // dependent launches, their FAST cells a fifth of the pixels - are produced on the auxiliary stream behind level 0's FAST
-      // cells, so that the main stream's FAST launch (levels 1 .. k - 1) starts after k - 1 resizes instead of L - 1.
-      // Round 3: k = 4 144.7 k, k = 3 144.3 k, k = 5 143.0 k against 142.9 - 143.3 k frames/s, left off.  Round 5, three A/B
-      // calls on the KITTI step: k = 4 +1.8 ... +2.7 % (145.4 / 146.3 / 144.4 k against 142.8 / 142.9 / 140.6 k), k = 3 and 5
-      // nothing; the small levels' quad-trees on the auxiliary stream as well: -2 %.  The default since.
-      RGBL_HIP(hipEventRecord(e->ev_start, s));
-      RGBL_HIP(hipStreamWaitEvent(bs, e->ev_start, 0));
-      launch_fast(bs, 0, cells0);
-      for (int l = 1; l < sp; ++l) launch_resize(s, l);
-      RGBL_HIP(hipEventRecord(e->ev_r, s));
-      RGBL_HIP(hipStreamWaitEvent(bs, e->ev_r, 0));
-      for (int l = sp; l < L; ++l) launch_resize(bs, l);
-      launch_fast(bs, e->geom[sp].cell_off, e->cells_frame);
-      RGBL_HIP(hipEventRecord(e->ev_fb, bs));
-      launch_gauss(bs, 0, tiles0);
-      launch_octree(bs, 0, 1);
-      RGBL_HIP(hipEventRecord(e->ev_fast0, bs));
-      launch_gauss(bs, tiles0, e->blur_tiles.tile_off[L]);
-      RGBL_HIP(hipEventRecord(e->ev_blur, bs));
-      launch_fast(s, cells0, e->geom[sp].cell_off);
-      RGBL_HIP(hipStreamWaitEvent(s, e->ev_fb, 0));
-      launch_octree(s, 1, L);
-      RGBL_HIP(hipStreamWaitEvent(s, e->ev_fast0, 0));
-      RGBL_HIP(hipStreamWaitEvent(s, e->ev_blur, 0));
-    } else if (overlap && batch < 8 && e->level_split >= 2 && e->level_split < L) {
-      // A single frame is a race of dependent chains, and the longest one sets its latency.  Until round 4: main stream =
-      // 7 resizes -> FAST of ALL upper levels -> their quad-trees (the level-1 problem: 53 us) -> descriptors.  Level 1 exists
-      // after ONE resize: the levels 1 .. k - 1 (k = 3) now take a third stream - FAST and quad-tree behind their own resizes -
-      // while the main stream finishes the pyramid and handles the small levels k .. L - 1; level 0 stays on the auxiliary
-      // stream.  Critical path 29 + 14 + 55 us -> max(level 0: 14 + quad-tree, levels 1 - 2: 8 + 12 + quad-tree, rest: 29 + 8 + 32).
-      const int k = e->level_split;
-      hipStream_t ls = e->lvl_stream;
-      // The captured graph dispatches its nodes in the order of capture, a few us apiece: level 0 first (it needs nothing but the
-      // image), the Gaussian of the upper levels - read by the descriptors only - LAST, behind FAST and quad-tree of the small
-      // levels (captured in front of them it delayed that branch, the last to finish: 0.332 -> 0.315 ms per frame on one box,
-      // no change on a faster one; capturing the longest branch first cost 60 us: 0.31 -> 0.38 ms).
-      RGBL_HIP(hipEventRecord(e->ev_start, s));
-      RGBL_HIP(hipStreamWaitEvent(bs, e->ev_start, 0));
-      launch_fast(bs, 0, cells0);
-      launch_gauss(bs, 0, tiles0);
-      launch_octree(bs, 0, 1);
-      RGBL_HIP(hipEventRecord(e->ev_fast0, bs));
-      for (int l = 1; l < k; ++l) launch_resize(s, l);
-      RGBL_HIP(hipEventRecord(e->ev_r, s));
-      RGBL_HIP(hipStreamWaitEvent(ls, e->ev_r, 0));
-      launch_fast(ls, cells0, e->geom[k].cell_off);
-      launch_octree(ls, 1, k);
-      RGBL_HIP(hipEventRecord(e->ev_fb, ls));
-      for (int l = k; l < L; ++l) launch_resize(s, l);
-      RGBL_HIP(hipEventRecord(e->ev_pyr, s));
-      launch_fast(s, e->geom[k].cell_off, e->cells_frame);
-      launch_octree(s, k, L);
-      RGBL_HIP(hipStreamWaitEvent(bs, e->ev_pyr, 0));
-      launch_gauss(bs, tiles0, e->blur_tiles.tile_off[L]);
-      RGBL_HIP(hipEventRecord(e->ev_blur, bs));
-      RGBL_HIP(hipStreamWaitEvent(s, e->ev_fb, 0));
-      RGBL_HIP(hipStreamWaitEvent(s, e->ev_fast0, 0));
-      RGBL_HIP(hipStreamWaitEvent(s, e->ev_blur, 0));
-    } else {
-    if (overlap) {
-      RGBL_HIP(hipEventRecord(e->ev_start, s));
-      RGBL_HIP(hipStreamWaitEvent(bs, e->ev_start, 0));
-      launch_fast(bs, 0, cells0);
-      // level 0's Gaussian in front of its quad-tree launch: the quad-tree workgroups (37 KB of LDS each) only get placed as the
-      // FAST cells of the upper levels drain anyway, the Gaussian fills the time until then (125.7 -> 126.8 k frames/s; the
-      // quad-tree launch on the main stream in front of the upper levels' FAST cells instead: 122.3 k)
-      launch_gauss(bs, 0, tiles0);
-      launch_octree(bs, 0, 1);
-      RGBL_HIP(hipEventRecord(e->ev_fast0, bs));
-    }
-    for (int l = 1; l < L; ++l) launch_resize(s, l);
-    // 4. Gaussian working images (ORBextractor.cc:1132-1133) of the upper levels, on the auxiliary stream next to 2. and 3.
-    if (overlap) {
-      RGBL_HIP(hipEventRecord(e->ev_pyr, s));
-      RGBL_HIP(hipStreamWaitEvent(bs, e->ev_pyr, 0));
-      launch_gauss(bs, tiles0, e->blur_tiles.tile_off[L]);
-      RGBL_HIP(hipEventRecord(e->ev_blur, bs));
-    } else {
-      launch_gauss(s, 0, e->blur_tiles.tile_off[L]);
-    }
-    // 2. FAST per detection cell (ORBextractor.cc:806-872)
-    if (overlap) {
-      launch_fast(s, cells0, e->cells_frame);
-    } else {
-      launch_fast(s, 0, e->cells_frame);
-    }
-    // 3. quad-tree distribution (ORBextractor.cc:555-779) of the remaining levels (level 0 went with its FAST cells above)
-    if (overlap) {
-      launch_octree(s, 1, L);
-      RGBL_HIP(hipStreamWaitEvent(s, e->ev_fast0, 0));
-    } else {
-      launch_octree(s, 0, L);
-    }
-    // 5. orientation + descriptors + packing (ORBextractor.cc:894-895, 1136-1165); needs the blurred levels
-    if (overlap) RGBL_HIP(hipStreamWaitEvent(s, e->ev_blur, 0));
-    }
-  }
+  // pyramid: level l from level l-1 (ORBextractor.cc:1170-1195)
+  auto launch_resize = [&](hipStream_t st, int l) {
+    const LevelGeom& g = e->geom[l];
+    const LevelGeom& p = e->geom[l - 1];
+    const uint8_t* src = (l == 1) ? d_imgs : e->d_pyr + p.img_off;
+    const int spitch = (l == 1) ? stride : p.pitch;
+    const size_t sframe = (l == 1) ? frame_stride : e->pyr_frame;
+    e->timer.begin("k_resize_linear", st);
+    const int rtx = (g.w + 4 * kResizeLanes - 1) / (4 * kResizeLanes), rty = (g.h + 4 * kResizeRows - 1) / (4 * kResizeRows);
+    hipLaunchKernelGGL(k_resize_linear, xcd_grid(e->sw.xcd_map, rtx * rty, batch), dim3(kResizeWG), 0, st, src, spitch, sframe, p.w, p.h, e->d_pyr + g.img_off, g.pitch, e->pyr_frame, g.w, g.h,
+                     e->d_xtab + g.xtab_off, e->d_xgroups + g.xtab_off / 4, e->d_xsxa + g.xtab_off / 4, e->d_ytab + g.ytab_off, rtx);
+    e->timer.end(st);
+  };
   const bool lapping = lap1 >= 19 && lap1 >= lap0;  // keypoint x is always >= 19: nothing can fall into [lap0, lap1] otherwise
   rgbl_keypoint* kp_dst = lapping ? e->d_tmp_kp : d_kp;
   uint8_t* desc_dst = lapping ? e->d_tmp_desc : d_desc;
-  int lap_cap = cap;
-  if (lapping) lap_cap = std::min(cap, e->out_cap);
-  // Batches: level 0's keypoints (its quad-tree and its Gaussian are done long before the upper levels' quad-trees) are
-  // described on the auxiliary stream next to those quad-trees; the main stream takes the other levels and the frame totals.
-  const bool split_desc = !e->timer.enabled && batch >= 8 && L > 1 && e->geom[1].koff > 0;
-  const int slot_split = split_desc ? e->geom[1].koff : 0;
 #ifdef RGBL_ORIENT_STAMPS   // phase clocks of k_orient_brief, summed over the waves into the debug block (extractor_kernels.h)
 #define RGBL_OB_DBG_ARG , e->d_dbg
 #else
@@ -695,30 +779,42 @@ int enqueue_extract(rgbl_extractor* e, const uint8_t* d_imgs, int batch, int str
     if (slot_end <= slot_begin) return;
     e->timer.begin("k_orient_brief", st);
     // one-wave or two-wave workgroups were measured behind four-wave ones here (0.72 - 0.73 vs 0.70 ms): the waves are independent anyway
-    hipLaunchKernelGGL(k_orient_brief<256>, xcd_grid(e->xcd_map, (slot_end - slot_begin + 4 * kKpPerWave - 1) / (4 * kKpPerWave), batch), dim3(256), 0, st, e->d_geom, L, e->umax,
+    hipLaunchKernelGGL(k_orient_brief<256>, xcd_grid(e->sw.xcd_map, (slot_end - slot_begin + 4 * kKpPerWave - 1) / (4 * kKpPerWave), batch), dim3(256), 0, st, e->d_geom, L, e->umax,
                        e->d_pattern, d_imgs, stride, frame_stride, e->d_pyr, e->pyr_frame, e->d_blur, e->pyr_frame,
                        e->d_kpkey, e->d_kpcount, (size_t)e->kp_frame, kp_dst, desc_dst, lapping ? e->out_cap : cap, d_n,
                        lapping ? (int32_t*)nullptr : d_mono, e->d_err, slot_begin, slot_end, write_total RGBL_OB_DBG_ARG);
     e->timer.end(st);
   };
-  if (split_desc) {
-    // (the auxiliary stream has level 0's quad-tree and every level's Gaussian behind it at this point)
-    launch_desc(e->aux_stream, 0, slot_split, 0);
-    RGBL_HIP(hipEventRecord(e->ev_desc0, e->aux_stream));
-  }
-  launch_desc(s, slot_split, e->kp_frame, 1);
-  if (split_desc) RGBL_HIP(hipStreamWaitEvent(s, e->ev_desc0, 0));
-  if (lapping) {
-    (void)lap_cap;
+  auto launch_permute = [&](hipStream_t st) {
     if (cap < e->out_cap) {
       set_error("vLappingArea packing needs cap >= %d", e->out_cap);
       return RGBL_ERR_CAPACITY;
     }
-    e->timer.begin("k_lapping_permute", s);
+    e->timer.begin("k_lapping_permute", st);
     // the temporary arrays use out_cap as their frame stride, the destination uses cap
-    hipLaunchKernelGGL(k_lapping_permute, dim3(batch), dim3(256), 0, s, e->d_tmp_kp, e->d_tmp_desc, e->out_cap, d_kp,
+    hipLaunchKernelGGL(k_lapping_permute, dim3(batch), dim3(256), 0, st, e->d_tmp_kp, e->d_tmp_desc, e->out_cap, d_kp,
                        d_desc, cap, d_n, (float)lap0, (float)lap1, d_mono);
-    e->timer.end(s);
+    e->timer.end(st);
+    return RGBL_OK;
+  };
+  // the plan's ranges are levels; the launchers take detection cells, Gaussian tiles and keypoint slots
+  auto cell_at = [&](int l) { return l < L ? (int)e->geom[l].cell_off : e->cells_frame; };
+  auto slot_at = [&](int l) { return l < L ? e->geom[l].koff : e->kp_frame; };
+  const hipStream_t streams[kNumStreams] = {s, e->own[kAux], e->own[kLvl]};
+  const Plan plan = build_plan(e, batch, e->timer.enabled, lapping);
+  if (plan.marks > kMaxMarks) { set_error("launch plan uses %d marks, the handle has %d events", plan.marks, kMaxMarks); return RGBL_ERR_INVALID; }
+  for (const Step& t : plan.steps) {
+    const hipStream_t st = streams[t.stream];
+    switch (t.kind) {
+      case kResize: for (int l = t.begin; l < t.end; ++l) launch_resize(st, l); break;
+      case kFast: launch_fast(st, cell_at(t.begin), cell_at(t.end)); break;
+      case kGauss: launch_gauss(st, e->blur_tiles.tile_off[t.begin], e->blur_tiles.tile_off[t.end]); break;
+      case kOctree: launch_octree(st, t.begin, t.end); break;
+      case kDesc: launch_desc(st, slot_at(t.begin), slot_at(t.end), t.flag); break;
+      case kRecord: RGBL_HIP(hipEventRecord(e->marks[t.mark], st)); break;
+      case kWait: RGBL_HIP(hipStreamWaitEvent(st, e->marks[t.mark], 0)); break;
+      case kPermute: RGBL_TRY(launch_permute(st)); break;
+    }
   }
   RGBL_HIP(hipGetLastError());
   e->dense_dirty = false;
@@ -772,45 +868,26 @@ int rgbl_extractor_create(const rgbl_extractor_cfg* cfg, int device, rgbl_extrac
   RGBL_HIP(hipSetDevice(device));
   rgbl_extractor* e = new rgbl_extractor;
   e->cfg = *cfg;
-  // Tuning switches are read here, once per handle (include/rgbl_frontend.h lists them) - never on a launch path.
-  if (const char* v = getenv("RGBL_GRAPH")) e->graph_ok = atoi(v) != 0;
-  if (const char* v = getenv("RGBL_GAUSS_BS")) e->gauss_wg256 = atoi(v) == 256;
-  if (getenv("RGBL_OCTREE_STAMPS")) e->octree_stamps = true;
-  if (const char* v = getenv("RGBL_OCTREE_HIST")) e->octree_no_hist = v[0] == '0';
-  if (const char* v = getenv("RGBL_OCTREE_LDSKEYS")) e->octree_ldskeys = atoi(v) != 0;
-  if (const char* v = getenv("RGBL_LEVEL_SPLIT")) e->level_split = atoi(v);
-  if (const char* v = getenv("RGBL_OCTREE_WG")) { const int wg = atoi(v); if (wg == kOctNarrow || wg == kOctWide) e->octree_wg = wg; }
   e->device = device;
+  read_switches(&e->sw);
+  e->graph_ok = e->sw.graph;
   int rc = build_geometry(e);
   if (rc == RGBL_OK) {
-    // quad-tree kernel: the smallest LDS node capacity that holds every level's list (RGBL_OCTREE_NCAP=0 forces the
-    // key-moving kernel on global lists, 2048 the large instantiation - tests)
-    uint32_t node_cap = 0, key_cap = 0;
-    for (int l = 0; l < e->L; ++l) { node_cap = std::max(node_cap, e->geom[l].node_cap); key_cap = std::max(key_cap, e->geom[l].key_cap); }
-    e->octree_ncap = node_cap <= 512 ? 512 : (node_cap <= 2048 ? 2048 : 0);
-    if (key_cap >= (1u << 24)) e->octree_ncap = 0;  // candidate indices travel in 24 bits of its best-key word
-    if (const char* v = getenv("RGBL_OCTREE_NCAP")) {
-      const int want = atoi(v);
-      if (want == 0 || (want == 2048 && node_cap <= 2048 && e->octree_ncap != 0)) e->octree_ncap = want;
+    resolve_switches(e);
+    rc = upload_tables(e);
+  }
+  if (rc == RGBL_OK) rc = alloc_scratch(e);
+  if (rc == RGBL_OK) {
+    bool ok = true;
+    for (hipStream_t& st : e->own) ok = ok && hipStreamCreate(&st) == hipSuccess;
+    for (hipEvent_t& ev : e->marks) ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+      set_error("hipStreamCreate failed");
+      rc = RGBL_ERR_HIP;
     }
   }
-  if (rc == RGBL_OK) rc = upload_tables(e);
-  // dense candidate lists need the label-based quad-tree kernel (order-free) and the per-cell FAST kernel (RGBL_DENSE=0: cell slots)
-  if (rc == RGBL_OK) e->dense = e->octree_ncap != 0 && !(getenv("RGBL_DENSE") && getenv("RGBL_DENSE")[0] == '0');
-  if (rc == RGBL_OK) rc = alloc_scratch(e);
-  if (rc == RGBL_OK && (hipStreamCreate(&e->own_stream) != hipSuccess || hipStreamCreate(&e->aux_stream) != hipSuccess || hipStreamCreate(&e->lvl_stream) != hipSuccess ||
-                        hipEventCreateWithFlags(&e->ev_pyr, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&e->ev_blur, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&e->ev_start, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&e->ev_fast0, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&e->ev_desc0, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&e->ev_r, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&e->ev_fb, hipEventDisableTiming) != hipSuccess)) {
-    set_error("hipStreamCreate failed");
-    rc = RGBL_ERR_HIP;
-  }
   if (rc != RGBL_OK) { rgbl_extractor_destroy(e); return rc; }
-  e->stream = e->own_stream;
+  e->stream = e->own[kMain];
   *out = e;
   return RGBL_OK;
 }
@@ -828,17 +905,12 @@ void rgbl_extractor_destroy(rgbl_extractor* e) {
 #ifndef RGBL_EMU
   if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
 #endif
-  if (e->aux_stream) { (void)hipStreamSynchronize(e->aux_stream); (void)hipStreamDestroy(e->aux_stream); }
-  if (e->lvl_stream) { (void)hipStreamSynchronize(e->lvl_stream); (void)hipStreamDestroy(e->lvl_stream); }
-  if (e->ev_pyr) (void)hipEventDestroy(e->ev_pyr);
-  if (e->ev_blur) (void)hipEventDestroy(e->ev_blur);
   if (e->h_pinned) (void)hipHostFree(e->h_pinned);
-  if (e->ev_start) (void)hipEventDestroy(e->ev_start);
-  if (e->ev_fast0) (void)hipEventDestroy(e->ev_fast0);
-  if (e->ev_desc0) (void)hipEventDestroy(e->ev_desc0);
-  if (e->ev_r) (void)hipEventDestroy(e->ev_r);
-  if (e->ev_fb) (void)hipEventDestroy(e->ev_fb);
-  if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
+  for (hipStream_t st : e->own) {
+    if (st && st != e->stream) (void)hipStreamSynchronize(st);   // (e->stream was drained above)
+    if (st) (void)hipStreamDestroy(st);
+  }
+  for (hipEvent_t ev : e->marks) if (ev) (void)hipEventDestroy(ev);
   delete e;
 }
 
@@ -921,95 +993,71 @@ static int enqueue_extract_staged(rgbl_extractor* e, int batch, int dev_stride, 
                          e->d_out_mono);
 }
 
-// the frames already sit in e->d_img (row stride dev_stride): extraction, then the results back to the host.
-// Small batches (one frame per call above all): counts, error flags, keypoints and descriptors travel into ONE page-locked
-// block behind the kernels and the call synchronises ONCE - three blocking round trips (counts, the error flag, the
-// arrays) and copies into pageable memory were a third of a single frame's extraction latency.
 // an extraction begun with rgbl_extract_begin that another entry point now overtakes: wait for it, forget it
 static int drop_pending(rgbl_extractor* e) {
   if (e->pending.active) { e->pending.active = false; RGBL_HIP(hipStreamSynchronize(e->stream)); }
   return RGBL_OK;
 }
 
+// Small batches (one frame per call above all): counts, error flags, keypoints and descriptors travel into ONE page-locked
+// block behind the kernels and the call synchronises ONCE - three blocking round trips (counts, the error flag, the
+// arrays) and copies into pageable memory were a third of a single frame's extraction latency.
 static bool staged_one_trip(const rgbl_extractor* e, int batch) {
-  const size_t kp_bytes = stage_kp_bytes(e, batch), desc_bytes = (size_t)batch * e->out_cap * 32;
-  const size_t head = stage_head(e);
-  return e->h_pinned && head + kp_bytes + desc_bytes <= e->h_pinned_bytes;
+  return e->h_pinned && stage_layout(e, batch).bytes <= e->h_pinned_bytes;
 }
 
-// first half: the kernels and - for small batches - the copies of counts, error flag, keypoints and descriptors into the
-// page-locked block, all queued, nothing waited for
+// first half: the kernels and - for small batches - the copy of the result block into the page-locked one, all queued,
+// nothing waited for
 static int staged_enqueue(rgbl_extractor* e, int batch, int dev_stride, int lap0, int lap1) {
   hipStream_t s = e->stream;
   RGBL_TRY(enqueue_extract_staged(e, batch, dev_stride, lap0, lap1));
   if (!staged_one_trip(e, batch)) return RGBL_OK;
-  const size_t kp_bytes = stage_kp_bytes(e, batch), desc_bytes = (size_t)batch * e->out_cap * 32;
-  const size_t head = stage_head(e);
-  int32_t* p_err = reinterpret_cast<int32_t*>(e->h_pinned);
-  int32_t* p_n = reinterpret_cast<int32_t*>(e->h_pinned + 256);
-  int32_t* p_mono = p_n + e->cfg.max_batch;
-  uint8_t* p_kp = e->h_pinned + head;
-  uint8_t* p_desc = p_kp + kp_bytes;
-  (void)p_err; (void)p_n; (void)p_mono;
   // device block and page-locked block share their layout up to the keypoints of `batch` frames; the descriptors follow the
   // keypoints of ALL max_batch frames on the device, of `batch` frames on the host: one copy when the call fills the handle
+  const StageLayout h = stage_layout(e, batch);
   if (batch == e->cfg.max_batch) {
-    RGBL_HIP(hipMemcpyAsync(e->h_pinned, e->d_stage, head + kp_bytes + desc_bytes, hipMemcpyDeviceToHost, s));
+    RGBL_HIP(hipMemcpyAsync(e->h_pinned, e->d_stage, h.bytes, hipMemcpyDeviceToHost, s));
   } else {
-    RGBL_HIP(hipMemcpyAsync(e->h_pinned, e->d_stage, head + kp_bytes, hipMemcpyDeviceToHost, s));
-    RGBL_HIP(hipMemcpyAsync(p_desc, e->d_out_desc, desc_bytes, hipMemcpyDeviceToHost, s));
+    RGBL_HIP(hipMemcpyAsync(e->h_pinned, e->d_stage, h.desc, hipMemcpyDeviceToHost, s));
+    RGBL_HIP(hipMemcpyAsync(e->h_pinned + h.desc, e->d_out_desc, h.bytes - h.desc, hipMemcpyDeviceToHost, s));
   }
-  (void)p_kp;
   return RGBL_OK;
 }
 
-// second half: wait, then the results from the page-locked block (or, for big batches, straight from the device) to the caller.
-// Small batches (one frame per call above all): counts, error flags, keypoints and descriptors travel into ONE page-locked
-// block behind the kernels and the call synchronises ONCE - three blocking round trips (counts, the error flag, the
-// arrays) and copies into pageable memory were a third of a single frame's extraction latency.
+// second half: wait, then the results to the caller - from the page-locked block, or, for big batches, straight from the
+// device block (counts first, then every frame's keypoints and descriptors with copies of their own)
 static int staged_finish(rgbl_extractor* e, int batch, int lap1, rgbl_keypoint* out_kp, uint8_t* out_desc, int cap, int* out_n,
                          int* out_mono) {
   hipStream_t s = e->stream;
-  if (staged_one_trip(e, batch)) {
-    const size_t kp_bytes = stage_kp_bytes(e, batch);
-    const size_t head = stage_head(e);
-    int32_t* p_err = reinterpret_cast<int32_t*>(e->h_pinned);
-    int32_t* p_n = reinterpret_cast<int32_t*>(e->h_pinned + 256);
-    int32_t* p_mono = p_n + e->cfg.max_batch;
-    uint8_t* p_kp = e->h_pinned + head;
-    uint8_t* p_desc = p_kp + kp_bytes;
-    RGBL_HIP(hipStreamSynchronize(s));
-    e->timer.collect();
-    if (*p_err) RGBL_TRY(check_device_flags(e));  // resets the flag and names the error
-    int rc = RGBL_OK;
-    for (int b = 0; b < batch; ++b) {
-      const int n = p_n[b];
-      out_n[b] = n; out_mono[b] = p_mono[b];
-      const int ncopy = std::min(n, cap);
-      if (n > cap) { set_error("frame %d has %d keypoints, capacity %d", b, n, cap); rc = RGBL_ERR_CAPACITY; }
-      if (n > cap && lap1 >= 19) continue;  // a truncated lapping layout would be meaningless
-      memcpy(out_kp + (size_t)b * cap, p_kp + (size_t)b * e->out_cap * sizeof(rgbl_keypoint), sizeof(rgbl_keypoint) * ncopy);
-      memcpy(out_desc + (size_t)b * cap * 32, p_desc + (size_t)b * e->out_cap * 32, (size_t)ncopy * 32);
-    }
-    return rc;
+  const bool pinned = staged_one_trip(e, batch);
+  const StageLayout lay = stage_layout(e, pinned ? batch : e->cfg.max_batch);
+  const uint8_t* blk = pinned ? e->h_pinned : e->d_stage;
+  auto fetch = [&](void* dst, size_t off, size_t bytes) -> int {
+    if (pinned) memcpy(dst, blk + off, bytes);
+    else RGBL_HIP(hipMemcpyAsync(dst, blk + off, bytes, hipMemcpyDeviceToHost, s));
+    return RGBL_OK;
+  };
+  if (!pinned) {
+    RGBL_TRY(fetch(out_n, lay.counts, sizeof(int32_t) * batch));
+    RGBL_TRY(fetch(out_mono, lay.mono, sizeof(int32_t) * batch));
   }
-  RGBL_HIP(hipMemcpyAsync(out_n, e->d_out_n, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, s));
-  RGBL_HIP(hipMemcpyAsync(out_mono, e->d_out_mono, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, s));
   RGBL_HIP(hipStreamSynchronize(s));
   e->timer.collect();
-  RGBL_TRY(check_device_flags(e));
+  if (!pinned || *reinterpret_cast<const int32_t*>(blk)) RGBL_TRY(check_device_flags(e));  // resets the flag and names the error
+  if (pinned) {
+    RGBL_TRY(fetch(out_n, lay.counts, sizeof(int32_t) * batch));
+    RGBL_TRY(fetch(out_mono, lay.mono, sizeof(int32_t) * batch));
+  }
   int rc = RGBL_OK;
   for (int b = 0; b < batch; ++b) {
     const int n = out_n[b];
     const int ncopy = std::min(n, cap);
     if (n > cap) { set_error("frame %d has %d keypoints, capacity %d", b, n, cap); rc = RGBL_ERR_CAPACITY; }
     if (n > cap && lap1 >= 19) continue;  // a truncated lapping layout would be meaningless
-    RGBL_HIP(hipMemcpyAsync(out_kp + (size_t)b * cap, e->d_out_kp + (size_t)b * e->out_cap, sizeof(rgbl_keypoint) * ncopy,
-                            hipMemcpyDeviceToHost, s));
-    RGBL_HIP(hipMemcpyAsync(out_desc + (size_t)b * cap * 32, e->d_out_desc + (size_t)b * e->out_cap * 32, (size_t)ncopy * 32,
-                            hipMemcpyDeviceToHost, s));
+    RGBL_TRY(fetch(out_kp + (size_t)b * cap, lay.kp + (size_t)b * e->out_cap * sizeof(rgbl_keypoint), sizeof(rgbl_keypoint) * ncopy));
+    RGBL_TRY(fetch(out_desc + (size_t)b * cap * 32, lay.desc + (size_t)b * e->out_cap * 32, (size_t)ncopy * 32));
   }
-  RGBL_HIP(hipStreamSynchronize(s));
+  if (!pinned) RGBL_HIP(hipStreamSynchronize(s));
   return rc;
 }
 
@@ -1321,7 +1369,7 @@ int rgbl_extractor_get_candidates(rgbl_extractor* e, int frame, int level, rgbl_
     }
   };
   int n = 0;
-  if (e->dense) {
+  if (e->sw.dense) {
     // the level's list in the order the cells finished: back into the reference's order (cell after cell, row-major inside)
     uint32_t C = 0;
     RGBL_HIP(hipMemcpy(&C, e->d_levelcnt + ((size_t)e->cfg.max_batch + frame) * e->L + level, sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1360,12 +1408,12 @@ int rgbl_extractor_debug_stamps(rgbl_extractor* e, unsigned long long* out, int 
 int rgbl_extractor_set_stream(rgbl_extractor* e, void* hip_stream) {
   if (!e) { set_error("null handle"); return RGBL_ERR_INVALID; }
   RGBL_HIP(hipStreamSynchronize(e->stream));
-  e->stream = hip_stream ? (hipStream_t)hip_stream : e->own_stream;
+  e->stream = hip_stream ? (hipStream_t)hip_stream : e->own[kMain];
   return RGBL_OK;
 }
 
 void* rgbl_extractor_stream(rgbl_extractor* e) { return e ? (void*)e->stream : nullptr; }
-void* rgbl_extractor_aux_stream(rgbl_extractor* e) { return e ? (void*)e->aux_stream : nullptr; }
+void* rgbl_extractor_aux_stream(rgbl_extractor* e) { return e ? (void*)e->own[kAux] : nullptr; }
 
 int rgbl_stream_wait(void* waiter, void* signaler) {
   // everything enqueued on `signaler` so far must finish before work enqueued on `waiter` after this call starts
@@ -1616,6 +1664,12 @@ int rgbl_selftest_wrappers(int device, int n, unsigned seed) {
 void rgbl_test_std_sort(uint64_t* key, uint32_t* val, int n) { rgbl::std_sort_restated(key, val, n); }
 void rgbl_test_block_sort(uint64_t* key, uint32_t* val, int n) {
   hipLaunchKernelGGL(rgbl::k_test_block_sort, dim3(1), dim3(rgbl::kOctWide), 0, (hipStream_t) nullptr, key, val, n);
+}
+// test hook (emulation build only): the steps (12 bytes each: Step) a call of `batch` frames would execute; returns their number
+int rgbl_test_extract_plan(const rgbl_extractor* e, int batch, int timer_on, int lapping, void* out, int cap) {
+  const Plan p = build_plan(e, batch, timer_on != 0, lapping != 0);
+  memcpy(out, p.steps.data(), sizeof(Step) * std::min<size_t>(p.steps.size(), (size_t)std::max(cap, 0)));
+  return p.marks <= kMaxMarks ? (int)p.steps.size() : -1;
 }
 #endif
 
