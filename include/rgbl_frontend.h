@@ -846,6 +846,82 @@ int rgbl_feeder_device_outputs(rgbl_feeder* f, int slot, rgbl_feeder_results* ou
 long long rgbl_feeder_pinned_bytes(const rgbl_feeder* f);
 
 /* ------------------------------------------------------------------------------------------------
+ * KeyFrameDatabase      the BoW place-recognition queries of src/KeyFrameDatabase.cc
+ *   add / erase / clear / clearMap (:39-98) and the part of the two Detect* functions the reference calls that depends on
+ *   nothing but BowVectors:
+ *     DetectRelocalizationCandidates (:733-790; caller Tracking::Relocalization, src/Tracking.cc:3651)
+ *     DetectNBestCandidates          (:604-669; caller LoopClosing::NewDetectCommonRegions, src/LoopClosing.cc:491)
+ *   i.e. lKFsSharingWords with mn*Words (:615-635, :741-756), maxCommonWords and minCommonWords = int(max * 0.8f) (:641-648,
+ *   :762-769), and mpVoc->score() = L1Scoring::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68) of the key frames with
+ *   more than minCommonWords common words (:655-666, :776-787).  The covisibility accumulation and the selection (:671-729,
+ *   :792-844) read GetBestCovisibilityKeyFrames / GetMap / isBad of the caller's objects and stay with the caller
+ *   (orb_slam3_rgbl_amd/shim/KeyFrameDatabase.h, frontend.KeyFrameDatabase).  DetectLoopCandidates, DetectCandidates and
+ *   DetectBestCandidates have no caller in the reference and are not provided.
+ * ----------------------------------------------------------------------------------------------
+ * The stored BowVectors live in an append-only device arena that doubles when it is full; erased key frames leave tombstones
+ * and the arena is compacted once more than half of its words are dead.  Neither changes any query result.  Every entry point
+ * takes the handle's own mutex (the reference's mMutex: add comes from loop closing, erase from KeyFrame::SetBadFlag, the
+ * queries from tracking) and works on the handle's own stream.
+ *
+ * Order: every add gets the next sequence number - the key frame's position in every inverted list it joins in the reference
+ * (list::push_back, :44).  Erasing a key frame and adding it again puts it at the end.  A query returns lKFsSharingWords in
+ * the reference's first-encounter order: ascending by (smallest common word id, sequence number), which is what walking the
+ * query's words in ascending order and each list front to back produces. */
+typedef struct rgbl_kf_database rgbl_kf_database;
+int rgbl_kfdb_create(int device, int n_vocab_words, rgbl_kf_database** out);
+void rgbl_kfdb_destroy(rgbl_kf_database* db);
+/* KeyFrameDatabase::add: the ascending word ids and values of rgbl_bow_transform*.  RGBL_ERR_INVALID for ids that do not
+ * ascend or are >= n_vocab_words, and for a kf_id that is in the database already (the reference would push it into its lists
+ * a second time and count every word twice; no caller of the reference does that). */
+int rgbl_kfdb_add(rgbl_kf_database* db, int64_t kf_id, int32_t map_id, int n_words, const uint32_t* word_id, const double* word_val);
+/* erase (:47-66; a key frame that is not stored: nothing happens), clear (:68-72), clearMap (:74-98). */
+int rgbl_kfdb_erase(rgbl_kf_database* db, int64_t kf_id);
+int rgbl_kfdb_clear(rgbl_kf_database* db);
+int rgbl_kfdb_clear_map(rgbl_kf_database* db, int32_t map_id);
+/* KeyFrame::UpdateMap: a stored key frame moves to another map (LoopClosing.cc:1527, :1736, :1898 after a merge).  clearMap tests
+ * GetMap() when it runs (:87), so rgbl_kfdb_clear_map goes by the id set last.  Its place in the order does not change.
+ * A key frame that is not stored: nothing happens. */
+int rgbl_kfdb_set_map(rgbl_kf_database* db, int64_t kf_id, int32_t map_id);
+/* stored key frames and the words they hold */
+int rgbl_kfdb_size(rgbl_kf_database* db, int* n_alive, long long* n_words);
+/* A test aid, not part of the reference's interface - the arena: words in use (tombstones included), capacity in words, entry slots (tombstones included), compactions so far */
+int rgbl_kfdb_arena_info(rgbl_kf_database* db, long long* used_words, long long* cap_words, int* n_slots, int* n_compactions);
+
+typedef struct {
+  int n_words;                    /* the query's BowVector: ascending ids, values */
+  const uint32_t* word_id;
+  const double* word_val;
+  int n_excluded;                 /* key frames that are no shared entries and do not count towards the maximum:           */
+  const int64_t* excluded_kf;     /*   DetectNBestCandidates passes pKF->GetConnectedKeyFrames() (:613, :626); NULL / 0 else */
+  int min_words_floor;            /* minCommonWords = max(int(maxCommonWords * 0.8f), min_words_floor); 0 for both callers  */
+} rgbl_kfdb_query_input;
+typedef struct {
+  int cap;                        /* room in the four arrays */
+  int64_t* share_kf;              /* lKFsSharingWords, in the reference's order                                            */
+  int32_t* share_words;           /* mnRelocWords / mnPlaceRecognitionWords of that key frame                              */
+  float* share_score;             /* mRelocScore / mPlaceRecognitionScore where scored[i]; NOT written where it is 0       */
+  uint8_t* scored;                /* share_words[i] > min_common_words                                                     */
+  int n_share, max_common_words, min_common_words;
+} rgbl_kfdb_query_output;
+/* Host pointers, synchronous.  Every key frame that shares a word is returned, not only the scored ones: the covisibility
+ * step reads mn*Query and the (possibly stale) m*Score of neighbours below the threshold (:686-690, :807-811), so a caller
+ * has to stamp all of them.  RGBL_ERR_CAPACITY, with n_share set and no array written, when cap < n_share.  Queries hold at
+ * most 15360 words. */
+int rgbl_kfdb_query(rgbl_kf_database* db, const rgbl_kfdb_query_input* in, rgbl_kfdb_query_output* out);
+/* n_queries queries in one launch over (query, entry); rgbl_kfdb_query is its n_queries = 1 case.  Query q's words are
+ * word_id / word_val[word_off[q] .. word_off[q+1]), its excluded key frames excl_kf[excl_off[q] .. excl_off[q+1]) (excl_off
+ * NULL: none), its floor min_words_floor[q] (NULL: 0); its results go to row q of the n_queries x cap arrays and to entry q
+ * of n_share / max_common_words / min_common_words.  RGBL_ERR_CAPACITY if any row is too small (the other rows are filled).  At most
+ * 65535 queries per call (RGBL_ERR_INVALID beyond). */
+int rgbl_kfdb_query_batch(rgbl_kf_database* db, int n_queries, const int32_t* word_off, const uint32_t* word_id,
+                          const double* word_val, const int32_t* excl_off, const int64_t* excl_kf,
+                          const int32_t* min_words_floor, int cap, int64_t* share_kf, int32_t* share_words, float* share_score,
+                          uint8_t* scored, int32_t* n_share, int32_t* max_common_words, int32_t* min_common_words);
+/* A measurement aid (tools/kfdb_bench.py): per-kernel times of the queries (HIP events), as rgbl_matcher_profile / _profile_read */
+int rgbl_kfdb_profile(rgbl_kf_database* db, int enable);
+int rgbl_kfdb_profile_read(rgbl_kf_database* db, const char** names, double* total_ms, long* launches, int cap);
+
+/* ------------------------------------------------------------------------------------------------
  * Environment switches.  Every one of them is read ONCE, when the handle it concerns is created (never on a launch path:
  * the entry points are called from the three SLAM threads), and is a tuning / test aid - the defaults are what is measured
  * and shipped.  Results are bit-identical under all of them (parity_checks.check_switches: the batch and the single-frame

@@ -124,6 +124,18 @@ class FeederResults(C.Structure):
                 ("mono", C.c_void_p), ("depth", C.c_void_p), ("uright", C.c_void_p), ("kpun_xy", C.c_void_p)]
 
 
+class KfdbQueryInput(C.Structure):
+    """rgbl_kfdb_query_input (the BowVector side of KeyFrameDatabase::Detect*Candidates)."""
+    _fields_ = [("n_words", C.c_int), ("word_id", C.c_void_p), ("word_val", C.c_void_p), ("n_excluded", C.c_int),
+                ("excluded_kf", C.c_void_p), ("min_words_floor", C.c_int)]
+
+
+class KfdbQueryOutput(C.Structure):
+    """rgbl_kfdb_query_output (lKFsSharingWords with mn*Words and the scores)."""
+    _fields_ = [("cap", C.c_int), ("share_kf", C.c_void_p), ("share_words", C.c_void_p), ("share_score", C.c_void_p),
+                ("scored", C.c_void_p), ("n_share", C.c_int), ("max_common_words", C.c_int), ("min_common_words", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol of include/rgbl_frontend.h
 _V, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -255,6 +267,19 @@ SYMBOLS = {
     "rgbl_feeder_device_outputs": (_I, [_V, _I, C.POINTER(FeederResults), C.POINTER(_V)]),
     "rgbl_feeder_pinned_bytes": (C.c_longlong, [_V]),
     "rgbl_bow_transform_frame": (_I, [_V, _V, _I, _V, _V, _I, C.POINTER(_I), _V, _V, _V, _I, C.POINTER(_I)]),
+    "rgbl_kfdb_create": (_I, [_I, _I, C.POINTER(_V)]),
+    "rgbl_kfdb_destroy": (None, [_V]),
+    "rgbl_kfdb_add": (_I, [_V, C.c_int64, C.c_int32, _I, _V, _V]),
+    "rgbl_kfdb_erase": (_I, [_V, C.c_int64]),
+    "rgbl_kfdb_clear": (_I, [_V]),
+    "rgbl_kfdb_clear_map": (_I, [_V, C.c_int32]),
+    "rgbl_kfdb_set_map": (_I, [_V, C.c_int64, C.c_int32]),
+    "rgbl_kfdb_size": (_I, [_V, C.POINTER(_I), C.POINTER(C.c_longlong)]),
+    "rgbl_kfdb_arena_info": (_I, [_V, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(_I), C.POINTER(_I)]),
+    "rgbl_kfdb_query": (_I, [_V, C.POINTER(KfdbQueryInput), C.POINTER(KfdbQueryOutput)]),
+    "rgbl_kfdb_query_batch": (_I, [_V, _I, _V, _V, _V, _V, _V, _V, _I, _V, _V, _V, _V, _V, _V, _V]),
+    "rgbl_kfdb_profile": (_I, [_V, _I]),
+    "rgbl_kfdb_profile_read": (_I, [_V, _V, _V, _V, _I]),
 }
 
 

@@ -909,3 +909,196 @@ class ORBVocabulary:
             self.close()
         except Exception:
             pass
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM3::KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc) with the stored BowVectors on the
+    device: add / erase / clear / clearMap, the BoW part of a query (`query`), and the two Detect* functions the reference
+    calls, whose covisibility tail runs here on plain arrays, in float32 like the reference's `float` locals.
+
+    Key frames are integers.  The stamps the reference keeps on the KeyFrame objects (mnRelocQuery / mnRelocWords /
+    mRelocScore and the mnPlaceRecognition* trio) are kept in `self.stamps`; a score that was never written reads 0 (the
+    reference leaves mRelocScore uninitialised).  Query ids are taken to differ from 0 and from every earlier query's, as
+    Frame::mnId / KeyFrame::mnId of the reference's callers do."""
+
+    def __init__(self, n_vocab_words, device=0, lib=None):
+        self.lib = lib or L.load()
+        self.h = C.c_void_p()
+        L.check(self.lib, self.lib.rgbl_kfdb_create(device, int(n_vocab_words), C.byref(self.h)))
+        self.stamps = {"reloc": {}, "place": {}}
+
+    def close(self):
+        if self.h:
+            self.lib.rgbl_kfdb_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, kf_id, map_id, word_id, word_val):
+        wid, wval = np.ascontiguousarray(word_id, np.uint32), np.ascontiguousarray(word_val, np.float64)
+        L.check(self.lib, self.lib.rgbl_kfdb_add(self.h, int(kf_id), int(map_id), len(wid), L.ptr(wid), L.ptr(wval)))
+
+    def erase(self, kf_id):
+        L.check(self.lib, self.lib.rgbl_kfdb_erase(self.h, int(kf_id)))
+
+    def clear(self):
+        L.check(self.lib, self.lib.rgbl_kfdb_clear(self.h))
+
+    def clearMap(self, map_id):
+        L.check(self.lib, self.lib.rgbl_kfdb_clear_map(self.h, int(map_id)))
+
+    def setMap(self, kf_id, map_id):
+        """KeyFrame::UpdateMap of a stored key frame: clearMap goes by the map a key frame has when it runs."""
+        L.check(self.lib, self.lib.rgbl_kfdb_set_map(self.h, int(kf_id), int(map_id)))
+
+    def size(self):
+        n, w = C.c_int(0), C.c_longlong(0)
+        L.check(self.lib, self.lib.rgbl_kfdb_size(self.h, C.byref(n), C.byref(w)))
+        return n.value, w.value
+
+    def arena_info(self):
+        used, cap, slots, comp = C.c_longlong(0), C.c_longlong(0), C.c_int(0), C.c_int(0)
+        L.check(self.lib, self.lib.rgbl_kfdb_arena_info(self.h, C.byref(used), C.byref(cap), C.byref(slots), C.byref(comp)))
+        return dict(used_words=used.value, cap_words=cap.value, n_slots=slots.value, n_compactions=comp.value)
+
+    def query(self, word_id, word_val, excluded=None, min_words_floor=0, cap=None):
+        return self.prepare_query(word_id, word_val, excluded, min_words_floor, cap)()
+
+    def prepare_query(self, word_id, word_val, excluded=None, min_words_floor=0, cap=None):
+        """lKFsSharingWords of one query through rgbl_kfdb_query: dict(kf, words, score, scored, max_common_words,
+        min_common_words); score is meaningful where scored."""
+        wid, wval = np.ascontiguousarray(word_id, np.uint32), np.ascontiguousarray(word_val, np.float64)
+        ex = np.ascontiguousarray([] if excluded is None else sorted(excluded), np.int64)
+        cap = self.arena_info()["n_slots"] if cap is None else int(cap)
+        kf, words = np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.int32)
+        score, scored = np.zeros(max(cap, 1), np.float32), np.zeros(max(cap, 1), np.uint8)
+        qin = L.KfdbQueryInput(len(wid), L.ptr(wid).value, L.ptr(wval).value, len(ex), L.ptr(ex).value if len(ex) else None,
+                               int(min_words_floor))
+        out = L.KfdbQueryOutput(cap, L.ptr(kf).value, L.ptr(words).value, L.ptr(score).value, L.ptr(scored).value, 0, 0, 0)
+        keep = (wid, wval, ex)
+
+        def call():
+            L.check(self.lib, self.lib.rgbl_kfdb_query(self.h, C.byref(qin), C.byref(out)))
+            n = out.n_share
+            assert keep is not None
+            return dict(kf=kf[:n].copy(), words=words[:n].copy(), score=score[:n].copy(), scored=scored[:n].astype(bool),
+                        max_common_words=out.max_common_words, min_common_words=out.min_common_words)
+        return call
+
+    def query_batch(self, queries, cap=None):
+        return self.prepare_query_batch(queries, cap)()
+
+    def prepare_query_batch(self, queries, cap=None):
+        """queries: a list of dict(word_id, word_val[, excluded][, min_words_floor]); one rgbl_kfdb_query_batch call.
+        Returns one result dict per query, as `query` does."""
+        Q = len(queries)
+        off = np.zeros(Q + 1, np.int32)
+        xoff = np.zeros(Q + 1, np.int32)
+        for i, q in enumerate(queries):
+            off[i + 1] = off[i] + len(q["word_id"])
+            xoff[i + 1] = xoff[i] + len(q.get("excluded") or ())
+        wid = np.ascontiguousarray(np.concatenate([np.asarray(q["word_id"], np.uint32) for q in queries] + [np.zeros(0, np.uint32)]))
+        wval = np.ascontiguousarray(np.concatenate([np.asarray(q["word_val"], np.float64) for q in queries] + [np.zeros(0, np.float64)]))
+        ex = np.ascontiguousarray(np.concatenate([np.asarray(sorted(q.get("excluded") or ()), np.int64) for q in queries] + [np.zeros(0, np.int64)]))
+        floor = np.ascontiguousarray([int(q.get("min_words_floor", 0)) for q in queries], np.int32)
+        cap = self.arena_info()["n_slots"] if cap is None else int(cap)
+        c1 = max(cap, 1)
+        kf, words = np.zeros((Q, c1), np.int64), np.zeros((Q, c1), np.int32)
+        score, scored = np.zeros((Q, c1), np.float32), np.zeros((Q, c1), np.uint8)
+        ns, mx, mn = np.zeros(Q, np.int32), np.zeros(Q, np.int32), np.zeros(Q, np.int32)
+        if cap == 0:
+            kf, words, score, scored = kf[:, :0], words[:, :0], score[:, :0], scored[:, :0]
+        args = (self.h, Q, L.ptr(off), L.ptr(wid), L.ptr(wval), L.ptr(xoff) if xoff[Q] else None, L.ptr(ex), L.ptr(floor), c1 if cap else 0,
+                L.ptr(kf), L.ptr(words), L.ptr(score), L.ptr(scored), L.ptr(ns), L.ptr(mx), L.ptr(mn))
+
+        def call():
+            L.check(self.lib, self.lib.rgbl_kfdb_query_batch(*args))
+            return [dict(kf=kf[i, :ns[i]].copy(), words=words[i, :ns[i]].copy(), score=score[i, :ns[i]].copy(),
+                         scored=scored[i, :ns[i]].astype(bool), max_common_words=int(mx[i]), min_common_words=int(mn[i]))
+                    for i in range(Q)]
+        return call
+
+    def profile(self, enable):
+        L.check(self.lib, self.lib.rgbl_kfdb_profile(self.h, int(enable)))
+
+    def profile_read(self):
+        return L.read_profile(self.lib, self.lib.rgbl_kfdb_profile_read, self.h)
+
+    # ---- the host tails (KeyFrameDatabase.cc:671-729, :792-844)
+    def _stamp(self, which, query_id, r):
+        st = self.stamps[which]
+        scored = []
+        for kf, w, s, ok in zip(r["kf"].tolist(), r["words"].tolist(), r["score"], r["scored"].tolist()):
+            e = st.setdefault(kf, [0, 0, np.float32(0)])
+            e[0], e[1] = query_id, w
+            if ok:
+                e[2] = np.float32(s)
+                scored.append((np.float32(s), kf))
+        return st, scored
+
+    @staticmethod
+    def _accumulate(st, scored, query_id, covisibility):
+        acc_list, best_acc = [], np.float32(0)
+        for si, kf in scored:
+            best, acc, best_kf = si, si, kf
+            for kf2 in list(covisibility.get(kf, ()))[:10]:     # GetBestCovisibilityKeyFrames(10)
+                e2 = st.get(kf2)
+                if e2 is None or e2[0] != query_id:
+                    continue
+                acc = np.float32(acc + e2[2])
+                if e2[2] > best:
+                    best_kf, best = kf2, e2[2]
+            acc_list.append((acc, best_kf))
+            if acc > best_acc:
+                best_acc = acc
+        return acc_list, best_acc
+
+    def DetectRelocalizationCandidates(self, frame_id, word_id, word_val, map_id, covisibility, kf_map):
+        """KeyFrameDatabase::DetectRelocalizationCandidates(F, pMap) (:733-845).  covisibility: {kf: its covisible key
+        frames, best first}; kf_map: {kf: map id}.  Returns vpRelocCandidates."""
+        r = self.query(word_id, word_val)
+        st, scored = self._stamp("reloc", frame_id, r)
+        if not scored:
+            return []
+        acc_list, best_acc = self._accumulate(st, scored, frame_id, covisibility)
+        min_retain = np.float32(np.float32(0.75) * best_acc)
+        out, seen = [], set()
+        for si, kf in acc_list:
+            if si > min_retain:
+                if kf_map[kf] != map_id:
+                    continue
+                if kf not in seen:
+                    out.append(kf)
+                    seen.add(kf)
+        return out
+
+    def DetectNBestCandidates(self, kf_id, word_id, word_val, map_id, connected, nNumCandidates, covisibility, kf_map,
+                              bad_kfs=(), bad_maps=()):
+        """KeyFrameDatabase::DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, nNumCandidates) (:604-730); connected =
+        pKF->GetConnectedKeyFrames().  Returns (vpLoopCand, vpMergeCand).  A bad key frame in the sorted list is stepped
+        over (the reference's `continue` at :712 does not advance and would spin; bad key frames are erased from the database
+        before they can be met, KeyFrame.cc:678)."""
+        r = self.query(word_id, word_val, excluded=connected)
+        st, scored = self._stamp("place", kf_id, r)
+        if not scored:
+            return [], []
+        acc_list, _ = self._accumulate(st, scored, kf_id, covisibility)
+        acc_list = sorted(acc_list, key=lambda p: -float(p[0]))   # list::sort(compFirst): stable, descending
+        loop, merge, seen = [], [], set()
+        bad_kfs, bad_maps = set(bad_kfs), set(bad_maps)
+        for _, kf in acc_list:
+            if not (len(loop) < nNumCandidates or len(merge) < nNumCandidates):
+                break
+            if kf in bad_kfs:
+                continue
+            if kf not in seen:
+                if map_id == kf_map[kf] and len(loop) < nNumCandidates:
+                    loop.append(kf)
+                elif map_id != kf_map[kf] and len(merge) < nNumCandidates and kf_map[kf] not in bad_maps:
+                    merge.append(kf)
+                seen.add(kf)
+        return loop, merge

@@ -3,8 +3,9 @@
 // transform(features, BowVector, FeatureVector, levelsup) (Frame::ComputeBoW, src/Frame.cc:828-835; KeyFrame::ComputeBoW,
 // src/KeyFrame.cc:98-107) - the vocabulary tree lives on the device, the per-feature descent runs there.
 // transform() is a template over the two container types so that DBoW2's own BowVector / FeatureVector
-// (std::map<WordId, WordValue>, std::map<NodeId, std::vector<unsigned>>) are filled directly; the scoring side of the
-// vocabulary (score(), used by KeyFrameDatabase) stays with DBoW2.
+// (std::map<WordId, WordValue>, std::map<NodeId, std::vector<unsigned>>) are filled directly.  score() has one user in the
+// reference, KeyFrameDatabase: its drop-in (KeyFrameDatabase.h here) scores on the device, so a host that takes both needs
+// no DBoW2 vocabulary object; size() below is what that class asks of a vocabulary.
 #ifndef RGBL_ORBVOCABULARY_H
 #define RGBL_ORBVOCABULARY_H
 
@@ -34,6 +35,12 @@ class DeviceORBVocabulary {
     return true;
   }
   bool empty() const { return mpHandle == nullptr; }
+  // number of words (TemplatedVocabulary::size(), KeyFrameDatabase.cc:35)
+  unsigned int size() const {
+    int nw = 0;
+    if (mpHandle) rgbl_vocabulary_info(mpHandle, nullptr, nullptr, nullptr, &nw);
+    return (unsigned int)nw;
+  }
 
   template <class BowVectorT, class FeatureVectorT>
   void transform(const std::vector<cv::Mat>& features, BowVectorT& v, FeatureVectorT& fv, int levelsup) const {
