@@ -705,6 +705,84 @@ typedef struct {
  * (entry left as it was).  *out_nmatches = return value of the reference function. */
 int rgbl_search_local_points(rgbl_matcher* h, const rgbl_local_points_input* in, int32_t* match2, int* out_nmatches);
 
+/* ---- Tracking::SearchLocalPoints in one call: Frame::isInFrustum + MapPoint::PredictScale on the device -----------------
+ * A pool of map-point data that lives on the device, the map-side counterpart of rgbl_device_frame: what Frame::isInFrustum
+ * (src/Frame.cc:602-664) and the matcher read from a MapPoint - GetWorldPos(), GetNormal(), mfMinDistance, mfMaxDistance
+ * (src/MapPoint.cc:500-512 return 0.8f / 1.2f times these; the RAW values are stored), GetDescriptor().  A slot is 64 bytes:
+ * 12 + 12 + 4 + 4 + 32, kept as five arrays (SoA).  The caller owns the slot numbers (shim/LocalMap.h maps MapPoint* to slot).
+ * Every call that touches a pool - update, reserve, a search that reads it - takes the pool's own mutex for its whole
+ * duration, so LocalMapping may update while Tracking searches; calls on different pools are independent.  A slot that was
+ * never updated reads as zeros. */
+typedef struct rgbl_map_points rgbl_map_points;
+int rgbl_map_points_create(int device, int capacity, rgbl_map_points** out);
+void rgbl_map_points_destroy(rgbl_map_points* p);
+/* grows the pool to at least `capacity` slots (never shrinks); the contents stay */
+int rgbl_map_points_reserve(rgbl_map_points* p, int capacity);
+int rgbl_map_points_capacity(rgbl_map_points* p);
+/* Writes n slots: entry k of every non-NULL array goes to slot[k] (world_pos / normal 3 floats, desc 32 bytes per entry); a
+ * NULL array leaves that field of the slots as it is.  A slot listed more than once takes its LAST entry.  RGBL_ERR_INVALID
+ * for a slot outside [0, capacity) (nothing is written).  Host pointers, synchronous. */
+int rgbl_map_points_update(rgbl_map_points* p, int n, const int32_t* slot, const float* world_pos, const float* normal,
+                           const float* min_dist, const float* max_dist, const uint8_t* desc);
+
+/* The frame side is that of rgbl_local_points_input; the map side is what the loop of Tracking::SearchLocalPoints
+ * (src/Tracking.cc:3399-3420) reads before it calls isInFrustum, either as host arrays or as slots of a pool. */
+typedef struct {
+  int n1;                      /* mvpLocalMapPoints.size() (< 2^20) */
+  const uint8_t* consider1;    /* pMP->mnLastFrameSeen != F.mnId && !pMP->isBad() (Tracking.cc:3406-3409); NULL: every point */
+  /* map points, form 1 (pool == NULL): host arrays */
+  const float* world_pos1;     /* pMP->GetWorldPos(), 3 floats per point */
+  const float* normal1;        /* pMP->GetNormal(), 3 floats per point */
+  const float* min_dist1;      /* pMP->mfMinDistance (GetMinDistanceInvariance() / 0.8f) */
+  const float* max_dist1;      /* pMP->mfMaxDistance */
+  const uint8_t* mp_desc1;     /* pMP->GetDescriptor(), 32 bytes per point (rgbl_frustum_cull does not read it) */
+  /* map points, form 2: slots of a pool on the matcher's device; the five arrays above are then not read */
+  rgbl_map_points* pool;
+  const int32_t* slot1;        /* n1 slots in [0, capacity); any order, a slot may repeat */
+  const uint8_t* mp_observed1; /* pMP->Observations() > 0 */
+  int n2;                      /* F.N (<= 65535) */
+  const float* kp2_xy;         /* F.mvKeysUn[i].pt */
+  const int32_t* kp2_octave;
+  const float* uright2;        /* F.mvuRight */
+  const uint8_t* desc2;        /* F.mDescriptors */
+  const uint8_t* blocked2;     /* F.mvpMapPoints[i] != NULL && ->Observations() > 0 on entry (nullable: none) */
+  float grid[6];               /* Frame::mnMinX, mnMinY, mnMaxX, mnMaxY (also isInFrustum's image bounds), mfGridElementWidthInv, mfGridElementHeightInv */
+  const float* scale_factors;  /* F.mvScaleFactors */
+  int n_levels;                /* F.mnScaleLevels (1 .. 16) */
+  float th;
+  float nnratio;               /* mfNNratio */
+  const rgbl_device_frame* device2; /* nullable: F resident on the device - kp2_xy, kp2_octave, uright2, desc2 are then not read */
+  float Rcw[9], tcw[3], Ow[3]; /* F.mRcw (row-major), F.mtcw, F.mOw as Frame::UpdatePoseMatrices leaves them (Frame.cc:562-569) */
+  float K[4];                  /* fx, fy, cx, cy of F.mpCamera (Pinhole::project, src/CameraModels/Pinhole.cpp:43-49) */
+  float mbf;                   /* F.mbf */
+  float log_scale_factor;      /* F.mfLogScaleFactor */
+  float viewing_cos_limit;     /* isInFrustum's second argument: 0.5 (Tracking.cc:3411) */
+  int far_points;              /* mpLocalMapper->mbFarPoints */
+  float th_far_points;         /* mpLocalMapper->mThFarPoints */
+} rgbl_track_local_input;
+/* What isInFrustum leaves in a MapPoint (Frame.cc:605-607, 629-630, 653-661). */
+typedef struct {
+  float proj_x, proj_y;        /* mTrackProjX, mTrackProjY: (-1, -1) for a point rejected by depth or image bounds or not considered,
+                                  the projection for one rejected by distance or viewing angle and for a point in view */
+  float proj_xr, depth, view_cos; /* mTrackProjXR, mTrackDepth, mTrackViewCos of a point in view; 0 otherwise (the reference leaves them as they were) */
+  int32_t level;               /* mnTrackScaleLevel = PredictScale(dist, &F) (src/MapPoint.cc:531-546) of a point in view; 0 otherwise */
+} rgbl_frustum_record;
+/* bool Frame::isInFrustum(MapPoint* pMP, float viewingCosLimit) (include/Frame.h:100, src/Frame.cc:602-664, the Nleft == -1
+ * branch) for every considered point: in_view[i] = mbTrackInView (0 for a point that is not considered), rec (nullable) as
+ * above, *n_in_view = the number of points in view = nToMatch (Tracking.cc:3399-3415).  The frame's feature arrays are not
+ * read.  fp32 in the reference's order, logf as glibc 2.35 evaluates it (csrc/logf_glibc.h); a ratio mfMaxDistance / dist that
+ * is not finite and positive, for which the reference's float -> int conversion is undefined, gives level 0.
+ * Host pointers, synchronous.  Errors as for rgbl_search_local_points; a slot outside the pool: RGBL_ERR_INVALID. */
+int rgbl_frustum_cull(rgbl_matcher* h, const rgbl_track_local_input* in, uint8_t* in_view, rgbl_frustum_record* rec, int* n_in_view);
+/* Tracking.cc:3399-3448: the loop above and ORBmatcher::SearchByProjection(F, mvpLocalMapPoints, th, bFarPoints, thFarPoints)
+ * (src/ORBmatcher.cc:43-213) behind it, with one upload and one read-back.  in_view, rec (nullable), *n_to_match as for
+ * rgbl_frustum_cull; match2 / *out_nmatches as for rgbl_search_local_points (all -1 / 0 when nothing is in view: the reference
+ * does not call the matcher then, Tracking.cc:3422).  The search kernels are not launched when the host can tell that
+ * nothing will be in view (no point considered, or n2 == 0); when the cull itself rejects every point they run over an
+ * all-invalid list. */
+int rgbl_track_local_points(rgbl_matcher* h, const rgbl_track_local_input* in, uint8_t* in_view, rgbl_frustum_record* rec,
+                            int* n_to_match, int32_t* match2, int* out_nmatches);
+
 /* ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>& vbPrevMatched, vector<int>& vnMatches12,
  * int windowSize)    /root/reference/include/ORBmatcher.h:72, src/ORBmatcher.cc:648-763 (Tracking::MonocularInitialization,
  * src/Tracking.cc:2526; not on the RGB-L / stereo path - built so that every search routine of ORBmatcher has a device form).

@@ -103,6 +103,24 @@ class LocalPointsInput(C.Structure):
                 ("n_levels", C.c_int), ("th", C.c_float), ("nnratio", C.c_float), ("device2", C.c_void_p)]
 
 
+class TrackLocalInput(C.Structure):
+    """rgbl_track_local_input (Tracking::SearchLocalPoints from its isInFrustum loop on: map points as host arrays or pool slots)."""
+    _fields_ = [("n1", C.c_int), ("consider1", C.c_void_p), ("world_pos1", C.c_void_p), ("normal1", C.c_void_p),
+                ("min_dist1", C.c_void_p), ("max_dist1", C.c_void_p), ("mp_desc1", C.c_void_p), ("pool", C.c_void_p),
+                ("slot1", C.c_void_p), ("mp_observed1", C.c_void_p),
+                ("n2", C.c_int), ("kp2_xy", C.c_void_p), ("kp2_octave", C.c_void_p), ("uright2", C.c_void_p),
+                ("desc2", C.c_void_p), ("blocked2", C.c_void_p), ("grid", C.c_float * 6), ("scale_factors", C.c_void_p),
+                ("n_levels", C.c_int), ("th", C.c_float), ("nnratio", C.c_float), ("device2", C.c_void_p),
+                ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("K", C.c_float * 4),
+                ("mbf", C.c_float), ("log_scale_factor", C.c_float), ("viewing_cos_limit", C.c_float),
+                ("far_points", C.c_int), ("th_far_points", C.c_float)]
+
+
+# rgbl_frustum_record: what Frame::isInFrustum leaves in a MapPoint
+FRUSTUM_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"),
+                          ("level", "<i4")])
+
+
 class InitializationInput(C.Structure):
     """rgbl_initialization_input (ORBmatcher::SearchForInitialization as flat arrays)."""
     _fields_ = [("n1", C.c_int), ("kp1_octave", C.c_void_p), ("kp1_angle", C.c_void_p), ("desc1", C.c_void_p),
@@ -236,6 +254,13 @@ SYMBOLS = {
     "rgbl_search_by_bow_keyframes": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_projection": (_I, [_V, _V, _V, C.POINTER(_I)]),
     "rgbl_search_local_points": (_I, [_V, _V, _V, C.POINTER(_I)]),
+    "rgbl_map_points_create": (_I, [_I, _I, C.POINTER(_V)]),
+    "rgbl_map_points_destroy": (None, [_V]),
+    "rgbl_map_points_reserve": (_I, [_V, _I]),
+    "rgbl_map_points_capacity": (_I, [_V]),
+    "rgbl_map_points_update": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]),
+    "rgbl_frustum_cull": (_I, [_V, _V, _V, _V, C.POINTER(_I)]),
+    "rgbl_track_local_points": (_I, [_V, _V, _V, _V, C.POINTER(_I), _V, C.POINTER(_I)]),
     "rgbl_search_for_initialization": (_I, [_V, _V, _V, _V, C.POINTER(_I)]),
     "rgbl_fuse_search": (_I, [_V, _V, _V, _V]),
     "rgbl_project_search": (_I, [_V, _V, _V, _V]),

@@ -363,3 +363,89 @@ def make_initialization_case(n1=5000, seed=61, w=synth.KITTI_W, h=synth.KITTI_H,
     grid = np.array([0, 0, gw, gh, np.float32(64) / gw, np.float32(48) / gh], np.float32)
     return dict(kp1_octave=oct1, kp1_angle=ang1, desc1=desc1, prev_matched=prev, kp2_xy=xy2, kp2_octave=oct2, kp2_angle=ang2,
                 desc2=desc2, grid=grid)
+
+
+def _rotation_matrix_f32(q):
+    """Eigen QuaternionBase::toRotationMatrix in float32 (what SE3f::rotationMatrix() returns), row-major, 9 floats."""
+    f = np.float32
+    x, y, z, w = [f(v) for v in q]
+    tx, ty, tz = f(2) * x, f(2) * y, f(2) * z
+    twx, twy, twz, txx, txy, txz, tyy, tyz, tzz = tx * w, ty * w, tz * w, tx * x, ty * x, tz * x, ty * y, tz * y, tz * z
+    return np.array([f(1) - (tyy + tzz), txy - twz, txz + twy, txy + twz, f(1) - (txx + tzz), tyz - twx,
+                     txz - twy, tyz + twx, f(1) - (txx + tyy)], np.float32)
+
+
+def make_local_map_case(n1=3000, n2=2000, seed=71, w=synth.KITTI_W, h=synth.KITTI_H):
+    """The local map of Tracking::SearchLocalPoints BEFORE Frame::isInFrustum has run: world points (most aimed at features of
+    the frame, as in make_relocalization_case), normals, scale-invariance ranges, descriptors - and the frame with its pose as
+    Frame::UpdatePoseMatrices leaves it.  Every exit of isInFrustum gets its share of the points: behind the camera, outside
+    the image, outside the invariance range (too far, too close), seen from the side or from behind, and in view with
+    predicted levels over the whole pyramid, including ratios beyond its top (upper clamp).  n1, n2 >= 1."""
+    c = make_projection_case(n1, n2, seed, "none", w, h)
+    rng = np.random.default_rng(seed + 3000)
+    K, q, t = c["K"], c["Tcw_q"], c["Tcw_t"]
+    Rc = _rot(q)
+    Cw = -Rc.T @ t.astype(np.float64)                          # camera centre
+    world = c["world_pos1"].astype(np.float64)
+    cat = rng.random(n1)
+    behind = cat < 0.07
+    world[behind] = 2 * Cw - world[behind]                     # mirrored through the camera centre: Pc -> -Pc
+    outside = (cat >= 0.07) & (cat < 0.16)
+    no = int(outside.sum())
+    side = rng.integers(0, 4, no)
+    off = rng.uniform(0.5, 80, no)
+    u = np.where(side == 0, -off, np.where(side == 1, w + off, rng.uniform(0, w, no)))
+    v = np.where(side == 2, -off, np.where(side == 3, h + off, rng.uniform(0, h, no)))
+    z = rng.uniform(4, 70, no)
+    xc = np.stack([(u - K[2]) / K[0] * z, (v - K[3]) / K[1] * z, z], 1)
+    world[outside] = (xc - t.astype(np.float64)) @ Rc
+    world = world.astype(np.float32)
+    PO = world.astype(np.float64) - Cw
+    dist = np.linalg.norm(PO, axis=1)
+    # mfMaxDistance = dist * scale^level of the observation that made the point: near the octave of the feature it aims at
+    lvl = c["octave1"].astype(np.int64)
+    max_d = dist * 1.2 ** lvl * rng.uniform(0.85, 1.0, n1)
+    rcat = rng.random(n1)
+    top = rcat < 0.06
+    max_d[top] = dist[top] * 1.2 ** 7 * rng.uniform(1.02, 1.2, int(top.sum()))    # ratio beyond the top level, still in range
+    far = (rcat >= 0.06) & (rcat < 0.14)
+    max_d[far] = dist[far] * rng.uniform(0.4, 0.8, int(far.sum()))               # dist > 1.2 max
+    min_d = max_d / 1.2 ** 7
+    near = (rcat >= 0.14) & (rcat < 0.21)
+    min_d[near] = dist[near] * rng.uniform(1.3, 2.0, int(near.sum()))            # dist < 0.8 min
+    normal = PO / np.maximum(dist, 1e-6)[:, None] + rng.normal(0, 0.3, PO.shape)  # roughly towards the camera ...
+    normal /= np.linalg.norm(normal, axis=1, keepdims=True)
+    ncat = rng.random(n1)
+    normal[ncat < 0.08] *= -1                                                    # ... some from behind
+    sideways = (ncat >= 0.08) & (ncat < 0.16)
+    tang = np.cross(PO, rng.normal(0, 1, PO.shape))
+    tang /= np.maximum(np.linalg.norm(tang, axis=1, keepdims=True), 1e-9)
+    mix = rng.uniform(0.0, 0.45, (n1, 1))                                        # viewCos below the limit of 0.5
+    side_n = mix * PO / np.maximum(dist, 1e-6)[:, None] + np.sqrt(1 - mix * mix) * tang
+    normal[sideways] = side_n[sideways]
+    qf = np.asarray(q, np.float32)
+
+    def rotate(qv, p):  # Eigen QuaternionBase::_transformVector in float32
+        uu = np.float32(2) * np.cross(qv[:3], p).astype(np.float32)
+        return (p + qv[3] * uu + np.cross(qv[:3], uu).astype(np.float32)).astype(np.float32)
+    Ow = rotate(np.array([-qf[0], -qf[1], -qf[2], qf[3]], np.float32), (-np.asarray(t, np.float32)).astype(np.float32))
+    return dict(world_pos1=world, normal1=normal.astype(np.float32), min_dist1=min_d.astype(np.float32),
+                max_dist1=max_d.astype(np.float32), mp_desc1=c["mp_desc1"], mp_observed1=c["mp_observed1"],
+                consider1=(rng.random(n1) < 0.92).astype(np.uint8),
+                kp2_xy=c["kp2_xy"], kp2_octave=c["kp2_octave"], uright2=c["uright2"], desc2=c["desc2"],
+                blocked2=(rng.random(len(c["kp2_xy"])) < 0.3).astype(np.uint8), grid=c["grid"], scale_factors=c["scale_factors"],
+                Rcw=_rotation_matrix_f32(qf), tcw=np.asarray(t, np.float32), Ow=Ow, K=K, mbf=np.float32(c["mbf"]),
+                log_scale_factor=np.float32(np.log(np.float32(1.2))), viewing_cos_limit=np.float32(0.5), far_points=0,
+                th_far_points=np.float32(40.0))
+
+
+def local_points_from_cull(case, in_view, rec):
+    """(in_view, rec: what frontend.frustum_restatement or ORBmatcher.FrustumCull returned.)  The make_local_points_case-style dict that ORBmatcher::SearchByProjection(F, vpMapPoints, ...) sees after the loop:
+    valid1 = mbTrackInView && !(bFarPoints && mTrackDepth > thFarPoints) (ORBmatcher.cc:52-59; isBad is part of consider1)."""
+    valid = (np.asarray(in_view) != 0)
+    if int(case["far_points"]):
+        valid = valid & ~(rec["depth"] > np.float32(case["th_far_points"]))
+    return dict(valid1=valid.astype(np.uint8), proj1=np.stack([rec["proj_x"], rec["proj_y"], rec["proj_xr"]], 1).astype(np.float32),
+                level1=rec["level"].astype(np.int32), view_cos1=rec["view_cos"].astype(np.float32), mp_desc1=case["mp_desc1"],
+                mp_observed1=case["mp_observed1"], kp2_xy=case["kp2_xy"], kp2_octave=case["kp2_octave"], uright2=case["uright2"],
+                desc2=case["desc2"], blocked2=case["blocked2"], grid=case["grid"], scale_factors=case["scale_factors"])

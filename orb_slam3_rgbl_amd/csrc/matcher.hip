@@ -23,6 +23,8 @@
 #include <vector>
 
 #include "common.h"
+#include "frustum_math.h"
+#include "logf_glibc.h"
 
 namespace rgbl {
 
@@ -1348,6 +1350,116 @@ __global__ __launch_bounds__(kResolveBS) void k_local_resolve(ProjDev P) {
   };
   if (LDS && staged.clist != P.clist) run(ListView{s_ref, s_list});
   else run(ListView{LDS ? s_ref : P.cref, P.clist});
+}
+
+// ------------------------------------------------------------------------------------------------
+// bool Frame::isInFrustum(MapPoint*, float viewingCosLimit) (src/Frame.cc:602-664, Nleft == -1) with MapPoint::PredictScale
+// (src/MapPoint.cc:531-546) and Pinhole::project (src/CameraModels/Pinhole.cpp:43-49): the loop Tracking::SearchLocalPoints
+// (src/Tracking.cc:3399-3420) runs in front of the matcher above.  Every point on its own, fp32 in the reference's order (the
+// three Eigen reductions: frustum_math.h), `/` and sqrt correctly rounded, logf as glibc evaluates it (logf_glibc.h).
+// The comparisons are written in the reference's sense, so a NaN or infinite projection passes and fails what it does there.
+struct FrustumDev {
+  int n1;
+  // map points: index j = slot1 ? slot1[i] : i into the five arrays (the call's staged arrays, or a pool's)
+  const uint8_t* consider1;
+  const int32_t* slot1;
+  const float* wpos; const float* normal; const float* min_dist; const float* max_dist;
+  const uint8_t* desc;         // read only with slot1: a considered point's descriptor is copied to mpdesc1[i]
+  float Rcw[9], tcw[3], Ow[3], K[4], bounds[4], mbf, log_scale, cos_limit, th_far;
+  int far_points, n_levels;
+  // results
+  uint8_t* in_view;
+  rgbl_frustum_record* rec;
+  // what k_local_candidates reads (ProjDev::valid1, proj1, level1, viewcos1, mpdesc1); nullptr for the cull alone
+  uint8_t* valid1; float* proj1; int32_t* level1; float* viewcos1; uint8_t* mpdesc1;
+};
+
+// grid = ceil(n1 / 256), block = 256: one work-item per map point
+__global__ __launch_bounds__(256) void k_frustum(FrustumDev F) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= F.n1) return;
+  uint8_t in_view = 0;
+  rgbl_frustum_record r;
+  r.proj_x = -1.f; r.proj_y = -1.f;               // Frame.cc:605-607
+  r.proj_xr = 0.f; r.depth = 0.f; r.view_cos = 0.f; r.level = 0;
+  if (!F.consider1 || F.consider1[i]) {
+    const int j = F.slot1 ? F.slot1[i] : i;
+    if (F.mpdesc1 && F.slot1) {
+      const uint4* src = reinterpret_cast<const uint4*>(F.desc + (size_t)j * 32);
+      uint4* dst = reinterpret_cast<uint4*>(F.mpdesc1 + (size_t)i * 32);
+      const uint4 a = src[0], b = src[1];
+      dst[0] = a; dst[1] = b;
+    }
+    const float p0 = F.wpos[3 * j], p1 = F.wpos[3 * j + 1], p2 = F.wpos[3 * j + 2];
+    const float x = fr_row_times(F.Rcw, p0, p1, p2) + F.tcw[0], y = fr_row_times(F.Rcw + 3, p0, p1, p2) + F.tcw[1],
+                z = fr_row_times(F.Rcw + 6, p0, p1, p2) + F.tcw[2];
+    const float pc_dist = fr_norm(x, y, z);
+    const float invz = __fdiv_rn(1.0f, z);
+    do {
+      if (z < 0.0f) break;                          // :619 (a zero depth goes on)
+      const float u = __fdiv_rn(F.K[0] * x, z) + F.K[2], v = __fdiv_rn(F.K[1] * y, z) + F.K[3];
+      if (u < F.bounds[0] || u > F.bounds[2]) break;   // :624-627
+      if (v < F.bounds[1] || v > F.bounds[3]) break;
+      r.proj_x = u; r.proj_y = v;                   // :629-630
+      const float max_raw = F.max_dist[j];
+      const float max_d = 1.2f * max_raw, min_d = 0.8f * F.min_dist[j];   // Get{Max,Min}DistanceInvariance
+      const float o0 = p0 - F.Ow[0], o1 = p1 - F.Ow[1], o2 = p2 - F.Ow[2];
+      const float dist = fr_norm(o0, o1, o2);
+      if (dist < min_d || dist > max_d) break;      // :638
+      const float view_cos = __fdiv_rn(fr_dot(o0, o1, o2, F.normal[3 * j], F.normal[3 * j + 1], F.normal[3 * j + 2]), dist);
+      if (view_cos < F.cos_limit) break;            // :646
+      // PredictScale: int nScale = ceil(log(ratio) / mfLogScaleFactor), clamped to the pyramid
+      const float ratio = __fdiv_rn(max_raw, dist);
+      int level = 0;
+      if (ratio > 0.f && ratio <= 3.402823466e+38f) {
+        const float c = ceilf(__fdiv_rn(logf_glibc(ratio), F.log_scale));
+        if (!(c >= 0.f)) level = 0;
+        else if (c >= (float)F.n_levels) level = F.n_levels - 1;
+        else level = (int)c;
+      }
+      in_view = 1;
+      r.proj_xr = u - F.mbf * invz; r.depth = pc_dist; r.view_cos = view_cos; r.level = level;   // :653-661
+    } while (false);
+  }
+  F.in_view[i] = in_view;
+  if (F.rec) F.rec[i] = r;
+  if (F.valid1) {
+    F.valid1[i] = in_view && !(F.far_points && r.depth > F.th_far);   // ORBmatcher.cc:52-59
+    F.proj1[3 * i] = r.proj_x; F.proj1[3 * i + 1] = r.proj_y; F.proj1[3 * i + 2] = r.proj_xr;
+    F.level1[i] = r.level;
+    F.viewcos1[i] = r.view_cos;
+  }
+}
+
+// rgbl_map_points_update: entry k of the packed arrays goes to slot[k]; slot < 0 = an entry a later one of the same slot overrides
+struct PoolScatter {
+  int n;
+  const int32_t* slot;
+  const float *wpos, *normal, *min_dist, *max_dist;   // packed, nullable
+  const uint8_t* desc;
+  float *p_wpos, *p_normal, *p_min, *p_max;
+  uint8_t* p_desc;
+};
+__global__ __launch_bounds__(256) void k_map_points_scatter(PoolScatter S) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= S.n) return;
+  const int j = S.slot[k];
+  if (j < 0) return;
+  if (S.wpos) { S.p_wpos[3 * j] = S.wpos[3 * k]; S.p_wpos[3 * j + 1] = S.wpos[3 * k + 1]; S.p_wpos[3 * j + 2] = S.wpos[3 * k + 2]; }
+  if (S.normal) { S.p_normal[3 * j] = S.normal[3 * k]; S.p_normal[3 * j + 1] = S.normal[3 * k + 1]; S.p_normal[3 * j + 2] = S.normal[3 * k + 2]; }
+  if (S.min_dist) S.p_min[j] = S.min_dist[k];
+  if (S.max_dist) S.p_max[j] = S.max_dist[k];
+  if (S.desc) {
+    const uint4* src = reinterpret_cast<const uint4*>(S.desc + (size_t)k * 32);
+    uint4* dst = reinterpret_cast<uint4*>(S.p_desc + (size_t)j * 32);
+    const uint4 a = src[0], b = src[1];
+    dst[0] = a; dst[1] = b;
+  }
+}
+
+__global__ void k_test_logf(const float* x, float* y, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) y[i] = logf_glibc(x[i]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2774,6 +2886,294 @@ int rgbl_search_local_points(rgbl_matcher* m, const rgbl_local_points_input* in,
   for (int i = 0; i < n1; ++i)
     if (choice[i] >= 0) { match2[choice[i]] = i; ++nmatches; }  // a later point overwrites an unobserved earlier one
   *out_nmatches = nmatches;
+  return RGBL_OK;
+}
+
+// ---- rgbl_map_points: map-point data resident on the device ------------------------------------------------------------
+// One allocation: world_pos [cap x 3] | normal [cap x 3] | min [cap] | max [cap] | desc [cap x 32], every array 256-byte
+// aligned (64 bytes per slot).  `mu` is held by every call that reads or writes the arrays until its device work is done.
+struct rgbl_map_points {
+  int device = 0, cap = 0;
+  std::mutex mu;
+  uint8_t* block = nullptr;
+  float *d_wpos = nullptr, *d_normal = nullptr, *d_min = nullptr, *d_max = nullptr;
+  uint8_t* d_desc = nullptr;
+  hipStream_t stream = nullptr;
+  uint8_t *d_stage = nullptr, *h_stage = nullptr;   // one update's packed arrays and their page-locked mirror (grow-only)
+  size_t stage_size = 0;
+};
+
+namespace {
+constexpr int kMaxPoolSlots = 1 << 26;   // 4 GiB of slots: keeps every byte offset far inside size_t / int arithmetic
+struct PoolArrays { size_t wpos, normal, min_d, max_d, desc, total; };
+PoolArrays pool_arrays(int cap) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  PoolArrays a;
+  a.wpos = 0;
+  a.normal = up(a.wpos + (size_t)cap * 12);
+  a.min_d = up(a.normal + (size_t)cap * 12);
+  a.max_d = up(a.min_d + (size_t)cap * 4);
+  a.desc = up(a.max_d + (size_t)cap * 4);
+  a.total = up(a.desc + (size_t)cap * 32);
+  return a;
+}
+// a zeroed block for `cap` slots with the first `keep` slots of the pool's present arrays copied over; replaces the old block
+int pool_resize(rgbl_map_points* p, int cap, int keep) {
+  const PoolArrays a = pool_arrays(cap);
+  uint8_t* nb = nullptr;
+  RGBL_HIP(hipMalloc(reinterpret_cast<void**>(&nb), a.total));
+  hipError_t e = hipMemset(nb, 0, a.total);
+  if (e == hipSuccess && keep > 0) {
+    const struct { size_t off; const void* src; size_t bytes; } part[5] = {
+        {a.wpos, p->d_wpos, (size_t)keep * 12}, {a.normal, p->d_normal, (size_t)keep * 12}, {a.min_d, p->d_min, (size_t)keep * 4},
+        {a.max_d, p->d_max, (size_t)keep * 4}, {a.desc, p->d_desc, (size_t)keep * 32}};
+    for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipMemcpy(nb + part[k].off, part[k].src, part[k].bytes, hipMemcpyDeviceToDevice);
+  }
+  // the matcher streams that read the block next are non-blocking or the caller's: nothing above is left in flight
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { (void)hipFree(nb); set_error("map point pool: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
+  if (p->block) (void)hipFree(p->block);
+  p->block = nb; p->cap = cap;
+  p->d_wpos = reinterpret_cast<float*>(nb + a.wpos); p->d_normal = reinterpret_cast<float*>(nb + a.normal);
+  p->d_min = reinterpret_cast<float*>(nb + a.min_d); p->d_max = reinterpret_cast<float*>(nb + a.max_d);
+  p->d_desc = nb + a.desc;
+  return RGBL_OK;
+}
+}  // namespace
+
+int rgbl_map_points_create(int device, int capacity, rgbl_map_points** out) {
+  if (!out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  *out = nullptr;
+  if (capacity < 1 || capacity > kMaxPoolSlots) { set_error("map point pool: capacity 1 .. %d", kMaxPoolSlots); return RGBL_ERR_INVALID; }
+  if (rgbl_device_count() <= device || device < 0) {
+    set_error("no usable HIP device %d (this library has no CPU fallback)", device);
+    return RGBL_ERR_NO_DEVICE;
+  }
+  RGBL_HIP(hipSetDevice(device));
+  rgbl_map_points* p = new rgbl_map_points;
+  p->device = device;
+  int rc = pool_resize(p, capacity, 0);
+  if (rc == RGBL_OK && hipStreamCreate(&p->stream) != hipSuccess) { set_error("hipStreamCreate failed"); rc = RGBL_ERR_HIP; }
+  if (rc != RGBL_OK) { if (p->block) (void)hipFree(p->block); delete p; return rc; }
+  *out = p;
+  return RGBL_OK;
+}
+
+void rgbl_map_points_destroy(rgbl_map_points* p) {
+  if (!p) return;
+  (void)hipSetDevice(p->device);
+  { std::lock_guard<std::mutex> lock(p->mu); (void)hipStreamSynchronize(p->stream); }
+  if (p->block) (void)hipFree(p->block);
+  if (p->d_stage) (void)hipFree(p->d_stage);
+  if (p->h_stage) (void)hipHostFree(p->h_stage);
+  if (p->stream) (void)hipStreamDestroy(p->stream);
+  delete p;
+}
+
+int rgbl_map_points_capacity(rgbl_map_points* p) {
+  if (!p) return 0;
+  std::lock_guard<std::mutex> lock(p->mu);
+  return p->cap;
+}
+
+int rgbl_map_points_reserve(rgbl_map_points* p, int capacity) {
+  if (!p || capacity < 1 || capacity > kMaxPoolSlots) { set_error("map point pool: capacity 1 .. %d", kMaxPoolSlots); return RGBL_ERR_INVALID; }
+  std::lock_guard<std::mutex> lock(p->mu);
+  if (capacity <= p->cap) return RGBL_OK;
+  RGBL_HIP(hipSetDevice(p->device));
+  return pool_resize(p, capacity, p->cap);
+}
+
+int rgbl_map_points_update(rgbl_map_points* p, int n, const int32_t* slot, const float* world_pos, const float* normal,
+                           const float* min_dist, const float* max_dist, const uint8_t* desc) {
+  if (!p || n < 0 || (n > 0 && !slot)) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  if (n == 0) return RGBL_OK;
+  std::lock_guard<std::mutex> lock(p->mu);
+  for (int k = 0; k < n; ++k)
+    if (slot[k] < 0 || slot[k] >= p->cap) { set_error("map point pool: slot %d outside [0, %d)", slot[k], p->cap); return RGBL_ERR_INVALID; }
+  RGBL_HIP(hipSetDevice(p->device));
+  // the packed arrays, 256-byte aligned: slot | world_pos | normal | min | max | desc (only the ones given)
+  size_t off = 0;
+  auto take = [&](size_t bytes, bool present) { off = (off + 255) / 256 * 256; const size_t o = off; if (present) off += bytes; return o; };
+  const size_t o_slot = take((size_t)n * 4, true), o_wpos = take((size_t)n * 12, world_pos), o_normal = take((size_t)n * 12, normal),
+               o_min = take((size_t)n * 4, min_dist), o_max = take((size_t)n * 4, max_dist), o_desc = take((size_t)n * 32, desc);
+  if (off > p->stage_size) {
+    if (p->d_stage) { (void)hipFree(p->d_stage); p->d_stage = nullptr; }
+    if (p->h_stage) { (void)hipHostFree(p->h_stage); p->h_stage = nullptr; }
+    p->stage_size = 0;
+    const size_t sz = std::max(off, (size_t)1 << 16);
+    RGBL_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_stage), sz));
+    RGBL_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_stage), sz, hipHostMallocDefault));
+    p->stage_size = sz;
+  }
+  int32_t* h_slot = reinterpret_cast<int32_t*>(p->h_stage + o_slot);
+  memcpy(h_slot, slot, (size_t)n * 4);
+  {  // a slot listed more than once keeps its last entry: the earlier ones are struck out, so no two work-items write one slot
+    std::vector<std::pair<int32_t, int32_t>> order((size_t)n);
+    for (int k = 0; k < n; ++k) order[(size_t)k] = {slot[k], k};
+    std::sort(order.begin(), order.end());
+    for (int k = 0; k + 1 < n; ++k)
+      if (order[(size_t)k].first == order[(size_t)k + 1].first) h_slot[order[(size_t)k].second] = -1;
+  }
+  if (world_pos) memcpy(p->h_stage + o_wpos, world_pos, (size_t)n * 12);
+  if (normal) memcpy(p->h_stage + o_normal, normal, (size_t)n * 12);
+  if (min_dist) memcpy(p->h_stage + o_min, min_dist, (size_t)n * 4);
+  if (max_dist) memcpy(p->h_stage + o_max, max_dist, (size_t)n * 4);
+  if (desc) memcpy(p->h_stage + o_desc, desc, (size_t)n * 32);
+  StreamDrain drain(p->stream);
+  RGBL_HIP(hipMemcpyAsync(p->d_stage, p->h_stage, off, hipMemcpyHostToDevice, p->stream));
+  PoolScatter S{};
+  S.n = n;
+  S.slot = reinterpret_cast<const int32_t*>(p->d_stage + o_slot);
+  S.wpos = world_pos ? reinterpret_cast<const float*>(p->d_stage + o_wpos) : nullptr;
+  S.normal = normal ? reinterpret_cast<const float*>(p->d_stage + o_normal) : nullptr;
+  S.min_dist = min_dist ? reinterpret_cast<const float*>(p->d_stage + o_min) : nullptr;
+  S.max_dist = max_dist ? reinterpret_cast<const float*>(p->d_stage + o_max) : nullptr;
+  S.desc = desc ? p->d_stage + o_desc : nullptr;
+  S.p_wpos = p->d_wpos; S.p_normal = p->d_normal; S.p_min = p->d_min; S.p_max = p->d_max; S.p_desc = p->d_desc;
+  hipLaunchKernelGGL(k_map_points_scatter, dim3((n + 255) / 256), dim3(256), 0, p->stream, S);
+  RGBL_HIP(hipGetLastError());
+  RGBL_HIP(hipStreamSynchronize(p->stream));
+  return RGBL_OK;
+}
+
+// Tracking::SearchLocalPoints from its second loop on (Tracking.cc:3399-3448): k_frustum, and behind it - on the arrays it
+// left in the call's scratch - the kernels of rgbl_search_local_points, unchanged.
+namespace {
+int track_local_core(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t* in_view, rgbl_frustum_record* rec, int* n_in_view,
+                     bool search, int32_t* match2, int* out_nmatches) {
+  if (!m || !in || !n_in_view || in->n1 < 0 || in->n_levels < 1 || in->n_levels > kProjMaxLevels || (in->n1 > 0 && !in_view) ||
+      (search && (!match2 || !out_nmatches || in->n2 < 0 || in->n2 > 65535))) {
+    set_error("invalid argument (the frame may hold at most 65535 features, %d pyramid levels)", kProjMaxLevels);
+    return RGBL_ERR_INVALID;
+  }
+  if (in->n1 >= (1 << 20)) { set_error("at most 2^20 - 1 map points per call (a point's index travels in 20 bits of the resolve kernel's announcements)"); return RGBL_ERR_INVALID; }
+  const int n1 = in->n1, n2 = search ? in->n2 : 0;
+  *n_in_view = 0;
+  if (search) {
+    *out_nmatches = 0;
+    for (int i = 0; i < n2; ++i) match2[i] = -1;
+  }
+  if (n1 == 0) return RGBL_OK;
+  const bool do_search = search && n2 > 0;
+  rgbl_map_points* pool = in->pool;
+  if (pool ? (!in->slot1 || pool->device != m->device)
+           : (!in->world_pos1 || !in->normal1 || !in->min_dist1 || !in->max_dist1 || (do_search && !in->mp_desc1))) {
+    set_error("map points: either host arrays (world_pos1, normal1, min_dist1, max_dist1, mp_desc1) or a pool on the matcher's device with slot1");
+    return RGBL_ERR_INVALID;
+  }
+  if (do_search && !in->mp_observed1) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  const rgbl_frustum_record none = {-1.f, -1.f, 0.f, 0.f, 0.f, 0};
+  bool any = !in->consider1;
+  for (int i = 0; i < n1 && !any; ++i) any = in->consider1[i] != 0;
+  if (!any) {   // nothing to project: what isInFrustum would have left is known here
+    memset(in_view, 0, (size_t)n1);
+    if (rec) for (int i = 0; i < n1; ++i) rec[i] = none;
+    return RGBL_OK;
+  }
+  std::unique_lock<std::mutex> pool_lock;
+  if (pool) {
+    pool_lock = std::unique_lock<std::mutex>(pool->mu);
+    for (int i = 0; i < n1; ++i)
+      if (in->slot1[i] < 0 || in->slot1[i] >= pool->cap) { set_error("map point pool: slot %d outside [0, %d)", in->slot1[i], pool->cap); return RGBL_ERR_INVALID; }
+  }
+  RGBL_HIP(hipSetDevice(m->device));
+  StreamDrain drain(m->stream);  // error returns included; declared behind pool_lock: the stream is drained before the pool is released
+  HostCall hc(m);
+  hipStream_t s = hc.s;
+  FrustumDev F;
+  memset(&F, 0, sizeof(F));
+  ProjDev P;
+  memset(&P, 0, sizeof(P));
+  F.n1 = n1; P.n1 = n1; P.n2 = n2;
+  RGBL_TRY(hc.begin([&]() -> int {
+    if (in->consider1) hc.put(&F.consider1, in->consider1, (size_t)n1);
+    if (pool) {
+      hc.put(&F.slot1, in->slot1, (size_t)n1);
+      F.wpos = pool->d_wpos; F.normal = pool->d_normal; F.min_dist = pool->d_min; F.max_dist = pool->d_max; F.desc = pool->d_desc;
+    } else {
+      hc.put(&F.wpos, in->world_pos1, (size_t)n1 * 3);
+      hc.put(&F.normal, in->normal1, (size_t)n1 * 3);
+      hc.put(&F.min_dist, in->min_dist1, (size_t)n1);
+      hc.put(&F.max_dist, in->max_dist1, (size_t)n1);
+      if (do_search) hc.put(&P.mpdesc1, in->mp_desc1, (size_t)n1 * 32);
+    }
+    if (do_search) {
+      hc.put(&P.obs1, in->mp_observed1, (size_t)n1);
+      RGBL_TRY(put_features(hc, in->device2, n2, in->desc2, in->kp2_xy, in->kp2_octave, in->uright2, &P.desc2, &P.xy2, &P.oct2, &P.ur2));
+      if (in->blocked2) hc.put(&P.blocked2, in->blocked2, (size_t)n2);
+      F.valid1 = hc.scratch<uint8_t>(n1);
+      F.proj1 = hc.scratch<float>((size_t)n1 * 3);
+      F.level1 = hc.scratch<int32_t>(n1);
+      F.viewcos1 = hc.scratch<float>(n1);
+      if (pool) { F.mpdesc1 = hc.scratch<uint8_t>((size_t)n1 * 32); P.mpdesc1 = F.mpdesc1; }
+      P.valid1 = F.valid1; P.proj1 = F.proj1; P.level1 = F.level1; P.viewcos1 = F.viewcos1;
+    }
+    F.in_view = hc.result<uint8_t>(n1);   // the results back to back: one copy back
+    if (rec) F.rec = hc.result<rgbl_frustum_record>(n1);
+    if (do_search) greedy_layout(hc, P);
+    return RGBL_OK;
+  }));
+  memcpy(F.Rcw, in->Rcw, sizeof(F.Rcw));
+  memcpy(F.tcw, in->tcw, sizeof(F.tcw));
+  memcpy(F.Ow, in->Ow, sizeof(F.Ow));
+  memcpy(F.K, in->K, sizeof(F.K));
+  memcpy(F.bounds, in->grid, sizeof(F.bounds));
+  F.mbf = in->mbf; F.log_scale = in->log_scale_factor; F.cos_limit = in->viewing_cos_limit;
+  F.far_points = in->far_points; F.th_far = in->th_far_points; F.n_levels = in->n_levels;
+  m->timer.begin("k_frustum", s);
+  hipLaunchKernelGGL(k_frustum, dim3((n1 + 255) / 256), dim3(256), 0, s, F);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  if (do_search) {
+    memcpy(P.grid, in->grid, sizeof(P.grid));
+    P.th = in->th;
+    P.nnratio = in->nnratio;
+    for (int l = 0; l < kProjMaxLevels; ++l) P.scale[l] = l < in->n_levels ? in->scale_factors[l] : 1.f;
+    RGBL_TRY(greedy_search(m, s, P, in->device2, {k_local_candidates, k_local_resolve<true>, k_local_resolve<false>, "k_local_candidates", "k_local_resolve"}));
+  }
+  RGBL_TRY(hc.fetch());
+  memcpy(in_view, hc.host(F.in_view), (size_t)n1);
+  if (rec) memcpy(rec, hc.host(F.rec), sizeof(rgbl_frustum_record) * (size_t)n1);
+  int nv = 0;
+  for (int i = 0; i < n1; ++i) nv += in_view[i] != 0;
+  *n_in_view = nv;
+  if (do_search) {
+    const int32_t* choice = hc.host(P.choice);
+    int nmatches = 0;
+    for (int i = 0; i < n1; ++i)
+      if (choice[i] >= 0) { match2[choice[i]] = i; ++nmatches; }  // a later point overwrites an unobserved earlier one
+    *out_nmatches = nmatches;
+  }
+  return RGBL_OK;
+}
+}  // namespace
+
+int rgbl_frustum_cull(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t* in_view, rgbl_frustum_record* rec, int* n_in_view) {
+  return track_local_core(m, in, in_view, rec, n_in_view, false, nullptr, nullptr);
+}
+
+int rgbl_track_local_points(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t* in_view, rgbl_frustum_record* rec,
+                            int* n_to_match, int32_t* match2, int* out_nmatches) {
+  return track_local_core(m, in, in_view, rec, n_to_match, true, match2, out_nmatches);
+}
+
+// test hooks (tests/test_logf_glibc.py): the restatement on the host, and the same function compiled for the device
+float rgbl_test_logf(float x) { return rgbl::logf_glibc(x); }
+int rgbl_test_logf_device(const float* x, float* y, int n) {
+  if (!x || !y || n < 1) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  float *d_x = nullptr, *d_y = nullptr;
+  RGBL_HIP(hipMalloc(reinterpret_cast<void**>(&d_x), sizeof(float) * (size_t)n));
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_y), sizeof(float) * (size_t)n);
+  if (e == hipSuccess) e = hipMemcpy(d_x, x, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_test_logf, dim3((n + 255) / 256), dim3(256), 0, 0, (const float*)d_x, d_y, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(y, d_y, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
+  (void)hipFree(d_x);
+  if (d_y) (void)hipFree(d_y);
+  if (e != hipSuccess) { set_error("logf test hook: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
   return RGBL_OK;
 }
 

@@ -395,6 +395,43 @@ def _dev(d, key):
     return f.h if f is not None else None
 
 
+class MapPointPool:
+    """rgbl_map_points: what isInFrustum and the matcher read from the map points (GetWorldPos, GetNormal, mfMinDistance,
+    mfMaxDistance, GetDescriptor), resident on the device in caller-numbered slots of 64 bytes.  Thread-safe."""
+
+    def __init__(self, capacity, device=0, lib=None):
+        self.lib = lib or L.load()
+        self.h = C.c_void_p()
+        L.check(self.lib, self.lib.rgbl_map_points_create(device, int(capacity), C.byref(self.h)))
+
+    def capacity(self):
+        return self.lib.rgbl_map_points_capacity(self.h)
+
+    def reserve(self, capacity):
+        L.check(self.lib, self.lib.rgbl_map_points_reserve(self.h, int(capacity)))
+
+    def update(self, slot, world_pos=None, normal=None, min_dist=None, max_dist=None, desc=None):
+        """Entry k of every array that is given goes to slot[k]; a field that is None stays as it is."""
+        slot = np.ascontiguousarray(slot, np.int32)
+        a = [None if v is None else np.ascontiguousarray(v, dt) for v, dt in
+             ((world_pos, np.float32), (normal, np.float32), (min_dist, np.float32), (max_dist, np.float32), (desc, np.uint8))]
+        for v, per in zip(a, (3, 3, 1, 1, 32)):
+            if v is not None and v.size != per * len(slot):
+                raise ValueError("MapPointPool.update: an array does not hold one entry per slot")
+        L.check(self.lib, self.lib.rgbl_map_points_update(self.h, len(slot), L.ptr(slot), *[L.ptr(v) for v in a]))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.rgbl_map_points_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ORBmatcher:
     TH_LOW, TH_HIGH, HISTO_LENGTH = 50, 100, 30  # src/ORBmatcher.cc:35-37
 
@@ -654,6 +691,11 @@ class ORBmatcher:
         return match, n.value
 
     def SearchLocalPoints(self, pts, th):
+        """Tracking::SearchLocalPoints.  pts with the map points themselves (world_pos1 ..., or pool + slot1; cases.make_local_map_case):
+        the isInFrustum loop and the matcher in one call (prepare_TrackLocalPoints) -> (in_view, records, nToMatch, match2, nmatches).
+        pts with what the loop left in the MapPoints (proj1 ...; cases.make_local_points_case): the matcher alone -> (match2, nmatches)."""
+        if "proj1" not in pts:
+            return self.prepare_TrackLocalPoints(pts, th)()
         return self.prepare_SearchLocalPoints(pts, th)()
 
     def prepare_SearchLocalPoints(self, pts, th):
@@ -688,6 +730,79 @@ class ORBmatcher:
         def call(_keep=keep):   # the closure owns the input arrays
             L.check(self.lib, fn(h, pP, pm, pn))
             return match2, n.value
+        return call
+
+    def _track_local_input(self, case, th, keep):
+        """rgbl_track_local_input from a cases.make_local_map_case dict; with case["pool"] (a MapPointPool) and case["slot1"] the
+        map points come from the pool's slots instead of the host arrays."""
+        def arr(v, dt):
+            a = np.ascontiguousarray(v, dt)
+            keep.append(a)
+            return a.ctypes.data
+        P = L.TrackLocalInput()
+        pool = case.get("pool")
+        if pool is not None:
+            P.pool, P.slot1 = pool.h, arr(case["slot1"], np.int32)
+            P.n1 = len(case["slot1"])
+        else:
+            P.n1 = len(case["world_pos1"])
+            P.world_pos1, P.normal1 = arr(case["world_pos1"], np.float32), arr(case["normal1"], np.float32)
+            P.min_dist1, P.max_dist1 = arr(case["min_dist1"], np.float32), arr(case["max_dist1"], np.float32)
+            P.mp_desc1 = arr(case["mp_desc1"], np.uint8)
+        if case.get("consider1") is not None:
+            P.consider1 = arr(case["consider1"], np.uint8)
+        P.mp_observed1 = arr(case["mp_observed1"], np.uint8)
+        P.n2 = len(case["kp2_xy"])
+        P.kp2_xy, P.kp2_octave = arr(case["kp2_xy"], np.float32), arr(case["kp2_octave"], np.int32)
+        P.uright2, P.desc2 = arr(case["uright2"], np.float32), arr(case["desc2"], np.uint8)
+        if case.get("blocked2") is not None:
+            P.blocked2 = arr(case["blocked2"], np.uint8)
+        for name, n in (("grid", 6), ("Rcw", 9), ("tcw", 3), ("Ow", 3), ("K", 4)):
+            for i in range(n):
+                getattr(P, name)[i] = float(case[name][i])
+        P.scale_factors = arr(case["scale_factors"], np.float32)
+        P.n_levels = int(case.get("n_levels", len(case["scale_factors"])))
+        P.th, P.nnratio = float(th), float(self.mfNNratio)
+        P.device2 = _dev(case, "device2")
+        P.mbf, P.log_scale_factor = float(case["mbf"]), float(case["log_scale_factor"])
+        P.viewing_cos_limit = float(case["viewing_cos_limit"])
+        P.far_points, P.th_far_points = int(case["far_points"]), float(case["th_far_points"])
+        return P
+
+    def FrustumCull(self, case):
+        return self.prepare_FrustumCull(case)()
+
+    def prepare_FrustumCull(self, case):
+        """Frame::isInFrustum (Frame.cc:602-664) + MapPoint::PredictScale for every considered local map point, the loop of
+        Tracking::SearchLocalPoints (Tracking.cc:3399-3420).  Returns (in_view uint8, records of _lib.FRUSTUM_DTYPE, nToMatch)."""
+        keep = []
+        P = self._track_local_input(case, 1.0, keep)
+        in_view = np.zeros(P.n1, np.uint8)
+        rec = np.zeros(P.n1, L.FRUSTUM_DTYPE)
+        n = C.c_int(0)
+        fn, h, pP, pv, pr, pn = self.lib.rgbl_frustum_cull, self.h, C.byref(P), L.ptr(in_view), L.ptr(rec), C.byref(n)
+
+        def call(_keep=keep):
+            L.check(self.lib, fn(h, pP, pv, pr, pn))
+            return in_view, rec, n.value
+        return call
+
+    def prepare_TrackLocalPoints(self, case, th, records=True):
+        """Tracking::SearchLocalPoints from its isInFrustum loop on (Tracking.cc:3399-3448) in one call: the cull above and
+        ORBmatcher::SearchByProjection(F, mvpLocalMapPoints, th, bFarPoints, thFarPoints) behind it.
+        Returns (in_view, records, nToMatch, match2: map point index per frame feature or -1, nmatches)."""
+        keep = []
+        P = self._track_local_input(case, th, keep)
+        in_view = np.zeros(P.n1, np.uint8)
+        rec = np.zeros(P.n1, L.FRUSTUM_DTYPE) if records else None
+        match2 = np.zeros(P.n2, np.int32)
+        n, nm = C.c_int(0), C.c_int(0)
+        fn, h, pP, pv, pr, pn, pm, pnm = (self.lib.rgbl_track_local_points, self.h, C.byref(P), L.ptr(in_view), L.ptr(rec), C.byref(n),
+                                          L.ptr(match2), C.byref(nm))
+
+        def call(_keep=keep):
+            L.check(self.lib, fn(h, pP, pv, pr, pn, pm, pnm))
+            return in_view, rec, n.value, match2, nm.value
         return call
 
     def SearchForInitialization(self, case, windowSize=100):
@@ -1102,3 +1217,69 @@ class KeyFrameDatabase:
                     merge.append(kf)
                 seen.add(kf)
         return loop, merge
+
+def frustum_terms(case):
+    """The float32 intermediates of isInFrustum for every point, in the reference's order: Pc (x, y, z), invz, u, v, |Pc|,
+    dist = |P - Ow|, viewCos, ratio = mfMaxDistance / dist."""
+    f = np.float32
+    P = np.ascontiguousarray(case["world_pos1"], f).reshape(-1, 3)
+    Pn = np.ascontiguousarray(case["normal1"], f).reshape(-1, 3)
+    R, t, Ow, K = [np.asarray(case[k], f) for k in ("Rcw", "tcw", "Ow", "K")]
+    with np.errstate(all="ignore"):
+        p0, p1, p2 = P[:, 0], P[:, 1], P[:, 2]
+
+        def row(k):
+            return ((R[3 * k] * p0 + R[3 * k + 1] * p1) + R[3 * k + 2] * p2) + t[k]
+        x, y, z = row(0), row(1), row(2)
+
+        def norm(a, b, c):
+            return np.sqrt((a * a + b * b) + c * c)
+        o0, o1, o2 = p0 - Ow[0], p1 - Ow[1], p2 - Ow[2]
+        dist = norm(o0, o1, o2)
+        return dict(x=x, y=y, z=z, invz=f(1) / z, u=(K[0] * x) / z + K[2], v=(K[1] * y) / z + K[3], pc_dist=norm(x, y, z), dist=dist,
+                    view_cos=((o0 * Pn[:, 0] + o1 * Pn[:, 1]) + o2 * Pn[:, 2]) / dist, ratio=np.asarray(case["max_dist1"], f) / dist)
+
+
+def frustum_restatement(case):
+    """Frame::isInFrustum (src/Frame.cc:602-664, single camera) + MapPoint::PredictScale (src/MapPoint.cc:531-546) for the
+    points of a cases.make_local_map_case dict, in numpy float32 in the reference's order (three-term sums left to right, as
+    csrc/frustum_math.h) with the C library's logf.  Returns (in_view uint8, records of _lib.FRUSTUM_DTYPE, stage): stage 0 =
+    not considered, 1 .. 4 = rejected by depth / image bounds / distance / viewing angle, 5 = in view."""
+    f = np.float32
+    n1 = len(case["world_pos1"])
+    consider = np.ones(n1, bool) if case.get("consider1") is None else np.asarray(case["consider1"]) != 0
+    minX, minY, maxX, maxY = [f(v) for v in np.asarray(case["grid"], f)[:4]]
+    rec = np.zeros(n1, L.FRUSTUM_DTYPE)
+    rec["proj_x"] = -1
+    rec["proj_y"] = -1
+    stage = np.zeros(n1, np.int32)
+    if n1 == 0:
+        return np.zeros(0, np.uint8), rec, stage
+    with np.errstate(all="ignore"):
+        T = frustum_terms(case)
+        z, u, v, invz, pc_dist, dist, view_cos, ratio = [T[k] for k in ("z", "u", "v", "invz", "pc_dist", "dist", "view_cos", "ratio")]
+        max_d, min_d = f(1.2) * np.asarray(case["max_dist1"], f), f(0.8) * np.asarray(case["min_dist1"], f)
+        r1 = z < f(0)
+        r2 = (u < minX) | (u > maxX) | (v < minY) | (v > maxY)
+        r3 = (dist < min_d) | (dist > max_d)
+        r4 = view_cos < f(case["viewing_cos_limit"])
+        stage[:] = np.where(r1, 1, np.where(r2, 2, np.where(r3, 3, np.where(r4, 4, 5))))
+        stage[~consider] = 0
+        keep_uv = stage >= 3
+        rec["proj_x"][keep_uv] = u[keep_uv]
+        rec["proj_y"][keep_uv] = v[keep_uv]
+        seen = stage == 5
+        rec["proj_xr"][seen] = (u - f(case["mbf"]) * invz)[seen]
+        rec["depth"][seen] = pc_dist[seen]
+        rec["view_cos"][seen] = view_cos[seen]
+        libm = C.CDLL("libm.so.6")
+        libm.logf.restype, libm.logf.argtypes = C.c_float, [C.c_float]
+        lsf, n_levels = f(case["log_scale_factor"]), int(case.get("n_levels", len(case["scale_factors"])))
+        for i in np.nonzero(seen)[0]:
+            r = ratio[i]
+            level = 0
+            if r > 0 and np.isfinite(r):   # else: the reference's float -> int conversion is undefined; the device says 0
+                c = np.ceil(f(libm.logf(float(r))) / lsf)
+                level = 0 if not c >= 0 else (n_levels - 1 if c >= n_levels else int(c))
+            rec["level"][i] = level
+    return seen.astype(np.uint8), rec, stage

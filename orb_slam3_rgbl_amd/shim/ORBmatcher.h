@@ -4,6 +4,7 @@
 //   SearchByProjection(CurrentFrame, LastFrame, th, bMono)           (ORBmatcher.h:48,  ORBmatcher.cc:1676-1887)
 //   SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints)  (ORBmatcher.h:45,  ORBmatcher.cc:43-213)
 //   SearchByBoW(pKF, F, vpMapPointMatches)                           (ORBmatcher.h:57,  ORBmatcher.cc:223-425)
+//   SearchLocalPoints(F, vpLocalMapPoints, th, ...)  NEW: Tracking::SearchLocalPoints' isInFrustum loop + the matcher in one call
 // The other Search*/Fuse members of the reference class are untouched (SURVEY.md §8(f) lists them as "next");
 // in the ORB_SLAM3 tree this header is merged into the existing one, see INTEGRATION.md.
 //
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "../../include/rgbl_frontend.h"
+#include "LocalMap.h"
 #include "cv_compat.h"
 
 namespace rgbl_shim {
@@ -616,6 +618,123 @@ class ORBmatcher {
     }
     for (int i2 = 0; i2 < n2; ++i2)
       if (match2[i2] >= 0) F.mvpMapPoints[i2] = vpMapPoints[match2[i2]];
+    return nmatches;
+  }
+
+  // Tracking::SearchLocalPoints from its second loop on (Tracking.cc:3399-3448) in ONE device call: Frame::isInFrustum
+  // (Frame.cc:602-664) with MapPoint::PredictScale for every local map point that was not seen in this frame and is not bad,
+  // and the SearchByProjection above on the points in view.  Writes what the reference's loop writes: mbTrackInView,
+  // mTrackProjX / Y and, for a point in view, mTrackProjXR, mTrackDepth, mnTrackScaleLevel, mTrackViewCos; IncreaseVisible();
+  // F.mmProjectPoints; F.mvpMapPoints.  Returns the matcher's return value (0 when nothing is in view: the reference does not
+  // call it then), *nToMatch = the loop's counter.
+  // pLocalMap (shim/LocalMap.h): the map points are read from their device-resident slots - a point without one is uploaded
+  // on the spot; nullptr: positions, normals, distances and descriptors are flattened and uploaded with the call.
+  // Needs MapPoint::GetMinDistance() / GetMaxDistance(), the raw mfMinDistance / mfMaxDistance.
+  template <class FrameT, class MapPointT>
+  int SearchLocalPoints(FrameT& F, const std::vector<MapPointT*>& vpLocalMapPoints, const float th, const bool bFarPoints,
+                        const float thFarPoints, const float viewingCosLimit = 0.5f, rgbl_shim::DeviceLocalMap* pLocalMap = nullptr,
+                        int* nToMatch = nullptr) {
+    if (nToMatch) *nToMatch = 0;
+    if (!mpHandle) return 0;
+    if (F.Nleft != -1) {
+      std::cerr << "[ORBmatcher] SearchByProjection: fisheye stereo rigs (Nleft != -1) are not covered by the device path" << std::endl;
+      return 0;
+    }
+    const int n1 = (int)vpLocalMapPoints.size(), n2 = F.N;
+    std::vector<uint8_t> consider(n1, 0), observed(n1, 0), blocked(n2, 0), desc1;
+    std::vector<float> pos, normal, dmin, dmax, xy2((size_t)n2 * 2);
+    std::vector<int32_t> slot, oct2(n2);
+    if (pLocalMap) slot.assign(n1, 0);
+    else { pos.assign((size_t)n1 * 3, 0.f); normal.assign((size_t)n1 * 3, 0.f); dmin.assign(n1, 0.f); dmax.assign(n1, 0.f); desc1.assign((size_t)n1 * 32, 0); }
+    std::vector<MapPointT*> vpNew;
+    std::vector<int> vnNew;
+    // from the first slot read until the device call is back, slots that LocalMapping erases are not handed to other points
+    struct SearchBracket {
+      rgbl_shim::DeviceLocalMap* p;
+      explicit SearchBracket(rgbl_shim::DeviceLocalMap* q) : p(q) { if (p) p->BeginSearch(); }
+      ~SearchBracket() { if (p) p->EndSearch(); }
+    } bracket(pLocalMap);
+    for (int i = 0; i < n1; ++i) {
+      MapPointT* pMP = vpLocalMapPoints[i];
+      if (pMP->mnLastFrameSeen == F.mnId) continue;   // Tracking.cc:3406-3409
+      if (pMP->isBad()) continue;
+      consider[i] = 1;
+      observed[i] = pMP->Observations() > 0 ? 1 : 0;
+      if (pLocalMap) {
+        slot[i] = pLocalMap->SlotOf(pMP);
+        if (slot[i] < 0) { vpNew.push_back(pMP); vnNew.push_back(i); }
+        continue;
+      }
+      const auto P = pMP->GetWorldPos();
+      const auto Pn = pMP->GetNormal();
+      for (int k = 0; k < 3; ++k) { pos[3 * (size_t)i + k] = P(k); normal[3 * (size_t)i + k] = Pn(k); }
+      dmin[i] = pMP->GetMinDistance();
+      dmax[i] = pMP->GetMaxDistance();
+      const cv::Mat d = pMP->GetDescriptor();
+      memcpy(&desc1[(size_t)i * 32], d.ptr<uint8_t>(), 32);
+    }
+    if (!vpNew.empty()) {
+      std::vector<int32_t> vnSlots;
+      if (!pLocalMap->Update(vpNew, &vnSlots)) return 0;
+      for (size_t k = 0; k < vnNew.size(); ++k) slot[vnNew[k]] = vnSlots[k];
+    }
+    for (int i = 0; i < n2; ++i) {
+      xy2[2 * (size_t)i] = F.mvKeysUn[i].pt.x;
+      xy2[2 * (size_t)i + 1] = F.mvKeysUn[i].pt.y;
+      oct2[i] = F.mvKeysUn[i].octave;
+      blocked[i] = (F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0) ? 1 : 0;
+    }
+    rgbl_track_local_input in{};
+    in.n1 = n1; in.consider1 = consider.data(); in.mp_observed1 = observed.data();
+    if (pLocalMap) { in.pool = pLocalMap->handle(); in.slot1 = slot.data(); }
+    else { in.world_pos1 = pos.data(); in.normal1 = normal.data(); in.min_dist1 = dmin.data(); in.max_dist1 = dmax.data(); in.mp_desc1 = desc1.data(); }
+    in.n2 = n2; in.kp2_xy = xy2.data(); in.kp2_octave = oct2.data(); in.uright2 = F.mvuRight.data();
+    in.desc2 = F.mDescriptors.template ptr<uint8_t>(); in.blocked2 = blocked.data();
+    in.grid[0] = FrameT::mnMinX; in.grid[1] = FrameT::mnMinY; in.grid[2] = FrameT::mnMaxX; in.grid[3] = FrameT::mnMaxY;
+    in.grid[4] = FrameT::mfGridElementWidthInv; in.grid[5] = FrameT::mfGridElementHeightInv;
+    in.scale_factors = F.mvScaleFactors.data();
+    in.n_levels = F.mnScaleLevels;
+    in.th = th; in.nnratio = mfNNratio;
+    in.device2 = rgbl_shim::device_frame_of(F, 0);
+    // mRcw, mtcw (private in Frame) are mTcw.rotationMatrix() / translation() (Frame::UpdatePoseMatrices, Frame.cc:562-569)
+    const auto Tcw = F.GetPose();
+    const auto Rcw = Tcw.rotationMatrix();
+    const auto tcw = Tcw.translation();
+    const auto Ow = F.GetOw();
+    for (int i = 0; i < 3; ++i) {
+      in.tcw[i] = tcw(i); in.Ow[i] = Ow(i);
+      for (int j = 0; j < 3; ++j) in.Rcw[3 * i + j] = Rcw(i, j);
+    }
+    for (int i = 0; i < 4; ++i) in.K[i] = F.mpCamera->getParameter(i);
+    in.mbf = F.mbf; in.log_scale_factor = F.mfLogScaleFactor; in.viewing_cos_limit = viewingCosLimit;
+    in.far_points = bFarPoints ? 1 : 0; in.th_far_points = thFarPoints;
+    std::vector<uint8_t> inView(n1, 0);
+    std::vector<rgbl_frustum_record> rec(n1);
+    std::vector<int32_t> match2(n2, -1);
+    int nInView = 0, nmatches = 0;
+    if (rgbl_track_local_points(mpHandle, &in, inView.data(), rec.data(), &nInView, match2.data(), &nmatches) != RGBL_OK) {
+      std::cerr << "[ORBmatcher] " << rgbl_last_error() << std::endl;
+      return 0;
+    }
+    for (int i = 0; i < n1; ++i) {
+      if (!consider[i]) continue;
+      MapPointT* pMP = vpLocalMapPoints[i];
+      pMP->mbTrackInView = inView[i] != 0;           // Frame.cc:605-607, 629-630, 653-661
+      pMP->mTrackProjX = rec[i].proj_x;
+      pMP->mTrackProjY = rec[i].proj_y;
+      if (inView[i]) {
+        pMP->mTrackProjXR = rec[i].proj_xr;
+        pMP->mTrackDepth = rec[i].depth;
+        pMP->mnTrackScaleLevel = rec[i].level;
+        pMP->mTrackViewCos = rec[i].view_cos;
+        pMP->IncreaseVisible();                      // Tracking.cc:3411-3419
+        F.mmProjectPoints[pMP->mnId] = cv::Point2f(pMP->mTrackProjX, pMP->mTrackProjY);
+      }
+    }
+    if (nToMatch) *nToMatch = nInView;
+    if (nInView == 0) return 0;
+    for (int i2 = 0; i2 < n2; ++i2)
+      if (match2[i2] >= 0) F.mvpMapPoints[i2] = vpLocalMapPoints[match2[i2]];
     return nmatches;
   }
 
