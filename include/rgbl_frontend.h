@@ -157,7 +157,9 @@ int rgbl_extractor_get_candidates(rgbl_extractor* h, int frame, int level, rgbl_
  * resident pyramids are read directly (the reference reads mpORBextractor{Left,Right}->mvImagePyramid), so the stereo
  * path needs no pyramid download.  Outputs mvuRight / mvDepth (-1 = no match).
  * Host variant: frame 0 of the last call, host arrays, synchronous.  Device variant: the layout of
- * rgbl_extract_batch_device() for both sides (frame b at + b*cap), enqueued on the left handle's stream. */
+ * rgbl_extract_batch_device() for both sides (frame b at + b*cap), enqueued on the left handle's stream.
+ * At most 65535 keypoints per view: n_left, n_right and cap above that are refused with RGBL_ERR_INVALID; the per-frame counts must not exceed cap.
+ * Every octave must lie in 0 .. nlevels - 1: the host variant refuses the call otherwise; the device variant cannot look at device data, so there this is the caller's contract. */
 int rgbl_stereo_matches(rgbl_extractor* left, rgbl_extractor* right, const rgbl_keypoint* kp_left,
                         const uint8_t* desc_left, int n_left, const rgbl_keypoint* kp_right,
                         const uint8_t* desc_right, int n_right, float mb, float mbf, float* out_uright,

@@ -1470,9 +1470,8 @@ int rgbl_event_wait(void* stream, void* ev) {
 }
 
 // ---- Frame::ComputeStereoMatches (Frame.cc:901-1071) ---------------------------------------------------------
-static int stereo_enqueue(rgbl_extractor* L, rgbl_extractor* R, int batch, const rgbl_keypoint* d_kpl, const uint8_t* d_dl,
-                          const int32_t* d_nl, const rgbl_keypoint* d_kpr, const uint8_t* d_dr, const int32_t* d_nr, int cap,
-                          float mb, float mbf, float* d_uright, float* d_depth) {
+// what the host can refuse before anything is copied or launched (both entry points call it first)
+static int stereo_check(const rgbl_extractor* L, const rgbl_extractor* R, int batch, int cap, float mb) {
   if (L->cfg.width != R->cfg.width || L->cfg.height != R->cfg.height || L->L != R->L || L->device != R->device ||
       L->cfg.scale_factor != R->cfg.scale_factor) {
     set_error("left and right extractor differ in geometry");
@@ -1483,6 +1482,15 @@ static int stereo_enqueue(rgbl_extractor* L, rgbl_extractor* R, int batch, const
     return RGBL_ERR_INVALID;
   }
   if (!(mb > 0) || cap < 1) { set_error("invalid stereo parameters"); return RGBL_ERR_INVALID; }
+  // k_stereo_match merges its lanes through the key (distance << 16) | right index
+  if (cap > 65535) { set_error("stereo matching: at most 65535 keypoints per view (cap %d)", cap); return RGBL_ERR_INVALID; }
+  return RGBL_OK;
+}
+
+static int stereo_enqueue(rgbl_extractor* L, rgbl_extractor* R, int batch, const rgbl_keypoint* d_kpl, const uint8_t* d_dl,
+                          const int32_t* d_nl, const rgbl_keypoint* d_kpr, const uint8_t* d_dr, const int32_t* d_nr, int cap,
+                          float mb, float mbf, float* d_uright, float* d_depth) {
+  RGBL_TRY(stereo_check(L, R, batch, cap, mb));
   RGBL_HIP(hipSetDevice(L->device));
   const size_t need = (size_t)batch * cap;
   if (need > L->stereo_sad_count) {
@@ -1533,8 +1541,18 @@ int rgbl_stereo_matches(rgbl_extractor* left, rgbl_extractor* right, const rgbl_
     return RGBL_ERR_INVALID;
   }
   if (n_left == 0) return RGBL_OK;
-  RGBL_HIP(hipSetDevice(left->device));
   const int cap = std::max(std::max(n_left, n_right), 1);
+  RGBL_TRY(stereo_check(left, right, 1, cap, mb));
+  // the kernels index the scale tables and the level geometry with the octave
+  for (int side = 0; side < 2; ++side) {
+    const rgbl_keypoint* kp = side ? kp_right : kp_left;
+    for (int i = 0, n = side ? n_right : n_left; i < n; ++i)
+      if (kp[i].octave < 0 || kp[i].octave >= left->L) {
+        set_error("stereo matching: %s keypoint %d has octave %d, outside 0 .. %d", side ? "right" : "left", i, kp[i].octave, left->L - 1);
+        return RGBL_ERR_INVALID;
+      }
+  }
+  RGBL_HIP(hipSetDevice(left->device));
   const size_t rec = (size_t)cap * (sizeof(rgbl_keypoint) + 32);
   const size_t bytes = 2 * rec + 256 + 2 * (size_t)cap * sizeof(float) + 1024;
   if (bytes > left->stereo_stage_bytes) {

@@ -1,6 +1,6 @@
 """Randomised device-vs-oracle cases (image sizes / feature counts / level counts / thresholds for the extractor, image sizes
 that are no multiples of the dilation tile and every structuring element for the depth module, train-set sizes around the
-launch-slice and sweep boundaries for the Hamming scan).  One function = one random case drawn from `rng`, checked bit for
+launch-slice and sweep boundaries for the Hamming scan, stereo pairs of random size, level count, feature count and disparity).  One function = one random case drawn from `rng`, checked bit for
 bit against the oracle; used by tests/test_fuzz_gpu.py (fixed seeds, `-m gpu`; RGBL_FUZZ_SECONDS adds time-boxed fresh
 seeds) and by tools/gpu_random_*_checks.py."""
 import numpy as np
@@ -105,5 +105,46 @@ def node_search_case(lib, rng):
     return "SearchByBoW(KF, KF) %5d features, %3d nodes: %d matches" % (n, nodes, m)
 
 
-CASES = {"node_search": node_search_case, "extractor": extractor_case, "low_contrast": low_contrast_case, "depth": depth_case, "hamming": hamming_case,
+def stereo_draw(rng):
+    """the random parameters of stereo_case (apart, so that a seed's keypoint counts can be looked up with the oracle alone)"""
+    while True:   # the level rule of extractor_case
+        w, h = int(rng.integers(200, 1400)), int(rng.integers(120, 700))
+        nlevels = int(rng.integers(1, 9))
+        sizes = [(round(w / 1.2 ** l), round(h / 1.2 ** l)) for l in range(nlevels)]
+        if all(1 <= round((wl - 32) / max(hl - 32, 1) - 0.05) and round((wl - 32) / max(hl - 32, 1) + 0.05) <= 16 for wl, hl in sizes) and \
+                min(w, h) / 1.2 ** (nlevels - 1) >= 80:
+            break
+    nf = int(rng.choice([300, 2000, 3500, 6000]))
+    ini, mn = int(rng.choice([12, 20, 30])), int(rng.choice([5, 7]))
+    dscale = float(rng.choice([0.25, 0.5, 1.0, 1.5]))
+    # (mb, mbf) of the reference's KITTI00-02 and EuRoC stereo settings: mb = mbf / fx
+    mb, mbf = [(386.1448 / 718.856, 386.1448), (47.90639384423901 / 435.2046959714599, 47.90639384423901)][int(rng.integers(0, 2))]
+    return w, h, nlevels, nf, ini, mn, dscale, mb, mbf, int(rng.integers(0, 1000))
+
+
+def stereo_case(lib, rng):
+    """Frame::ComputeStereoMatches on the keypoints of two device extractions, through the host-pointer call: nfeatures up to 6000 on
+    large images puts more than one tile of right keypoints (2048) and the filter's tail in front of the kernels with real keypoints"""
+    w, h, nlevels, nf, ini, mn, dscale, mb, mbf, seq = stereo_draw(rng)
+    left, right = pc.stereo_pair(seq, w, h, disparity_scale=dscale)
+    exl, exr = (F.ORBextractor(nf, 1.2, nlevels, ini, mn, w, h, lib=lib) for _ in range(2))
+    ol, orr = (O.Extractor(nf, 1.2, nlevels, ini, mn) for _ in range(2))
+    kl, dl, _ = exl(left)
+    kr, dr, _ = exr(right)
+    okl, odl, _ = ol(left)
+    okr, odr, _ = orr(right)
+    pc.assert_keypoints_equal(kl, okl, "left")
+    pc.assert_keypoints_equal(kr, okr, "right")
+    assert np.array_equal(dl, odl) and np.array_equal(dr, odr)
+    ur, dp = F.ComputeStereoMatches(exl, exr, kl, dl, kr, dr, mb, mbf)
+    our, odp = O.stereo_matches(ol, orr, okl, odl, okr, odr, mb, mbf)
+    assert np.array_equal(pc.bits(ur), pc.bits(our)), "mvuRight"
+    assert np.array_equal(pc.bits(dp), pc.bits(odp)), "mvDepth"
+    exl.close(); exr.close()
+    stereo_case.last = (len(kl), len(kr))
+    return "stereo %4dx%-4d levels %d nfeatures %4d FAST %2d/%d disparity x%.2f mb %.3f -> %d x %d keypoints, %d matches" % (
+        w, h, nlevels, nf, ini, mn, dscale, mb, len(kl), len(kr), int((odp > 0).sum()))
+
+
+CASES = {"stereo": stereo_case, "node_search": node_search_case, "extractor": extractor_case, "low_contrast": low_contrast_case, "depth": depth_case, "hamming": hamming_case,
          "greedy_search": greedy_search_case}
