@@ -287,10 +287,12 @@ __global__ __launch_bounds__(256) void k_hamming_mfma(const uint8_t* __restrict_
 // four-bit float +-4 (0x6 / 0xE): train bit a -> 4 (1 - 2a), query bit b -> -4 (1 - 2b); both operands carry the block scale
 // 2^4 (E8M0 byte 131), so a product is +-4096 and the 256-long sum is 8192 * hamming - 2^20 - the numbers of the i8 form,
 // exact in the f32 accumulator (all values are integers below 2^22).  The accumulator starts at 2^20 + row, the tracking
-// key comes out as a float and is tracked with v_med3_f32 / v_min_f32.  Dword w of a descriptor is the 32 values one lane
+// key comes out as a float and is tracked with two v_med3_f32 per value (bf_track_rel_f).  Dword w of a descriptor is the 32 values one lane
 // group feeds to step w / 2 (group w & 1); which bit lands in which nibble of the group does not matter as long as train
-// and query agree.  Everything else - query tiles in VGPRs, 64 train rows per double-buffered LDS stage, relative keys,
+// and query agree.  Everything else - query tiles in VGPRs, kBfStageRowsF4 train rows per double-buffered LDS stage, relative keys,
 // sweeps - as in k_hamming_mfma.  grid = (ceil(cap / 256), n_pairs), block = 256.
+constexpr int kBfStageRowsF4 = 64;  // train rows per LDS stage of k_hamming_fp4: a multiple of 32, the kernel follows it
+constexpr int kBfStageLoadsF4 = kBfStageRowsF4 * 8 / 256;  // dwords of a stage per work-item (32 rows apart)
 constexpr int kBfRowBytesF4 = 144;  // 128 bytes of nibbles + 16: the 16-byte fragment reads of a wave spread over the banks
 constexpr float kBfIdleF = 1073741824.f;
 
@@ -306,14 +308,27 @@ __device__ __forceinline__ v4i bf_expand_fp4(uint32_t x) {  // bit j of x -> nib
   }
   return r;
 }
-__device__ __forceinline__ void bf_track_rel_f(float& best, float& second, float cur) {
+// Two vector instructions per accumulator value, both visible to the compiler: it is the compiler's hazard recogniser that
+// puts the wait states between the last MFMA of a tile and the first read of its accumulator, and it does not look into
+// inline assembly.  min(a, b) is written as med3(a, b, -inf): fminf() under strict floating-point rules costs a
+// canonicalising v_max_f32 x, x in front of every v_min_f32, the median intrinsic takes its operands as they are (no NaNs
+// here, all values are integers).  `neg_inf` is -infinity in a register the compiler cannot see through (bf_neg_inf).
+__device__ __forceinline__ float bf_neg_inf() {
+  float v = -INFINITY;
+#ifndef RGBL_EMU
+  asm("" : "+s"(v));  // opaque: keeps med3(a, b, -inf) from being folded back into a canonicalising minimum
+#endif
+  return v;
+}
+__device__ __forceinline__ void bf_track_rel_f(float& best, float& second, float cur, float neg_inf) {
 #ifdef RGBL_EMU
   const float hi = best > cur ? best : cur;
   second = second < hi ? second : hi;
+  best = best < cur ? best : cur;
 #else
-  asm("v_med3_f32 %0, %1, %2, %3" : "=v"(second) : "v"(best), "v"(cur), "v"(second));
+  second = __builtin_amdgcn_fmed3f(best, cur, second);  // best <= second always: the median is the new second
+  best = __builtin_amdgcn_fmed3f(best, cur, neg_inf);
 #endif
-  best = fminf(best, cur);  // one v_min_f32 (a compare + select under strict floating-point rules otherwise); no NaNs here
 }
 
 __global__ __launch_bounds__(256) void k_hamming_fp4(const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_rows,
@@ -321,7 +336,7 @@ __global__ __launch_bounds__(256) void k_hamming_fp4(const uint8_t* __restrict__
                                                      const int32_t* __restrict__ pair_b, int32_t* __restrict__ best_idx,
                                                      int32_t* __restrict__ best_dist, int32_t* __restrict__ second_dist,
                                                      int splits, uint32_t* __restrict__ partial) {
-  __shared__ __attribute__((aligned(16))) uint8_t s_rows[2][kBfStageRows * kBfRowBytesF4];
+  __shared__ __attribute__((aligned(16))) uint8_t s_rows[2][kBfStageRowsF4 * kBfRowBytesF4];
   __shared__ uint32_t s_lut[256];  // byte -> its eight nibbles: the train rows are expanded with four table reads per dword
   // splits > 1 (one pair per call, rgbl_hamming_bf): the launch's frame index is a slice of the train set instead of a pair;
   // every slice leaves its packed best / second per query in `partial`, k_hamming_merge folds them (a frame against a frame is
@@ -346,10 +361,11 @@ __global__ __launch_bounds__(256) void k_hamming_fp4(const uint8_t* __restrict__
     const int qi = q_base + wave * 64 + ct * 32 + col;
     const uint4* src = reinterpret_cast<const uint4*>(desc + ((size_t)fa * cap + (qi < na ? qi : 0)) * 32);
     const uint4 lo = src[0], hi = src[1];
-    const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    // the lane's dword of every step picked value by value: an array indexed by `half` ends up in scratch memory
+    const uint32_t x[4] = {half ? lo.y : lo.x, half ? lo.w : lo.z, half ? hi.y : hi.x, half ? hi.w : hi.z};
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const v4i e = bf_expand_fp4(~(half ? x[2 * s + 1] : x[2 * s]));
+      const v4i e = bf_expand_fp4(~x[s]);
       bq[ct][s] = v8i{e[0], e[1], e[2], e[3], 0, 0, 0, 0};
     }
   }
@@ -361,20 +377,23 @@ __global__ __launch_bounds__(256) void k_hamming_fp4(const uint8_t* __restrict__
   const uint32_t kNone = (256u << 16) | 0xffffu;
   uint32_t out_best[2] = {kNone, kNone}, out_second[2] = {kNone, kNone};
 
-  // stage s of the whole scan = train rows [64 s, 64 s + 64); work-item tid expands dwords tid and tid + 256 of it
-  const int all_stages = (nb + kBfStageRows - 1) / kBfStageRows;
+  // stage s of the whole scan = kBfStageRowsF4 train rows; work-item tid expands dwords tid, tid + 256, ... of it
+  const int all_stages = (nb + kBfStageRowsF4 - 1) / kBfStageRowsF4;
   const int stages_per = (all_stages + splits - 1) / (splits > 1 ? splits : 1);
   const int s_begin = split * stages_per, n_stages = imin(all_stages, s_begin + stages_per);  // this launch slice: stages [s_begin, n_stages)
-  auto load_stage = [&](int stage, uint32_t& x0, uint32_t& x1) {
-    const int d0 = stage * (kBfStageRows * 8) + tid, d1 = d0 + 256;
-    x0 = (d0 >> 3) < nb ? train[d0] : 0u;
-    x1 = (d1 >> 3) < nb ? train[d1] : 0u;
+  auto load_stage = [&](int stage, uint32_t (&x)[kBfStageLoadsF4]) {
+#pragma unroll
+    for (int k = 0; k < kBfStageLoadsF4; ++k) {
+      const int d = stage * (kBfStageRowsF4 * 8) + k * 256 + tid;
+      x[k] = (d >> 3) < nb ? train[d] : 0u;
+    }
   };
-  uint32_t nx0 = 0, nx1 = 0;
-  if (n_stages > s_begin) load_stage(s_begin, nx0, nx1);
+  uint32_t nx[kBfStageLoadsF4] = {};
+  if (n_stages > s_begin) load_stage(s_begin, nx);
   float best[2] = {kBfIdleF, kBfIdleF}, second[2] = {kBfIdleF, kBfIdleF};
+  const float neg_inf = bf_neg_inf();
   int tiles_in_sweep = 0;
-  int sweep_start = s_begin * kBfStageRows;  // first train row of the sweep in progress
+  int sweep_start = s_begin * kBfStageRowsF4;  // first train row of the sweep in progress
   auto close_sweep = [&](int sweep_base) {
     // relative keys -> (distance << 16 | absolute index), folded into the results of the earlier sweeps
 #pragma unroll
@@ -390,23 +409,24 @@ __global__ __launch_bounds__(256) void k_hamming_fp4(const uint8_t* __restrict__
   };
   for (int stage = s_begin; stage < n_stages; ++stage) {
     uint8_t* buf = s_rows[stage & 1];
-    const uint32_t x0 = nx0, x1 = nx1;
-    if (stage + 1 < n_stages) load_stage(stage + 1, nx0, nx1);
+    uint32_t x[kBfStageLoadsF4];
+#pragma unroll
+    for (int k = 0; k < kBfStageLoadsF4; ++k) x[k] = nx[k];
+    if (stage + 1 < n_stages) load_stage(stage + 1, nx);
     {
       uint8_t* r0 = buf + (tid >> 3) * kBfRowBytesF4 + (tid & 7) * 16;
-      if (stage == s_begin) {  // the table is not published yet
-        *reinterpret_cast<v4i*>(r0) = bf_expand_fp4(x0);
-        *reinterpret_cast<v4i*>(r0 + 32 * kBfRowBytesF4) = bf_expand_fp4(x1);
-      } else {
-        *reinterpret_cast<v4i*>(r0) = v4i{(int)s_lut[x0 & 0xff], (int)s_lut[(x0 >> 8) & 0xff], (int)s_lut[(x0 >> 16) & 0xff], (int)s_lut[x0 >> 24]};
-        *reinterpret_cast<v4i*>(r0 + 32 * kBfRowBytesF4) = v4i{(int)s_lut[x1 & 0xff], (int)s_lut[(x1 >> 8) & 0xff], (int)s_lut[(x1 >> 16) & 0xff], (int)s_lut[x1 >> 24]};
+#pragma unroll
+      for (int k = 0; k < kBfStageLoadsF4; ++k) {
+        v4i* dst = reinterpret_cast<v4i*>(r0 + k * 32 * kBfRowBytesF4);
+        if (stage == s_begin) *dst = bf_expand_fp4(x[k]);  // the table is not published yet
+        else *dst = v4i{(int)s_lut[x[k] & 0xff], (int)s_lut[(x[k] >> 8) & 0xff], (int)s_lut[(x[k] >> 16) & 0xff], (int)s_lut[x[k] >> 24]};
       }
     }
     __syncthreads();
     if (!wave_has_queries) continue;
 #pragma unroll 1
-    for (int rt = 0; rt < 2; ++rt) {
-      const int row0 = stage * kBfStageRows + rt * 32;  // first train row of the tile
+    for (int rt = 0; rt < kBfStageRowsF4 / 32; ++rt) {
+      const int row0 = stage * kBfStageRowsF4 + rt * 32;  // first train row of the tile
       if (row0 >= nb) break;
       const uint8_t* frag = buf + (rt * 32 + col) * kBfRowBytesF4 + half * 16;
       v16f acc0 = c_init, acc1 = c_init;
@@ -421,13 +441,13 @@ __global__ __launch_bounds__(256) void k_hamming_fp4(const uint8_t* __restrict__
       ++tiles_in_sweep;
       if (row0 + 32 <= nb) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { bf_track_rel_f(best[0], second[0], acc0[r]); bf_track_rel_f(best[1], second[1], acc1[r]); }
+        for (int r = 0; r < 16; ++r) { bf_track_rel_f(best[0], second[0], acc0[r], neg_inf); bf_track_rel_f(best[1], second[1], acc1[r], neg_inf); }
       } else {  // the last tile of the train set: rows beyond it never win
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const bool live = row0 + (r & 3) + 8 * (r >> 2) + 4 * half < nb;
-          bf_track_rel_f(best[0], second[0], live ? acc0[r] : kBfIdleF);
-          bf_track_rel_f(best[1], second[1], live ? acc1[r] : kBfIdleF);
+          bf_track_rel_f(best[0], second[0], live ? acc0[r] : kBfIdleF, neg_inf);
+          bf_track_rel_f(best[1], second[1], live ? acc1[r] : kBfIdleF, neg_inf);
         }
       }
       if (row0 + 32 - sweep_start == kBfSweep) { close_sweep(sweep_start); sweep_start = row0 + 32; }
@@ -2347,8 +2367,8 @@ int rgbl_hamming_bf(rgbl_matcher* m, const uint8_t* desc_a, int na, const uint8_
   StreamDrain drain(m->stream);  // error returns included
   const int cap = std::max(std::max(na, nb), 1);
   // One pair per call: the query blocks alone (8 for 2000 descriptors) would leave most of the chip idle, so the train set is
-  // cut into slices of whole 64-row stages, one launch slice each, folded by k_hamming_merge (FP4 kernel only).
-  const int qblocks = (na + kBfQueriesPerBlock - 1) / kBfQueriesPerBlock, stages = (nb + kBfStageRows - 1) / kBfStageRows;
+  // cut into slices of whole stages, one launch slice each, folded by k_hamming_merge (FP4 kernel only).
+  const int qblocks = (na + kBfQueriesPerBlock - 1) / kBfQueriesPerBlock, stages = (nb + kBfStageRowsF4 - 1) / kBfStageRowsF4;
   int splits = 1;
   if (bf_on_matrix_cores(m) && bf_on_fp4(m) && m->bf_split)
     splits = std::max(1, std::min(std::min(16, stages / 4), 128 / std::max(qblocks, 1)));
