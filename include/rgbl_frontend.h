@@ -727,6 +727,58 @@ int rgbl_map_points_capacity(rgbl_map_points* p);
 int rgbl_map_points_update(rgbl_map_points* p, int n, const int32_t* slot, const float* world_pos, const float* normal,
                            const float* min_dist, const float* max_dist, const uint8_t* desc);
 
+/* test / debug aid, like rgbl_device_frame_download: n slots back to the host, any array NULL */
+int rgbl_map_points_download(rgbl_map_points* p, int n, const int32_t* slot, float* world_pos, float* normal,
+                             float* min_dist, float* max_dist, uint8_t* desc);
+
+/* ---- MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:426-494) and MapPoint::ComputeDistinctiveDescriptors (:329-403) on
+ * the device: the pool's normal, mfMinDistance, mfMaxDistance and descriptor recomputed from observations given as
+ * (key frame, feature) pairs of key frames that are resident on the device (rgbl_device_frame), for every listed point in
+ * one call.  Single-camera key frames (rightIndex == -1); the caller leaves mbBad points out. */
+typedef struct {
+  int n_points;               /* <= 2^24 */
+  const int32_t* slot;        /* pool slot of point p; each slot at most once per call (RGBL_ERR_INVALID otherwise) */
+  const float* world_pos;     /* nullable: 3 floats per point, written to the slots FIRST (SetWorldPos after BA); NULL: the pool's */
+  const int32_t* obs_off;     /* n_points + 1, from 0; point p's observations = [obs_off[p], obs_off[p+1]) in the order the reference
+                                 iterates mObservations (std::map<KeyFrame*,...>: the caller's pointer order) */
+  const int32_t* obs_kf;      /* index into the key-frame table below */
+  const int32_t* obs_feat;    /* leftIndex of that observation */
+  const int32_t* ref_kf;      /* per point: mpRefKF as an index into the table (read with do_normal) */
+  const int32_t* ref_level;   /* per point: the octave the reference reads at :471-482 (incl. its quirk: observations[pRefKF]
+                                 default-inserts (0,0) when the reference key frame does not observe the point -> feature 0) */
+  int n_kfs;
+  const rgbl_device_frame* const* kf_frame; /* resident key frames; an entry may be NULL only when do_descriptor == 0 */
+  const float* kf_center;     /* GetCameraCenter(), 3 floats per key frame (read with do_normal) */
+  const uint8_t* kf_bad;      /* pKF->isBad(): skipped by ComputeDistinctiveDescriptors (:352), NOT by UpdateNormalAndDepth; NULL: none */
+  const float* scale_factors; /* pRefKF->mvScaleFactors (one table per call; a host with several extractor settings groups its calls) */
+  int n_levels;               /* 1 .. 16 */
+  int do_normal, do_descriptor;
+} rgbl_map_refresh_input;
+typedef struct {              /* every pointer nullable; n_points entries each */
+  float* normal;              /* 3 per point */
+  float* min_dist; float* max_dist;   /* RAW mfMinDistance / mfMaxDistance */
+  int32_t* best_obs;          /* position inside the point's OWN observation list (bad key frames counted) of the descriptor that
+                                 became mDescriptor, -1 = unchanged */
+  uint8_t* desc;              /* 32 per point (the slot's descriptor after the call) */
+  uint8_t* status;            /* bit 0: normal/distances written, bit 1: descriptor written */
+} rgbl_map_refresh_output;
+/* do_normal: a point without observations stays as it is (:441); otherwise normal = sum over ALL its observations, in list
+ * order, of (Pos - Ow_kf) / |Pos - Ow_kf|, divided by their number; mfMaxDistance = |Pos - Ow_ref| * scale_factors[ref_level];
+ * mfMinDistance = mfMaxDistance / scale_factors[n_levels - 1].  fp32 in the order of csrc/frustum_math.h, square root and
+ * division correctly rounded; a point at a camera centre gives NaN as on the host.
+ * do_descriptor: the rows are the observations of key frames that are not bad, in list order; none: the descriptor stays
+ * (:365); otherwise the rule of rgbl_distinctive_descriptors picks the row whose 32 bytes go into the slot.
+ * The result arrays hold the slots' values after the call, also for fields the call did not recompute.
+ * RGBL_ERR_INVALID, before anything is launched or written: a slot outside the pool or listed twice; obs_kf / ref_kf outside
+ * [0, n_kfs); obs_feat outside [0, rgbl_device_frame_size(frame)) (checked wherever the frame is given); ref_level outside
+ * [0, n_levels) (ref_kf / ref_level are checked for every point, with do_normal); a NULL frame with do_descriptor; a frame or
+ * pool on another device than the matcher; obs_off that does not start at 0 or descends; more than 65535 observations on
+ * one point.  n_points == 0: RGBL_OK.
+ * Holds the pool's mutex for its duration, runs on the handle's stream behind every key frame's last fill, one upload and one
+ * read-back.  Host pointers, synchronous.  As for the matchers, a key frame must not be refilled (upload / capture) while the
+ * call runs. */
+int rgbl_map_points_refresh(rgbl_matcher* h, rgbl_map_points* pool, const rgbl_map_refresh_input* in, rgbl_map_refresh_output* out);
+
 /* The frame side is that of rgbl_local_points_input; the map side is what the loop of Tracking::SearchLocalPoints
  * (src/Tracking.cc:3399-3420) reads before it calls isInFrustum, either as host arrays or as slots of a pool. */
 typedef struct {

@@ -116,6 +116,20 @@ class TrackLocalInput(C.Structure):
                 ("far_points", C.c_int), ("th_far_points", C.c_float)]
 
 
+class MapRefreshInput(C.Structure):
+    """rgbl_map_refresh_input (MapPoint::UpdateNormalAndDepth / ComputeDistinctiveDescriptors from resident key frames)."""
+    _fields_ = [("n_points", C.c_int), ("slot", C.c_void_p), ("world_pos", C.c_void_p), ("obs_off", C.c_void_p),
+                ("obs_kf", C.c_void_p), ("obs_feat", C.c_void_p), ("ref_kf", C.c_void_p), ("ref_level", C.c_void_p),
+                ("n_kfs", C.c_int), ("kf_frame", C.c_void_p), ("kf_center", C.c_void_p), ("kf_bad", C.c_void_p),
+                ("scale_factors", C.c_void_p), ("n_levels", C.c_int), ("do_normal", C.c_int), ("do_descriptor", C.c_int)]
+
+
+class MapRefreshOutput(C.Structure):
+    """rgbl_map_refresh_output: what the MapPoint objects need to stay in step (every pointer nullable)."""
+    _fields_ = [("normal", C.c_void_p), ("min_dist", C.c_void_p), ("max_dist", C.c_void_p), ("best_obs", C.c_void_p),
+                ("desc", C.c_void_p), ("status", C.c_void_p)]
+
+
 # rgbl_frustum_record: what Frame::isInFrustum leaves in a MapPoint
 FRUSTUM_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"),
                           ("level", "<i4")])
@@ -259,6 +273,8 @@ SYMBOLS = {
     "rgbl_map_points_reserve": (_I, [_V, _I]),
     "rgbl_map_points_capacity": (_I, [_V]),
     "rgbl_map_points_update": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]),
+    "rgbl_map_points_download": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]),
+    "rgbl_map_points_refresh": (_I, [_V, _V, C.POINTER(MapRefreshInput), C.POINTER(MapRefreshOutput)]),
     "rgbl_frustum_cull": (_I, [_V, _V, _V, _V, C.POINTER(_I)]),
     "rgbl_track_local_points": (_I, [_V, _V, _V, _V, C.POINTER(_I), _V, C.POINTER(_I)]),
     "rgbl_search_for_initialization": (_I, [_V, _V, _V, _V, C.POINTER(_I)]),

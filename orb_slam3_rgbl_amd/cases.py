@@ -449,3 +449,94 @@ def local_points_from_cull(case, in_view, rec):
                 level1=rec["level"].astype(np.int32), view_cos1=rec["view_cos"].astype(np.float32), mp_desc1=case["mp_desc1"],
                 mp_observed1=case["mp_observed1"], kp2_xy=case["kp2_xy"], kp2_octave=case["kp2_octave"], uright2=case["uright2"],
                 desc2=case["desc2"], blocked2=case["blocked2"], grid=case["grid"], scale_factors=case["scale_factors"])
+
+
+def make_map_refresh_case(n_points=1500, n_kfs=40, seed=5, obs_counts=None, features=None, base_desc=None):
+    """Map points and the key frames that observe them, as rgbl_map_points_refresh reads them (MapPoint::UpdateNormalAndDepth,
+    ComputeDistinctiveDescriptors): key frames on a trajectory, each with its own feature count (`features`: one count for all,
+    or (low, high)), about 5 % of them bad; per point a base descriptor, every observation that base with each bit flipped
+    with probability 0.08 (`base_desc`: the bases instead of random ones), some observations exact copies of an earlier one
+    (ties); observation counts mostly 2 .. 30, with 0
+    and 1 present and a few up to 200 (`obs_counts`: the count of every point instead); a key frame is listed once per point
+    while the count allows it, in ascending order; some points have a reference key frame that does not observe them (its
+    level is then the octave of that frame's feature 0, the reference's quirk).  The first observation of the case is on
+    feature 0 of its key frame, the last one on the last feature of its.  Slots 0 .. n_points - 1; normal0, min_dist0,
+    max_dist0, desc0 are what the pool holds before the refresh."""
+    rng = np.random.default_rng(seed)
+    n_levels = 8
+    scale = np.ones(n_levels, np.float32)
+    for l in range(1, n_levels):
+        scale[l] = scale[l - 1] * np.float32(1.2)
+    if features is None:
+        features = (300, 2000)
+    if np.isscalar(features):
+        kf_n = np.full(n_kfs, features, np.int64)
+    else:   # all different where the range allows it
+        span = np.arange(features[0], features[1] + 1)
+        kf_n = rng.choice(span, n_kfs, replace=len(span) < n_kfs).astype(np.int64)
+    k = np.arange(n_kfs, dtype=np.float64)
+    kf_center = np.stack([0.9 * k, 0.1 * np.sin(0.7 * k), 4.0 * np.sin(0.11 * k)], 1).astype(np.float32)
+    kf_bad = (rng.random(n_kfs) < 0.05).astype(np.uint8)
+    if n_kfs >= 20 and not kf_bad.any():
+        kf_bad[int(rng.integers(0, n_kfs))] = 1
+    kf_desc = [rng.integers(0, 256, (int(n), 32), dtype=np.uint8) for n in kf_n]
+    kf_octave = [rng.integers(0, n_levels, int(n)).astype(np.int32) for n in kf_n]
+    kf_xy = [rng.uniform(0, 1200, (int(n), 2)).astype(np.float32) for n in kf_n]
+    next_feat = [rng.permutation(int(n)) for n in kf_n]
+    used = np.zeros(n_kfs, np.int64)
+    if obs_counts is None:
+        cat = rng.random(n_points)
+        counts = rng.integers(2, 31, n_points)
+        counts[cat < 0.03] = 0
+        counts[(cat >= 0.03) & (cat < 0.07)] = 1
+        few = cat > 0.985
+        counts[few] = rng.integers(100, 201, int(few.sum()))
+    else:
+        counts = np.broadcast_to(np.asarray(obs_counts, np.int64), (n_points,)).copy()
+    if n_kfs == 0:
+        counts[:] = 0
+    anchor = rng.integers(0, max(n_kfs, 1), n_points)
+    world = (kf_center[anchor].astype(np.float64) if n_kfs else np.zeros((n_points, 3))) + \
+        rng.normal(0, 1, (n_points, 3)) * rng.uniform(2, 40, (n_points, 1))
+    obs_off = np.zeros(n_points + 1, np.int32)
+    obs_off[1:] = np.cumsum(counts)
+    obs_kf = np.zeros(int(obs_off[-1]), np.int32)
+    obs_feat = np.zeros(int(obs_off[-1]), np.int32)
+    ref_kf = np.zeros(n_points, np.int32)
+    ref_level = np.zeros(n_points, np.int32)
+    base = rng.integers(0, 256, (n_points, 32), dtype=np.uint8)
+    if base_desc is not None:
+        base = np.ascontiguousarray(base_desc, np.uint8).reshape(n_points, 32)
+    for p in range(n_points):
+        c, b = int(counts[p]), int(obs_off[p])
+        kfs = np.sort(rng.choice(n_kfs, c, replace=c > n_kfs)) if c else np.zeros(0, np.int64)
+        flips = np.packbits(rng.random((c, 256)) < 0.08, axis=1)
+        rows = base[p][None, :] ^ flips
+        for i in range(1, c):
+            if rng.random() < 0.15:
+                rows[i] = rows[int(rng.integers(0, i))]
+        for i in range(c):
+            kf = int(kfs[i])
+            f = int(next_feat[kf][used[kf] % kf_n[kf]])
+            if b + i == 0:
+                f = 0
+            if b + i == len(obs_kf) - 1:
+                f = int(kf_n[kf]) - 1
+            used[kf] += 1
+            obs_kf[b + i], obs_feat[b + i] = kf, f
+            kf_desc[kf][f] = rows[i]
+        outsider = n_kfs > 0 and (c == 0 or (rng.random() < 0.1 and c < n_kfs))
+        if outsider:
+            rest = np.setdiff1d(np.arange(n_kfs), kfs)
+            ref_kf[p] = int(rest[rng.integers(0, len(rest))])
+            ref_level[p] = kf_octave[ref_kf[p]][0]          # observations[pRefKF] default-inserts (0, 0)
+        elif n_kfs > 0:
+            i = int(rng.integers(0, c))
+            ref_kf[p] = obs_kf[b + i]
+            ref_level[p] = kf_octave[obs_kf[b + i]][obs_feat[b + i]]
+    normal0 = rng.normal(0, 1, (n_points, 3)).astype(np.float32)
+    return dict(slot=np.arange(n_points, dtype=np.int32), world_pos=world.astype(np.float32), normal0=normal0,
+                min_dist0=rng.uniform(1, 5, n_points).astype(np.float32), max_dist0=rng.uniform(20, 90, n_points).astype(np.float32),
+                desc0=rng.integers(0, 256, (n_points, 32), dtype=np.uint8), obs_off=obs_off, obs_kf=obs_kf, obs_feat=obs_feat,
+                ref_kf=ref_kf, ref_level=ref_level, kf_n=kf_n.astype(np.int32), kf_desc=kf_desc, kf_octave=kf_octave, kf_xy=kf_xy,
+                kf_center=kf_center, kf_bad=kf_bad, scale_factors=scale, n_levels=n_levels)

@@ -1,4 +1,5 @@
-// frustum_math.h — the three fixed-size Eigen reductions of Frame::isInFrustum (src/Frame.cc:602-664), in ONE place.
+// frustum_math.h — the three fixed-size Eigen reductions of Frame::isInFrustum (src/Frame.cc:602-664), in ONE place, and the
+// quotient MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:426-494) needs besides them.
 //
 // The order is the one the Eigen stand-in oracle/cvcompat/sophus/sim3.hpp defines (the stand-in is what the reference's own
 // lines are compiled against in the tests): products summed left to right.  Real Eigen's fixed-size redux may group a
@@ -37,6 +38,18 @@ RGBL_HD float fr_norm(float a0, float a1, float a2) {
   return (float)sqrt((double)fr_dot(a0, a1, a2, a0, a1, a2));
 #else
   return sqrtf(fr_dot(a0, a1, a2, a0, a1, a2));
+#endif
+}
+
+// Vector / scalar and scalar / scalar (`normali / normali.norm()`, `normal / n`, `mfMaxDistance / mvScaleFactors[nLevels - 1]`,
+// MapPoint.cc:457, 491-492): one IEEE fp32 division per component
+RGBL_HD float fr_quot(float a, float s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  // the fp64 quotient is IEEE, and rounding it to fp32 equals the correctly rounded fp32 quotient (53 >= 2 * 24 + 2 bits),
+  // whatever the compiler's switches make of an fp32 division; 0 / 0 stays a NaN
+  return (float)((double)a / (double)s);
+#else
+  return a / s;
 #endif
 }
 

@@ -1477,6 +1477,153 @@ __global__ __launch_bounds__(256) void k_map_points_scatter(PoolScatter S) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// rgbl_map_points_refresh: MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:426-494) and
+// MapPoint::ComputeDistinctiveDescriptors (:329-403) for pool slots whose observations are (key frame, feature) pairs of key
+// frames resident on the device.  One wave per point in both kernels; grid = points, block = 64.
+constexpr int kRefreshLdsRows = 128;   // a point's descriptor rows in LDS: 4 KiB per wave; longer lists take the call's scratch
+struct RefreshDev {
+  const int32_t *slot, *off, *obs_kf, *obs_feat;   // point p: slot[p], observations [off[p], off[p + 1])
+  const int32_t *ref_kf, *ref_level;
+  const float *kf_center, *scale;
+  const uint8_t* kf_bad;
+  const uint8_t* const* kf_desc;     // the key frames' descriptor arrays
+  const int32_t* long_off;           // first row in `rows` of a point with more than kRefreshLdsRows rows, else -1
+  unsigned long long* rows;
+  float top_scale;                   // mvScaleFactors[nLevels - 1]
+  int compute;                       // 0: the slots' present values go to the result arrays, nothing is written to the pool
+  float *p_wpos, *p_normal, *p_min, *p_max;
+  uint8_t* p_desc;
+  float *o_normal, *o_min, *o_max;   // results, each nullable
+  int32_t* o_best;
+  uint8_t *o_desc, *o_wrote;
+};
+
+// The unit vectors of 64 observations at a time, one per lane, go through LDS; every lane then adds them up in list order
+// (the same LDS address in all lanes: a broadcast read) - the sum is sequential as in the reference's loop, never a tree.
+__global__ __launch_bounds__(64) void k_map_refresh_normal(RefreshDev R) {
+  __shared__ float unit[64 * 3];
+  const int p = blockIdx.x, lane = threadIdx.x;
+  const int j = R.slot[p];
+  const int b = R.off[p], n = R.off[p + 1] - b;
+  const bool compute = R.compute && n > 0;   // :441 a point without observations stays as it is
+  const float p0 = R.p_wpos[3 * (size_t)j], p1 = R.p_wpos[3 * (size_t)j + 1], p2 = R.p_wpos[3 * (size_t)j + 2];
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f;        // :445 normal.setZero()
+  if (compute) {
+    for (int c0 = 0; c0 < n; c0 += 64) {
+      const int o = c0 + lane;
+      if (o < n) {                           // :455-457 normali = Pos - Owi; normali / normali.norm()
+        const float* C = R.kf_center + 3 * (size_t)R.obs_kf[b + o];
+        const float d0 = p0 - C[0], d1 = p1 - C[1], d2 = p2 - C[2];
+        const float len = fr_norm(d0, d1, d2);
+        unit[3 * lane] = fr_quot(d0, len); unit[3 * lane + 1] = fr_quot(d1, len); unit[3 * lane + 2] = fr_quot(d2, len);
+      }
+      __syncthreads();
+      const int m = imin(64, n - c0);
+      for (int k = 0; k < m; ++k) { a0 = a0 + unit[3 * k]; a1 = a1 + unit[3 * k + 1]; a2 = a2 + unit[3 * k + 2]; }
+      __syncthreads();
+    }
+  }
+  if (lane != 0) return;
+  float n0, n1, n2, dmin, dmax;
+  if (compute) {
+    const float* C = R.kf_center + 3 * (size_t)R.ref_kf[p];
+    const float dist = fr_norm(p0 - C[0], p1 - C[1], p2 - C[2]);   // :468-469
+    dmax = dist * R.scale[R.ref_level[p]];                          // :490
+    dmin = fr_quot(dmax, R.top_scale);                              // :491
+    const float fn = (float)n;                                      // :492 normal / n
+    n0 = fr_quot(a0, fn); n1 = fr_quot(a1, fn); n2 = fr_quot(a2, fn);
+    R.p_normal[3 * (size_t)j] = n0; R.p_normal[3 * (size_t)j + 1] = n1; R.p_normal[3 * (size_t)j + 2] = n2;
+    R.p_min[j] = dmin; R.p_max[j] = dmax;
+  } else {
+    n0 = R.p_normal[3 * (size_t)j]; n1 = R.p_normal[3 * (size_t)j + 1]; n2 = R.p_normal[3 * (size_t)j + 2];
+    dmin = R.p_min[j]; dmax = R.p_max[j];
+  }
+  if (R.o_normal) { R.o_normal[3 * (size_t)p] = n0; R.o_normal[3 * (size_t)p + 1] = n1; R.o_normal[3 * (size_t)p + 2] = n2; }
+  if (R.o_min) R.o_min[p] = dmin;
+  if (R.o_max) R.o_max[p] = dmax;
+  if (R.o_wrote) R.o_wrote[p] = compute ? 1 : 0;
+}
+
+// observation c0 + lane of the point's list: does it contribute a descriptor row (its key frame is not bad, :352), and which
+__device__ __forceinline__ bool refresh_row(const RefreshDev& R, int b, int n, int o, int* kf) {
+  if (o >= n) return false;
+  *kf = R.obs_kf[b + o];
+  return R.kf_bad[*kf] == 0;
+}
+
+// k_distinctive's rule on `rows` gathered rows at D (LDS or the call's scratch; a row per lane, the other row of a pair
+// wave-uniform: a broadcast read): median = sorted row[(N - 1) >> 1], own zero included, strict '<', the first row wins.  The
+// winner goes to slot j and to the results, with its position in the point's full observation list.
+__device__ __forceinline__ void refresh_pick(const RefreshDev& R, const unsigned long long* D, int rows, int p, int j, int b, int n, int lane) {
+  const int k = (rows - 1) >> 1;
+  uint32_t wbest = 0xffffffffu;  // median << 16 | row
+  for (int r0 = 0; r0 < rows; r0 += 64) {
+    const int i = r0 + lane;
+    const bool live = i < rows;
+    const unsigned long long* Q = D + 4 * (size_t)(live ? i : 0);
+    const unsigned long long q[4] = {Q[0], Q[1], Q[2], Q[3]};
+    int lo = 0, hi = 256;
+    for (int it = 0; it < 9; ++it) {  // 257 possible values
+      const int mid = (lo + hi) >> 1;
+      int c = 0;
+      for (int r = 0; r < rows; ++r) c += hamming256(q, D + 4 * (size_t)r) <= mid ? 1 : 0;
+      if (c >= k + 1) hi = mid; else lo = mid + 1;
+    }
+    const uint32_t key = wave_min_uniform(live ? ((uint32_t)lo << 16) | (uint32_t)i : 0xffffffffu);
+    wbest = key < wbest ? key : wbest;
+  }
+  const int win = (int)(wbest & 0xffffu);
+  if (lane < 4) {
+    const unsigned long long v = D[4 * (size_t)win + lane];
+    reinterpret_cast<unsigned long long*>(R.p_desc + (size_t)j * 32)[lane] = v;
+    if (R.o_desc) reinterpret_cast<unsigned long long*>(R.o_desc + (size_t)p * 32)[lane] = v;
+  }
+  if (!R.o_best) return;
+  for (int c0 = 0, seen = 0; c0 < n; c0 += 64) {   // the observation that gave row `win`
+    int kf = 0;
+    const bool good = refresh_row(R, b, n, c0 + lane, &kf);
+    const unsigned long long mask = __ballot(good);
+    if (good && seen + __popcll(mask & lanemask_lt()) == win) R.o_best[p] = c0 + lane;
+    seen += __popcll(mask);
+  }
+}
+
+__global__ __launch_bounds__(64) void k_map_refresh_desc(RefreshDev R) {
+  __shared__ __attribute__((aligned(16))) unsigned long long lds_rows[kRefreshLdsRows * 4];
+  const int p = blockIdx.x, lane = threadIdx.x;
+  const int j = R.slot[p];
+  const int b = R.off[p], n = R.off[p + 1] - b;
+  int rows = 0;
+  if (R.compute && n > 0) {
+    const int first = R.long_off[p];
+    unsigned long long* G = first >= 0 ? R.rows + 4 * (size_t)first : nullptr;
+    for (int c0 = 0; c0 < n; c0 += 64) {   // gather: the rows of the key frames that are not bad, in list order
+      int kf = 0;
+      const bool good = refresh_row(R, b, n, c0 + lane, &kf);
+      const unsigned long long mask = __ballot(good);
+      const int at = rows + __popcll(mask & lanemask_lt());
+      if (good && (G || at < kRefreshLdsRows)) {
+        const uint4* src = reinterpret_cast<const uint4*>(R.kf_desc[kf] + (size_t)R.obs_feat[b + c0 + lane] * 32);
+        const uint4 x = src[0], y = src[1];
+        if (G) { uint4* dst = reinterpret_cast<uint4*>(G + 4 * (size_t)at); dst[0] = x; dst[1] = y; }
+        else { uint4* dst = reinterpret_cast<uint4*>(lds_rows + 4 * at); dst[0] = x; dst[1] = y; }
+      }
+      rows += __popcll(mask);
+    }
+    __syncthreads();
+    if (rows > 0) {                        // :365 no row: the descriptor stays
+      if (G) refresh_pick(R, G, rows, p, j, b, n, lane);
+      else refresh_pick(R, lds_rows, rows, p, j, b, n, lane);
+    }
+  }
+  if (rows == 0) {
+    if (lane < 4 && R.o_desc) reinterpret_cast<unsigned long long*>(R.o_desc + (size_t)p * 32)[lane] = reinterpret_cast<const unsigned long long*>(R.p_desc + (size_t)j * 32)[lane];
+    if (lane == 0 && R.o_best) R.o_best[p] = -1;
+  }
+  if (lane == 0 && R.o_wrote) R.o_wrote[p] = rows > 0 ? 1 : 0;
+}
+
 __global__ void k_test_logf(const float* x, float* y, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) y[i] = logf_glibc(x[i]);
@@ -3054,6 +3201,169 @@ int rgbl_map_points_update(rgbl_map_points* p, int n, const int32_t* slot, const
   hipLaunchKernelGGL(k_map_points_scatter, dim3((n + 255) / 256), dim3(256), 0, p->stream, S);
   RGBL_HIP(hipGetLastError());
   RGBL_HIP(hipStreamSynchronize(p->stream));
+  return RGBL_OK;
+}
+
+int rgbl_map_points_download(rgbl_map_points* p, int n, const int32_t* slot, float* world_pos, float* normal, float* min_dist,
+                             float* max_dist, uint8_t* desc) {
+  if (!p || n < 0 || (n > 0 && !slot)) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  if (n == 0) return RGBL_OK;
+  std::lock_guard<std::mutex> lock(p->mu);
+  int lo = p->cap, hi = -1;
+  for (int k = 0; k < n; ++k) {
+    if (slot[k] < 0 || slot[k] >= p->cap) { set_error("map point pool: slot %d outside [0, %d)", slot[k], p->cap); return RGBL_ERR_INVALID; }
+    lo = std::min(lo, slot[k]); hi = std::max(hi, slot[k]);
+  }
+  RGBL_HIP(hipSetDevice(p->device));
+  // the slots between the lowest and the highest one listed, one copy per array
+  const size_t span = (size_t)(hi - lo) + 1;
+  std::vector<uint8_t> buf(span * 32);
+  const struct { const void* src; void* dst; size_t per; } part[5] = {
+      {p->d_wpos, world_pos, 12}, {p->d_normal, normal, 12}, {p->d_min, min_dist, 4}, {p->d_max, max_dist, 4}, {p->d_desc, desc, 32}};
+  for (int a = 0; a < 5; ++a) {
+    if (!part[a].dst) continue;
+    const size_t per = part[a].per;
+    RGBL_HIP(hipMemcpy(buf.data(), static_cast<const uint8_t*>(part[a].src) + (size_t)lo * per, span * per, hipMemcpyDeviceToHost));
+    for (int k = 0; k < n; ++k) memcpy(static_cast<uint8_t*>(part[a].dst) + (size_t)k * per, buf.data() + (size_t)(slot[k] - lo) * per, per);
+  }
+  return RGBL_OK;
+}
+
+// MapPoint::UpdateNormalAndDepth and MapPoint::ComputeDistinctiveDescriptors for pool slots (include/rgbl_frontend.h).
+// Everything is checked on the host before the first launch: the kernels index with the caller's numbers.
+int rgbl_map_points_refresh(rgbl_matcher* m, rgbl_map_points* pool, const rgbl_map_refresh_input* in, rgbl_map_refresh_output* out) {
+  if (!m || !pool || !in || in->n_points < 0) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  const int np = in->n_points, nk = in->n_kfs;
+  if (np == 0) return RGBL_OK;
+  const bool do_n = in->do_normal != 0, do_d = in->do_descriptor != 0;
+  if (np > (1 << 24) || !in->slot || !in->obs_off || in->obs_off[0] != 0 || nk < 0) { set_error("map refresh: 1 .. 2^24 points with slots and offsets that start at 0"); return RGBL_ERR_INVALID; }
+  if (pool->device != m->device) { set_error("map refresh: the pool is on device %d, the matcher on %d", pool->device, m->device); return RGBL_ERR_INVALID; }
+  for (int p = 0; p < np; ++p)
+    if (in->obs_off[p + 1] < in->obs_off[p] || in->obs_off[p + 1] - in->obs_off[p] > 65535) { set_error("map refresh: offsets must ascend, at most 65535 observations per point"); return RGBL_ERR_INVALID; }
+  const int total = in->obs_off[np];
+  if ((total > 0 && (!in->obs_kf || !in->obs_feat)) || (nk > 0 && ((do_n && !in->kf_center) || (do_d && !in->kf_frame)))) { set_error("map refresh: null argument"); return RGBL_ERR_INVALID; }
+  if (do_n) {
+    if (in->n_levels < 1 || in->n_levels > kProjMaxLevels || !in->scale_factors || !in->ref_kf || !in->ref_level) { set_error("map refresh: 1 .. %d pyramid levels with their scale factors, a reference key frame and level per point", kProjMaxLevels); return RGBL_ERR_INVALID; }
+    for (int p = 0; p < np; ++p) {
+      if (in->ref_kf[p] < 0 || in->ref_kf[p] >= nk) { set_error("map refresh: reference key frame %d of point %d outside [0, %d)", in->ref_kf[p], p, nk); return RGBL_ERR_INVALID; }
+      if (in->ref_level[p] < 0 || in->ref_level[p] >= in->n_levels) { set_error("map refresh: reference level %d of point %d outside [0, %d)", in->ref_level[p], p, in->n_levels); return RGBL_ERR_INVALID; }
+    }
+  }
+  for (int k = 0; k < nk; ++k) {
+    const rgbl_device_frame* f = in->kf_frame ? in->kf_frame[k] : nullptr;
+    if (do_d && !f) { set_error("map refresh: key frame %d is not resident on the device", k); return RGBL_ERR_INVALID; }
+    if (f && f->device != m->device) { set_error("map refresh: key frame %d is on device %d, the matcher on %d", k, f->device, m->device); return RGBL_ERR_INVALID; }
+  }
+  std::vector<uint8_t> observed((size_t)nk, 0);   // the key frames some observation names: the ones the stream waits for
+  for (int o = 0; o < total; ++o) {
+    const int kf = in->obs_kf[o];
+    if (kf >= 0 && kf < nk) observed[(size_t)kf] = 1;
+    if (kf < 0 || kf >= nk) { set_error("map refresh: observation %d names key frame %d outside [0, %d)", o, kf, nk); return RGBL_ERR_INVALID; }
+    const rgbl_device_frame* f = in->kf_frame ? in->kf_frame[kf] : nullptr;
+    if (f && (in->obs_feat[o] < 0 || in->obs_feat[o] >= f->n)) { set_error("map refresh: observation %d names feature %d of a key frame with %d", o, in->obs_feat[o], f->n); return RGBL_ERR_INVALID; }
+  }
+  // rows per point (the observations of key frames that are not bad); the lists too long for LDS get room in the scratch
+  std::vector<int32_t> long_off;
+  size_t long_rows = 0;
+  if (do_d) {
+    long_off.assign((size_t)np, -1);
+    for (int p = 0; p < np; ++p) {
+      int rows = 0;
+      for (int o = in->obs_off[p]; o < in->obs_off[p + 1]; ++o) rows += !(in->kf_bad && in->kf_bad[in->obs_kf[o]]);
+      if (rows > kRefreshLdsRows) { long_off[(size_t)p] = (int32_t)long_rows; long_rows += (size_t)rows; }
+    }
+    if (long_rows > (size_t)INT_MAX) { set_error("map refresh: too many observations"); return RGBL_ERR_INVALID; }
+  }
+  std::lock_guard<std::mutex> pool_lock(pool->mu);
+  {
+    std::vector<int32_t> sorted(in->slot, in->slot + np);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.front() < 0 || sorted.back() >= pool->cap) { set_error("map point pool: slot %d outside [0, %d)", sorted.front() < 0 ? sorted.front() : sorted.back(), pool->cap); return RGBL_ERR_INVALID; }
+    for (int p = 0; p + 1 < np; ++p)
+      if (sorted[(size_t)p] == sorted[(size_t)p + 1]) { set_error("map refresh: slot %d is listed twice", sorted[(size_t)p]); return RGBL_ERR_INVALID; }
+  }
+  RGBL_HIP(hipSetDevice(m->device));
+  StreamDrain drain(m->stream);  // error returns included; declared behind pool_lock: the stream is drained before the pool is released
+  HostCall hc(m);
+  hipStream_t s = hc.s;
+  RefreshDev R;
+  memset(&R, 0, sizeof(R));
+  const float* d_wpos = nullptr;
+  const bool want_n = out && (out->normal || out->min_dist || out->max_dist), want_d = out && out->desc;
+  const bool run_n = do_n || want_n, run_d = do_d || want_d;
+  uint8_t *wrote_n = nullptr, *wrote_d = nullptr;
+  RGBL_TRY(hc.begin([&]() -> int {
+    hc.put(&R.slot, in->slot, (size_t)np);
+    hc.put(&R.off, in->obs_off, (size_t)np + 1);
+    if (in->world_pos) hc.put(&d_wpos, in->world_pos, (size_t)np * 3);
+    if (do_n || do_d) hc.put(&R.obs_kf, in->obs_kf, (size_t)total);
+    if (do_n) {
+      hc.put(&R.ref_kf, in->ref_kf, (size_t)np);
+      hc.put(&R.ref_level, in->ref_level, (size_t)np);
+      hc.put(&R.kf_center, in->kf_center, (size_t)nk * 3);
+      hc.put(&R.scale, in->scale_factors, (size_t)in->n_levels);
+    }
+    if (do_d) {
+      hc.put(&R.obs_feat, in->obs_feat, (size_t)total);
+      hc.put(&R.long_off, (const int32_t*)long_off.data(), (size_t)np);
+      if (in->kf_bad) hc.put(&R.kf_bad, in->kf_bad, (size_t)nk);
+      else R.kf_bad = hc.put_fill<uint8_t>((size_t)nk, 0);
+      R.kf_desc = hc.stage<const uint8_t*>((size_t)nk, [&](const uint8_t** t) { for (int k = 0; k < nk; ++k) t[k] = in->kf_frame[k]->d_desc; });
+      if (hc.carving)   // the stream waits for whatever filled the observed key frames last
+        for (int k = 0; k < nk; ++k)
+          if (observed[(size_t)k]) RGBL_HIP(hipStreamWaitEvent(s, in->kf_frame[k]->ready, 0));
+      R.rows = hc.scratch<unsigned long long>(long_rows * 4);
+    }
+    if (out) {   // the results back to back: one copy back
+      if (out->normal) R.o_normal = hc.result<float>((size_t)np * 3);
+      if (out->min_dist) R.o_min = hc.result<float>((size_t)np);
+      if (out->max_dist) R.o_max = hc.result<float>((size_t)np);
+      if (out->best_obs && do_d) R.o_best = hc.result<int32_t>((size_t)np);
+      if (out->desc) R.o_desc = hc.result<uint8_t>((size_t)np * 32);
+      if (out->status && run_n) wrote_n = hc.result<uint8_t>((size_t)np);
+      if (out->status && run_d) wrote_d = hc.result<uint8_t>((size_t)np);
+    }
+    return RGBL_OK;
+  }));
+  R.p_wpos = pool->d_wpos; R.p_normal = pool->d_normal; R.p_min = pool->d_min; R.p_max = pool->d_max; R.p_desc = pool->d_desc;
+  if (in->world_pos) {   // SetWorldPos first: the kernels below read the new positions
+    PoolScatter S{};
+    S.n = np; S.slot = R.slot; S.wpos = d_wpos;
+    S.p_wpos = pool->d_wpos; S.p_normal = pool->d_normal; S.p_min = pool->d_min; S.p_max = pool->d_max; S.p_desc = pool->d_desc;
+    m->timer.begin("k_map_points_scatter", s);
+    hipLaunchKernelGGL(k_map_points_scatter, dim3((np + 255) / 256), dim3(256), 0, s, S);
+    m->timer.end(s);
+    RGBL_HIP(hipGetLastError());
+  }
+  if (run_n) {
+    if (do_n) R.top_scale = in->scale_factors[in->n_levels - 1];
+    R.compute = do_n; R.o_wrote = wrote_n;
+    m->timer.begin("k_map_refresh_normal", s);
+    hipLaunchKernelGGL(k_map_refresh_normal, dim3(np), dim3(64), 0, s, R);
+    m->timer.end(s);
+    RGBL_HIP(hipGetLastError());
+  }
+  if (run_d) {
+    R.compute = do_d; R.o_wrote = wrote_d;
+    m->timer.begin("k_map_refresh_desc", s);
+    hipLaunchKernelGGL(k_map_refresh_desc, dim3(np), dim3(64), 0, s, R);
+    m->timer.end(s);
+    RGBL_HIP(hipGetLastError());
+  }
+  RGBL_TRY(hc.fetch());
+  if (out) {
+    if (out->normal) memcpy(out->normal, hc.host(R.o_normal), sizeof(float) * 3 * (size_t)np);
+    if (out->min_dist) memcpy(out->min_dist, hc.host(R.o_min), sizeof(float) * (size_t)np);
+    if (out->max_dist) memcpy(out->max_dist, hc.host(R.o_max), sizeof(float) * (size_t)np);
+    if (out->best_obs) {
+      if (R.o_best) memcpy(out->best_obs, hc.host(R.o_best), sizeof(int32_t) * (size_t)np);
+      else for (int p = 0; p < np; ++p) out->best_obs[p] = -1;
+    }
+    if (out->desc) memcpy(out->desc, hc.host(R.o_desc), (size_t)np * 32);
+    if (out->status)
+      for (int p = 0; p < np; ++p)
+        out->status[p] = (uint8_t)((wrote_n ? hc.host(wrote_n)[p] : 0) | (wrote_d ? hc.host(wrote_d)[p] << 1 : 0));
+  }
   return RGBL_OK;
 }
 

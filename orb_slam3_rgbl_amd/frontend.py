@@ -420,6 +420,62 @@ class MapPointPool:
                 raise ValueError("MapPointPool.update: an array does not hold one entry per slot")
         L.check(self.lib, self.lib.rgbl_map_points_update(self.h, len(slot), L.ptr(slot), *[L.ptr(v) for v in a]))
 
+    def download(self, slots):
+        """The slots' present values (test / debug aid): dict(world_pos, normal, min_dist, max_dist, desc)."""
+        slot = np.ascontiguousarray(slots, np.int32)
+        n = len(slot)
+        r = dict(world_pos=np.zeros((n, 3), np.float32), normal=np.zeros((n, 3), np.float32), min_dist=np.zeros(n, np.float32),
+                 max_dist=np.zeros(n, np.float32), desc=np.zeros((n, 32), np.uint8))
+        L.check(self.lib, self.lib.rgbl_map_points_download(self.h, n, L.ptr(slot), *[L.ptr(r[k]) for k in
+                                                            ("world_pos", "normal", "min_dist", "max_dist", "desc")]))
+        return r
+
+    def refresh_input(self, case, keep):
+        """rgbl_map_refresh_input of a cases.make_map_refresh_case-style dict: slot, obs_off, obs_kf, obs_feat, ref_kf, ref_level,
+        kf_frames (DeviceFrame or None per key frame), kf_center, kf_bad, scale_factors; optional new_world_pos (written to
+        the slots first), do_normal, do_descriptor (default 1).  `keep` collects the arrays the struct points to."""
+        def arr(key, dt):
+            v = case.get(key)
+            if v is None:
+                return None
+            keep.append(np.ascontiguousarray(v, dt))
+            return L.ptr(keep[-1])
+        P = L.MapRefreshInput()
+        P.n_points = len(case["slot"])
+        P.slot, P.world_pos = arr("slot", np.int32), arr("new_world_pos", np.float32)
+        P.obs_off, P.obs_kf, P.obs_feat = arr("obs_off", np.int32), arr("obs_kf", np.int32), arr("obs_feat", np.int32)
+        P.ref_kf, P.ref_level = arr("ref_kf", np.int32), arr("ref_level", np.int32)
+        frames = case.get("kf_frames")
+        P.n_kfs = len(case["kf_center"]) if frames is None else len(frames)
+        if frames is not None:
+            keep.append((C.c_void_p * max(len(frames), 1))(*[f.h.value if f is not None else None for f in frames]))
+            P.kf_frame = C.cast(keep[-1], C.c_void_p)
+        P.kf_center, P.kf_bad = arr("kf_center", np.float32), arr("kf_bad", np.uint8)
+        P.scale_factors = arr("scale_factors", np.float32)
+        P.n_levels = int(case.get("n_levels", len(case["scale_factors"]) if case.get("scale_factors") is not None else 0))
+        P.do_normal, P.do_descriptor = int(case.get("do_normal", 1)), int(case.get("do_descriptor", 1))
+        return P
+
+    def prepare_refresh(self, matcher, case):
+        """MapPoint::UpdateNormalAndDepth and ComputeDistinctiveDescriptors (MapPoint.cc:426-494, 329-403) of the listed slots
+        from their observations in resident key frames, in one call on `matcher`'s stream.  The call returns
+        dict(normal, min_dist, max_dist, best_obs, desc, status): the slots' values afterwards."""
+        keep = []
+        P = self.refresh_input(case, keep)
+        n = P.n_points
+        r = dict(normal=np.zeros((n, 3), np.float32), min_dist=np.zeros(n, np.float32), max_dist=np.zeros(n, np.float32),
+                 best_obs=np.zeros(n, np.int32), desc=np.zeros((n, 32), np.uint8), status=np.zeros(n, np.uint8))
+        out = L.MapRefreshOutput(*[L.ptr(r[k]) for k in ("normal", "min_dist", "max_dist", "best_obs", "desc", "status")])
+        fn, mh, ph, pP, pO = self.lib.rgbl_map_points_refresh, matcher.h, self.h, C.byref(P), C.byref(out)
+
+        def call(_keep=keep):
+            L.check(self.lib, fn(mh, ph, pP, pO))
+            return r
+        return call
+
+    def refresh(self, matcher, case):
+        return self.prepare_refresh(matcher, case)()
+
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             self.lib.rgbl_map_points_destroy(self.h)

@@ -26,16 +26,24 @@
 
 #include <iostream>
 #include <mutex>
+#include <tuple>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/rgbl_frontend.h"
 
 namespace rgbl_shim {
 
+// A Frame / KeyFrame class with a member `rgbl_device_frame* mpDeviceFrame` (one line in Frame.h / KeyFrame.h,
+// filled by ORBextractor::CaptureDeviceFrame in the Frame constructor) is matched from its resident copy: descriptors,
+// mvKeysUn and mvuRight are not uploaded again.  Classes without the member behave as before.
+template <class T> auto device_frame_of(const T& f, int) -> decltype(static_cast<const rgbl_device_frame*>(f.mpDeviceFrame)) { return f.mpDeviceFrame; }
+template <class T> const rgbl_device_frame* device_frame_of(const T&, long) { return nullptr; }
+
 class DeviceLocalMap {
  public:
-  explicit DeviceLocalMap(int device = 0, int capacity = 4096) : mnCapacity(capacity < 1 ? 1 : capacity) {
+  explicit DeviceLocalMap(int device = 0, int capacity = 4096) : mnDevice(device), mnCapacity(capacity < 1 ? 1 : capacity) {
     if (rgbl_map_points_create(device, mnCapacity, &mpPool) != RGBL_OK) {
       std::cerr << "[DeviceLocalMap] " << rgbl_last_error() << std::endl;
       mpPool = nullptr;
@@ -110,6 +118,147 @@ class DeviceLocalMap {
     if (pSlots) pSlots->swap(slot);
     return true;
   }
+  // MapPoint::UpdateNormalAndDepth (`normal`) and / or MapPoint::ComputeDistinctiveDescriptors (`descriptor`) for many points
+  // with ONE device call (rgbl_map_points_refresh): the observations go up as (key frame, feature) pairs, the descriptors
+  // are read from the key frames' resident copies (KeyFrame::mpDeviceFrame), the slots take the results and
+  // the MapPoint objects get them back through SetNormalVector / SetMinMaxDistance / SetDescriptor.  The
+  // slots also take the points' present GetWorldPos() (SetWorldPos after bundle adjustment needs no Update of its own).
+  // Bad points are skipped, as the two functions return at once for them.  A point that cannot go this way - a key frame
+  // among its observers without a resident copy, an observation with a right index and, when `normal` is asked for, a
+  // reference key frame without a resident copy or with another scale table than the call's - gets the MapPoint's own
+  // UpdateNormalAndDepth() / ComputeDistinctiveDescriptors() on the host and is uploaded with Update: no listed point is
+  // left stale, whichever way it went.
+  // Locks as for Update: the MapPoints' and KeyFrames' own mutexes are taken (by their accessors) and released before
+  // mMutex, mMutex is held until the device call has returned, and the setters run after it has been released.  Call it
+  // where the reference calls the two functions, outside the MapPoint's own locks.  *pnOnDevice: points that went the device way.
+  template <class MapPointT> bool Refresh(const std::vector<MapPointT*>& vpMPs, bool normal, bool descriptor, int* pnOnDevice = nullptr) {
+    if (pnOnDevice) *pnOnDevice = 0;
+    if (!mpPool) return false;
+    if (!normal && !descriptor) return true;
+    std::vector<MapPointT*> device, host, unregistered;
+    std::vector<float> pos, center, scale;
+    std::vector<int32_t> off(1, 0), obsKF, obsFeat, refKF, refLevel;
+    std::vector<const rgbl_device_frame*> frame;
+    std::vector<uint8_t> bad;
+    std::unordered_map<const void*, int32_t> table;   // key frame -> index
+    int nLevels = 0;
+    auto index_of = [&](auto* pKF) -> int32_t {   // -1: no resident copy
+      auto it = table.find(pKF);
+      if (it != table.end()) return it->second;
+      const rgbl_device_frame* f = device_frame_of(*pKF, 0);
+      int32_t k = -1;
+      if (f) {
+        k = (int32_t)frame.size();
+        frame.push_back(f);
+        const auto Ow = pKF->GetCameraCenter();
+        for (int c = 0; c < 3; ++c) center.push_back(Ow(c));
+        bad.push_back(pKF->isBad() ? 1 : 0);
+      }
+      table[pKF] = k;
+      return k;
+    };
+    std::unordered_set<const void*> listed;
+    for (MapPointT* pMP : vpMPs) {
+      if (!listed.insert(pMP).second) continue;                // a point listed twice is refreshed once
+      if (pMP->isBad()) continue;                              // MapPoint.cc:338, 434
+      auto observations = pMP->GetObservations();              // :340, 436
+      auto* pRefKF = pMP->GetReferenceKeyFrame();              // :437
+      const auto Pos = pMP->GetWorldPos();                     // :438
+      if (observations.empty()) continue;                      // :343, 441
+      const size_t mark = obsKF.size();
+      bool ok = !normal || pRefKF != nullptr;
+      for (auto mit = observations.begin(); ok && mit != observations.end(); ++mit) {
+        const int leftIndex = std::get<0>(mit->second), rightIndex = std::get<1>(mit->second);
+        const int32_t k = (leftIndex == -1 || rightIndex != -1) ? -1 : index_of(mit->first);
+        ok = k >= 0;
+        obsKF.push_back(k);
+        obsFeat.push_back(leftIndex);
+      }
+      int32_t kRef = 0, level = 0;
+      if (ok && normal) {
+        kRef = index_of(pRefKF);
+        // :471-475 observations[pRefKF] inserts (0, 0) for a reference key frame that does not observe the point
+        auto it = observations.find(pRefKF);
+        const int leftIndex = it == observations.end() ? 0 : std::get<0>(it->second);
+        ok = kRef >= 0 && pRefKF->NLeft == -1 && leftIndex >= 0 && leftIndex < (int)pRefKF->mvKeysUn.size();
+        if (ok) level = pRefKF->mvKeysUn[leftIndex].octave;
+      }
+      if (ok && normal) {   // one scale table per call: the first point's
+        const std::vector<float>& sf = pRefKF->mvScaleFactors;
+        if (scale.empty()) { scale = sf; nLevels = pRefKF->mnScaleLevels; }
+        ok = nLevels == pRefKF->mnScaleLevels && sf.size() == scale.size() && memcmp(sf.data(), scale.data(), sizeof(float) * sf.size()) == 0 &&
+             nLevels >= 1 && nLevels <= (int)sf.size() && level >= 0 && level < nLevels;
+      }
+      if (!ok) {
+        obsKF.resize(mark); obsFeat.resize(mark);
+        host.push_back(pMP);
+        continue;
+      }
+      device.push_back(pMP);
+      for (int c = 0; c < 3; ++c) pos.push_back(Pos(c));
+      off.push_back((int32_t)obsKF.size());
+      refKF.push_back(kRef);
+      refLevel.push_back(level);
+    }
+    for (MapPointT* pMP : host) {   // the reference's own functions, as before this class
+      if (normal) pMP->UpdateNormalAndDepth();
+      if (descriptor) pMP->ComputeDistinctiveDescriptors();
+    }
+    bool ok = host.empty() || Update(host);
+    const size_t n = device.size();
+    if (n == 0) return ok;
+    for (MapPointT* pMP : device)
+      if (SlotOf(pMP) < 0) unregistered.push_back(pMP);
+    if (!unregistered.empty() && !Update(unregistered)) return false;   // a new slot starts from the point's present values
+    std::vector<int32_t> slot(n);
+    std::vector<float> outNormal(3 * n), outMin(n), outMax(n);
+    std::vector<uint8_t> outDesc(32 * n), status(n, 0);
+    {
+      std::lock_guard<std::mutex> lock(mMutex);   // held until the call has returned: no slot below is erased and re-used meanwhile
+      for (size_t i = 0; i < n; ++i) {
+        auto it = mSlot.find(device[i]);
+        if (it == mSlot.end()) { std::cerr << "[DeviceLocalMap] a point was erased during Refresh" << std::endl; return false; }
+        slot[i] = it->second;
+      }
+      rgbl_map_refresh_input in{};
+      in.n_points = (int)n; in.slot = slot.data(); in.world_pos = pos.data();
+      in.obs_off = off.data(); in.obs_kf = obsKF.data(); in.obs_feat = obsFeat.data();
+      in.ref_kf = refKF.data(); in.ref_level = refLevel.data();
+      in.n_kfs = (int)frame.size(); in.kf_frame = frame.data(); in.kf_center = center.data(); in.kf_bad = bad.data();
+      in.scale_factors = scale.data(); in.n_levels = nLevels;
+      in.do_normal = normal; in.do_descriptor = descriptor;
+      rgbl_map_refresh_output out{};
+      out.normal = outNormal.data(); out.min_dist = outMin.data(); out.max_dist = outMax.data();
+      out.desc = outDesc.data(); out.status = status.data();
+      rgbl_matcher* handle = nullptr;
+      int rc = rgbl_matcher_acquire(mnDevice, &handle);
+      if (rc == RGBL_OK) {
+        rc = rgbl_map_points_refresh(handle, mpPool, &in, &out);
+        rgbl_matcher_release(handle);
+      }
+      if (rc != RGBL_OK) {
+        std::cerr << "[DeviceLocalMap] " << rgbl_last_error() << std::endl;
+        return false;
+      }
+    }
+    // the MapPoint objects stay in step (their setters take the MapPoint's own mutexes: no lock of this class is held)
+    for (size_t i = 0; i < n; ++i) {
+      if (status[i] & 1) {
+        auto nv = device[i]->GetNormal();
+        for (int c = 0; c < 3; ++c) nv(c) = outNormal[3 * i + c];
+        device[i]->SetNormalVector(nv);                                  // MapPoint.cc:492
+        device[i]->SetMinMaxDistance(outMin[i], outMax[i]);              // :490-491
+      }
+      if (status[i] & 2) {
+        auto d = device[i]->GetDescriptor();
+        if (d.rows != 1 || d.cols != 32) d.create(1, 32, 0 /* CV_8U */);
+        memcpy(d.template ptr<uint8_t>(), &outDesc[32 * i], 32);
+        device[i]->SetDescriptor(d);                                     // :401
+      }
+    }
+    if (pnOnDevice) *pnOnDevice = (int)n;
+    return ok;
+  }
   // the point's slot becomes free for the next new point (MapPoint::SetBadFlag); a point without a slot: nothing happens
   void Erase(const void* pMP) {
     std::lock_guard<std::mutex> lock(mMutex);
@@ -136,6 +285,7 @@ class DeviceLocalMap {
   std::mutex mMutex;
   std::unordered_map<const void*, int32_t> mSlot;
   std::vector<int32_t> mFree, mPending;   // mPending: erased while a search was running
+  int mnDevice;
   int mnNext = 0, mnCapacity, mnSearching = 0;
   rgbl_map_points* mpPool = nullptr;
 };

@@ -31,13 +31,7 @@
 #include "LocalMap.h"
 #include "cv_compat.h"
 
-namespace rgbl_shim {
-// A Frame / KeyFrame class with a member `rgbl_device_frame* mpDeviceFrame` (one line in Frame.h / KeyFrame.h,
-// filled by ORBextractor::CaptureDeviceFrame in the Frame constructor) is matched from its resident copy: descriptors,
-// mvKeysUn and mvuRight are not uploaded again.  Classes without the member behave as before.
-template <class T> auto device_frame_of(const T& f, int) -> decltype(static_cast<const rgbl_device_frame*>(f.mpDeviceFrame)) { return f.mpDeviceFrame; }
-template <class T> const rgbl_device_frame* device_frame_of(const T&, long) { return nullptr; }
-}  // namespace rgbl_shim
+// rgbl_shim::device_frame_of (a Frame / KeyFrame's resident copy, if its class has the member) lives in LocalMap.h
 
 namespace ORB_SLAM3 {
 
