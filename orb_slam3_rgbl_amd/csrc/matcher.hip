@@ -45,6 +45,15 @@ __device__ __forceinline__ int hamming256(const unsigned long long q[4], const u
   }
   return (int)acc;
 }
+// a 32-byte descriptor in registers: row i of an array of them, and its distance to row c of another
+struct Desc256 { unsigned long long w[4]; };
+__device__ __forceinline__ Desc256 load_desc(const uint8_t* base, int i) {
+  const unsigned long long* D = reinterpret_cast<const unsigned long long*>(base + (size_t)i * 32);
+  return Desc256{{D[0], D[1], D[2], D[3]}};
+}
+__device__ __forceinline__ int desc_dist(const Desc256& d, const uint8_t* base, int c) {
+  return hamming256(d.w, reinterpret_cast<const unsigned long long*>(base + (size_t)c * 32));
+}
 
 // A workgroup owns 64 query descriptors (one per lane, 4 x u64 in VGPRs).  Its four waves split the train set
 // into four contiguous index ranges; inside a wave the train descriptor address is wave-uniform, so it is
@@ -690,6 +699,18 @@ __host__ __device__ __forceinline__ void quat_rotate(const float q[4], float px,
   *rx = px + q[3] * ux + cx; *ry = py + q[3] * uy + cy; *rz = pz + q[3] * uz + cz;
 }
 
+// The grid cells GetFeaturesInArea(x, y, radius) walks, as ProjDev::rng holds them (lo | hi << 8); false: no cell (a NaN or
+// infinite coordinate ends here as it does in the reference: the arithmetic and the order of the comparisons are its own)
+__device__ __forceinline__ bool cell_window(const float grid[6], float x, float y, float radius, int* xr, int* yr) {
+  const int x0 = imax(0, (int)floorf((x - grid[0] - radius) * grid[4]));
+  const int x1 = imin(kGridCols - 1, (int)ceilf((x - grid[0] + radius) * grid[4]));
+  const int y0 = imax(0, (int)floorf((y - grid[1] - radius) * grid[5]));
+  const int y1 = imin(kGridRows - 1, (int)ceilf((y - grid[1] + radius) * grid[5]));
+  if (!(x0 < kGridCols && x1 >= 0 && y0 < kGridRows && y1 >= 0)) return false;
+  *xr = x0 | (x1 << 8); *yr = y0 | (y1 << 8);
+  return true;
+}
+
 // the static tests of GetFeaturesInArea + the stereo check (ORBmatcher.cc:1749-1755) for feature c of a point's window
 __device__ __forceinline__ bool window_accepts(const ProjDev& P, const float4& w, const int4& r, bool check_levels, int c) {
   if (check_levels) {
@@ -900,23 +921,40 @@ __device__ __forceinline__ void init_taken_by(const ProjDev& P) {
     P.taken_by[c] = (P.blocked2 && P.blocked2[c]) ? -1 : INT_MAX;
 }
 
-// grid = ceil(n1 / 4), block = 256 = one wave per LastFrame map point: projection and search window (ORBmatcher.cc:1696-1735,
-// computed by every lane alike), then its viable candidates by wave_candidates
+// The frame of the three candidate kernels (grid = ceil(n1 / 4), block = 256 = one wave per point, wave_point() names it): what a
+// point leaves for its resolve kernel, collected by collect_candidates when it has a window and stored by store_candidates
 constexpr int kPointsPerBlock = 4;
+__device__ __forceinline__ int wave_point() { return blockIdx.x * kPointsPerBlock + wave_id(); }
+struct CandResult { uint32_t ref = 0; uint8_t st = 1; };   // no window: an empty list, resolved
+// walk, window, list: key_of / keys as for wave_candidates, sorted / enc as for publish_candidates.  All 64 lanes call it.
+template <class KeyOf, class Enc>
+__device__ __forceinline__ CandResult collect_candidates(const ProjDev& P, int i, const float4& w, const int4& r, unsigned long long* keys,
+                                                         bool sorted, KeyOf&& key_of, Enc&& enc) {
+  CandResult res;
+  const int total = wave_candidates(P, w, r, keys, key_of);
+  if (lane_id() == 0) { P.win[i] = w; P.rng[i] = r; }
+  res.ref = publish_candidates(P, i, keys, total, sorted, enc);
+  res.st = total > 0 ? 0 : 1;  // no viable candidate: no match whatever the others do
+  return res;
+}
+// blockers: the search has points that block the feature they take (P.obs1)
+__device__ __forceinline__ void store_candidates(const ProjDev& P, int i, const CandResult& res, bool blockers) {
+  if (lane_id() == 0) { P.choice[i] = -1; P.cref[i] = res.ref; P.state[i] = res.st | ((blockers && P.obs1[i]) ? kStateObs : 0); }
+}
+
+// one wave per LastFrame map point: projection and search window (ORBmatcher.cc:1696-1735, computed by every lane alike), then
+// its viable candidates by wave_candidates
 __global__ __launch_bounds__(256) void k_proj_candidates(ProjDev P) {
   __shared__ unsigned long long s_keys[kPointsPerBlock][kProjCand];
   init_taken_by(P);
-  const int i = blockIdx.x * kPointsPerBlock + wave_id();
+  const int i = wave_point();
   if (i >= P.n1) return;
-  const int lane = lane_id();
-  uint8_t st = 1;
-  uint32_t ref = 0;
+  CandResult res;
   // everything the point needs is requested up front (it was four dependent global reads: valid -> position -> octave -> descriptor)
   const uint8_t valid = P.valid1[i];
   const float wx = P.wpos1[3 * i], wy = P.wpos1[3 * i + 1], wz = P.wpos1[3 * i + 2];
   const int oct_i = P.oct1[i];
-  const unsigned long long* D = reinterpret_cast<const unsigned long long*>(P.mpdesc1 + (size_t)i * 32);
-  const unsigned long long d[4] = {D[0], D[1], D[2], D[3]};
+  const Desc256 d = load_desc(P.mpdesc1, i);
   if (valid) {
     float x, y, z;
     if (P.sim3_mode) {
@@ -940,31 +978,21 @@ __global__ __launch_bounds__(256) void k_proj_candidates(ProjDev P) {
     if (in_view) {
       const int oct = oct_i;
       const float radius = P.th * P.scale[oct];
-      int min_level, max_level;
-      if (P.sim3_mode) { min_level = oct - 1; max_level = oct; }
-      else if (P.forward) { min_level = oct; max_level = -1; }
-      else if (P.backward) { min_level = 0; max_level = oct; }
-      else { min_level = oct - 1; max_level = oct + 1; }
-      const int x0 = imax(0, (int)floorf((u - P.grid[0] - radius) * P.grid[4]));
-      const int x1 = imin(kGridCols - 1, (int)ceilf((u - P.grid[0] + radius) * P.grid[4]));
-      const int y0 = imax(0, (int)floorf((v - P.grid[1] - radius) * P.grid[5]));
-      const int y1 = imin(kGridRows - 1, (int)ceilf((v - P.grid[1] + radius) * P.grid[5]));
-      if (x0 < kGridCols && x1 >= 0 && y0 < kGridRows && y1 >= 0) {
+      int4 r;
+      if (P.sim3_mode) { r.z = oct - 1; r.w = oct; }
+      else if (P.forward) { r.z = oct; r.w = -1; }
+      else if (P.backward) { r.z = 0; r.w = oct; }
+      else { r.z = oct - 1; r.w = oct + 1; }
+      if (cell_window(P.grid, u, v, radius, &r.x, &r.y)) {
         const float4 w = make_float4(u, v, radius, u - P.mbf * invzc);
-        const int4 r = make_int4(x0 | (x1 << 8), y0 | (y1 << 8), min_level, max_level);
-        auto dist_of = [&](int c) { return hamming256(d, reinterpret_cast<const unsigned long long*>(P.desc2 + (size_t)c * 32)); };
-        const int total = wave_candidates(P, w, r, s_keys[wave_id()], [&](int c, int cell) {
-          const int dist = dist_of(c);
-          return dist <= P.max_dist ? proj_key(dist, cell, c) : ~0ull;
-        });
-        if (lane == 0) { P.win[i] = w; P.rng[i] = r; }
-        ref = publish_candidates(P, i, s_keys[wave_id()], total, true,
-                                 [](unsigned long long key) { return cand_entry((int)(key >> 32), 0, (int)(key & 0xffffu)); });
-        st = total > 0 ? 0 : 1;  // no viable candidate: bestDist > TH_HIGH whatever the others do
+        res = collect_candidates(P, i, w, r, s_keys[wave_id()], true, [&](int c, int cell) {
+          const int dist = desc_dist(d, P.desc2, c);
+          return dist <= P.max_dist ? proj_key(dist, cell, c) : ~0ull;   // bestDist > TH_HIGH: not viable
+        }, [](unsigned long long key) { return cand_entry((int)(key >> 32), 0, (int)(key & 0xffffu)); });
       }
     }
   }
-  if (lane == 0) { P.choice[i] = -1; P.cref[i] = ref; P.state[i] = st | (P.obs1[i] ? kStateObs : 0); }
+  store_candidates(P, i, res, true);
 }
 
 // the feature point i takes among those not held by a lower-index blocker: the smallest key (-1 = none)
@@ -979,11 +1007,10 @@ __device__ __forceinline__ int proj_best(const ProjDev& P, const int32_t* taken_
     return -1;
   }
   unsigned long long best = ~0ull;
-  const unsigned long long* D = reinterpret_cast<const unsigned long long*>(P.mpdesc1 + (size_t)i * 32);
-  const unsigned long long d[4] = {D[0], D[1], D[2], D[3]};
+  const Desc256 d = load_desc(P.mpdesc1, i);
   for_candidates(P, P.win[i], P.rng[i], [&](int c, int cell) {
     if (taken_by[c] < i) return;
-    const int dist = hamming256(d, reinterpret_cast<const unsigned long long*>(P.desc2 + (size_t)c * 32));
+    const int dist = desc_dist(d, P.desc2, c);
     if (dist > P.max_dist) return;
     const unsigned long long key = proj_key(dist, cell, c);
     if (key < best) best = key;
@@ -1108,59 +1135,84 @@ __device__ __forceinline__ void resolve_rounds(int n1, int n2, int32_t* min_unre
   }
 }
 
+// What a resolve kernel keeps in LDS, declared ONCE per kernel as `__shared__`.  LDS = false: the round counters only, everything
+// else stays where the candidate kernels left it.  LDS = true: members in descending alignment, so no padding - the kernels sit
+// 8 KB below what a workgroup can have.
+template <bool LDS>
+struct ResolveShared { int s_unres[2]; };
+template <>
+struct ResolveShared<true> {
+  int s_unres[2], s_total;
+  int32_t s_taken[kResolveLdsN2], s_min[kResolveLdsN2];
+  uint32_t s_ref[kResolveLdsN1], s_list[kResolveLdsList];
+  uint16_t s_ulist[2][kUCap];
+  uint8_t s_state[kResolveLdsN1];
+};
+static_assert(sizeof(ResolveShared<true>) == 12 + 8 * kResolveLdsN2 + 5 * kResolveLdsN1 + 4 * kResolveLdsList + 4 * kUCap, "padding in the resolve kernels' LDS");
+// what a search's announce / decide see of the call: who holds a feature, the lowest unresolved blocker per feature, the points'
+// states (LDS or global memory) and the candidate lists
+struct ResolveView {
+  int32_t* taken_by;
+  int32_t* min_unres;
+  uint8_t* state;
+  ListView L;
+};
+// The body of a resolve kernel: stages the call's arrays, then runs the rounds with the search's two rules - announce(R, i, stamp)
+// and decide(R, i, stamp), see resolve_rounds.  With LDS the rounds are instantiated twice, for the lists in LDS and for the lists
+// where the candidate kernel left them: with ONE pointer chosen at run time the entries were read with flat loads.
+template <bool LDS, class Announce, class Decide>
+__device__ __forceinline__ void resolve_run(const ProjDev& P, ResolveShared<LDS>& sh, Announce&& announce, Decide&& decide) {
+  auto run = [&](const ResolveView R, uint16_t (*ulist)[LDS ? kUCap : 1]) {
+    resolve_rounds<LDS>(P.n1, P.n2, R.min_unres, sh.s_unres, ulist, [&](int i, int stamp) { announce(R, i, stamp); },
+                        [&](int i, int stamp) { return decide(R, i, stamp); });
+  };
+  if constexpr (LDS) {
+    const ListView staged = stage_lists<true>(P, sh.s_taken, sh.s_state, sh.s_ref, sh.s_list, &sh.s_total);
+    if (staged.clist != P.clist) run(ResolveView{sh.s_taken, sh.s_min, sh.s_state, ListView{sh.s_ref, sh.s_list}}, sh.s_ulist);
+    else run(ResolveView{sh.s_taken, sh.s_min, sh.s_state, ListView{sh.s_ref, P.clist}}, sh.s_ulist);
+  } else {
+    run(ResolveView{P.taken_by, P.min_unres, P.state, ListView{P.cref, P.clist}}, nullptr);   // no list of the unresolved without LDS
+  }
+}
+
 template <bool LDS>
 __global__ __launch_bounds__(kResolveBS) void k_proj_resolve(ProjDev P) {
-  __shared__ int s_unres[2], s_total;
-  __shared__ int32_t s_taken[LDS ? kResolveLdsN2 : 1], s_min[LDS ? kResolveLdsN2 : 1];
-  __shared__ uint8_t s_state[LDS ? kResolveLdsN1 : 1];
-  int32_t* taken_by = LDS ? s_taken : P.taken_by;
-  int32_t* min_unres = LDS ? s_min : P.min_unres;
-  uint8_t* state = LDS ? s_state : P.state;
-  __shared__ uint32_t s_ref[LDS ? kResolveLdsN1 : 1], s_list[LDS ? kResolveLdsList : 1];
-  __shared__ uint16_t s_ulist[2][LDS ? kUCap : 1];
-  const ListView staged = stage_lists<LDS>(P, s_taken, s_state, s_ref, s_list, &s_total);
-  // Instantiated twice, for the lists in LDS and for the lists where the candidate kernel left them: with ONE pointer chosen at run
-  // time the entries were read with flat loads
-  auto run = [&](const ListView L) {
+  __shared__ ResolveShared<LDS> sh;
+  resolve_run<LDS>(P, sh,
     // every unresolved blocker announces itself on the features it may still take
-    auto announce = [&](int i, int stamp) {
-      if (state[i] != kStateObs) return;   // unresolved and a blocker
-      const uint32_t r = L.cref[i];
+    [&](const ResolveView& R, int i, int stamp) {
+      if (R.state[i] != kStateObs) return;   // unresolved and a blocker
+      const uint32_t r = R.L.cref[i];
       const int me = (stamp << 20) | i;
       if (!(r & kRefOverflow)) {
-        const uint32_t* e = L.clist + ref_start(r);
+        const uint32_t* e = R.L.clist + ref_start(r);
         for (int k = 0, n = ref_n(r); k < n; ++k) {
           const int c = entry_feature(e[k]);
-          if (taken_by[c] >= i) atomicMin(&min_unres[c], me);
+          if (R.taken_by[c] >= i) atomicMin(&R.min_unres[c], me);
         }
       } else {
-        const unsigned long long* D = reinterpret_cast<const unsigned long long*>(P.mpdesc1 + (size_t)i * 32);
-        const unsigned long long d[4] = {D[0], D[1], D[2], D[3]};
+        const Desc256 d = load_desc(P.mpdesc1, i);
         for_candidates(P, P.win[i], P.rng[i], [&](int c, int) {
-          if (taken_by[c] < i) return;
-          if (hamming256(d, reinterpret_cast<const unsigned long long*>(P.desc2 + (size_t)c * 32)) <= P.max_dist) atomicMin(&min_unres[c], me);
+          if (R.taken_by[c] < i) return;
+          if (desc_dist(d, P.desc2, c) <= P.max_dist) atomicMin(&R.min_unres[c], me);
         });
       }
-    };
+    },
     // decide AND commit in one pass: a point whose best available feature no lower unresolved blocker can still take is final
     // and occupies it at once.  What a concurrent work-item sees of that store does not matter: a HIGHER point that misses it
     // picks the same feature, finds this point's announcement in front of it and waits a round; one that sees it takes its next
     // choice, which is what the sequential loop would have given it; LOWER points never want a feature that becomes final here
     // (their announcement would have held this point back).  Two blockers never become final on one feature in the same round.
-    auto decide = [&](int i, int stamp) {
-      const uint8_t st = state[i];
+    [&](const ResolveView& R, int i, int stamp) {
+      const uint8_t st = R.state[i];
       if (st & 0x7f) return false;
-      const int c = proj_best(P, taken_by, L.cref, L.clist, i);
-      if (c < 0) { state[i] = st | 1; P.choice[i] = -1; return false; }   // everything viable is taken: no match
-      if (lower_unresolved(min_unres[c], stamp, i)) return true;           // somebody in front of i can still take c
-      state[i] = st | 1; P.choice[i] = c;
-      if (st & kStateObs) taken_by[c] = i;
+      const int c = proj_best(P, R.taken_by, R.L.cref, R.L.clist, i);
+      if (c < 0) { R.state[i] = st | 1; P.choice[i] = -1; return false; }   // everything viable is taken: no match
+      if (lower_unresolved(R.min_unres[c], stamp, i)) return true;          // somebody in front of i can still take c
+      R.state[i] = st | 1; P.choice[i] = c;
+      if (st & kStateObs) R.taken_by[c] = i;
       return false;
-    };
-    resolve_rounds<LDS>(P.n1, P.n2, min_unres, s_unres, s_ulist, announce, decide);
-  };
-  if (LDS && staged.clist != P.clist) run(ListView{s_ref, s_list});
-  else run(ListView{LDS ? s_ref : P.cref, P.clist});
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1182,7 +1234,7 @@ struct FuseDev {
 // key of its cells - the cell number grows along the traversal, so the smallest key IS the reference's first minimum - and the
 // wave's minimum over (distance, cell) names the one lane that holds it.
 __global__ __launch_bounds__(256) void k_fuse_search(ProjDev P, FuseDev Fz) {
-  const int i = blockIdx.x * kPointsPerBlock + wave_id();
+  const int i = wave_point();
   if (i >= P.n1) return;
   const int lane = lane_id();
   unsigned long long best = ~0ull;
@@ -1203,14 +1255,10 @@ __global__ __launch_bounds__(256) void k_fuse_search(ProjDev P, FuseDev Fz) {
         const float ur = u - P.mbf * invz;
         const int level = P.oct1[i];
         const float radius = P.th * P.scale[level];
-        const int x0 = imax(0, (int)floorf((u - P.grid[0] - radius) * P.grid[4]));
-        const int x1 = imin(kGridCols - 1, (int)ceilf((u - P.grid[0] + radius) * P.grid[4]));
-        const int y0 = imax(0, (int)floorf((v - P.grid[1] - radius) * P.grid[5]));
-        const int y1 = imin(kGridRows - 1, (int)ceilf((v - P.grid[1] + radius) * P.grid[5]));
-        if (x0 < kGridCols && x1 >= 0 && y0 < kGridRows && y1 >= 0) {
-          const unsigned long long* D = reinterpret_cast<const unsigned long long*>(P.mpdesc1 + (size_t)i * 32);
-          const unsigned long long d[4] = {D[0], D[1], D[2], D[3]};
-          const int ny = y1 - y0 + 1, ncells = (x1 - x0 + 1) * ny;
+        int xr, yr;
+        if (cell_window(P.grid, u, v, radius, &xr, &yr)) {
+          const Desc256 d = load_desc(P.mpdesc1, i);
+          const int x0 = xr & 0xff, x1 = xr >> 8, y0 = yr & 0xff, y1 = yr >> 8, ny = y1 - y0 + 1, ncells = (x1 - x0 + 1) * ny;
           for (int t = lane; t < ncells; t += 64) {
             const int cell = (x0 + t / ny) * kGridRows + y0 + t % ny;
             const uint32_t kb = P.cell_start[cell], ke = P.cell_start[cell + 1];
@@ -1232,7 +1280,7 @@ __global__ __launch_bounds__(256) void k_fuse_search(ProjDev P, FuseDev Fz) {
                 const float e2 = ex * ex + ey * ey;
                 if ((double)(e2 * Fz.inv_sigma2[kl]) > 5.99) continue;
               }
-              const int dist = hamming256(d, reinterpret_cast<const unsigned long long*>(P.desc2 + (size_t)c * 32));
+              const int dist = desc_dist(d, P.desc2, c);
               const unsigned long long key = proj_key(dist, cell, c);
               if (key < best) best = key;  // strict '<' over the traversal order
             }
@@ -1265,48 +1313,33 @@ struct LocalScan {
   }
 };
 
-// grid = ceil(n1 / 4), block = 256 = one wave per map point
+// one wave per map point (the candidate kernels' frame: wave_point)
 __global__ __launch_bounds__(256) void k_local_candidates(ProjDev P) {
   __shared__ unsigned long long s_keys[kPointsPerBlock][kProjCand];
   init_taken_by(P);
-  const int i = blockIdx.x * kPointsPerBlock + wave_id();
+  const int i = wave_point();
   if (i >= P.n1) return;
-  const int lane = lane_id();
-  uint8_t st = 1;
-  uint32_t ref = 0;
+  CandResult res;
   // (requested up front, as in k_proj_candidates)
   const uint8_t valid = P.valid1[i];
   const int level_i = P.level1[i];
   const float viewcos = P.viewcos1[i], px = P.proj1[3 * i], py = P.proj1[3 * i + 1], pxr = P.proj1[3 * i + 2];
-  const unsigned long long* D = reinterpret_cast<const unsigned long long*>(P.mpdesc1 + (size_t)i * 32);
-  const unsigned long long d[4] = {D[0], D[1], D[2], D[3]};
+  const Desc256 d = load_desc(P.mpdesc1, i);
   if (valid) {
     const int level = level_i;
     float r = (double)viewcos > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos: the literal is a double in the reference
     if (P.th != 1.0f) r *= P.th;
     const float x = px, y = py;
     const float radius = r * P.scale[level];
-    if (x == x && y == y) {
-      const int x0 = imax(0, (int)floorf((x - P.grid[0] - radius) * P.grid[4]));
-      const int x1 = imin(kGridCols - 1, (int)ceilf((x - P.grid[0] + radius) * P.grid[4]));
-      const int y0 = imax(0, (int)floorf((y - P.grid[1] - radius) * P.grid[5]));
-      const int y1 = imin(kGridRows - 1, (int)ceilf((y - P.grid[1] + radius) * P.grid[5]));
-      if (x0 < kGridCols && x1 >= 0 && y0 < kGridRows && y1 >= 0) {
-        const float4 w = make_float4(x, y, radius, pxr);
-        const int4 rg = make_int4(x0 | (x1 << 8), y0 | (y1 << 8), level - 1, level);
-        const int total = wave_candidates(P, w, rg, s_keys[wave_id()], [&](int c, int) {
-          const int dist = hamming256(d, reinterpret_cast<const unsigned long long*>(P.desc2 + (size_t)c * 32));
-          return ((unsigned long long)dist << 32) | ((unsigned long long)P.oct2[c] << 16) | (unsigned)c;
-        });
-        if (lane == 0) { P.win[i] = w; P.rng[i] = rg; }
-        ref = publish_candidates(P, i, s_keys[wave_id()], total, false, [](unsigned long long key) {   // traversal order: the scan is replayed
-          return cand_entry((int)(key >> 32), (int)((key >> 16) & 0xffffu), (int)(key & 0xffffu));
-        });
-        st = total > 0 ? 0 : 1;
-      }
+    int4 rg = make_int4(0, 0, level - 1, level);
+    if (x == x && y == y && cell_window(P.grid, x, y, radius, &rg.x, &rg.y)) {
+      const float4 w = make_float4(x, y, radius, pxr);
+      res = collect_candidates(P, i, w, rg, s_keys[wave_id()], false /* traversal order: the scan is replayed */, [&](int c, int) {
+        return ((unsigned long long)desc_dist(d, P.desc2, c) << 32) | ((unsigned long long)P.oct2[c] << 16) | (unsigned)c;
+      }, [](unsigned long long key) { return cand_entry((int)(key >> 32), (int)((key >> 16) & 0xffffu), (int)(key & 0xffffu)); });
     }
   }
-  if (lane == 0) { P.choice[i] = -1; P.cref[i] = ref; P.state[i] = st | (P.obs1[i] ? kStateObs : 0); }
+  store_candidates(P, i, res, true);
 }
 
 // visits the candidates of point i that no lower-index blocker holds, in traversal order: f(dist, level, c)
@@ -1321,55 +1354,40 @@ __device__ __forceinline__ void local_available(const ProjDev& P, const int32_t*
     }
     return;
   }
-  const unsigned long long* D = reinterpret_cast<const unsigned long long*>(P.mpdesc1 + (size_t)i * 32);
-  const unsigned long long d[4] = {D[0], D[1], D[2], D[3]};
+  const Desc256 d = load_desc(P.mpdesc1, i);
   for_candidates(P, P.win[i], P.rng[i], [&](int c, int) {
     if (taken_by[c] < i) return;
-    f(hamming256(d, reinterpret_cast<const unsigned long long*>(P.desc2 + (size_t)c * 32)), P.oct2[c], c);
+    f(desc_dist(d, P.desc2, c), P.oct2[c], c);
   });
 }
 
 // grid = 1, block = kResolveBS; LDS, round stamps and the merged decide + commit pass as for k_proj_resolve
 template <bool LDS>
 __global__ __launch_bounds__(kResolveBS) void k_local_resolve(ProjDev P) {
-  __shared__ int s_unres[2], s_total;
-  __shared__ int32_t s_taken[LDS ? kResolveLdsN2 : 1], s_min[LDS ? kResolveLdsN2 : 1];
-  __shared__ uint8_t s_state[LDS ? kResolveLdsN1 : 1];
-  int32_t* taken_by = LDS ? s_taken : P.taken_by;
-  int32_t* min_unres = LDS ? s_min : P.min_unres;
-  uint8_t* state = LDS ? s_state : P.state;
-  __shared__ uint32_t s_ref[LDS ? kResolveLdsN1 : 1], s_list[LDS ? kResolveLdsList : 1];
-  __shared__ uint16_t s_ulist[2][LDS ? kUCap : 1];
-  const ListView staged = stage_lists<LDS>(P, s_taken, s_state, s_ref, s_list, &s_total);
-  // Instantiated twice, for the lists in LDS and for the lists where the candidate kernel left them: with ONE pointer chosen at run
-  // time the entries were read with flat loads
-  auto run = [&](const ListView L) {
-    auto announce = [&](int i, int stamp) {
-      if (state[i] != kStateObs) return;   // unresolved and a blocker
+  __shared__ ResolveShared<LDS> sh;
+  resolve_run<LDS>(P, sh,
+    [&](const ResolveView& R, int i, int stamp) {
+      if (R.state[i] != kStateObs) return;   // unresolved and a blocker
       const int me = (stamp << 20) | i;
-      local_available(P, taken_by, L, i, [&](int dist, int, int c) { if (dist <= 100) atomicMin(&min_unres[c], me); });
-    };
+      local_available(P, R.taken_by, R.L, i, [&](int dist, int, int c) { if (dist <= 100) atomicMin(&R.min_unres[c], me); });
+    },
     // (a settled point's available candidates carry no announcement of a lower point, so no lower point can occupy one of them in
     // this pass; a higher point's store leaves taken_by[c] >= i: still available to i)
-    auto decide = [&](int i, int stamp) {
-      const uint8_t st = state[i];
+    [&](const ResolveView& R, int i, int stamp) {
+      const uint8_t st = R.state[i];
       if (st & 0x7f) return false;
       LocalScan sc;
       bool settled = true;
-      local_available(P, taken_by, L, i, [&](int dist, int level, int c) {
+      local_available(P, R.taken_by, R.L, i, [&](int dist, int level, int c) {
         sc.visit(dist, level, c);
-        if (lower_unresolved(min_unres[c], stamp, i)) settled = false;  // somebody in front of i may still take this feature
+        if (lower_unresolved(R.min_unres[c], stamp, i)) settled = false;  // somebody in front of i may still take this feature
       });
       if (!settled) return true;
       const int c = sc.accept(P.nnratio);
-      state[i] = st | 1; P.choice[i] = c;
-      if (c >= 0 && (st & kStateObs)) taken_by[c] = i;
+      R.state[i] = st | 1; P.choice[i] = c;
+      if (c >= 0 && (st & kStateObs)) R.taken_by[c] = i;
       return false;
-    };
-    resolve_rounds<LDS>(P.n1, P.n2, min_unres, s_unres, s_ulist, announce, decide);
-  };
-  if (LDS && staged.clist != P.clist) run(ListView{s_ref, s_list});
-  else run(ListView{LDS ? s_ref : P.cref, P.clist});
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1651,46 +1669,31 @@ __device__ __forceinline__ void init_available(const ProjDev& P, const int32_t* 
     }
     return;
   }
-  const unsigned long long* D = reinterpret_cast<const unsigned long long*>(P.mpdesc1 + (size_t)i * 32);
-  const unsigned long long d[4] = {D[0], D[1], D[2], D[3]};
+  const Desc256 d = load_desc(P.mpdesc1, i);
   for_candidates(P, P.win[i], P.rng[i], [&](int c, int) {
-    const int dist = hamming256(d, reinterpret_cast<const unsigned long long*>(P.desc2 + (size_t)c * 32));
+    const int dist = desc_dist(d, P.desc2, c);
     if (dist <= P.max_dist && taken_by[c] > dist) f(dist, c);
   });
 }
 
-// grid = ceil(n1 / 64), block = 64
-__global__ __launch_bounds__(256) void k_init_candidates(ProjDev P) {   // one wave per F1 feature (wave_candidates), grid = ceil(n1 / 4)
+// grid = ceil(n1 / 4), block = 256 = one wave per F1 feature (the candidate kernels' frame).  No blockers (the state carries no
+// kStateObs), and no init_taken_by: F2 is never a resident frame here, so k_proj_grid has filled taken_by (= vMatchedDistance).
+__global__ __launch_bounds__(256) void k_init_candidates(ProjDev P) {
   __shared__ unsigned long long s_keys[kPointsPerBlock][kProjCand];
-  const int i = blockIdx.x * kPointsPerBlock + wave_id();
+  const int i = wave_point();
   if (i >= P.n1) return;
-  const int lane = lane_id();
-  uint8_t st = 1;
-  uint32_t ref = 0;
+  CandResult res;
   const float x = P.proj1[2 * i], y = P.proj1[2 * i + 1];
-  if (P.oct1[i] == 0 && x == x && y == y) {  // level1 > 0: continue (:664-666)
-    const float radius = P.th;
-    const int x0 = imax(0, (int)floorf((x - P.grid[0] - radius) * P.grid[4]));
-    const int x1 = imin(kGridCols - 1, (int)ceilf((x - P.grid[0] + radius) * P.grid[4]));
-    const int y0 = imax(0, (int)floorf((y - P.grid[1] - radius) * P.grid[5]));
-    const int y1 = imin(kGridRows - 1, (int)ceilf((y - P.grid[1] + radius) * P.grid[5]));
-    if (x0 < kGridCols && x1 >= 0 && y0 < kGridRows && y1 >= 0) {
-      const float4 w = make_float4(x, y, radius, 0.f);
-      const int4 rg = make_int4(x0 | (x1 << 8), y0 | (y1 << 8), 0, 0);  // minLevel = maxLevel = level1 = 0
-      const unsigned long long* D = reinterpret_cast<const unsigned long long*>(P.mpdesc1 + (size_t)i * 32);
-      const unsigned long long d[4] = {D[0], D[1], D[2], D[3]};
-      auto dist_of = [&](int c) { return hamming256(d, reinterpret_cast<const unsigned long long*>(P.desc2 + (size_t)c * 32)); };
-      const int total = wave_candidates(P, w, rg, s_keys[wave_id()], [&](int c, int) {
-        const int dist = dist_of(c);
-        return dist <= P.max_dist ? (((unsigned long long)dist << 32) | (unsigned)c) : ~0ull;
-      });
-      if (lane == 0) { P.win[i] = w; P.rng[i] = rg; }
-      ref = publish_candidates(P, i, s_keys[wave_id()], total, false,
-                               [](unsigned long long key) { return cand_entry((int)(key >> 32), 0, (int)(key & 0xffffu)); });
-      st = total > 0 ? 0 : 1;
-    }
+  int4 rg = make_int4(0, 0, 0, 0);  // minLevel = maxLevel = level1 = 0
+  if (P.oct1[i] == 0 && x == x && y == y && cell_window(P.grid, x, y, P.th, &rg.x, &rg.y)) {  // level1 > 0: continue (:664-666)
+    const float4 w = make_float4(x, y, P.th, 0.f);
+    const Desc256 d = load_desc(P.mpdesc1, i);
+    res = collect_candidates(P, i, w, rg, s_keys[wave_id()], false, [&](int c, int) {
+      const int dist = desc_dist(d, P.desc2, c);
+      return dist <= P.max_dist ? (((unsigned long long)dist << 32) | (unsigned)c) : ~0ull;
+    }, [](unsigned long long key) { return cand_entry((int)(key >> 32), 0, (int)(key & 0xffffu)); });
   }
-  if (lane == 0) { P.choice[i] = -1; P.cref[i] = ref; P.state[i] = st; }
+  store_candidates(P, i, res, false);
 }
 
 // grid = 1, block = kResolveBS; state, lists, round stamps and the merged decide + commit pass as for k_proj_resolve (taken_by holds
@@ -1699,45 +1702,30 @@ __global__ __launch_bounds__(256) void k_init_candidates(ProjDev P) {   // one w
 // from features that were going to lose it to this one anyway - they wait behind its announcement.
 template <bool LDS>
 __global__ __launch_bounds__(kResolveBS) void k_init_resolve(ProjDev P) {
-  __shared__ int s_unres[2], s_total;
-  __shared__ int32_t s_taken[LDS ? kResolveLdsN2 : 1], s_min[LDS ? kResolveLdsN2 : 1];
-  __shared__ uint8_t s_state[LDS ? kResolveLdsN1 : 1];
-  __shared__ uint32_t s_ref[LDS ? kResolveLdsN1 : 1], s_list[LDS ? kResolveLdsList : 1];
-  __shared__ uint16_t s_ulist[2][LDS ? kUCap : 1];
-  int32_t* taken_by = LDS ? s_taken : P.taken_by;
-  int32_t* min_unres = LDS ? s_min : P.min_unres;
-  uint8_t* state = LDS ? s_state : P.state;
-  const int tid = threadIdx.x;
-  for (int c = tid; c < P.n2; c += kResolveBS) P.owner[c] = -1;
-  const ListView staged = stage_lists<LDS>(P, s_taken, s_state, s_ref, s_list, &s_total);
-  // Instantiated twice, for the lists in LDS and for the lists where the candidate kernel left them: with ONE pointer chosen at run
-  // time the entries were read with flat loads
-  auto run = [&](const ListView L) {
-    auto announce = [&](int i, int stamp) {
-      if (state[i] != 0) return;
+  __shared__ ResolveShared<LDS> sh;
+  for (int c = threadIdx.x; c < P.n2; c += kResolveBS) P.owner[c] = -1;
+  resolve_run<LDS>(P, sh,
+    [&](const ResolveView& R, int i, int stamp) {
+      if (R.state[i] != 0) return;
       const int me = (stamp << 20) | i;
-      init_available(P, taken_by, L, i, [&](int, int c) { atomicMin(&min_unres[c], me); });
-    };
-    auto decide = [&](int i, int stamp) {
-      if (state[i] != 0) return false;
+      init_available(P, R.taken_by, R.L, i, [&](int, int c) { atomicMin(&R.min_unres[c], me); });
+    },
+    [&](const ResolveView& R, int i, int stamp) {
+      if (R.state[i] != 0) return false;
       int best = INT_MAX, best2 = INT_MAX, best_idx = -1;
       bool settled = true;
-      init_available(P, taken_by, L, i, [&](int dist, int c) {
+      init_available(P, R.taken_by, R.L, i, [&](int dist, int c) {
         if (dist < best) { best2 = best; best = dist; best_idx = c; }  // :692-701
         else if (dist < best2) best2 = dist;
-        if (lower_unresolved(min_unres[c], stamp, i)) settled = false;
+        if (lower_unresolved(R.min_unres[c], stamp, i)) settled = false;
       });
       if (!settled) return true;
       const bool ok = best <= 50 /* TH_LOW */ && (float)best < (float)best2 * P.nnratio;  // :704-706
-      state[i] = 1;
+      R.state[i] = 1;
       P.choice[i] = ok ? best_idx : -1;
-      if (ok) { taken_by[best_idx] = best; P.owner[best_idx] = i; }  // vMatchedDistance, vnMatches21 (:713-715)
+      if (ok) { R.taken_by[best_idx] = best; P.owner[best_idx] = i; }  // vMatchedDistance, vnMatches21 (:713-715)
       return false;
-    };
-    resolve_rounds<LDS>(P.n1, P.n2, min_unres, s_unres, s_ulist, announce, decide);
-  };
-  if (LDS && staged.clist != P.clist) run(ListView{s_ref, s_list});
-  else run(ListView{LDS ? s_ref : P.cref, P.clist});
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2740,6 +2728,30 @@ void greedy_layout(HostCall& hc, ProjDev& P) {
   P.state = hc.scratch<uint8_t>(P.n1);
 }
 
+// The entry points' shared argument tests and host passes.  sizes_ok: a feature's index travels in 16 bits, a level indexes P.scale.
+bool sizes_ok(int n1, int n2, int n_levels) { return n1 >= 0 && n2 >= 0 && n2 <= 65535 && n_levels >= 1 && n_levels <= kProjMaxLevels; }
+int check_point_count(int n1) {
+  if (n1 < (1 << 20)) return RGBL_OK;
+  set_error("at most 2^20 - 1 map points per call (a point's index travels in 20 bits of the resolve kernel's announcements)");
+  return RGBL_ERR_INVALID;
+}
+// the levels of the points the call looks at index n_levels scale factors
+int check_levels(const uint8_t* valid, const int32_t* level, int n, int n_levels, const char* what) {
+  for (int i = 0; i < n; ++i)
+    if (valid[i] && (level[i] < 0 || level[i] >= n_levels)) { set_error("%s", what); return RGBL_ERR_INVALID; }
+  return RGBL_OK;
+}
+void set_scales(ProjDev& P, const float* factors, int n_levels) {
+  for (int l = 0; l < kProjMaxLevels; ++l) P.scale[l] = l < n_levels ? factors[l] : 1.f;
+}
+// what the loop leaves in the frame's mvpMapPoints (a later point overwrites an unobserved earlier one); returns the match count
+int scatter_matches(const int32_t* choice, int n1, int32_t* match2) {
+  int nmatches = 0;
+  for (int i = 0; i < n1; ++i)
+    if (choice[i] >= 0) { match2[choice[i]] = i; ++nmatches; }
+  return nmatches;
+}
+
 int greedy_search(rgbl_matcher* m, hipStream_t s, ProjDev& P, const rgbl_device_frame* dev2, const GreedyKernels& K) {
   grid_for_call(m, s, P, dev2);
   m->timer.begin(K.candidates_name, s);
@@ -2758,9 +2770,8 @@ int projection_core(rgbl_matcher* m, const ProjHost& in, int32_t* match2, int* o
   const int n1 = in.n1, n2 = in.n2;
   for (int i = 0; i < n2; ++i) match2[i] = -1;
   if (n1 == 0 || n2 == 0) return RGBL_OK;
-  if (n1 >= (1 << 20)) { set_error("at most 2^20 - 1 map points per call (a point's index travels in 20 bits of the resolve kernel's announcements)"); return RGBL_ERR_INVALID; }
-  for (int i = 0; i < n1; ++i)
-    if (in.valid1[i] && (in.oct1[i] < 0 || in.oct1[i] >= in.n_levels)) { set_error("octave out of range"); return RGBL_ERR_INVALID; }
+  RGBL_TRY(check_point_count(n1));
+  RGBL_TRY(check_levels(in.valid1, in.oct1, n1, in.n_levels, "octave out of range"));
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
   HostCall hc(m);
@@ -2787,7 +2798,7 @@ int projection_core(rgbl_matcher* m, const ProjHost& in, int32_t* match2, int* o
   memcpy(P.K, in.K, sizeof(P.K));
   P.mbf = in.mbf;
   P.th = in.th;
-  for (int l = 0; l < kProjMaxLevels; ++l) P.scale[l] = l < in.n_levels ? in.scale_factors[l] : 1.f;
+  set_scales(P, in.scale_factors, in.n_levels);
   P.forward = in.forward; P.backward = in.backward;
   P.skip_behind = in.skip_behind; P.max_dist = in.max_dist;
   P.sim3_mode = in.sim3_mode;
@@ -2795,7 +2806,7 @@ int projection_core(rgbl_matcher* m, const ProjHost& in, int32_t* match2, int* o
   RGBL_TRY(hc.fetch());
   const int32_t* choice = hc.host(P.choice);
   // what the loop leaves in CurrentFrame.mvpMapPoints (a later point overwrites an unobserved earlier one), the match
-  // count, and the rotation-consistency pass (ORBmatcher.cc:1768-1790, 1860-1884 / 1961-2006)
+  // count, and the rotation-consistency pass (ORBmatcher.cc:1768-1790, 1860-1884 / 1961-2006): one pass, so not scatter_matches
   int nmatches = 0;
   RotationFilter rf;
   for (int i = 0; i < n1; ++i) {
@@ -2813,8 +2824,7 @@ int projection_core(rgbl_matcher* m, const ProjHost& in, int32_t* match2, int* o
 }  // namespace
 
 int rgbl_search_by_projection(rgbl_matcher* m, const rgbl_projection_input* in, int32_t* match2, int* out_nmatches) {
-  if (!m || !in || !match2 || !out_nmatches || in->n1 < 0 || in->n2 < 0 || in->n2 > 65535 || in->n_levels < 1 ||
-      in->n_levels > kProjMaxLevels) {
+  if (!m || !in || !match2 || !out_nmatches || !sizes_ok(in->n1, in->n2, in->n_levels)) {
     set_error("invalid argument (CurrentFrame may hold at most 65535 features, %d pyramid levels)", kProjMaxLevels);
     return RGBL_ERR_INVALID;
   }
@@ -2849,8 +2859,7 @@ int rgbl_search_by_projection(rgbl_matcher* m, const rgbl_projection_input* in, 
 // [predicted - 1, predicted + 1], radius th * scale[predicted], no stereo-coordinate test and no test of the sign of the depth.
 int rgbl_search_by_projection_keyframe(rgbl_matcher* m, const rgbl_keyframe_projection_input* in, int32_t* match2,
                                        int* out_nmatches) {
-  if (!m || !in || !match2 || !out_nmatches || in->n1 < 0 || in->n2 < 0 || in->n2 > 65535 || in->n_levels < 1 ||
-      in->n_levels > kProjMaxLevels || in->orb_dist < 0 || in->orb_dist > 255) {
+  if (!m || !in || !match2 || !out_nmatches || !sizes_ok(in->n1, in->n2, in->n_levels) || in->orb_dist < 0 || in->orb_dist > 255) {
     set_error("invalid argument (CurrentFrame may hold at most 65535 features, %d pyramid levels, ORBdist 0..255)", kProjMaxLevels);
     return RGBL_ERR_INVALID;
   }
@@ -2900,15 +2909,14 @@ int rgbl_distinctive_descriptors(rgbl_matcher* m, const uint8_t* desc, const int
 
 static int fuse_core(rgbl_matcher* m, const rgbl_fuse_input* in, int cam_frame, int proj_form, int chi2_gate, int max_dist,
                      int want_ur2, int32_t* best_idx, int32_t* best_dist) {
-  if (!m || !in || !best_idx || in->n1 < 0 || in->n2 < 0 || in->n2 > 65535 || in->n_levels < 1 || in->n_levels > kProjMaxLevels) {
+  if (!m || !in || !best_idx || !sizes_ok(in->n1, in->n2, in->n_levels)) {
     set_error("invalid argument (the key frame may hold at most 65535 features, %d pyramid levels)", kProjMaxLevels);
     return RGBL_ERR_INVALID;
   }
   const int n1 = in->n1, n2 = in->n2;
   for (int i = 0; i < n1; ++i) { best_idx[i] = -1; if (best_dist) best_dist[i] = 256; }
   if (n1 == 0 || n2 == 0) return RGBL_OK;
-  for (int i = 0; i < n1; ++i)
-    if (in->valid1[i] && (in->level1[i] < 0 || in->level1[i] >= in->n_levels)) { set_error("predicted level out of range"); return RGBL_ERR_INVALID; }
+  RGBL_TRY(check_levels(in->valid1, in->level1, n1, in->n_levels, "predicted level out of range"));
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
   HostCall hc(m);
@@ -2936,10 +2944,8 @@ static int fuse_core(rgbl_matcher* m, const rgbl_fuse_input* in, int cam_frame, 
   P.th = in->th;
   FuseDev Fz;
   Fz.cam_frame = cam_frame; Fz.proj_form = proj_form; Fz.chi2_gate = chi2_gate;
-  for (int l = 0; l < kProjMaxLevels; ++l) {
-    P.scale[l] = l < in->n_levels ? in->scale_factors[l] : 1.f;
-    Fz.inv_sigma2[l] = l < in->n_levels ? in->inv_level_sigma2[l] : 1.f;
-  }
+  set_scales(P, in->scale_factors, in->n_levels);
+  for (int l = 0; l < kProjMaxLevels; ++l) Fz.inv_sigma2[l] = l < in->n_levels ? in->inv_level_sigma2[l] : 1.f;
   grid_for_call(m, s, P, in->device2);
   m->timer.begin("k_fuse_search", s);
   hipLaunchKernelGGL(k_fuse_search, dim3((n1 + kPointsPerBlock - 1) / kPointsPerBlock), dim3(256), 0, s, P, Fz);
@@ -2962,8 +2968,8 @@ static int fuse_core(rgbl_matcher* m, const rgbl_fuse_input* in, int cam_frame, 
 // skipped by the points after it - on camera-frame points.
 int rgbl_search_by_projection_sim3(rgbl_matcher* m, const rgbl_project_search_input* in, const uint8_t* matched2, int32_t* match2,
                                    int* out_nmatches) {
-  if (!m || !in || !match2 || !out_nmatches || in->n1 < 0 || in->n2 < 0 || in->n2 > 65535 || in->n_levels < 1 ||
-      in->n_levels > kProjMaxLevels || (in->proj_form != 0 && in->proj_form != 2) || in->max_dist < 0 || in->max_dist > 255) {
+  if (!m || !in || !match2 || !out_nmatches || !sizes_ok(in->n1, in->n2, in->n_levels) || (in->proj_form != 0 && in->proj_form != 2) ||
+      in->max_dist < 0 || in->max_dist > 255) {
     set_error("invalid argument (at most 65535 features, %d pyramid levels, proj_form 0 / 2, max_dist 0..255)", kProjMaxLevels);
     return RGBL_ERR_INVALID;
   }
@@ -3011,18 +3017,16 @@ int rgbl_project_search(rgbl_matcher* m, const rgbl_project_search_input* in, in
 }
 
 int rgbl_search_local_points(rgbl_matcher* m, const rgbl_local_points_input* in, int32_t* match2, int* out_nmatches) {
-  if (!m || !in || !match2 || !out_nmatches || in->n1 < 0 || in->n2 < 0 || in->n2 > 65535 || in->n_levels < 1 ||
-      in->n_levels > kProjMaxLevels) {
+  if (!m || !in || !match2 || !out_nmatches || !sizes_ok(in->n1, in->n2, in->n_levels)) {
     set_error("invalid argument (the frame may hold at most 65535 features, %d pyramid levels)", kProjMaxLevels);
     return RGBL_ERR_INVALID;
   }
-  if (in->n1 >= (1 << 20)) { set_error("at most 2^20 - 1 map points per call (a point's index travels in 20 bits of the resolve kernel's announcements)"); return RGBL_ERR_INVALID; }
+  RGBL_TRY(check_point_count(in->n1));
   *out_nmatches = 0;
   const int n1 = in->n1, n2 = in->n2;
   for (int i = 0; i < n2; ++i) match2[i] = -1;
   if (n1 == 0 || n2 == 0) return RGBL_OK;
-  for (int i = 0; i < n1; ++i)
-    if (in->valid1[i] && (in->level1[i] < 0 || in->level1[i] >= in->n_levels)) { set_error("predicted level out of range"); return RGBL_ERR_INVALID; }
+  RGBL_TRY(check_levels(in->valid1, in->level1, n1, in->n_levels, "predicted level out of range"));
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
   HostCall hc(m);
@@ -3045,14 +3049,10 @@ int rgbl_search_local_points(rgbl_matcher* m, const rgbl_local_points_input* in,
   memcpy(P.grid, in->grid, sizeof(P.grid));
   P.th = in->th;
   P.nnratio = in->nnratio;
-  for (int l = 0; l < kProjMaxLevels; ++l) P.scale[l] = l < in->n_levels ? in->scale_factors[l] : 1.f;
+  set_scales(P, in->scale_factors, in->n_levels);
   RGBL_TRY(greedy_search(m, s, P, in->device2, {k_local_candidates, k_local_resolve<true>, k_local_resolve<false>, "k_local_candidates", "k_local_resolve"}));
   RGBL_TRY(hc.fetch());
-  const int32_t* choice = hc.host(P.choice);
-  int nmatches = 0;
-  for (int i = 0; i < n1; ++i)
-    if (choice[i] >= 0) { match2[choice[i]] = i; ++nmatches; }  // a later point overwrites an unobserved earlier one
-  *out_nmatches = nmatches;
+  *out_nmatches = scatter_matches(hc.host(P.choice), n1, match2);
   return RGBL_OK;
 }
 
@@ -3372,12 +3372,12 @@ int rgbl_map_points_refresh(rgbl_matcher* m, rgbl_map_points* pool, const rgbl_m
 namespace {
 int track_local_core(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t* in_view, rgbl_frustum_record* rec, int* n_in_view,
                      bool search, int32_t* match2, int* out_nmatches) {
-  if (!m || !in || !n_in_view || in->n1 < 0 || in->n_levels < 1 || in->n_levels > kProjMaxLevels || (in->n1 > 0 && !in_view) ||
-      (search && (!match2 || !out_nmatches || in->n2 < 0 || in->n2 > 65535))) {
+  if (!m || !in || !n_in_view || !sizes_ok(in->n1, search ? in->n2 : 0, in->n_levels) || (in->n1 > 0 && !in_view) ||
+      (search && (!match2 || !out_nmatches))) {
     set_error("invalid argument (the frame may hold at most 65535 features, %d pyramid levels)", kProjMaxLevels);
     return RGBL_ERR_INVALID;
   }
-  if (in->n1 >= (1 << 20)) { set_error("at most 2^20 - 1 map points per call (a point's index travels in 20 bits of the resolve kernel's announcements)"); return RGBL_ERR_INVALID; }
+  RGBL_TRY(check_point_count(in->n1));
   const int n1 = in->n1, n2 = search ? in->n2 : 0;
   *n_in_view = 0;
   if (search) {
@@ -3459,7 +3459,7 @@ int track_local_core(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t*
     memcpy(P.grid, in->grid, sizeof(P.grid));
     P.th = in->th;
     P.nnratio = in->nnratio;
-    for (int l = 0; l < kProjMaxLevels; ++l) P.scale[l] = l < in->n_levels ? in->scale_factors[l] : 1.f;
+    set_scales(P, in->scale_factors, in->n_levels);
     RGBL_TRY(greedy_search(m, s, P, in->device2, {k_local_candidates, k_local_resolve<true>, k_local_resolve<false>, "k_local_candidates", "k_local_resolve"}));
   }
   RGBL_TRY(hc.fetch());
@@ -3468,13 +3468,7 @@ int track_local_core(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t*
   int nv = 0;
   for (int i = 0; i < n1; ++i) nv += in_view[i] != 0;
   *n_in_view = nv;
-  if (do_search) {
-    const int32_t* choice = hc.host(P.choice);
-    int nmatches = 0;
-    for (int i = 0; i < n1; ++i)
-      if (choice[i] >= 0) { match2[choice[i]] = i; ++nmatches; }  // a later point overwrites an unobserved earlier one
-    *out_nmatches = nmatches;
-  }
+  if (do_search) *out_nmatches = scatter_matches(hc.host(P.choice), n1, match2);
   return RGBL_OK;
 }
 }  // namespace
