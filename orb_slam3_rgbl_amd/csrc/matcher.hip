@@ -54,6 +54,7 @@ __device__ __forceinline__ Desc256 load_desc(const uint8_t* base, int i) {
 __device__ __forceinline__ int desc_dist(const Desc256& d, const uint8_t* base, int c) {
   return hamming256(d.w, reinterpret_cast<const unsigned long long*>(base + (size_t)c * 32));
 }
+__device__ __forceinline__ int desc_dist(const Desc256& a, const Desc256& b) { return hamming256(a.w, b.w); }
 
 // A workgroup owns 64 query descriptors (one per lane, 4 x u64 in VGPRs).  Its four waves split the train set
 // into four contiguous index ranges; inside a wave the train descriptor address is wave-uniform, so it is
@@ -535,14 +536,26 @@ __global__ __launch_bounds__(64) void k_distinctive(const uint8_t* __restrict__ 
   if (lane == 0) best[p] = (int32_t)(wbest & 0xffffu);
 }
 
+// The searches over the vocabulary nodes two FeatureVectors share (SearchForTriangulation here, SearchByBoW further down) launch
+// one workgroup per shared node: node_span() is where workgroup blockIdx.x finds its two buckets.
+struct NodePairsDev {
+  const int32_t *off1, *feat1, *off2, *feat2;  // CSR buckets
+  const int32_t *pair_n1, *pair_n2;            // matched node pairs (indices into off1 / off2)
+};
+struct NodeSpan { int b1, n1, b2, n2; };       // the buckets are feat1[b1 .. b1 + n1) and feat2[b2 .. b2 + n2)
+__device__ __forceinline__ NodeSpan node_span(const NodePairsDev& N) {
+  const int a = N.pair_n1[blockIdx.x], b = N.pair_n2[blockIdx.x];
+  const int b1 = N.off1[a], b2 = N.off2[b];
+  return NodeSpan{b1, N.off1[a + 1] - b1, b2, N.off2[b + 1] - b2};
+}
+
 struct TriDev {
   const uint8_t *desc1, *desc2;
   const float *xy1, *xy2;
   const int32_t* oct2;
   const float *ur1, *ur2;
   const uint8_t *mp1, *mp2;
-  const int32_t *off1, *feat1, *off2, *feat2;  // CSR buckets
-  const int32_t *pair_n1, *pair_n2;            // matched node pairs (indices into off1/off2)
+  NodePairsDev fv;
   float F[9], ep[2];
   const float *scale2, *sigma2;
   int only_stereo, coarse;
@@ -559,15 +572,15 @@ struct TriDev {
 // takes a first-image feature, its lanes the candidates, and one DPP minimum over (distance << 26 | 2^26 - 1 - position) names the match.
 constexpr int kTriCap = 256;
 struct TriEntry {
-  unsigned long long d[4];
+  Desc256 d;
   float x, y;
   int32_t idx;
   int32_t oct_flags;  // octave | stereo << 8 | skip << 9 (holds a map point, or not stereo under only_stereo)
 };
+static_assert(sizeof(TriEntry) == 48, "k_search_triangulation's 24 576 bytes of LDS are 2 * kTriCap entries of 48 bytes");
 __device__ __forceinline__ TriEntry tri_load(const TriDev& T, bool second, int idx) {
   TriEntry e;
-  const unsigned long long* D = reinterpret_cast<const unsigned long long*>((second ? T.desc2 : T.desc1) + (size_t)idx * 32);
-  e.d[0] = D[0]; e.d[1] = D[1]; e.d[2] = D[2]; e.d[3] = D[3];
+  e.d = load_desc(second ? T.desc2 : T.desc1, idx);
   const float* xy = second ? T.xy2 : T.xy1;
   e.x = xy[2 * idx]; e.y = xy[2 * idx + 1];
   e.idx = idx;
@@ -578,15 +591,15 @@ __device__ __forceinline__ TriEntry tri_load(const TriDev& T, bool second, int i
 }
 __global__ __launch_bounds__(256) void k_search_triangulation(TriDev T) {
   __shared__ TriEntry s_1[kTriCap], s_2[kTriCap];
-  const int np = blockIdx.x, tid = threadIdx.x, lane = lane_id();
-  const int a = T.pair_n1[np], b = T.pair_n2[np];
-  const int b1 = T.off1[a], n1 = T.off1[a + 1] - b1, b2 = T.off2[b], n2 = T.off2[b + 1] - b2;
-  if (tid < n1) s_1[tid] = tri_load(T, false, T.feat1[b1 + tid]);
-  if (tid < n2) s_2[tid] = tri_load(T, true, T.feat2[b2 + tid]);
+  const int tid = threadIdx.x, lane = lane_id();
+  const NodeSpan S = node_span(T.fv);
+  const int b1 = S.b1, n1 = S.n1, b2 = S.b2, n2 = S.n2;
+  if (tid < n1) s_1[tid] = tri_load(T, false, T.fv.feat1[b1 + tid]);
+  if (tid < n2) s_2[tid] = tri_load(T, true, T.fv.feat2[b2 + tid]);
   __syncthreads();
   for (int p = wave_id(); p < n1; p += 4) {   // wave-uniform
     TriEntry e1;
-    if (p < kTriCap) e1 = s_1[p]; else e1 = tri_load(T, false, T.feat1[b1 + p]);
+    if (p < kTriCap) e1 = s_1[p]; else e1 = tri_load(T, false, T.fv.feat1[b1 + p]);
     if (e1.oct_flags & 0x200) continue;
     const bool stereo1 = (e1.oct_flags & 0x100) != 0;
     // epipolar line of kp1 in image 2 (Pinhole.cpp:115-117), constant over the candidates
@@ -597,9 +610,9 @@ __global__ __launch_bounds__(256) void k_search_triangulation(TriDev T) {
     uint32_t best = 0xffffffffu;
     for (int j = lane; j < n2; j += 64) {
       TriEntry e2;
-      if (j < kTriCap) e2 = s_2[j]; else e2 = tri_load(T, true, T.feat2[b2 + j]);
+      if (j < kTriCap) e2 = s_2[j]; else e2 = tri_load(T, true, T.fv.feat2[b2 + j]);
       if (e2.oct_flags & 0x200) continue;
-      const int dist = hamming256(e1.d, e2.d);
+      const int dist = desc_dist(e1.d, e2.d);
       if (dist > 50 /* TH_LOW */) continue;
       const int oct2 = e2.oct_flags & 0xff;
       if (!stereo1 && !(e2.oct_flags & 0x100)) {
@@ -619,7 +632,7 @@ __global__ __launch_bounds__(256) void k_search_triangulation(TriDev T) {
     best = wave_min_uniform(best);
     if (lane == 0 && best != 0xffffffffu) {
       const int j = 0x3ffffff - (int)(best & 0x3ffffffu);
-      T.matches12[e1.idx] = j < kTriCap ? s_2[j].idx : T.feat2[b2 + j];
+      T.matches12[e1.idx] = j < kTriCap ? s_2[j].idx : T.fv.feat2[b2 + j];
     }
   }
 }
@@ -1773,17 +1786,20 @@ __global__ __launch_bounds__(256) void k_bow_descend(VocDev V, const uint8_t* __
 }
 
 // ------------------------------------------------------------------------------------------------
-// ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) (ORBmatcher.cc:223-425, single
-// camera), the matcher of Tracking::TrackReferenceKeyFrame.  The vocabulary nodes shared by both FeatureVectors are
-// independent problems (a feature lives in exactly one node), inside a node the key-frame features are visited in
-// bucket order and a frame feature that got a match is skipped by all later ones.  One wave per shared node: the
+// ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) (ORBmatcher.cc:223-425), the matcher of
+// Tracking::TrackReferenceKeyFrame, and the key-frame / key-frame overload (:765-905).  The vocabulary nodes shared by both
+// FeatureVectors are independent problems (a feature lives in exactly one node), inside a node the key-frame features are visited in
+// bucket order and a frame feature that got a match is skipped by all later ones (:296-299).  One wave per shared node: the
 // key-frame features one after the other, the frame bucket spread over the lanes; best / second-best with the
 // reference's order rules = minimum of (distance << 16 | bucket position) and the second order statistic.
+// Two-camera frames (F.Nleft != -1, :298-326, 357-386; kRig): a key-frame feature keeps a best / second best among the node's
+// LEFT frame features and a best among its RIGHT ones; the left one is taken under the usual tests, the right one - only if the
+// left best passed `<= TH_LOW` - whenever its own distance does (`|| true`: no ratio test).  Both are gone for the later ones.
 struct BowDev {
   const uint8_t* desc1; const uint8_t* desc2;
   const uint8_t* valid1;
   const uint8_t* valid2;  // candidates must hold a good map point as well (the key-frame / key-frame overload), or nullptr
-  const int32_t *off1, *feat1, *off2, *feat2, *pair_n1, *pair_n2;
+  NodePairsDev fv;
   float nnratio;
   int max_best;           // largest accepted best distance: TH_LOW ("<=", :315) or TH_LOW - 1 ("<", :854)
   int n_left2;            // F.Nleft of a two-camera frame (k_search_by_bow_rig): features from n_left2 on belong to the right camera
@@ -1791,29 +1807,43 @@ struct BowDev {
   int32_t* match2;  // per frame feature: the key-frame feature, or -1
 };
 constexpr int kBowBucket = 16384;  // frame features of one node tracked in LDS (one byte each)
+struct BowShared {
+  uint8_t taken[kBowBucket];  // frame features at bucket positions beyond the register trips: taken or masked out
+  Desc256 q[64];              // the key-frame features' descriptors, 64 at a time, and their indices (-1: holds no map point)
+  int idx1[64];
+};
 
 // The node's work for a frame bucket of up to 64 * kRegTrips features (kRegTrips = 4: any size, positions from 256 on are read from
 // memory): instantiated per trip count so that a node pays for the lanes' registers it uses - the serial chain of the LARGEST node
-// is the kernel's time, and with one body for all sizes every step computed four trips' distances.
-template <int kRegTrips>
-__device__ __forceinline__ void bow_node(const BowDev& T, uint8_t* s_taken, unsigned long long (*s_q)[4], int* s_idx1, int lane, int b1, int e1, int b2, int n2) {
+// is the kernel's time, and with one body for all sizes every step computed four trips' distances.  The node's key-frame features
+// are taken one after the other, so what sits inside that serial loop decides the kernel's time: their descriptors are staged in
+// LDS 64 at a time, and instead of three dependent global loads per key-frame feature (100 -> ~15 us for a frame pair) the loop
+// body is LDS reads and register work.
+template <int kRegTrips, bool kRig>
+__device__ __forceinline__ void bow_node(const BowDev& T, BowShared& sh, int lane, const NodeSpan& S) {
+  const int b1 = S.b1, e1 = S.b1 + S.n1, b2 = S.b2, n2 = S.n2;
+  const int32_t *feat1 = T.fv.feat1, *feat2 = T.fv.feat2;
+  auto is_right = [&](int idx2) {
+    if constexpr (kRig) return idx2 >= T.n_left2; else return false;
+  };
   // the frame features at bucket positions lane, lane + 64, lane + 128, lane + 192 live in the lane's registers (index,
   // descriptor and whether the feature is taken): buckets of up to 256 features - a KITTI frame's largest hold ~100 - cost
   // neither a global nor an LDS access inside the serial loop
-  for (int j = lane + 64 * kRegTrips; j < n2; j += 64) s_taken[j] = (T.valid2 && !T.valid2[T.feat2[b2 + j]]) ? 1 : 0;   // beyond the register trips
-  unsigned long long t0[kRegTrips][4];
+  for (int j = lane + 64 * kRegTrips; j < n2; j += 64) sh.taken[j] = (T.valid2 && !T.valid2[feat2[b2 + j]]) ? 1 : 0;   // beyond the register trips
+  Desc256 t0[kRegTrips];
   int my_idx2[kRegTrips];
-  bool gone[kRegTrips];   // taken, masked out, or no such position
+  bool gone[kRegTrips], right[kRegTrips];   // gone: taken, masked out, or no such position
 #pragma unroll
   for (int r = 0; r < kRegTrips; ++r) {
     my_idx2[r] = -1;
     gone[r] = true;
-    t0[r][0] = t0[r][1] = t0[r][2] = t0[r][3] = 0ull;
+    right[r] = false;
+    t0[r] = Desc256{{0ull, 0ull, 0ull, 0ull}};
     if (lane + 64 * r < n2) {
-      my_idx2[r] = T.feat2[b2 + lane + 64 * r];
+      my_idx2[r] = feat2[b2 + lane + 64 * r];
       gone[r] = T.valid2 && !T.valid2[my_idx2[r]];
-      const unsigned long long* D2 = reinterpret_cast<const unsigned long long*>(T.desc2 + (size_t)my_idx2[r] * 32);
-      t0[r][0] = D2[0]; t0[r][1] = D2[1]; t0[r][2] = D2[2]; t0[r][3] = D2[3];
+      right[r] = is_right(my_idx2[r]);
+      t0[r] = load_desc(T.desc2, my_idx2[r]);
     }
   }
   for (int p0 = b1; p0 < e1; p0 += 64) {
@@ -1821,32 +1851,31 @@ __device__ __forceinline__ void bow_node(const BowDev& T, uint8_t* s_taken, unsi
     {
       const int p = p0 + lane;
       int idx1 = -1;
-      if (p < e1) { idx1 = T.feat1[p]; if (!T.valid1[idx1]) idx1 = -1; }
-      s_idx1[lane] = idx1;
-      if (idx1 >= 0) {
-        const unsigned long long* D1 = reinterpret_cast<const unsigned long long*>(T.desc1 + (size_t)idx1 * 32);
-        s_q[lane][0] = D1[0]; s_q[lane][1] = D1[1]; s_q[lane][2] = D1[2]; s_q[lane][3] = D1[3];
-      }
+      if (p < e1) { idx1 = feat1[p]; if (!T.valid1[idx1]) idx1 = -1; }
+      sh.idx1[lane] = idx1;
+      if (idx1 >= 0) sh.q[lane] = load_desc(T.desc1, idx1);
     }
     wave_sync();
     const int cnt = imin(64, e1 - p0);
     // the next key-frame feature's descriptor is fetched from LDS while the current one is worked on
-    int idx1_n = s_idx1[0];
-    unsigned long long qn[4] = {s_q[0][0], s_q[0][1], s_q[0][2], s_q[0][3]};
+    int idx1_n = sh.idx1[0];
+    Desc256 qn = sh.q[0];
     for (int k = 0; k < cnt; ++k) {
       const int idx1 = idx1_n;
-      const unsigned long long q[4] = {qn[0], qn[1], qn[2], qn[3]};
-      if (k + 1 < cnt) {
-        idx1_n = s_idx1[k + 1];
-        qn[0] = s_q[k + 1][0]; qn[1] = s_q[k + 1][1]; qn[2] = s_q[k + 1][2]; qn[3] = s_q[k + 1][3];
-      }
+      const Desc256 q = qn;
+      if (k + 1 < cnt) { idx1_n = sh.idx1[k + 1]; qn = sh.q[k + 1]; }
       if (idx1 < 0) continue;  // wave-uniform
-      uint32_t best = 0xffffffffu;  // dist << 16 | bucket position
+      uint32_t best = 0xffffffffu;  // dist << 16 | bucket position (kRig: among the left camera's)
       uint32_t second = 256;
+      uint32_t best_r = 0xffffffffu;  // kRig, right camera: the first minimum is all that is used
       // best / second-best without a branch (the loop body is what a node's serial chain is made of): the smaller key stays, the
       // larger one's distance competes for second place - the key it displaces when it is the new best (second >= best's distance
       // always), itself otherwise; an absent candidate is the key 0xffffffff and changes nothing
-      auto visit = [&](uint32_t key) {
+      auto visit = [&](uint32_t key, bool is_r) {
+        if constexpr (kRig) {
+          best_r = (is_r && key < best_r) ? key : best_r;
+          key = is_r ? 0xffffffffu : key;
+        }
         const uint32_t lo = key < best ? key : best, hi = key < best ? best : key;
         second = (hi >> 16) < second ? (hi >> 16) : second;
         best = lo;
@@ -1854,152 +1883,62 @@ __device__ __forceinline__ void bow_node(const BowDev& T, uint8_t* s_taken, unsi
 #pragma unroll
       for (int r = 0; r < kRegTrips; ++r) {
         if (64 * r >= n2) break;  // wave-uniform
-        const uint32_t key = ((uint32_t)hamming256(q, t0[r]) << 16) | (uint32_t)(lane + 64 * r);
-        visit(gone[r] ? 0xffffffffu : key);
-      }
-      for (int j = lane + 64 * kRegTrips; j < n2; j += 64) {
-        if (s_taken[j]) continue;
-        const int idx2 = T.feat2[b2 + j];
-        visit(((uint32_t)hamming256(q, reinterpret_cast<const unsigned long long*>(T.desc2 + (size_t)idx2 * 32)) << 16) | (uint32_t)j);
-      }
-      // wave-wide: the smallest key, and the smallest distance among everything else
-      const uint32_t wbest = wave_min_uniform(best);   // register-file DPP steps: the two reductions sit in the node's serial loop
-      const int other = (int)wave_min_uniform(best == wbest ? second : (best == 0xffffffffu ? 256u : best >> 16));
-      if (wbest == 0xffffffffu) continue;
-      const int best_dist = (int)(wbest >> 16), pos = (int)(wbest & 0xffffu);
-      if (best_dist <= T.max_best && (float)best_dist < T.nnratio * (float)other) {
-        if (lane == (pos & 63)) {   // the lane that holds the feature's index
-          int idx2 = -1;
-#pragma unroll
-          for (int r = 0; r < kRegTrips; ++r)
-            if ((pos >> 6) == r) { idx2 = my_idx2[r]; gone[r] = true; }
-          if (pos >= 64 * kRegTrips) { idx2 = T.feat2[b2 + pos]; s_taken[pos] = 1; }
-          T.match1[idx1] = idx2;
-          T.match2[idx2] = idx1;
-        }
-        if (pos >= 64 * kRegTrips) wave_sync();   // wave-uniform: the other lanes read s_taken
-      }
-    }
-  }
-}
-
-// grid = shared nodes, block = 64.  The node's key-frame features are taken one after the other (a frame feature taken by an
-// earlier one is gone for the later ones: ORBmatcher.cc:296-299), so what sits inside that serial loop decides the kernel's
-// time.  Round 6: the key-frame features' descriptors are staged in LDS 64 at a time and a lane keeps the descriptor of ITS
-// frame feature (bucket position = lane, every bucket of a KITTI frame's ~100 nodes fits) in registers - the loop body is LDS
-// reads and register work instead of three dependent global loads per key-frame feature (100 -> ~15 us for a frame pair).
-__global__ __launch_bounds__(64) void k_search_by_bow(BowDev T) {
-  __shared__ uint8_t s_taken[kBowBucket];
-  __shared__ unsigned long long s_q[64][4];
-  __shared__ int s_idx1[64];
-  const int np = blockIdx.x, lane = threadIdx.x;
-  const int a = T.pair_n1[np], b = T.pair_n2[np];
-  const int b1 = T.off1[a], e1 = T.off1[a + 1], b2 = T.off2[b], n2 = T.off2[b + 1] - b2;
-  if (n2 <= 64) bow_node<1>(T, s_taken, s_q, s_idx1, lane, b1, e1, b2, n2);
-  else if (n2 <= 128) bow_node<2>(T, s_taken, s_q, s_idx1, lane, b1, e1, b2, n2);
-  else if (n2 <= 192) bow_node<3>(T, s_taken, s_q, s_idx1, lane, b1, e1, b2, n2);
-  else bow_node<4>(T, s_taken, s_q, s_idx1, lane, b1, e1, b2, n2);
-}
-
-
-// Two-camera frames (F.Nleft != -1, ORBmatcher.cc:298-326, 357-386): a key-frame feature keeps a best / second best among the
-// node's LEFT frame features and a best among its RIGHT ones; the left one is taken under the usual tests, the right one - only if
-// the left best passed `<= TH_LOW` - whenever its own distance does (`|| true`: no ratio test).  Both are gone for the later
-// key-frame features.  One wave per node as above; the frame features of a lane live in registers for buckets of up to 256.
-__device__ __forceinline__ void bow_node_rig(const BowDev& T, uint8_t* s_taken, unsigned long long (*s_q)[4], int* s_idx1, int lane, int b1, int e1, int b2, int n2) {
-  constexpr int kRegTrips = 4;
-  for (int j = lane + 64 * kRegTrips; j < n2; j += 64) s_taken[j] = 0;
-  unsigned long long t0[kRegTrips][4];
-  int my_idx2[kRegTrips];
-  bool gone[kRegTrips], right[kRegTrips];
-#pragma unroll
-  for (int r = 0; r < kRegTrips; ++r) {
-    my_idx2[r] = -1;
-    gone[r] = true;
-    right[r] = false;
-    t0[r][0] = t0[r][1] = t0[r][2] = t0[r][3] = 0ull;
-    if (lane + 64 * r < n2) {
-      my_idx2[r] = T.feat2[b2 + lane + 64 * r];
-      gone[r] = false;
-      right[r] = my_idx2[r] >= T.n_left2;
-      const unsigned long long* D2 = reinterpret_cast<const unsigned long long*>(T.desc2 + (size_t)my_idx2[r] * 32);
-      t0[r][0] = D2[0]; t0[r][1] = D2[1]; t0[r][2] = D2[2]; t0[r][3] = D2[3];
-    }
-  }
-  for (int p0 = b1; p0 < e1; p0 += 64) {
-    wave_sync();
-    {
-      const int p = p0 + lane;
-      int idx1 = -1;
-      if (p < e1) { idx1 = T.feat1[p]; if (!T.valid1[idx1]) idx1 = -1; }
-      s_idx1[lane] = idx1;
-      if (idx1 >= 0) {
-        const unsigned long long* D1 = reinterpret_cast<const unsigned long long*>(T.desc1 + (size_t)idx1 * 32);
-        s_q[lane][0] = D1[0]; s_q[lane][1] = D1[1]; s_q[lane][2] = D1[2]; s_q[lane][3] = D1[3];
-      }
-    }
-    wave_sync();
-    const int cnt = imin(64, e1 - p0);
-    for (int k = 0; k < cnt; ++k) {
-      const int idx1 = s_idx1[k];
-      if (idx1 < 0) continue;  // wave-uniform
-      const unsigned long long q[4] = {s_q[k][0], s_q[k][1], s_q[k][2], s_q[k][3]};
-      uint32_t best = 0xffffffffu, second = 256;   // left camera: dist << 16 | bucket position, and the runner-up's distance
-      uint32_t best_r = 0xffffffffu;               // right camera: the first minimum is all that is used
-      auto visit = [&](uint32_t key, bool is_right) {
-        const uint32_t kl = is_right ? 0xffffffffu : key, kr = is_right ? key : 0xffffffffu;
-        const uint32_t lo = kl < best ? kl : best, hi = kl < best ? best : kl;
-        second = (hi >> 16) < second ? (hi >> 16) : second;
-        best = lo;
-        best_r = kr < best_r ? kr : best_r;
-      };
-#pragma unroll
-      for (int r = 0; r < kRegTrips; ++r) {
-        if (64 * r >= n2) break;  // wave-uniform
-        const uint32_t key = ((uint32_t)hamming256(q, t0[r]) << 16) | (uint32_t)(lane + 64 * r);
+        const uint32_t key = ((uint32_t)desc_dist(q, t0[r]) << 16) | (uint32_t)(lane + 64 * r);
         visit(gone[r] ? 0xffffffffu : key, right[r]);
       }
       for (int j = lane + 64 * kRegTrips; j < n2; j += 64) {
-        if (s_taken[j]) continue;
-        const int idx2 = T.feat2[b2 + j];
-        visit(((uint32_t)hamming256(q, reinterpret_cast<const unsigned long long*>(T.desc2 + (size_t)idx2 * 32)) << 16) | (uint32_t)j, idx2 >= T.n_left2);
+        if (sh.taken[j]) continue;
+        const int idx2 = feat2[b2 + j];
+        visit(((uint32_t)desc_dist(q, T.desc2, idx2) << 16) | (uint32_t)j, is_right(idx2));
       }
-      const uint32_t wbest = wave_min_uniform(best);
+      // wave-wide: the smallest key, and the smallest distance among everything else
+      const uint32_t wbest = wave_min_uniform(best);   // register-file DPP steps: the reductions sit in the node's serial loop
       const int other = (int)wave_min_uniform(best == wbest ? second : (best == 0xffffffffu ? 256u : best >> 16));
-      const uint32_t wbest_r = wave_min_uniform(best_r);
-      if (wbest == 0xffffffffu || (int)(wbest >> 16) > T.max_best) continue;   // :315: the right camera's match sits inside this test
+      uint32_t wbest_r = 0xffffffffu;
+      if constexpr (kRig) wbest_r = wave_min_uniform(best_r);
       const int best_dist = (int)(wbest >> 16);
-      const bool take_l = (float)best_dist < T.nnratio * (float)other;
-      const bool take_r = wbest_r != 0xffffffffu && (int)(wbest_r >> 16) <= T.max_best;
-      bool beyond = false;
-#pragma unroll
-      for (int side = 0; side < 2; ++side) {
-        if (!(side == 0 ? take_l : take_r)) continue;   // wave-uniform
-        const int pos = (int)((side == 0 ? wbest : wbest_r) & 0xffffu);
+      if (wbest == 0xffffffffu || best_dist > T.max_best) continue;   // :315: the right camera's match sits inside this test
+      // the lane that holds the feature's index takes it (wave-uniform call); true: the position is one of sh.taken
+      auto take = [&](uint32_t wkey, bool left) {
+        const int pos = (int)(wkey & 0xffffu);
         if (lane == (pos & 63)) {
           int idx2 = -1;
 #pragma unroll
           for (int r = 0; r < kRegTrips; ++r)
             if ((pos >> 6) == r) { idx2 = my_idx2[r]; gone[r] = true; }
-          if (pos >= 64 * kRegTrips) { idx2 = T.feat2[b2 + pos]; s_taken[pos] = 1; }
-          if (side == 0) T.match1[idx1] = idx2;   // the result is match2; match1 keeps the left camera's feature
+          if (pos >= 64 * kRegTrips) { idx2 = feat2[b2 + pos]; sh.taken[pos] = 1; }
+          if (left) T.match1[idx1] = idx2;   // kRig: the result is match2; match1 keeps the left camera's feature
           T.match2[idx2] = idx1;
         }
-        beyond = beyond || pos >= 64 * kRegTrips;
-      }
-      if (beyond) wave_sync();   // wave-uniform: the other lanes read s_taken
+        return pos >= 64 * kRegTrips;
+      };
+      bool beyond = false;
+      if ((float)best_dist < T.nnratio * (float)other) beyond = take(wbest, true);
+      if constexpr (kRig)
+        if (wbest_r != 0xffffffffu && (int)(wbest_r >> 16) <= T.max_best) beyond = take(wbest_r, false) || beyond;
+      if (beyond) wave_sync();   // wave-uniform
     }
   }
 }
 
-__global__ __launch_bounds__(64) void k_search_by_bow_rig(BowDev T) {
-  __shared__ uint8_t s_taken[kBowBucket];
-  __shared__ unsigned long long s_q[64][4];
-  __shared__ int s_idx1[64];
-  const int np = blockIdx.x, lane = threadIdx.x;
-  const int a = T.pair_n1[np], b = T.pair_n2[np];
-  const int b1 = T.off1[a], e1 = T.off1[a + 1], b2 = T.off2[b], n2 = T.off2[b + 1] - b2;
-  bow_node_rig(T, s_taken, s_q, s_idx1, lane, b1, e1, b2, n2);
+// grid = shared nodes, block = 64: a lane keeps the descriptor of ITS frame feature (bucket position = lane, every bucket of a KITTI
+// frame's ~100 nodes fits one trip) in registers.  Both kernels choose the node body by the frame bucket's size.
+template <bool kRig>
+__device__ __forceinline__ void bow_dispatch(const BowDev& T, BowShared& sh) {
+  const NodeSpan S = node_span(T.fv);
+  const int lane = threadIdx.x;
+  if (S.n2 <= 64) bow_node<1, kRig>(T, sh, lane, S);
+  else if (S.n2 <= 128) bow_node<2, kRig>(T, sh, lane, S);
+  else if (S.n2 <= 192) bow_node<3, kRig>(T, sh, lane, S);
+  else bow_node<4, kRig>(T, sh, lane, S);
+}
+__global__ __launch_bounds__(64) void k_search_by_bow(BowDev T) {
+  __shared__ BowShared sh;
+  bow_dispatch<false>(T, sh);
+}
+__global__ __launch_bounds__(64) void k_search_by_bow_rig(BowDev T) {   // a two-camera frame
+  __shared__ BowShared sh;
+  bow_dispatch<true>(T, sh);
 }
 
 }  // namespace rgbl
@@ -2143,16 +2082,32 @@ void put_feature_vector(HostCall& hc, const rgbl_keyframe_view* v, const int32_t
   hc.put(d_feat, v->node_feat, (size_t)nf);
 }
 
-// The vocabulary nodes two sorted FeatureVectors share, in the order of the reference's merge walk
-// (ORBmatcher.cc:243-246, 388-401; 963-968, 1103-1116).
-void shared_nodes(const rgbl_keyframe_view* a, const rgbl_keyframe_view* b, std::vector<int32_t>& pa, std::vector<int32_t>& pb) {
-  pa.clear(); pb.clear();
-  for (int i = 0, j = 0; i < a->n_nodes && j < b->n_nodes;) {
-    if (a->node_id[i] == b->node_id[j]) { pa.push_back(i++); pb.push_back(j++); }
-    else if (a->node_id[i] < b->node_id[j]) ++i;
-    else ++j;
+// What a search over two FeatureVectors starts from (SearchForTriangulation, SearchByBoW): the vocabulary nodes both sorted
+// vectors share, in the order of the reference's merge walk (ORBmatcher.cc:243-246, 388-401; 963-968, 1103-1116).
+struct FeatDst { const uint8_t** desc; const float** xy; const int32_t** oct; const float** ur; };   // null: the kernel does not read it
+struct SharedNodes {
+  const rgbl_keyframe_view *a, *b;
+  std::vector<int32_t> pa, pb;   // positions of the shared nodes in a's and b's node lists
+  SharedNodes(const rgbl_keyframe_view* a_, const rgbl_keyframe_view* b_) : a(a_), b(b_) {
+    for (int i = 0, j = 0; i < a->n_nodes && j < b->n_nodes;) {
+      if (a->node_id[i] == b->node_id[j]) { pa.push_back(i++); pb.push_back(j++); }
+      else if (a->node_id[i] < b->node_id[j]) ++i;
+      else ++j;
+    }
   }
-}
+  int npairs() const { return (int)pa.size(); }
+  bool empty() const { return pa.empty() || a->n == 0 || b->n == 0; }   // nothing to launch
+  // inside the call's layout: both sides' per-feature arrays and FeatureVectors (resident or staged), then the pair lists
+  int put(HostCall& hc, FeatDst d1, FeatDst d2, NodePairsDev& N) const {
+    RGBL_TRY(put_features(hc, a->device, a->n, a->desc, a->kp_xy, a->kp_octave, a->uright, d1.desc, d1.xy, d1.oct, d1.ur));
+    put_feature_vector(hc, a, &N.off1, &N.feat1);
+    RGBL_TRY(put_features(hc, b->device, b->n, b->desc, b->kp_xy, b->kp_octave, b->uright, d2.desc, d2.xy, d2.oct, d2.ur));
+    put_feature_vector(hc, b, &N.off2, &N.feat2);
+    hc.put(&N.pair_n1, pa.data(), pa.size());
+    hc.put(&N.pair_n2, pb.data(), pb.size());
+    return RGBL_OK;
+  }
+};
 
 // The rotation-consistency check (e.g. ORBmatcher.cc:1083-1096, 1119-1136): add() bins an item by angle_a - angle_b in the
 // order the caller visits it; drop_outliers() hands every item outside the bins ComputeThreeMaxima keeps (:2012-2053) to drop.
@@ -2180,6 +2135,24 @@ struct RotationFilter {
         for (int item : hist[i]) drop(item);
   }
 };
+
+// What is left to do once matches12[idx1] (a's feature -> b's, or -1) is filled: count, the rotation check with its bins filled in
+// the order the reference visits idx1 - node by node in merge order, bucket order (ORBmatcher.cc:1083-1096, 1119-1136; 855-865, 886-901) -
+// and *out_nmatches.
+void finish_matches12(const SharedNodes& sn, int32_t* matches12, bool check_orientation, int* out_nmatches) {
+  int nmatches = 0;
+  for (int i = 0; i < sn.a->n; ++i) nmatches += matches12[i] >= 0;
+  if (check_orientation) {
+    RotationFilter rf;
+    for (int p = 0; p < sn.npairs(); ++p)
+      for (int q = sn.a->node_off[sn.pa[p]]; q < sn.a->node_off[sn.pa[p] + 1]; ++q) {
+        const int idx1 = sn.a->node_feat[q];
+        if (matches12[idx1] >= 0) rf.add(idx1, sn.a->kp_angle[idx1], sn.b->kp_angle[matches12[idx1]]);
+      }
+    rf.drop_outliers([&](int idx1) { matches12[idx1] = -1; --nmatches; });
+  }
+  *out_nmatches = nmatches;
+}
 }  // namespace
 
 extern "C" {
@@ -2623,24 +2596,17 @@ int rgbl_search_triangulation(rgbl_matcher* m, const rgbl_keyframe_view* k1, con
   *out_nmatches = 0;
   const int n1 = k1->n, n2 = k2->n;
   for (int i = 0; i < n1; ++i) matches12[i] = -1;
-  std::vector<int32_t> pa, pb;
-  shared_nodes(k1, k2, pa, pb);
-  const int npairs = (int)pa.size();
-  if (npairs > 0 && n1 > 0 && n2 > 0) {
+  const SharedNodes sn(k1, k2);
+  if (!sn.empty()) {
     RGBL_HIP(hipSetDevice(m->device));
     StreamDrain drain(m->stream);  // error returns included
     HostCall hc(m);
     hipStream_t s = hc.s;
     TriDev T;
     RGBL_TRY(hc.begin([&]() -> int {
-      RGBL_TRY(put_features(hc, k1->device, n1, k1->desc, k1->kp_xy, nullptr, k1->uright, &T.desc1, &T.xy1, nullptr, &T.ur1));
-      put_feature_vector(hc, k1, &T.off1, &T.feat1);
-      RGBL_TRY(put_features(hc, k2->device, n2, k2->desc, k2->kp_xy, k2->kp_octave, k2->uright, &T.desc2, &T.xy2, &T.oct2, &T.ur2));
-      put_feature_vector(hc, k2, &T.off2, &T.feat2);
+      RGBL_TRY(sn.put(hc, {&T.desc1, &T.xy1, nullptr, &T.ur1}, {&T.desc2, &T.xy2, &T.oct2, &T.ur2}, T.fv));
       hc.put(&T.mp1, k1->has_mappoint, (size_t)n1);
       hc.put(&T.mp2, k2->has_mappoint, (size_t)n2);
-      hc.put(&T.pair_n1, pa.data(), (size_t)npairs);
-      hc.put(&T.pair_n2, pb.data(), (size_t)npairs);
       hc.put(&T.scale2, prm->scale_factors2, (size_t)prm->n_levels);
       hc.put(&T.sigma2, prm->level_sigma2_2, (size_t)prm->n_levels);
       T.matches12 = hc.put_fill<int32_t>(n1, 0xff);   // all -1: travels with the upload
@@ -2653,25 +2619,13 @@ int rgbl_search_triangulation(rgbl_matcher* m, const rgbl_keyframe_view* k1, con
     T.only_stereo = prm->only_stereo;
     T.coarse = prm->coarse;
     m->timer.begin("k_search_triangulation", s);
-    hipLaunchKernelGGL(k_search_triangulation, dim3(npairs), dim3(256), 0, s, T);
+    hipLaunchKernelGGL(k_search_triangulation, dim3(sn.npairs()), dim3(256), 0, s, T);
     m->timer.end(s);
     RGBL_HIP(hipGetLastError());
     RGBL_TRY(hc.fetch());
     memcpy(matches12, hc.host(T.matches12), sizeof(int32_t) * n1);
   }
-  int nmatches = 0;
-  for (int i = 0; i < n1; ++i) nmatches += matches12[i] >= 0;
-  if (prm->check_orientation) {
-    // ORBmatcher.cc:1083-1096, 1119-1136: bins filled in the order the reference visits idx1, node by node, bucket order
-    RotationFilter rf;
-    for (int p = 0; p < npairs; ++p)
-      for (int q = k1->node_off[pa[p]]; q < k1->node_off[pa[p] + 1]; ++q) {
-        const int idx1 = k1->node_feat[q];
-        if (matches12[idx1] >= 0) rf.add(idx1, k1->kp_angle[idx1], k2->kp_angle[matches12[idx1]]);
-      }
-    rf.drop_outliers([&](int idx1) { matches12[idx1] = -1; --nmatches; });
-  }
-  *out_nmatches = nmatches;
+  finish_matches12(sn, matches12, prm->check_orientation != 0, out_nmatches);
   return RGBL_OK;
 }
 
@@ -3808,19 +3762,16 @@ int rgbl_bow_transform_frame(rgbl_vocabulary* v, const rgbl_device_frame* frame,
                             cap_nodes, n_nodes);
 }
 
-// device part of both SearchByBoW overloads: match1[idx1] = feature of `fr` taken by key-frame feature idx1 (or -1), match2 the
-// inverse; pa / pb = the shared vocabulary nodes in merge order
-static int bow_core(rgbl_matcher* m, const rgbl_keyframe_view* kf, const rgbl_keyframe_view* fr, float nnratio, bool second_needs_mp,
-                    int max_best, std::vector<int32_t>& pa, std::vector<int32_t>& pb, std::vector<int32_t>& match1,
-                    std::vector<int32_t>& match2, int n_left2 = -1) {
-  const int n1 = kf->n, n2 = fr->n;
-  match1.assign(n1, -1);
-  match2.assign(n2, -1);
-  shared_nodes(kf, fr, pa, pb);
-  const int npairs = (int)pa.size();
-  if (npairs == 0 || n1 == 0 || n2 == 0) return RGBL_OK;
+// device part of both SearchByBoW overloads over the shared nodes `sn` of (kf, fr): match1[idx1] = feature of `fr` taken by
+// key-frame feature idx1 (or -1), match2 the inverse; a caller passes nullptr for the one it does not want, and has filled the
+// other with -1
+static int bow_core(rgbl_matcher* m, const SharedNodes& sn, float nnratio, bool second_needs_mp, int max_best, int n_left2,
+                    int32_t* match1, int32_t* match2) {
+  const rgbl_keyframe_view *kf = sn.a, *fr = sn.b;
+  const int n1 = kf->n, n2 = fr->n, npairs = sn.npairs();
+  if (sn.empty()) return RGBL_OK;
   for (int p = 0; p < npairs; ++p)
-    if (fr->node_off[pb[p] + 1] - fr->node_off[pb[p]] > kBowBucket) {
+    if (fr->node_off[sn.pb[p] + 1] - fr->node_off[sn.pb[p]] > kBowBucket) {
       set_error("SearchByBoW: a vocabulary node holds more than %d features of the second set", kBowBucket);
       return RGBL_ERR_CAPACITY;
     }
@@ -3831,14 +3782,9 @@ static int bow_core(rgbl_matcher* m, const rgbl_keyframe_view* kf, const rgbl_ke
   BowDev T;
   T.valid2 = nullptr;
   RGBL_TRY(hc.begin([&]() -> int {
-    RGBL_TRY(put_features(hc, kf->device, n1, kf->desc, nullptr, nullptr, nullptr, &T.desc1, nullptr, nullptr, nullptr));
-    put_feature_vector(hc, kf, &T.off1, &T.feat1);
-    RGBL_TRY(put_features(hc, fr->device, n2, fr->desc, nullptr, nullptr, nullptr, &T.desc2, nullptr, nullptr, nullptr));
-    put_feature_vector(hc, fr, &T.off2, &T.feat2);
+    RGBL_TRY(sn.put(hc, {&T.desc1}, {&T.desc2}, T.fv));
     hc.put(&T.valid1, kf->has_mappoint, (size_t)n1);
     if (second_needs_mp) hc.put(&T.valid2, fr->has_mappoint, (size_t)n2);
-    hc.put(&T.pair_n1, pa.data(), (size_t)npairs);
-    hc.put(&T.pair_n2, pb.data(), (size_t)npairs);
     T.match1 = hc.put_fill<int32_t>(n1, 0xff);   // all -1: travel with the upload
     T.match2 = hc.put_fill<int32_t>(n2, 0xff);
     hc.mark_result(T.match1, n1);
@@ -3858,8 +3804,8 @@ static int bow_core(rgbl_matcher* m, const rgbl_keyframe_view* kf, const rgbl_ke
   m->timer.end(s);
   RGBL_HIP(hipGetLastError());
   RGBL_TRY(hc.fetch());
-  memcpy(match1.data(), hc.host(T.match1), sizeof(int32_t) * n1);
-  memcpy(match2.data(), hc.host(T.match2), sizeof(int32_t) * n2);
+  if (match1) memcpy(match1, hc.host(T.match1), sizeof(int32_t) * n1);
+  if (match2) memcpy(match2, hc.host(T.match2), sizeof(int32_t) * n2);
   return RGBL_OK;
 }
 
@@ -3880,14 +3826,13 @@ int rgbl_search_by_bow_rig(rgbl_matcher* m, const rgbl_keyframe_view* kf, const 
   *out_nmatches = 0;
   const int n2 = fr->n;
   for (int i = 0; i < n2; ++i) match_f[i] = -1;
-  std::vector<int32_t> pa, pb, match1, match2;
-  RGBL_TRY(bow_core(m, kf, fr, nnratio, false, 50 /* <= TH_LOW */, pa, pb, match1, match2, frame_n_left));
+  RGBL_TRY(bow_core(m, SharedNodes(kf, fr), nnratio, false, 50 /* <= TH_LOW */, frame_n_left, nullptr, match_f));
   int nmatches = 0;
-  for (int i = 0; i < n2; ++i) { match_f[i] = match2[i]; nmatches += match_f[i] >= 0; }
+  for (int i = 0; i < n2; ++i) nmatches += match_f[i] >= 0;
   if (check_orientation) {
     RotationFilter rf;
     for (int idx2 = 0; idx2 < n2; ++idx2)
-      if (match2[idx2] >= 0) rf.add(idx2, kf->kp_angle[match2[idx2]], fr->kp_angle[idx2]);
+      if (match_f[idx2] >= 0) rf.add(idx2, kf->kp_angle[match_f[idx2]], fr->kp_angle[idx2]);
     rf.drop_outliers([&](int idx2) { match_f[idx2] = -1; --nmatches; });
   }
   *out_nmatches = nmatches;
@@ -3900,23 +3845,10 @@ int rgbl_search_by_bow_keyframes(rgbl_matcher* m, const rgbl_keyframe_view* kf1,
                                  int check_orientation, int32_t* match12, int* out_nmatches) {
   if (!m || !kf1 || !kf2 || !match12 || !out_nmatches || kf1->n < 0 || kf2->n < 0) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
   *out_nmatches = 0;
-  const int n1 = kf1->n;
-  for (int i = 0; i < n1; ++i) match12[i] = -1;
-  std::vector<int32_t> pa, pb, match1, match2;
-  RGBL_TRY(bow_core(m, kf1, kf2, nnratio, true, 49 /* < TH_LOW */, pa, pb, match1, match2));
-  const int npairs = (int)pa.size();
-  int nmatches = 0;
-  for (int i = 0; i < n1; ++i) { match12[i] = match1[i]; nmatches += match12[i] >= 0; }
-  if (check_orientation) {
-    RotationFilter rf;
-    for (int p = 0; p < npairs; ++p)
-      for (int q = kf1->node_off[pa[p]]; q < kf1->node_off[pa[p] + 1]; ++q) {
-        const int idx1 = kf1->node_feat[q];
-        if (match1[idx1] >= 0) rf.add(idx1, kf1->kp_angle[idx1], kf2->kp_angle[match1[idx1]]);
-      }
-    rf.drop_outliers([&](int idx1) { match12[idx1] = -1; --nmatches; });
-  }
-  *out_nmatches = nmatches;
+  for (int i = 0; i < kf1->n; ++i) match12[i] = -1;
+  const SharedNodes sn(kf1, kf2);
+  RGBL_TRY(bow_core(m, sn, nnratio, true, 49 /* < TH_LOW */, -1, match12, nullptr));
+  finish_matches12(sn, match12, check_orientation != 0, out_nmatches);
   return RGBL_OK;
 }
 

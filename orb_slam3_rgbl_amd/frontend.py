@@ -961,23 +961,7 @@ class ORBmatcher:
         """kf = dict(desc, xy, octave, angle, uright, has_mp, node_id, node_off, node_feat).
         Returns (vMatchedPairs as [m,2] int array in ascending idx1, nmatches)."""
         keep = []
-
-        def view(kf):
-            v = L.KeyframeView()
-            v.n = len(kf["desc"])
-            for field, key, dt in (("desc", "desc", np.uint8), ("kp_xy", "xy", np.float32),
-                                   ("kp_octave", "octave", np.int32), ("kp_angle", "angle", np.float32),
-                                   ("uright", "uright", np.float32), ("has_mappoint", "has_mp", np.uint8),
-                                   ("node_id", "node_id", np.int32), ("node_off", "node_off", np.int32),
-                                   ("node_feat", "node_feat", np.int32)):
-                a = np.ascontiguousarray(kf[key], dt)
-                keep.append(a)
-                setattr(v, field, a.ctypes.data)
-            v.n_nodes = len(kf["node_id"])
-            v.device = _dev(kf, "device")
-            return v
-
-        v1, v2 = view(kf1), view(kf2)
+        v1, v2 = self._view(kf1, keep), self._view(kf2, keep)
         P = L.TriangulationParams()
         for i in range(9):
             P.F12[i] = float(F12[i])

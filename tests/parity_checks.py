@@ -784,6 +784,162 @@ def check_search_by_bow_keyframes(lib, seed=81, nnratio=0.75, check_ori=True, n=
     return nm
 
 
+# Second-set bucket sizes of the directed FeatureVector cases, one vocabulary node each: the edges of the register trips of
+# k_search_by_bow / k_search_by_bow_rig (64, 128, 192, 256 positions; 256 is the first one tracked in LDS), of the 64-wide staging
+# passes over the first set's bucket, and of kTriCap = 256 on both sides of k_search_triangulation.
+BUCKET_SIZES = (1, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 320)
+
+
+def make_bucket_case(seed, sizes=BUCKET_SIZES):
+    """make_triangulation_case's key frames with FeatureVectors built by hand: the second set's features go into the nodes in runs
+    of the prescribed sizes, a first-set feature into the node of the feature that was derived from it (equal bucket sizes).
+    An eighth of a bucket's first-set features are turned into TWINS of others of the same bucket (three bits apart), so that two
+    features want the same second-set feature and the later one has to find it gone: kf1["twins"] = rows of (first-set feature,
+    its twin, the second-set feature both are nearest to)."""
+    n = int(np.sum(sizes))
+    kf1, kf2, K, R, t, ep, sf, s2 = make_triangulation_case(n, seed, 1)
+    _, perm = synth.perturbed_descriptors(kf1["desc"], flip_p=0.04, seed=seed + 1)   # kf2's feature i comes from kf1's perm[i]
+    node2 = np.repeat(np.arange(len(sizes)), sizes)
+    node1 = np.empty(n, np.int64)
+    node1[perm] = node2
+    for kf, node in ((kf1, node1), (kf2, node2)):
+        kf["node_id"] = (3 + 7 * np.arange(len(sizes))).astype(np.int32)
+        kf["node_off"] = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        kf["node_feat"] = np.argsort(node, kind="stable").astype(np.int32)   # ascending inside a node, as DBoW2 fills it
+    rng = np.random.default_rng(seed + 500)
+    inv = np.argsort(perm)
+    desc1, twins = kf1["desc"].copy(), []
+    for k, s in enumerate(sizes):
+        members = kf1["node_feat"][kf1["node_off"][k]:kf1["node_off"][k + 1]]
+        pick = rng.permutation(s)[:2 * (s // 8)]
+        for src, dst in zip(members[pick[:len(pick) // 2]], members[pick[len(pick) // 2:]]):
+            bits = np.unpackbits(desc1[src])
+            bits[rng.choice(256, 3, replace=False)] ^= 1
+            desc1[dst] = np.packbits(bits)
+            twins.append((src, dst, inv[src]))
+    kf1["desc"], kf1["twins"] = desc1, np.array(twins, np.int64)
+    return kf1, kf2, K, R, t, ep, sf, s2
+
+
+def make_bucket_rig_case(seed, sizes=BUCKET_SIZES):
+    """A key frame and a two-camera frame whose buckets, left and right features together, have the prescribed sizes: the left
+    camera takes ceil(size / 2) features of a node, the right camera perturbed copies of them, one less where the size is odd."""
+    kf, left, *_ = make_bucket_case(seed, [(s + 1) // 2 for s in sizes])
+    n_left = len(left["desc"])
+    rng = np.random.default_rng(seed + 1000)
+    right_desc, perm = synth.perturbed_descriptors(left["desc"], flip_p=0.05, seed=seed + 3)
+    node_l = np.repeat(np.arange(len(sizes)), np.diff(left["node_off"]))   # left features sit in the nodes in runs
+    node_r = node_l[perm]
+    keep = np.ones(n_left, bool)
+    for k, s in enumerate(sizes):
+        if s % 2:
+            keep[np.nonzero(node_r == k)[0][-1]] = False
+    right_desc, perm, node_r = right_desc[keep], perm[keep], node_r[keep]
+    right_of = np.full(n_left, -1, np.int64)   # the right camera's copy of a left feature
+    right_of[perm] = n_left + np.arange(len(perm))
+    tw = kf["twins"]
+    kf["twins"] = np.concatenate([tw, np.stack([tw[:, 0], tw[:, 1], right_of[tw[:, 2]]], 1)[right_of[tw[:, 2]] >= 0]])
+    feat, off = [], [0]
+    for k in range(len(sizes)):
+        feat.extend(np.nonzero(node_l == k)[0].tolist())
+        feat.extend((np.nonzero(node_r == k)[0] + n_left).tolist())
+        off.append(len(feat))
+    assert tuple(np.diff(off)) == tuple(sizes)
+    n_right = len(perm)
+    ang_r = (left["angle"][perm] + rng.normal(0, 10, n_right)).astype(np.float32) % 360
+    n = n_left + n_right
+    frame = dict(desc=np.concatenate([left["desc"], right_desc]), xy=np.concatenate([left["xy"], left["xy"][perm]]),
+                 octave=np.concatenate([left["octave"], left["octave"][perm]]), angle=np.concatenate([left["angle"], ang_r]),
+                 uright=np.full(n, -1, np.float32), has_mp=np.zeros(n, np.uint8), node_id=left["node_id"],
+                 node_off=np.array(off, np.int32), node_feat=np.array(feat, np.int32))
+    return kf, frame, n_left
+
+
+def bucket_reach(second, matched2):
+    """Where the oracle's matches lie: (sizes of the second set's buckets that hold a matched feature, the largest bucket position
+    of one, bucket size per second-set feature)."""
+    off, feat = second["node_off"], second["node_feat"]
+    size = np.zeros(len(second["desc"]), np.int64)
+    pos = np.zeros(len(second["desc"]), np.int64)
+    for k in range(len(off) - 1):
+        size[feat[off[k]:off[k + 1]]] = off[k + 1] - off[k]
+        pos[feat[off[k]:off[k + 1]]] = np.arange(off[k + 1] - off[k])
+    return set(size[matched2].tolist()), int(pos[matched2].max()), size, pos
+
+
+def contested_positions(kf, owner2, pos2):
+    """Bucket positions of the second-set features that one of two twins (both with a map point) holds in the oracle's result
+    owner2 (second-set feature -> first-set feature or -1) while the other twin went without a match: it found the feature gone."""
+    out = []
+    for src, dst, f in kf["twins"]:
+        if kf["has_mp"][src] and kf["has_mp"][dst] and owner2[f] in (src, dst) and not (owner2 == (src + dst - owner2[f])).any():
+            out.append(int(pos2[f]))
+    return out
+
+
+def check_bucket_sizes(lib, seed=3, sizes=BUCKET_SIZES):
+    """All four FeatureVector searches on buckets of exactly the sizes in BUCKET_SIZES, bit for bit against the oracle.  Every case
+    first asserts on the ORACLE's output that it reaches what it is for: a match in a bucket of every size from 63 up, a match
+    taken at a bucket position >= 256 (beyond the register trips / kTriCap) and, in the SearchByBoW forms, a feature that had to
+    do without the second-set feature its twin took, at a position below and at one from 256 on."""
+    want = {s for s in sizes if s >= 63}
+
+    def reach(second, matched2, first=None, owner2=None):
+        hit, last, size, pos = bucket_reach(second, matched2)
+        assert want <= hit, "no match in buckets of %s" % sorted(want - hit)
+        assert last >= 256
+        if first is not None:
+            gone = contested_positions(first, owner2, pos)
+            assert min(gone) < 256 <= max(gone), "twins contested positions %s" % sorted(gone)
+        return size
+
+    kf1, kf2, K, R, t, ep, sf, s2 = make_bucket_case(seed, sizes)
+    assert tuple(np.diff(kf1["node_off"])) == tuple(np.diff(kf2["node_off"])) == tuple(sizes)
+    rng = np.random.default_rng(seed)
+    n = len(kf1["desc"])
+    # SearchByBoW(KF, F)
+    kf = dict(kf1, has_mp=(rng.random(n) < 0.7).astype(np.uint8))
+    om, onm = O.search_by_bow(kf, kf2, 0.7, True)
+    reach(kf2, om >= 0, kf, om)
+    mt = F.ORBmatcher(0.7, True, lib=lib)
+    m, nm = mt.SearchByBoW(kf, kf2)
+    assert nm == onm and np.array_equal(m, om), "SearchByBoW(KF, F)"
+    mt.close()
+    # SearchByBoW(KF, KF): both sides need a map point, so the second side's mask is live beyond the register trips
+    a = dict(kf1, has_mp=(rng.random(n) < 0.8).astype(np.uint8))
+    b = dict(kf2, has_mp=(rng.random(n) < 0.8).astype(np.uint8))
+    om, onm = O.search_by_bow_kf(a, b, 0.75, True)
+    owner2 = np.full(n, -1, np.int64)
+    owner2[om[om >= 0]] = np.nonzero(om >= 0)[0]
+    reach(b, om[om >= 0], a, owner2)
+    mt = F.ORBmatcher(0.75, True, lib=lib)
+    m, nm = mt.SearchByBoWKeyFrames(a, b)
+    assert nm == onm and np.array_equal(m, om), "SearchByBoW(KF, KF)"
+    mt.close()
+    # SearchForTriangulation
+    mt = F.ORBmatcher(0.6, True, lib=lib)
+    Fm = mt.fundamental(K, K, R, t)
+    for coarse in (False, True):
+        om, onm = O.search_triangulation(kf1, kf2, Fm, ep, sf, s2, False, coarse, True)
+        if coarse:
+            reach(kf2, om[om >= 0])
+        pairs, nm, m = mt.SearchForTriangulation(kf1, kf2, Fm, ep, sf, s2, False, coarse)
+        assert nm == onm == len(pairs) and np.array_equal(m, om), "SearchForTriangulation (coarse=%s)" % coarse
+    mt.close()
+    # SearchByBoW on a two-camera frame
+    kf, fr, n_left = make_bucket_rig_case(seed, sizes)
+    kf = dict(kf, has_mp=(rng.random(len(kf["desc"])) < 0.7).astype(np.uint8))
+    om, onm = O.search_by_bow(kf, fr, 0.7, True, n_left=n_left)
+    size = reach(fr, om >= 0, kf, om)
+    big = size > 256
+    both = np.intersect1d(om[:n_left][(om[:n_left] >= 0) & big[:n_left]], om[n_left:][(om[n_left:] >= 0) & big[n_left:]])
+    assert len(both) >= 1, "no map point went to a left and a right feature of a bucket beyond 256"
+    mt = F.ORBmatcher(0.7, True, lib=lib)
+    m, nm = mt.SearchByBoW(kf, fr, n_left)
+    assert nm == onm and np.array_equal(m, om), "SearchByBoW, two-camera frame"
+    mt.close()
+
+
 def check_fuse_search(lib, seed=91, th=3.0, n1=2500, n2=2000):
     case = make_fuse_case(n1, n2, seed)
     valid, level = fuse_prepass(case)

@@ -298,6 +298,10 @@ def test_search_by_bow_keyframes(emu_lib, seed, ratio, ori, nodes):
     assert pc.check_search_by_bow_keyframes(emu_lib, seed, ratio, ori, n=800, nodes=nodes) > 50
 
 
+def test_feature_vector_searches_on_bucket_size_edges(emu_lib):
+    pc.check_bucket_sizes(emu_lib)
+
+
 @pytest.mark.parametrize("seed,th", [(91, 3.0), (93, 4.0), (94, 1.5)])
 def test_fuse_search(emu_lib, seed, th):
     assert pc.check_fuse_search(emu_lib, seed, th, n1=1200, n2=1000) > 80

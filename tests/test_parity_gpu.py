@@ -275,6 +275,10 @@ def test_search_by_bow_keyframes(gpu_lib, seed, ratio, ori, nodes):
     assert pc.check_search_by_bow_keyframes(gpu_lib, seed, ratio, ori, n=2000, nodes=nodes) > 50
 
 
+def test_feature_vector_searches_on_bucket_size_edges(gpu_lib):
+    pc.check_bucket_sizes(gpu_lib)
+
+
 @pytest.mark.parametrize("seed,th", [(91, 3.0), (93, 4.0), (94, 1.5)])
 def test_fuse_search(gpu_lib, seed, th):
     assert pc.check_fuse_search(gpu_lib, seed, th) > 80
