@@ -125,6 +125,38 @@ int rgbl_extract_color(rgbl_extractor* h, const uint8_t* img, int channels, int 
                        int lap0, int lap1, rgbl_keypoint* out_kp, uint8_t* out_desc, int cap, int* out_n, int* out_mono,
                        uint8_t* out_gray, int gray_stride);
 
+/* Stereo rectification in front of cvtColor: the two cv::remap(im, imRect, M1, M2, cv::INTER_LINEAR) calls of
+ * System::TrackStereo (src/System.cc:260-268; the maps are Settings::precomputeRectificationMaps' M1l/M2l and M1r/M2r,
+ * src/Settings.cc:485-520, which the host keeps computing).  8-bit, 1, 3 or 4 interleaved channels, two CV_32FC1 maps of
+ * the destination's size, BORDER_CONSTANT 0.  Restated from OpenCV 4.x (parity vs the restatement, unpinned):
+ * sx = cvRound(map_x * 32) (fp32 product, half-to-even; NaN and |v| >= 2^31 give INT32_MIN), ix = saturate_cast<short>(sx >> 5),
+ * fx = sx & 31, likewise y; dst = (sum of the four taps times (32 - fx | fx) * (32 - fy | fy) + 512) >> 10, a tap outside the
+ * source counts as 0.
+ * rgbl_rectifier_create (System.cc:260-268) reads the host maps (row y at map + y*map_stride_floats) ONCE, turns them
+ * into fixed-point entries per 64 x 32 destination tile and uploads them; no later call allocates.  Sides 1 .. 16384. */
+typedef struct rgbl_rectifier rgbl_rectifier;
+int rgbl_rectifier_create(int device, int src_w, int src_h, int dst_w, int dst_h, const float* map_x, const float* map_y,
+                          int map_stride_floats, rgbl_rectifier** out);
+void rgbl_rectifier_destroy(rgbl_rectifier* r);
+/* Sizes, how many destination tiles take the LDS-staged kernel and how many the direct (per-tap gather) one, and the bytes
+ * of map storage on the device (System.cc:260-268 keeps 8 bytes of float map per pixel).  Any pointer may be NULL. */
+int rgbl_rectifier_info(const rgbl_rectifier* r, int* src_w, int* src_h, int* dst_w, int* dst_h, int* staged_tiles,
+                        int* direct_tiles, long long* map_bytes);
+/* cv::remap (System.cc:260-268) of `batch` device-resident frames: frame b at d_src + b*src_frame_stride /
+ * d_dst + b*dst_frame_stride (bytes).  Enqueued on the extractor's stream, so a following rgbl_cvt_gray_batch_device() or
+ * rgbl_extract_batch_device() of that handle is ordered behind it. */
+int rgbl_remap_batch_device(rgbl_rectifier* r, rgbl_extractor* h, const uint8_t* d_src, int batch, int channels,
+                            int src_stride, size_t src_frame_stride, uint8_t* d_dst, int dst_stride, size_t dst_frame_stride);
+/* cv::remap (System.cc:260-268) of one host image into a host image (imLeftRect / imRightRect), synchronous. */
+int rgbl_remap(rgbl_rectifier* r, const uint8_t* src, int channels, int src_stride, uint8_t* dst, int dst_stride);
+/* remap (System.cc:260-268) + cvtColor + operator() on one RAW host image: one upload, then rectification, the gray
+ * conversion when channels > 1, and the extraction.  The rectifier's source size must be src_w x src_h and its destination
+ * size the extractor's width x height (RGBL_ERR_INVALID otherwise).  out_gray (nullable) receives the rectified gray
+ * image, which Tracking keeps as mImGray. */
+int rgbl_extract_rectified(rgbl_extractor* h, rgbl_rectifier* r, const uint8_t* img, int channels, int blue_first, int src_w,
+                           int src_h, int stride, int lap0, int lap1, rgbl_keypoint* out_kp, uint8_t* out_desc, int cap,
+                           int* out_n, int* out_mono, uint8_t* out_gray, int gray_stride);
+
 /* Frame::UndistortKeyPoints / the corner undistortion of Frame::ComputeImageBounds (src/Frame.cc:837-870, 872-900):
  * cv::undistortPoints(mat, mat, K, mDistCoef, cv::Mat(), mK) - normalise, OpenCV's 5 fixed-point iterations of the inverse
  * Brown-Conrady model in double, re-project with the same K.  K = fx, fy, cx, cy; dist = k1, k2, p1, p2[, k3] (n_dist 4 or 5).
@@ -1072,7 +1104,7 @@ int rgbl_kfdb_profile_read(rgbl_kf_database* db, const char** names, double* tot
  *     RGBL_OCTREE_HIST=0            breadth-first rounds as passes over the keys instead of on the per-cell count pyramid
  *     RGBL_OCTREE_STAMPS=1          the quad-tree kernel leaves phase time stamps (rgbl_extractor_debug_stamps)
  *     RGBL_GAUSS_BS=256     four-wave workgroups for the Gaussian (default two waves)
- *     RGBL_XCD_MAP=0        plain (items, frames) grids instead of the XCD-aware (8, items, frames / 8) mapping (also rgbl_depth_create)
+ *     RGBL_XCD_MAP=0        plain (items, frames) grids instead of the XCD-aware (8, items, frames / 8) mapping (also rgbl_depth_create, rgbl_rectifier_create)
  *     RGBL_GRAPH=0          host-pointer extraction without hipGraph replay
  *   rgbl_depth_create
  *     RGBL_DEPTH_MAX_GEN=n  generations of the index map before it is cleared (tests of the wrap-around)

@@ -141,6 +141,10 @@ int rgbl_internal_depth_gather_xy(rgbl_depth* d, int batch, const rgbl_keypoint*
                                   const float* d_kpun_xy, float* d_depth, float* d_uright);
 int rgbl_internal_extractor_info(rgbl_extractor* e, int* w, int* h, int* max_batch, int* device, int** d_err);
 int rgbl_internal_extractor_take_flags(rgbl_extractor* e, int* d_dst);
+// rectify.hip: the remap kernels of a rectifier on any stream (arguments already checked), and what extractor.hip checks
+int rgbl_internal_remap_enqueue(rgbl_rectifier* r, hipStream_t s, const uint8_t* d_src, int batch, int channels, int src_stride,
+                                size_t src_frame, uint8_t* d_dst, int dst_stride, size_t dst_frame);
+int rgbl_internal_rectifier_info(const rgbl_rectifier* r, int* device, int* src_w, int* src_h, int* dst_w, int* dst_h);
 
 namespace rgbl {
 

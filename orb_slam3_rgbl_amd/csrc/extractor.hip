@@ -138,6 +138,8 @@ struct rgbl_extractor {
   size_t h_pinned_bytes = 0;
   void* d_color = nullptr;           // staging of one host colour frame (rgbl_extract_color), allocated on first use
   size_t color_bytes = 0;
+  void* d_rect = nullptr;            // the rectified colour frame between remap and k_cvt_gray (rgbl_extract_rectified), grow-only
+  size_t rect_bytes = 0;
   int32_t* d_stereo_sad = nullptr;   // ComputeStereoMatches scratch (grow-only)
   size_t stereo_sad_count = 0;
   void* d_stereo_stage = nullptr;
@@ -902,6 +904,7 @@ void rgbl_extractor_destroy(rgbl_extractor* e) {
   if (e->d_stereo_stage) (void)hipFree(e->d_stereo_stage);
   if (e->h_stereo_stage) (void)hipHostFree(e->h_stereo_stage);
   if (e->d_color) (void)hipFree(e->d_color);
+  if (e->d_rect) (void)hipFree(e->d_rect);
 #ifndef RGBL_EMU
   if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
 #endif
@@ -1290,6 +1293,50 @@ int rgbl_extract_color(rgbl_extractor* e, const uint8_t* img, int channels, int 
   }
   RGBL_HIP(hipMemcpyAsync(e->d_color, img, (size_t)(h - 1) * stride + (size_t)w * channels, hipMemcpyHostToDevice, s));
   RGBL_TRY(enqueue_cvt_gray(e, (const uint8_t*)e->d_color, 1, channels, blue_first, w, h, stride, 0, e->d_img, e->img_pitch, 0));
+  if (out_gray) RGBL_HIP(hipMemcpy2DAsync(out_gray, gray_stride, e->d_img, e->img_pitch, w, h, hipMemcpyDeviceToHost, s));
+  return run_staged(e, 1, e->img_pitch, lap0, lap1, out_kp, out_desc, cap, out_n, out_mono);
+}
+
+// grow-only staging of the host-pointer ingest paths
+static int grow_staging(void** p, size_t* have, size_t need) {
+  if (need <= *have) return RGBL_OK;
+  if (*p) RGBL_HIP(hipFree(*p));
+  *p = nullptr; *have = 0;
+  RGBL_HIP(hipMalloc(p, need));
+  *have = need;
+  return RGBL_OK;
+}
+
+int rgbl_extract_rectified(rgbl_extractor* e, rgbl_rectifier* r, const uint8_t* img, int channels, int blue_first, int src_w,
+                           int src_h, int stride, int lap0, int lap1, rgbl_keypoint* out_kp, uint8_t* out_desc, int cap,
+                           int* out_n, int* out_mono, uint8_t* out_gray, int gray_stride) {
+  if (out_n) *out_n = 0;
+  if (out_mono) *out_mono = -1;
+  if (!e || !r) { set_error("null handle"); return RGBL_ERR_INVALID; }
+  if (!img || src_w <= 0 || src_h <= 0) { set_error("empty image"); return RGBL_ERR_EMPTY; }
+  if (!out_kp || !out_desc || !out_n || !out_mono) { set_error("null output"); return RGBL_ERR_INVALID; }
+  int rdev = 0, rsw = 0, rsh = 0, rdw = 0, rdh = 0;
+  RGBL_TRY(rgbl_internal_rectifier_info(r, &rdev, &rsw, &rsh, &rdw, &rdh));
+  const int w = e->cfg.width, h = e->cfg.height;
+  if ((channels != 1 && channels != 3 && channels != 4) || rdev != e->device || rsw != src_w || rsh != src_h || rdw != w || rdh != h ||
+      stride < src_w * channels || cap < 1 || (out_gray && gray_stride < w)) {
+    set_error("raw image %dx%dx%d / rectifier %dx%d -> %dx%d does not match the handle (%dx%d)", src_w, src_h, channels, rsw, rsh,
+              rdw, rdh, w, h);
+    return RGBL_ERR_INVALID;
+  }
+  RGBL_HIP(hipSetDevice(e->device));
+  RGBL_TRY(drop_pending(e));
+  hipStream_t s = e->stream;
+  RGBL_TRY(grow_staging(&e->d_color, &e->color_bytes, (size_t)stride * src_h + 16));
+  RGBL_HIP(hipMemcpyAsync(e->d_color, img, (size_t)(src_h - 1) * stride + (size_t)src_w * channels, hipMemcpyHostToDevice, s));
+  if (channels == 1) {
+    RGBL_TRY(rgbl_internal_remap_enqueue(r, s, (const uint8_t*)e->d_color, 1, 1, stride, 0, e->d_img, e->img_pitch, 0));
+  } else {
+    const int rp = (w * channels + 3) & ~3;
+    RGBL_TRY(grow_staging(&e->d_rect, &e->rect_bytes, (size_t)rp * h + 16));
+    RGBL_TRY(rgbl_internal_remap_enqueue(r, s, (const uint8_t*)e->d_color, 1, channels, stride, 0, (uint8_t*)e->d_rect, rp, 0));
+    RGBL_TRY(enqueue_cvt_gray(e, (const uint8_t*)e->d_rect, 1, channels, blue_first, w, h, rp, 0, e->d_img, e->img_pitch, 0));
+  }
   if (out_gray) RGBL_HIP(hipMemcpy2DAsync(out_gray, gray_stride, e->d_img, e->img_pitch, w, h, hipMemcpyDeviceToHost, s));
   return run_staged(e, 1, e->img_pitch, lap0, lap1, out_kp, out_desc, cap, out_n, out_mono);
 }

@@ -123,6 +123,22 @@ class ORBextractor:
                                                       C.byref(n), C.byref(mono), L.ptr(gray), gray.strides[0]))
         return kps[:n.value].copy(), desc[:n.value].copy(), mono.value, gray
 
+    def extract_rectified(self, rectifier, image, mbRGB=True, vLappingArea=(0, 0)):
+        """System::TrackStereo's cv::remap (System.cc:260-268) + cvtColor + operator() on one RAW H x W[ x {3,4}] 8-bit image:
+        one upload, everything else on the device.  Returns (keypoints, descriptors, monoIndex, rectified mImGray)."""
+        image = np.ascontiguousarray(image, np.uint8)
+        h, w = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        cap = self.max_keypoints
+        kps = np.zeros(cap, KP_DTYPE)
+        desc = np.zeros((cap, 32), np.uint8)
+        gray = np.zeros((self.cfg.height, self.cfg.width), np.uint8)
+        n, mono = C.c_int(0), C.c_int(-1)
+        L.check(self.lib, self.lib.rgbl_extract_rectified(self.h, rectifier.h, L.ptr(image), ch, 0 if mbRGB else 1, w, h,
+                                                          image.strides[0], int(vLappingArea[0]), int(vLappingArea[1]), L.ptr(kps),
+                                                          L.ptr(desc), cap, C.byref(n), C.byref(mono), L.ptr(gray), gray.strides[0]))
+        return kps[:n.value].copy(), desc[:n.value].copy(), mono.value, gray
+
     def extract_batch(self, images, vLappingArea=(0, 0)):
         """images: [B, H, W] u8 contiguous. Returns list of (keypoints, descriptors, monoIndex)."""
         images = np.ascontiguousarray(images, np.uint8)
@@ -178,6 +194,60 @@ class ORBextractor:
 
     def profile_samples(self):
         return L.read_profile_samples(self.lib, self.lib.rgbl_extractor_profile_read, self.lib.rgbl_extractor_profile_samples, self.h)
+
+
+class Rectifier:
+    """The rectification maps of one camera (Settings::precomputeRectificationMaps' M1 / M2, Settings.cc:485-520) on the device:
+    cv::remap(src, dst, M1, M2, cv::INTER_LINEAR) of System::TrackStereo (System.cc:260-268) for 8-bit images with 1, 3 or 4
+    channels.  The maps (two float32 arrays of the destination's shape) are read once; src_size = (width, height)."""
+
+    def __init__(self, map_x, map_y, src_size, device=0, lib=None):
+        self.lib = lib or L.load()
+        mx, my = np.asarray(map_x), np.asarray(map_y)
+        if mx.dtype != np.float32 or my.dtype != np.float32 or mx.ndim != 2 or mx.shape != my.shape:
+            raise TypeError("maps must be two CV_32FC1 arrays of the same shape")
+        if mx.strides != my.strides or mx.strides[1] != 4 or mx.strides[0] % 4:
+            mx, my = np.ascontiguousarray(mx), np.ascontiguousarray(my)
+        self.dst_h, self.dst_w = mx.shape
+        self.src_w, self.src_h = int(src_size[0]), int(src_size[1])
+        self.h = C.c_void_p()
+        L.check(self.lib, self.lib.rgbl_rectifier_create(device, self.src_w, self.src_h, self.dst_w, self.dst_h, L.ptr(mx), L.ptr(my),
+                                                         mx.strides[0] // 4, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.rgbl_rectifier_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{src_w, src_h, dst_w, dst_h, staged_tiles, direct_tiles, map_bytes} (rgbl_rectifier_info)."""
+        v = [C.c_int() for _ in range(6)]
+        b = C.c_longlong()
+        L.check(self.lib, self.lib.rgbl_rectifier_info(self.h, *[C.byref(x) for x in v], C.byref(b)))
+        names = ("src_w", "src_h", "dst_w", "dst_h", "staged_tiles", "direct_tiles")
+        return dict({k: x.value for k, x in zip(names, v)}, map_bytes=b.value)
+
+    def remap(self, image):
+        """One host image H x W[ x C] (any row stride) -> the rectified host image (imLeftRect)."""
+        if image.dtype != np.uint8 or image.ndim not in (2, 3) or image.strides[-1] != 1 or (image.ndim == 3 and image.strides[1] != image.shape[2]):
+            image = np.ascontiguousarray(image, np.uint8)
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        if image.shape[0] != self.src_h or image.shape[1] != self.src_w:
+            raise ValueError("image is %dx%d, the maps were built for %dx%d" % (image.shape[1], image.shape[0], self.src_w, self.src_h))
+        out = np.zeros((self.dst_h, self.dst_w) if image.ndim == 2 else (self.dst_h, self.dst_w, ch), np.uint8)
+        L.check(self.lib, self.lib.rgbl_remap(self.h, L.ptr(image), ch, image.strides[0], L.ptr(out), out.strides[0]))
+        return out
+
+    def remap_batch_device(self, extractor, d_src, batch, channels, src_stride, src_frame_stride, d_dst, dst_stride, dst_frame_stride):
+        """Device pointers (ints), enqueued on the extractor's stream: a following cvtColor / extraction of that handle sees the result."""
+        L.check(self.lib, self.lib.rgbl_remap_batch_device(self.h, extractor.h, d_src, batch, channels, src_stride, src_frame_stride,
+                                                           d_dst, dst_stride, dst_frame_stride))
 
 
 def ComputeStereoMatches(extractorLeft, extractorRight, mvKeys, mDescriptors, mvKeysRight, mDescriptorsRight, mb, mbf):

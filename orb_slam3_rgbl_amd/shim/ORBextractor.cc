@@ -7,6 +7,7 @@
 #include <iostream>
 
 #include "../../include/rgbl_frontend.h"
+#include "StereoRectifier.h"
 
 namespace ORB_SLAM3 {
 
@@ -137,6 +138,37 @@ int ORBextractor::ExtractColor(const unsigned char* data, int channels, int step
   const int rc = rgbl_extract_color(mpHandle, data, channels, bRGB ? 0 : 1, width, height, step, lap0, lap1,
                                     reinterpret_cast<rgbl_keypoint*>(_keypoints.data()), desc.data, cap, &n, &mono, imGray.data,
                                     (int)imGray.step);
+  if (rc != RGBL_OK) {
+    std::cerr << "[ORBextractor] " << rgbl_last_error() << std::endl;
+    _keypoints.clear();
+    return -1;
+  }
+  _keypoints.resize(n);
+  if (n == 0) _descriptors.release();
+  else {
+    _descriptors.create(n, 32, CV_8U);
+    memcpy(_descriptors.data, desc.data, (size_t)n * 32);
+  }
+  FillPyramid();
+  return mono;
+}
+
+int ORBextractor::ExtractRectified(const rgbl_shim::StereoRectifier& rect, const unsigned char* data, int channels, int step, bool bRGB,
+                                   cv::Mat& imGray, std::vector<cv::KeyPoint>& _keypoints, cv::Mat& _descriptors,
+                                   std::vector<int>& vLappingArea) {
+  if (!data || !rect.ok()) return -1;
+  const int width = rect.dstWidth(), height = rect.dstHeight();
+  EnsureHandle(width, height);
+  if (!mpHandle) return -1;
+  const int cap = rgbl_extractor_max_keypoints(mpHandle);
+  _keypoints = std::vector<cv::KeyPoint>(cap);
+  cv::Mat desc(cap, 32, CV_8U);
+  imGray.create(height, width, CV_8UC1);
+  int n = 0, mono = -1;
+  const int lap0 = vLappingArea.size() > 0 ? vLappingArea[0] : 0, lap1 = vLappingArea.size() > 1 ? vLappingArea[1] : 0;
+  const int rc = rgbl_extract_rectified(mpHandle, rect.Handle(), data, channels, bRGB ? 0 : 1, rect.srcWidth(), rect.srcHeight(), step,
+                                        lap0, lap1, reinterpret_cast<rgbl_keypoint*>(_keypoints.data()), desc.data, cap, &n, &mono,
+                                        imGray.data, (int)imGray.step);
   if (rc != RGBL_OK) {
     std::cerr << "[ORBextractor] " << rgbl_last_error() << std::endl;
     _keypoints.clear();

@@ -10,6 +10,7 @@
 struct rgbl_extractor;
 struct rgbl_device_frame;
 struct rgbl_depth;
+namespace rgbl_shim { class StereoRectifier; }
 
 namespace ORB_SLAM3 {
 
@@ -38,6 +39,12 @@ class ORBextractor {
   // 8-bit image with 3 or 4 interleaved channels (1 = already gray), bRGB = Tracking::mbRGB.  imGray receives mImGray.
   int ExtractColor(const unsigned char* data, int channels, int step, int width, int height, bool bRGB, cv::Mat& imGray,
                    std::vector<cv::KeyPoint>& _keypoints, cv::Mat& _descriptors, std::vector<int>& vLappingArea);
+
+  // remap + cvtColor + operator() in one device round trip (System::TrackStereo's cv::remap, System.cc:260-268, in front of
+  // Tracking::GrabImageStereo): `data` is the RAW 8-bit image (1, 3 or 4 channels) of the size `rect` was built for; the
+  // extraction runs on the rectified image, imGray receives it (mImGray).  StereoRectifier.h has the rectifier.
+  int ExtractRectified(const rgbl_shim::StereoRectifier& rect, const unsigned char* data, int channels, int step, bool bRGB,
+                       cv::Mat& imGray, std::vector<cv::KeyPoint>& _keypoints, cv::Mat& _descriptors, std::vector<int>& vLappingArea);
 
   // Frame::UndistortKeyPoints (Frame.cc:837-870) on the device the keypoints came from: mvKeysUn = mvKeys with
   // cv::undistortPoints(pt, K, mDistCoef, noArray(), K) applied; a plain copy when mDistCoef[0] == 0, as in the reference.
