@@ -157,6 +157,42 @@ int rgbl_extract_rectified(rgbl_extractor* h, rgbl_rectifier* r, const uint8_t* 
                            int src_h, int stride, int lap0, int lap1, rgbl_keypoint* out_kp, uint8_t* out_desc, int cap,
                            int* out_n, int* out_mono, uint8_t* out_gray, int gray_stride);
 
+/* The image resize in front of cvtColor: cv::resize(im, imToFeed, settings_->newImSize()) that every System::Track* entry
+ * makes when the settings file carries Camera.newWidth / Camera.newHeight (src/System.cc:269-271, 349-351, 486-489, 557-560;
+ * the reference's EuRoC settings: 752 x 480 -> 600 x 350).  8-bit, 1, 3 or 4 interleaved channels, the default INTER_LINEAR, any
+ * ratio on either axis, sides 1 .. 16384.  Restated from OpenCV 4.x (parity vs the restatement = the oracle's cv::resize at one
+ * channel, unpinned): per axis f = (float)((d + 0.5) * scale - 0.5) with scale = 1.0 / ((double)dsize / ssize), s = floor(f),
+ * f -= s, on x s < 0 -> (0, 0) and s >= sw - 1 -> (sw - 1, 0), rows s and s + 1 clamped into the image, weights
+ * cvRound((1 - f) * 2048) and cvRound(f * 2048), dst = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2 with
+ * h = p0 * a0 + p1 * a1, every channel on its own.  At exactly half size OpenCV takes INTER_AREA instead, which on 8-bit
+ * images is the same number ((a + b + c + d + 2) >> 2), so one kernel serves both.  The depth map's resize of TrackRGBD
+ * (System.cc:354, 425: CV_32F / CV_16U) stays on the host.
+ * rgbl_resizer_create (System.cc:269-271, 349-351, 486-489, 557-560) builds the coefficient tables of both axes and the row
+ * spans of the destination tiles ONCE and uploads them. */
+typedef struct rgbl_resizer rgbl_resizer;
+int rgbl_resizer_create(int device, int src_w, int src_h, int dst_w, int dst_h, rgbl_resizer** out);
+void rgbl_resizer_destroy(rgbl_resizer* r);
+/* Sizes, whether OpenCV would reroute this pair of sizes to INTER_AREA (System.cc:269-271, 349-351, 486-489, 557-560 at exactly
+ * half size; the output is the same), and the bytes of tables on the device.  Any pointer may be NULL. */
+int rgbl_resizer_info(const rgbl_resizer* r, int* src_w, int* src_h, int* dst_w, int* dst_h,
+                      int* area_fast /* 1 when OpenCV would reroute to INTER_AREA */, long long* table_bytes);
+/* cv::resize (System.cc:269-271, 349-351, 486-489, 557-560) of `batch` device-resident frames: frame b at
+ * d_src + b*src_frame_stride / d_dst + b*dst_frame_stride (bytes), batch <= the extractor's max_batch.  Enqueued on the
+ * extractor's stream, so a following rgbl_cvt_gray_batch_device() or rgbl_extract_batch_device() of that handle is ordered
+ * behind it. */
+int rgbl_resize_batch_device(rgbl_resizer* r, rgbl_extractor* h, const uint8_t* d_src, int batch, int channels, int src_stride,
+                             size_t src_frame_stride, uint8_t* d_dst, int dst_stride, size_t dst_frame_stride);
+/* cv::resize (System.cc:269-271, 349-351, 486-489, 557-560) of one host image into a host image (imToFeed), synchronous. */
+int rgbl_resize(rgbl_resizer* r, const uint8_t* src, int channels, int src_stride, uint8_t* dst, int dst_stride);
+/* resize (System.cc:269-271, 349-351, 486-489, 557-560) + cvtColor + operator() on one RAW host image: one upload, then the
+ * resize AT THE IMAGE'S CHANNEL COUNT, the gray conversion when channels > 1, and the extraction - the reference's order
+ * (System resizes the colour image, Tracking converts afterwards; gray-then-resize gives other bits).  The resizer's source
+ * size must be src_w x src_h and its destination size the extractor's width x height (RGBL_ERR_INVALID otherwise).
+ * out_gray (nullable) receives mImGray. */
+int rgbl_extract_resized(rgbl_extractor* h, rgbl_resizer* r, const uint8_t* img, int channels, int blue_first, int src_w,
+                         int src_h, int stride, int lap0, int lap1, rgbl_keypoint* out_kp, uint8_t* out_desc, int cap,
+                         int* out_n, int* out_mono, uint8_t* out_gray, int gray_stride);
+
 /* Frame::UndistortKeyPoints / the corner undistortion of Frame::ComputeImageBounds (src/Frame.cc:837-870, 872-900):
  * cv::undistortPoints(mat, mat, K, mDistCoef, cv::Mat(), mK) - normalise, OpenCV's 5 fixed-point iterations of the inverse
  * Brown-Conrady model in double, re-project with the same K.  K = fx, fy, cx, cy; dist = k1, k2, p1, p2[, k3] (n_dist 4 or 5).
@@ -1104,7 +1140,7 @@ int rgbl_kfdb_profile_read(rgbl_kf_database* db, const char** names, double* tot
  *     RGBL_OCTREE_HIST=0            breadth-first rounds as passes over the keys instead of on the per-cell count pyramid
  *     RGBL_OCTREE_STAMPS=1          the quad-tree kernel leaves phase time stamps (rgbl_extractor_debug_stamps)
  *     RGBL_GAUSS_BS=256     four-wave workgroups for the Gaussian (default two waves)
- *     RGBL_XCD_MAP=0        plain (items, frames) grids instead of the XCD-aware (8, items, frames / 8) mapping (also rgbl_depth_create, rgbl_rectifier_create)
+ *     RGBL_XCD_MAP=0        plain (items, frames) grids instead of the XCD-aware (8, items, frames / 8) mapping (also rgbl_depth_create, rgbl_rectifier_create, rgbl_resizer_create)
  *     RGBL_GRAPH=0          host-pointer extraction without hipGraph replay
  *   rgbl_depth_create
  *     RGBL_DEPTH_MAX_GEN=n  generations of the index map before it is cleared (tests of the wrap-around)

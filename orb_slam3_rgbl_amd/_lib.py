@@ -196,6 +196,12 @@ SYMBOLS = {
     "rgbl_remap_batch_device": (_I, [_V, _V, _V, _I, _I, _I, _Z, _V, _I, _Z]),
     "rgbl_remap": (_I, [_V, _V, _I, _I, _V, _I]),
     "rgbl_extract_rectified": (_I, [_V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V, _I, C.POINTER(_I), C.POINTER(_I), _V, _I]),
+    "rgbl_resizer_create": (_I, [_I, _I, _I, _I, _I, C.POINTER(_V)]),
+    "rgbl_resizer_destroy": (None, [_V]),
+    "rgbl_resizer_info": (_I, [_V, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_longlong)]),
+    "rgbl_resize_batch_device": (_I, [_V, _V, _V, _I, _I, _I, _Z, _V, _I, _Z]),
+    "rgbl_resize": (_I, [_V, _V, _I, _I, _V, _I]),
+    "rgbl_extract_resized": (_I, [_V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V, _I, C.POINTER(_I), C.POINTER(_I), _V, _I]),
     "rgbl_stereo_matches": (_I, [_V, _V, _V, _V, _I, _V, _V, _I, _F, _F, _V, _V]),
     "rgbl_stereo_matches_batch_device": (_I, [_V, _V, _I, _V, _V, _V, _V, _V, _V, _I, _F, _F, _V, _V]),
     "rgbl_extractor_debug_stamps": (_I, [_V, _V, _I]),

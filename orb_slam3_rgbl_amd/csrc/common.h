@@ -37,6 +37,9 @@ const char* last_error();
     if (rc__ != RGBL_OK) return rc__; \
   } while (0)
 
+// grow-only device staging of the host-pointer ingest paths (extractor.hip): reallocates only when `need` exceeds `*have`
+int grow_staging(void** p, size_t* have, size_t need);
+
 constexpr int kWave = 64;  // gfx950 wavefront width; hard-coded on purpose
 
 // Host-pointer entry points queue uploads from caller / stack buffers; whichever way such a function is left - also through
@@ -145,6 +148,10 @@ int rgbl_internal_extractor_take_flags(rgbl_extractor* e, int* d_dst);
 int rgbl_internal_remap_enqueue(rgbl_rectifier* r, hipStream_t s, const uint8_t* d_src, int batch, int channels, int src_stride,
                                 size_t src_frame, uint8_t* d_dst, int dst_stride, size_t dst_frame);
 int rgbl_internal_rectifier_info(const rgbl_rectifier* r, int* device, int* src_w, int* src_h, int* dst_w, int* dst_h);
+// resize.hip: the same pair for a resizer
+int rgbl_internal_resize_enqueue(rgbl_resizer* r, hipStream_t s, const uint8_t* d_src, int batch, int channels, int src_stride,
+                                 size_t src_frame, uint8_t* d_dst, int dst_stride, size_t dst_frame);
+int rgbl_internal_resizer_info(const rgbl_resizer* r, int* device, int* src_w, int* src_h, int* dst_w, int* dst_h);
 
 namespace rgbl {
 

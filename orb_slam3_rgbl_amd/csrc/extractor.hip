@@ -42,6 +42,16 @@ static inline int floor_f(float v) { int i = (int)v; return i - (v < (float)i); 
 static inline int ceil_f(float v) { int i = (int)v; return i + (v > (float)i); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// grow-only staging of the host-pointer ingest paths (common.h)
+int grow_staging(void** p, size_t* have, size_t need) {
+  if (need <= *have) return RGBL_OK;
+  if (*p) RGBL_HIP(hipFree(*p));
+  *p = nullptr; *have = 0;
+  RGBL_HIP(hipMalloc(p, need));
+  *have = need;
+  return RGBL_OK;
+}
+
 }  // namespace rgbl
 
 using namespace rgbl;
@@ -138,7 +148,7 @@ struct rgbl_extractor {
   size_t h_pinned_bytes = 0;
   void* d_color = nullptr;           // staging of one host colour frame (rgbl_extract_color), allocated on first use
   size_t color_bytes = 0;
-  void* d_rect = nullptr;            // the rectified colour frame between remap and k_cvt_gray (rgbl_extract_rectified), grow-only
+  void* d_rect = nullptr;            // the rectified / resized colour frame in front of k_cvt_gray (rgbl_extract_rectified, _resized), grow-only
   size_t rect_bytes = 0;
   int32_t* d_stereo_sad = nullptr;   // ComputeStereoMatches scratch (grow-only)
   size_t stereo_sad_count = 0;
@@ -171,26 +181,6 @@ int dev_alloc(rgbl_extractor* e, T** p, size_t count) {
   RGBL_HIP(hipMalloc(p, std::max<size_t>(count, 1) * sizeof(T)));
   e->allocs.push_back((void*)*p);
   return RGBL_OK;
-}
-
-// cv::resize's coefficient tables for one axis (modules/imgproc/src/resize.cpp, INTER_LINEAR, fixed point)
-void build_resize_tab(int ssize, int dsize, bool clamp_x, std::vector<ResizeTab>& tab) {
-  const double inv_scale = (double)dsize / ssize;
-  const double scale = 1.0 / inv_scale;
-  for (int d = 0; d < dsize; ++d) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int s = floor_f(f);
-    f -= s;
-    if (clamp_x) {
-      if (s < 0) { f = 0; s = 0; }
-      if (s >= ssize - 1) { f = 0; s = ssize - 1; }
-    }
-    ResizeTab t;
-    t.sofs = s;
-    t.a0 = (int16_t)round_even_f((1.f - f) * 2048);
-    t.a1 = (int16_t)round_even_f(f * 2048);
-    tab.push_back(t);
-  }
 }
 
 // Every RGBL_* variable the extractor honours (depth.hip and matcher.hip read their own); called once per handle.
@@ -1297,14 +1287,35 @@ int rgbl_extract_color(rgbl_extractor* e, const uint8_t* img, int channels, int 
   return run_staged(e, 1, e->img_pitch, lap0, lap1, out_kp, out_desc, cap, out_n, out_mono);
 }
 
-// grow-only staging of the host-pointer ingest paths
-static int grow_staging(void** p, size_t* have, size_t need) {
-  if (need <= *have) return RGBL_OK;
-  if (*p) RGBL_HIP(hipFree(*p));
-  *p = nullptr; *have = 0;
-  RGBL_HIP(hipMalloc(p, need));
-  *have = need;
-  return RGBL_OK;
+// One RAW host image through an image-wide ingest step (rectification or resize: `enqueue` launches it on the stream, at the
+// image's channel count), then cvtColor when channels > 1, then the extraction.  (rdev, rsw x rsh -> rdw x rdh): the step's handle.
+typedef int (*IngestEnqueue)(void* handle, hipStream_t s, const uint8_t* d_src, int channels, int src_stride, uint8_t* d_dst, int dst_stride);
+static int extract_ingested(rgbl_extractor* e, const char* what, int rdev, int rsw, int rsh, int rdw, int rdh, IngestEnqueue enqueue,
+                            void* handle, const uint8_t* img, int channels, int blue_first, int src_w, int src_h, int stride, int lap0, int lap1,
+                            rgbl_keypoint* out_kp, uint8_t* out_desc, int cap, int* out_n, int* out_mono, uint8_t* out_gray,
+                            int gray_stride) {
+  const int w = e->cfg.width, h = e->cfg.height;
+  if ((channels != 1 && channels != 3 && channels != 4) || rdev != e->device || rsw != src_w || rsh != src_h || rdw != w || rdh != h ||
+      stride < src_w * channels || cap < 1 || (out_gray && gray_stride < w)) {
+    set_error("raw image %dx%dx%d / %s %dx%d -> %dx%d does not match the handle (%dx%d)", src_w, src_h, channels, what, rsw, rsh,
+              rdw, rdh, w, h);
+    return RGBL_ERR_INVALID;
+  }
+  RGBL_HIP(hipSetDevice(e->device));
+  RGBL_TRY(drop_pending(e));
+  hipStream_t s = e->stream;
+  RGBL_TRY(grow_staging(&e->d_color, &e->color_bytes, (size_t)stride * src_h + 16));
+  RGBL_HIP(hipMemcpyAsync(e->d_color, img, (size_t)(src_h - 1) * stride + (size_t)src_w * channels, hipMemcpyHostToDevice, s));
+  if (channels == 1) {
+    RGBL_TRY(enqueue(handle, s, (const uint8_t*)e->d_color, 1, stride, e->d_img, e->img_pitch));
+  } else {
+    const int rp = (w * channels + 3) & ~3;
+    RGBL_TRY(grow_staging(&e->d_rect, &e->rect_bytes, (size_t)rp * h + 16));
+    RGBL_TRY(enqueue(handle, s, (const uint8_t*)e->d_color, channels, stride, (uint8_t*)e->d_rect, rp));
+    RGBL_TRY(enqueue_cvt_gray(e, (const uint8_t*)e->d_rect, 1, channels, blue_first, w, h, rp, 0, e->d_img, e->img_pitch, 0));
+  }
+  if (out_gray) RGBL_HIP(hipMemcpy2DAsync(out_gray, gray_stride, e->d_img, e->img_pitch, w, h, hipMemcpyDeviceToHost, s));
+  return run_staged(e, 1, e->img_pitch, lap0, lap1, out_kp, out_desc, cap, out_n, out_mono);
 }
 
 int rgbl_extract_rectified(rgbl_extractor* e, rgbl_rectifier* r, const uint8_t* img, int channels, int blue_first, int src_w,
@@ -1317,28 +1328,28 @@ int rgbl_extract_rectified(rgbl_extractor* e, rgbl_rectifier* r, const uint8_t* 
   if (!out_kp || !out_desc || !out_n || !out_mono) { set_error("null output"); return RGBL_ERR_INVALID; }
   int rdev = 0, rsw = 0, rsh = 0, rdw = 0, rdh = 0;
   RGBL_TRY(rgbl_internal_rectifier_info(r, &rdev, &rsw, &rsh, &rdw, &rdh));
-  const int w = e->cfg.width, h = e->cfg.height;
-  if ((channels != 1 && channels != 3 && channels != 4) || rdev != e->device || rsw != src_w || rsh != src_h || rdw != w || rdh != h ||
-      stride < src_w * channels || cap < 1 || (out_gray && gray_stride < w)) {
-    set_error("raw image %dx%dx%d / rectifier %dx%d -> %dx%d does not match the handle (%dx%d)", src_w, src_h, channels, rsw, rsh,
-              rdw, rdh, w, h);
-    return RGBL_ERR_INVALID;
-  }
-  RGBL_HIP(hipSetDevice(e->device));
-  RGBL_TRY(drop_pending(e));
-  hipStream_t s = e->stream;
-  RGBL_TRY(grow_staging(&e->d_color, &e->color_bytes, (size_t)stride * src_h + 16));
-  RGBL_HIP(hipMemcpyAsync(e->d_color, img, (size_t)(src_h - 1) * stride + (size_t)src_w * channels, hipMemcpyHostToDevice, s));
-  if (channels == 1) {
-    RGBL_TRY(rgbl_internal_remap_enqueue(r, s, (const uint8_t*)e->d_color, 1, 1, stride, 0, e->d_img, e->img_pitch, 0));
-  } else {
-    const int rp = (w * channels + 3) & ~3;
-    RGBL_TRY(grow_staging(&e->d_rect, &e->rect_bytes, (size_t)rp * h + 16));
-    RGBL_TRY(rgbl_internal_remap_enqueue(r, s, (const uint8_t*)e->d_color, 1, channels, stride, 0, (uint8_t*)e->d_rect, rp, 0));
-    RGBL_TRY(enqueue_cvt_gray(e, (const uint8_t*)e->d_rect, 1, channels, blue_first, w, h, rp, 0, e->d_img, e->img_pitch, 0));
-  }
-  if (out_gray) RGBL_HIP(hipMemcpy2DAsync(out_gray, gray_stride, e->d_img, e->img_pitch, w, h, hipMemcpyDeviceToHost, s));
-  return run_staged(e, 1, e->img_pitch, lap0, lap1, out_kp, out_desc, cap, out_n, out_mono);
+  const IngestEnqueue enqueue = [](void* r, hipStream_t s, const uint8_t* d_src, int ch, int sp, uint8_t* d_dst, int dp) {
+    return rgbl_internal_remap_enqueue((rgbl_rectifier*)r, s, d_src, 1, ch, sp, 0, d_dst, dp, 0);
+  };
+  return extract_ingested(e, "rectifier", rdev, rsw, rsh, rdw, rdh, enqueue, r, img, channels, blue_first, src_w, src_h, stride, lap0, lap1,
+                          out_kp, out_desc, cap, out_n, out_mono, out_gray, gray_stride);
+}
+
+int rgbl_extract_resized(rgbl_extractor* e, rgbl_resizer* r, const uint8_t* img, int channels, int blue_first, int src_w, int src_h,
+                         int stride, int lap0, int lap1, rgbl_keypoint* out_kp, uint8_t* out_desc, int cap, int* out_n,
+                         int* out_mono, uint8_t* out_gray, int gray_stride) {
+  if (out_n) *out_n = 0;
+  if (out_mono) *out_mono = -1;
+  if (!e || !r) { set_error("null handle"); return RGBL_ERR_INVALID; }
+  if (!img || src_w <= 0 || src_h <= 0) { set_error("empty image"); return RGBL_ERR_EMPTY; }
+  if (!out_kp || !out_desc || !out_n || !out_mono) { set_error("null output"); return RGBL_ERR_INVALID; }
+  int rdev = 0, rsw = 0, rsh = 0, rdw = 0, rdh = 0;
+  RGBL_TRY(rgbl_internal_resizer_info(r, &rdev, &rsw, &rsh, &rdw, &rdh));
+  const IngestEnqueue enqueue = [](void* r, hipStream_t s, const uint8_t* d_src, int ch, int sp, uint8_t* d_dst, int dp) {
+    return rgbl_internal_resize_enqueue((rgbl_resizer*)r, s, d_src, 1, ch, sp, 0, d_dst, dp, 0);
+  };
+  return extract_ingested(e, "resizer", rdev, rsw, rsh, rdw, rdh, enqueue, r, img, channels, blue_first, src_w, src_h, stride, lap0, lap1,
+                          out_kp, out_desc, cap, out_n, out_mono, out_gray, gray_stride);
 }
 
 int rgbl_extractor_level_size(const rgbl_extractor* e, int level, int* w, int* h) {

@@ -12,6 +12,7 @@
 // with -ffp-contract=off.  Results are bit-exact with the CPU oracle.
 #pragma once
 #include "common.h"
+#include "resize_tab.h"
 #include "sincos_glibc.h"
 
 namespace rgbl {
@@ -19,11 +20,6 @@ namespace rgbl {
 constexpr int kMaxLevels = 16;
 constexpr int kMaxRoots = 16;
 constexpr int kMinBorder = 16;  // EDGE_THRESHOLD - 3
-
-struct ResizeTab {  // one output column / row of cv::resize's fixed-point tables
-  int32_t sofs;     // first source index
-  int16_t a0, a1;   // 11-bit weights (sum 2048)
-};
 
 struct LevelGeom {
   int w, h, pitch;            // level size; pitch of the pyramid / blur buffers (bytes)

@@ -139,6 +139,23 @@ class ORBextractor:
                                                           L.ptr(desc), cap, C.byref(n), C.byref(mono), L.ptr(gray), gray.strides[0]))
         return kps[:n.value].copy(), desc[:n.value].copy(), mono.value, gray
 
+    def extract_resized(self, resizer, image, mbRGB=True, vLappingArea=(0, 0)):
+        """System::Track*'s cv::resize to Camera.newWidth/newHeight (System.cc:269-271, 349-351, 486-489, 557-560) + cvtColor +
+        operator() on one RAW H x W[ x {3,4}] 8-bit image: one upload, the resize at the image's channel count, everything else on
+        the device.  Returns (keypoints, descriptors, monoIndex, resized mImGray)."""
+        image = np.ascontiguousarray(image, np.uint8)
+        h, w = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        cap = self.max_keypoints
+        kps = np.zeros(cap, KP_DTYPE)
+        desc = np.zeros((cap, 32), np.uint8)
+        gray = np.zeros((self.cfg.height, self.cfg.width), np.uint8)
+        n, mono = C.c_int(0), C.c_int(-1)
+        L.check(self.lib, self.lib.rgbl_extract_resized(self.h, resizer.h, L.ptr(image), ch, 0 if mbRGB else 1, w, h,
+                                                        image.strides[0], int(vLappingArea[0]), int(vLappingArea[1]), L.ptr(kps),
+                                                        L.ptr(desc), cap, C.byref(n), C.byref(mono), L.ptr(gray), gray.strides[0]))
+        return kps[:n.value].copy(), desc[:n.value].copy(), mono.value, gray
+
     def extract_batch(self, images, vLappingArea=(0, 0)):
         """images: [B, H, W] u8 contiguous. Returns list of (keypoints, descriptors, monoIndex)."""
         images = np.ascontiguousarray(images, np.uint8)
@@ -248,6 +265,54 @@ class Rectifier:
         """Device pointers (ints), enqueued on the extractor's stream: a following cvtColor / extraction of that handle sees the result."""
         L.check(self.lib, self.lib.rgbl_remap_batch_device(self.h, extractor.h, d_src, batch, channels, src_stride, src_frame_stride,
                                                            d_dst, dst_stride, dst_frame_stride))
+
+
+class Resizer:
+    """cv::resize(im, imToFeed, settings_->newImSize()) of the System::Track* entries (System.cc:269-271, 349-351, 486-489,
+    557-560) on the device: default INTER_LINEAR, 8-bit images with 1, 3 or 4 channels, any ratio.  src_size and dst_size are
+    (width, height); the tables of both axes are built once."""
+
+    def __init__(self, src_size, dst_size, device=0, lib=None):
+        self.lib = lib or L.load()
+        self.src_w, self.src_h = int(src_size[0]), int(src_size[1])
+        self.dst_w, self.dst_h = int(dst_size[0]), int(dst_size[1])
+        self.h = C.c_void_p()
+        L.check(self.lib, self.lib.rgbl_resizer_create(device, self.src_w, self.src_h, self.dst_w, self.dst_h, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.rgbl_resizer_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{src_w, src_h, dst_w, dst_h, area_fast, table_bytes} (rgbl_resizer_info)."""
+        v = [C.c_int() for _ in range(5)]
+        b = C.c_longlong()
+        L.check(self.lib, self.lib.rgbl_resizer_info(self.h, *[C.byref(x) for x in v], C.byref(b)))
+        names = ("src_w", "src_h", "dst_w", "dst_h", "area_fast")
+        return dict({k: x.value for k, x in zip(names, v)}, table_bytes=b.value)
+
+    def resize(self, image):
+        """One host image H x W[ x C] (any row stride) -> the resized host image (imToFeed)."""
+        if image.dtype != np.uint8 or image.ndim not in (2, 3) or image.strides[-1] != 1 or (image.ndim == 3 and image.strides[1] != image.shape[2]):
+            image = np.ascontiguousarray(image, np.uint8)
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        if image.shape[0] != self.src_h or image.shape[1] != self.src_w:
+            raise ValueError("image is %dx%d, the resizer was built for %dx%d" % (image.shape[1], image.shape[0], self.src_w, self.src_h))
+        out = np.zeros((self.dst_h, self.dst_w) if image.ndim == 2 else (self.dst_h, self.dst_w, ch), np.uint8)
+        L.check(self.lib, self.lib.rgbl_resize(self.h, L.ptr(image), ch, image.strides[0], L.ptr(out), out.strides[0]))
+        return out
+
+    def resize_batch_device(self, extractor, d_src, batch, channels, src_stride, src_frame_stride, d_dst, dst_stride, dst_frame_stride):
+        """Device pointers (ints), enqueued on the extractor's stream: a following cvtColor / extraction of that handle sees the result."""
+        L.check(self.lib, self.lib.rgbl_resize_batch_device(self.h, extractor.h, d_src, batch, channels, src_stride, src_frame_stride,
+                                                            d_dst, dst_stride, dst_frame_stride))
 
 
 def ComputeStereoMatches(extractorLeft, extractorRight, mvKeys, mDescriptors, mvKeysRight, mDescriptorsRight, mb, mbf):

@@ -7,6 +7,7 @@
 #include <iostream>
 
 #include "../../include/rgbl_frontend.h"
+#include "ImageResizer.h"
 #include "StereoRectifier.h"
 
 namespace ORB_SLAM3 {
@@ -153,11 +154,9 @@ int ORBextractor::ExtractColor(const unsigned char* data, int channels, int step
   return mono;
 }
 
-int ORBextractor::ExtractRectified(const rgbl_shim::StereoRectifier& rect, const unsigned char* data, int channels, int step, bool bRGB,
-                                   cv::Mat& imGray, std::vector<cv::KeyPoint>& _keypoints, cv::Mat& _descriptors,
-                                   std::vector<int>& vLappingArea) {
-  if (!data || !rect.ok()) return -1;
-  const int width = rect.dstWidth(), height = rect.dstHeight();
+template <class Call>
+int ORBextractor::ExtractIngested(int width, int height, Call call, cv::Mat& imGray, std::vector<cv::KeyPoint>& _keypoints,
+                                  cv::Mat& _descriptors, std::vector<int>& vLappingArea) {
   EnsureHandle(width, height);
   if (!mpHandle) return -1;
   const int cap = rgbl_extractor_max_keypoints(mpHandle);
@@ -166,9 +165,7 @@ int ORBextractor::ExtractRectified(const rgbl_shim::StereoRectifier& rect, const
   imGray.create(height, width, CV_8UC1);
   int n = 0, mono = -1;
   const int lap0 = vLappingArea.size() > 0 ? vLappingArea[0] : 0, lap1 = vLappingArea.size() > 1 ? vLappingArea[1] : 0;
-  const int rc = rgbl_extract_rectified(mpHandle, rect.Handle(), data, channels, bRGB ? 0 : 1, rect.srcWidth(), rect.srcHeight(), step,
-                                        lap0, lap1, reinterpret_cast<rgbl_keypoint*>(_keypoints.data()), desc.data, cap, &n, &mono,
-                                        imGray.data, (int)imGray.step);
+  const int rc = call(lap0, lap1, reinterpret_cast<rgbl_keypoint*>(_keypoints.data()), desc.data, cap, &n, &mono, imGray.data, (int)imGray.step);
   if (rc != RGBL_OK) {
     std::cerr << "[ORBextractor] " << rgbl_last_error() << std::endl;
     _keypoints.clear();
@@ -182,6 +179,28 @@ int ORBextractor::ExtractRectified(const rgbl_shim::StereoRectifier& rect, const
   }
   FillPyramid();
   return mono;
+}
+
+int ORBextractor::ExtractRectified(const rgbl_shim::StereoRectifier& rect, const unsigned char* data, int channels, int step, bool bRGB,
+                                   cv::Mat& imGray, std::vector<cv::KeyPoint>& _keypoints, cv::Mat& _descriptors,
+                                   std::vector<int>& vLappingArea) {
+  if (!data || !rect.ok()) return -1;
+  auto call = [&](int lap0, int lap1, rgbl_keypoint* kp, unsigned char* desc, int cap, int* n, int* mono, unsigned char* gray, int gray_step) {
+    return rgbl_extract_rectified(mpHandle, rect.Handle(), data, channels, bRGB ? 0 : 1, rect.srcWidth(), rect.srcHeight(), step, lap0, lap1,
+                                  kp, desc, cap, n, mono, gray, gray_step);
+  };
+  return ExtractIngested(rect.dstWidth(), rect.dstHeight(), call, imGray, _keypoints, _descriptors, vLappingArea);
+}
+
+int ORBextractor::ExtractResized(const rgbl_shim::ImageResizer& resizer, const unsigned char* data, int channels, int step, bool bRGB,
+                                 cv::Mat& imGray, std::vector<cv::KeyPoint>& _keypoints, cv::Mat& _descriptors,
+                                 std::vector<int>& vLappingArea) {
+  if (!data || !resizer.ok()) return -1;
+  auto call = [&](int lap0, int lap1, rgbl_keypoint* kp, unsigned char* desc, int cap, int* n, int* mono, unsigned char* gray, int gray_step) {
+    return rgbl_extract_resized(mpHandle, resizer.Handle(), data, channels, bRGB ? 0 : 1, resizer.srcWidth(), resizer.srcHeight(), step, lap0,
+                                lap1, kp, desc, cap, n, mono, gray, gray_step);
+  };
+  return ExtractIngested(resizer.dstWidth(), resizer.dstHeight(), call, imGray, _keypoints, _descriptors, vLappingArea);
 }
 
 void ORBextractor::UndistortKeyPoints(const std::vector<cv::KeyPoint>& mvKeys, const cv::Mat& K, const cv::Mat& mDistCoef,

@@ -10,7 +10,7 @@
 struct rgbl_extractor;
 struct rgbl_device_frame;
 struct rgbl_depth;
-namespace rgbl_shim { class StereoRectifier; }
+namespace rgbl_shim { class StereoRectifier; class ImageResizer; }
 
 namespace ORB_SLAM3 {
 
@@ -46,6 +46,13 @@ class ORBextractor {
   int ExtractRectified(const rgbl_shim::StereoRectifier& rect, const unsigned char* data, int channels, int step, bool bRGB,
                        cv::Mat& imGray, std::vector<cv::KeyPoint>& _keypoints, cv::Mat& _descriptors, std::vector<int>& vLappingArea);
 
+  // resize + cvtColor + operator() in one device round trip (System::Track*'s cv::resize to Camera.newWidth / newHeight,
+  // System.cc:269-271, 349-351, 486-489, 557-560, in front of Tracking::GrabImage*): `data` is the RAW 8-bit image (1, 3 or 4
+  // channels) of the resizer's original size; it is resized at its channel count, converted afterwards (the reference's order),
+  // the extraction runs on the result and imGray receives it (mImGray).  ImageResizer.h has the resizer.
+  int ExtractResized(const rgbl_shim::ImageResizer& resizer, const unsigned char* data, int channels, int step, bool bRGB,
+                     cv::Mat& imGray, std::vector<cv::KeyPoint>& _keypoints, cv::Mat& _descriptors, std::vector<int>& vLappingArea);
+
   // Frame::UndistortKeyPoints (Frame.cc:837-870) on the device the keypoints came from: mvKeysUn = mvKeys with
   // cv::undistortPoints(pt, K, mDistCoef, noArray(), K) applied; a plain copy when mDistCoef[0] == 0, as in the reference.
   // K: 3x3 CV_32F (Pinhole::toK()), mDistCoef: 4x1 or 5x1 CV_32F.  Call after operator() (the handle exists by then).
@@ -80,6 +87,10 @@ class ORBextractor {
 
  protected:
   void EnsureHandle(int width, int height);
+  // the body ExtractRectified and ExtractResized share: `call` is the C entry point with its ingest handle and the raw image bound
+  template <class Call>
+  int ExtractIngested(int width, int height, Call call, cv::Mat& imGray, std::vector<cv::KeyPoint>& _keypoints, cv::Mat& _descriptors,
+                      std::vector<int>& vLappingArea);
   void FillPyramid();
 
   int nfeatures;
