@@ -104,15 +104,89 @@ def _rot(q):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-def make_projection_case(n1=1800, n2=2000, seed=21, motion="forward", w=synth.KITTI_W, h=synth.KITTI_H, frame2=None):
+class Camera:
+    """What a projection search needs of a camera: the image size, K = (fx, fy, cx, cy), the bounds of the undistorted image
+    (Frame::mnMinX / mnMinY / mnMaxX / mnMaxY - the frame grid spans them) and mbf."""
+
+    def __init__(self, w, h, K, min_x, min_y, max_x, max_y, mbf):
+        self.w, self.h, self.K, self.mbf = w, h, np.array(K, np.float32), mbf
+        self.min_x, self.min_y, self.max_x, self.max_y = min_x, min_y, max_x, max_y
+
+    def grid(self):
+        """mnMinX, mnMinY, mnMaxX, mnMaxY, mfGridElementWidthInv, mfGridElementHeightInv as Frame.cc computes them (float)."""
+        f = np.float32
+        x0, y0, x1, y1 = f(self.min_x), f(self.min_y), f(self.max_x), f(self.max_y)
+        return np.array([x0, y0, x1, y1, f(64) / (x1 - x0), f(48) / (y1 - y0)], np.float32)
+
+
+def _kitti_camera(w=synth.KITTI_W, h=synth.KITTI_H):
+    return Camera(w, h, [718.856, 718.856, 607.1928, 185.2157], 0, 0, w, h, 386.1448)
+
+
+EUROC_K = (458.654, 457.296, 367.215, 248.375)                      # cam0 of the EuRoC settings files
+EUROC_DIST = (-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05)
+CAMERA_NAMES = ("kitti", "euroc_undistorted", "resized", "small_offset")
+PYRAMIDS = ((8, 1.2), (1, 1.2), (12, 1.2), (16, 1.1))                # (levels, scale factor); 16 levels is the library's limit
+
+
+def named_camera(name, undistort=None):
+    """kitti: what every generator uses by default.  euroc_undistorted: 752 x 480, the bounds Frame::ComputeImageBounds makes of
+    the four undistorted image corners (off the origin, fractional, not symmetric); undistort(xy, K, dist) is the
+    cv::undistortPoints to use (the tests pass their checker's; this package holds none that runs on the host).  resized: a KITTI frame after
+    Camera.newWidth / newHeight = 600 x 350, bounds at the origin.  small_offset: 320 x 240 with bounds a few fractional pixels
+    off the origin on every side and grid cells of 5 x 5 px (search windows wider than the grid clamp on both sides at once)."""
+    if name == "kitti":
+        return _kitti_camera()
+    if name == "euroc_undistorted":
+        w, h = 752, 480
+        c = undistort(np.array([[0, 0], [w, 0], [0, h], [w, h]], np.float32), EUROC_K, EUROC_DIST)
+        # Frame::ComputeImageBounds: min of the left / top corners, max of the right / bottom ones
+        return Camera(w, h, EUROC_K, min(c[0, 0], c[2, 0]), min(c[0, 1], c[1, 1]), max(c[1, 0], c[3, 0]), max(c[2, 1], c[3, 1]),
+                      47.90639384423901)
+    if name == "resized":
+        sx, sy = 600 / synth.KITTI_W, 350 / synth.KITTI_H
+        return Camera(600, 350, [718.856 * sx, 718.856 * sy, 607.1928 * sx, 185.2157 * sy], 0, 0, 600, 350, 386.1448 * sx)
+    if name == "small_offset":
+        return Camera(320, 240, [260.0, 260.0, 159.5, 119.5], -3.25, -2.625, 316.75, 237.375, 26.0)
+    raise KeyError(name)
+
+
+def _camera(camera, w=synth.KITTI_W, h=synth.KITTI_H):
+    if camera is None:
+        return _kitti_camera(w, h)
+    if camera == "euroc_undistorted":
+        raise ValueError("euroc_undistorted needs an undistortion: pass named_camera('euroc_undistorted', undistort=...) instead of the name")
+    return named_camera(camera) if isinstance(camera, str) else camera
+
+
+def _aim_spread(octave, scale_factors):
+    """Factor on the noise with which a point is aimed at a feature of `octave`: 1 on the levels the default pyramid has, the
+    level's scale factor above them - there the feature lies where only a window of radius th * scale[level] finds it, not one of
+    radius th * scale[level - 8] or th."""
+    octave = np.asarray(octave)
+    return np.where(octave >= 8, scale_factors[octave].astype(np.float64), 1.0)
+
+
+def _pyramid(pyramid):
+    """(levels, factor, mvScaleFactors as the generators have always built them)"""
+    n_levels, factor = (8, 1.2) if pyramid is None else pyramid
+    return int(n_levels), factor, (factor ** np.arange(int(n_levels))).astype(np.float32)
+
+
+def make_projection_case(n1=1800, n2=2000, seed=21, motion="forward", w=synth.KITTI_W, h=synth.KITTI_H, frame2=None, camera=None,
+                         pyramid=None):
     """A LastFrame with map points and a CurrentFrame whose features they should re-find.  Clusters of near-identical
     current features and several map points aiming at the same feature exercise the 'feature already holds an observed
     map point' rule (later points fall back to their second choice); unobserved (temporal) points get overwritten.
     frame2 (optional): dict(xy, desc, octave, angle[, uright]) of a real extraction to use as the CurrentFrame instead of
-    the synthetic features (n2 = its size; no clusters are added)."""
+    the synthetic features (n2 = its size; no clusters are added).
+    camera (a Camera, or the name of one that named_camera builds without an undistortion; None: KITTI intrinsics on a w x h image) and pyramid ((levels, factor); None:
+    (8, 1.2)): the features lie inside the camera's bounds, the octaves in the pyramid."""
     rng = np.random.default_rng(seed)
-    K = np.array([718.856, 718.856, 607.1928, 185.2157], np.float32)
-    mbf = 386.1448
+    cam = _camera(camera, w, h)
+    n_levels, _, scale_factors = _pyramid(pyramid)
+    K, mbf = cam.K, cam.mbf
+    x0, y0, x1, y1 = cam.min_x, cam.min_y, cam.max_x, cam.max_y
     if frame2 is not None:
         xy2 = np.ascontiguousarray(frame2["xy"], np.float32)
         n2 = len(xy2)
@@ -126,7 +200,7 @@ def make_projection_case(n1=1800, n2=2000, seed=21, motion="forward", w=synth.KI
         else:
             uright2 = np.where(rng.random(n2) < 0.6, xy2[:, 0] - mbf / depth2 + rng.normal(0, 1.0, n2), -1).astype(np.float32)
     else:
-        xy2 = np.stack([rng.uniform(5, w - 5, n2), rng.uniform(5, h - 5, n2)], 1).astype(np.float32)
+        xy2 = np.stack([rng.uniform(x0 + 5, x1 - 5, n2), rng.uniform(y0 + 5, y1 - 5, n2)], 1).astype(np.float32)
         desc2 = synth.descriptors(n2, seed)
         # clusters: copies of a feature a few pixels away with almost the same descriptor
         ncl = n2 // 10
@@ -135,9 +209,9 @@ def make_projection_case(n1=1800, n2=2000, seed=21, motion="forward", w=synth.KI
         xy2[dst] = xy2[src] + rng.uniform(-4, 4, (ncl, 2)).astype(np.float32)
         flips = rng.random((ncl, 256)) < 0.02
         desc2[dst] = desc2[src] ^ np.packbits(flips, axis=1, bitorder="little")
-        xy2[:, 0] = np.clip(xy2[:, 0], 1, w - 2)
-        xy2[:, 1] = np.clip(xy2[:, 1], 1, h - 2)
-        oct2 = rng.integers(0, 8, n2).astype(np.int32)
+        xy2[:, 0] = np.clip(xy2[:, 0], x0 + 1, x1 - 2)
+        xy2[:, 1] = np.clip(xy2[:, 1], y0 + 1, y1 - 2)
+        oct2 = rng.integers(0, n_levels, n2).astype(np.int32)
         oct2[dst] = oct2[src]
         ang2 = rng.uniform(0, 360, n2).astype(np.float32)
         depth2 = rng.uniform(4, 70, n2)
@@ -156,33 +230,36 @@ def make_projection_case(n1=1800, n2=2000, seed=21, motion="forward", w=synth.KI
     target[: n1 // 6] = target[n1 // 6: 2 * (n1 // 6)]        # duplicates
     aimed = rng.random(n1) < 0.8
     z = depth2[target] * rng.uniform(0.97, 1.03, n1)
-    uv = xy2[target] + rng.normal(0, 1.5, (n1, 2))
-    uv[~aimed] = np.stack([rng.uniform(-50, w + 50, (~aimed).sum()), rng.uniform(-50, h + 50, (~aimed).sum())], 1)
+    uv = xy2[target] + rng.normal(0, 1.5, (n1, 2)) * _aim_spread(oct2[target], scale_factors)[:, None]
+    uv[~aimed] = np.stack([rng.uniform(x0 - 50, x1 + 50, (~aimed).sum()), rng.uniform(y0 - 50, y1 + 50, (~aimed).sum())], 1)
     z[rng.random(n1) < 0.03] *= -1                            # behind the camera
     xc = np.stack([(uv[:, 0] - K[2]) / K[0] * z, (uv[:, 1] - K[3]) / K[1] * z, z], 1)
     world = ((xc - tc.astype(np.float64)) @ Rc).astype(np.float32)   # Rc^T (xc - tc)
     flips = rng.random((n1, 256)) < 0.03
     mp_desc = desc2[target] ^ np.packbits(flips, axis=1, bitorder="little")
     mp_desc[~aimed] = synth.descriptors(int((~aimed).sum()), seed + 1)
-    oct1 = np.clip(oct2[target] + rng.integers(-1, 2, n1), 0, 7).astype(np.int32)
+    oct1 = np.clip(oct2[target] + rng.integers(-1, 2, n1), 0, n_levels - 1).astype(np.int32)
     ang1 = ((ang2[target] + rng.normal(0, 20, n1)) % 360).astype(np.float32)
     ang1[rng.random(n1) < 0.1] = rng.uniform(0, 360, 1).astype(np.float32)[0]
-    gw, gh = np.float32(w), np.float32(h)
-    grid = np.array([0, 0, gw, gh, np.float32(64) / (gw - np.float32(0)), np.float32(48) / (gh - np.float32(0))], np.float32)
+    grid = cam.grid()
     return dict(valid1=(rng.random(n1) < 0.9).astype(np.uint8), world_pos1=world, mp_desc1=mp_desc,
                 mp_observed1=(rng.random(n1) < 0.75).astype(np.uint8), octave1=oct1, angle1=ang1,
                 kp2_xy=xy2, kp2_octave=oct2, kp2_angle=ang2, uright2=uright2, desc2=desc2, grid=grid,
                 Tcw_q=qc, Tcw_t=tc, Tlw_q=ql, Tlw_t=tl, K=K, mb=0.54, mbf=mbf,
-                scale_factors=(1.2 ** np.arange(8)).astype(np.float32))
+                scale_factors=scale_factors)
 
 
-def make_local_points_case(n1=3000, n2=2000, seed=41, w=synth.KITTI_W, h=synth.KITTI_H, frame2=None):
+def make_local_points_case(n1=3000, n2=2000, seed=41, w=synth.KITTI_W, h=synth.KITTI_H, frame2=None, camera=None, pyramid=None):
     """Local map points with predicted projections (what Frame::isInFrustum leaves in the MapPoint) against a frame in which
     a part of the features already holds tracked points.  Clusters of look-alike features make the ratio test bite,
     several map points aim at the same feature (the later one is blocked and falls back or fails its ratio test).
-    frame2 (optional): dict(xy, desc, octave[, uright]) of a real extraction to use as the frame (no clusters added)."""
+    frame2 (optional): dict(xy, desc, octave[, uright]) of a real extraction to use as the frame (no clusters added).
+    camera, pyramid: as for make_projection_case."""
     rng = np.random.default_rng(seed)
-    mbf = 386.1448
+    cam = _camera(camera, w, h)
+    n_levels, _, scale_factors = _pyramid(pyramid)
+    mbf = cam.mbf
+    x0, y0, x1, y1 = cam.min_x, cam.min_y, cam.max_x, cam.max_y
     if frame2 is not None:
         xy2 = np.ascontiguousarray(frame2["xy"], np.float32)
         n2 = len(xy2)
@@ -195,7 +272,7 @@ def make_local_points_case(n1=3000, n2=2000, seed=41, w=synth.KITTI_W, h=synth.K
         else:
             uright2 = np.where(rng.random(n2) < 0.6, xy2[:, 0] - mbf / depth2, -1).astype(np.float32)
     else:
-        xy2 = np.stack([rng.uniform(5, w - 5, n2), rng.uniform(5, h - 5, n2)], 1).astype(np.float32)
+        xy2 = np.stack([rng.uniform(x0 + 5, x1 - 5, n2), rng.uniform(y0 + 5, y1 - 5, n2)], 1).astype(np.float32)
         desc2 = synth.descriptors(n2, seed)
         ncl = n2 // 6
         src = rng.integers(0, n2, ncl)
@@ -203,38 +280,38 @@ def make_local_points_case(n1=3000, n2=2000, seed=41, w=synth.KITTI_W, h=synth.K
         xy2[dst] = xy2[src] + rng.uniform(-3, 3, (ncl, 2)).astype(np.float32)
         flips = rng.random((ncl, 256)) < rng.choice([0.01, 0.05, 0.15], ncl)[:, None]
         desc2[dst] = desc2[src] ^ np.packbits(flips, axis=1, bitorder="little")
-        xy2[:, 0] = np.clip(xy2[:, 0], 1, w - 2)
-        xy2[:, 1] = np.clip(xy2[:, 1], 1, h - 2)
-        oct2 = rng.integers(0, 8, n2).astype(np.int32)
-        oct2[dst] = np.where(rng.random(ncl) < 0.7, oct2[src], np.clip(oct2[src] - 1, 0, 7))
+        xy2[:, 0] = np.clip(xy2[:, 0], x0 + 1, x1 - 2)
+        xy2[:, 1] = np.clip(xy2[:, 1], y0 + 1, y1 - 2)
+        oct2 = rng.integers(0, n_levels, n2).astype(np.int32)
+        oct2[dst] = np.where(rng.random(ncl) < 0.7, oct2[src], np.clip(oct2[src] - 1, 0, n_levels - 1))
         depth2 = rng.uniform(4, 70, n2)
         uright2 = np.where(rng.random(n2) < 0.6, xy2[:, 0] - mbf / depth2, -1).astype(np.float32)
     blocked2 = (rng.random(n2) < 0.3).astype(np.uint8)          # already tracked by the motion model
     target = rng.integers(0, n2, n1)
     target[: n1 // 5] = target[n1 // 5: 2 * (n1 // 5)]
     aimed = rng.random(n1) < 0.8
-    uv = xy2[target] + rng.normal(0, 1.0, (n1, 2)).astype(np.float32)
-    uv[~aimed] = np.stack([rng.uniform(0, w, (~aimed).sum()), rng.uniform(0, h, (~aimed).sum())], 1)
+    uv = xy2[target] + rng.normal(0, 1.0, (n1, 2)).astype(np.float32) * _aim_spread(oct2[target], scale_factors)[:, None].astype(np.float32)
+    uv[~aimed] = np.stack([rng.uniform(x0, x1, (~aimed).sum()), rng.uniform(y0, y1, (~aimed).sum())], 1)
     xr = (uv[:, 0] - mbf / depth2[target] + rng.normal(0, 1.5, n1)).astype(np.float32)
     proj = np.concatenate([uv, xr[:, None]], 1).astype(np.float32)
-    level = np.clip(oct2[target] + rng.integers(0, 2, n1), 0, 7).astype(np.int32)   # window accepts level-1 .. level
+    level = np.clip(oct2[target] + rng.integers(0, 2, n1), 0, n_levels - 1).astype(np.int32)   # window accepts level-1 .. level
     flips = rng.random((n1, 256)) < 0.04
     mp_desc = desc2[target] ^ np.packbits(flips, axis=1, bitorder="little")
     mp_desc[~aimed] = synth.descriptors(int((~aimed).sum()), seed + 1)
-    gw, gh = np.float32(w), np.float32(h)
-    grid = np.array([0, 0, gw, gh, np.float32(64) / gw, np.float32(48) / gh], np.float32)
+    grid = cam.grid()
     return dict(valid1=(rng.random(n1) < 0.85).astype(np.uint8), proj1=proj, level1=level,
                 view_cos1=np.where(rng.random(n1) < 0.5, 0.9995, 0.9).astype(np.float32), mp_desc1=mp_desc,
                 mp_observed1=(rng.random(n1) < 0.9).astype(np.uint8), kp2_xy=xy2, kp2_octave=oct2, uright2=uright2, desc2=desc2,
-                blocked2=blocked2, grid=grid, scale_factors=(1.2 ** np.arange(8)).astype(np.float32))
+                blocked2=blocked2, grid=grid, scale_factors=scale_factors)
 
 
-def make_relocalization_case(n1=1500, n2=2000, seed=61):
+def make_relocalization_case(n1=1500, n2=2000, seed=61, camera=None, pyramid=None):
     """A key frame whose map points are searched in a frame with a (PnP-refined) pose: SearchByProjection(CurrentFrame, pKF,
     sAlreadyFound, th, ORBdist).  Built on the Frame-to-Frame case: same clusters / duplicate targets; on top of it points
     without a map point, bad and already-found ones, scale-invariance ranges that exclude some points, features of the
     frame that hold a map point on entry, and points behind the camera (the overload does not test the sign of the depth)."""
-    c = make_projection_case(n1, n2, seed, "none")
+    c = make_projection_case(n1, n2, seed, "none", camera=camera, pyramid=pyramid)
+    n_levels, factor, _ = _pyramid(pyramid)
     rng = np.random.default_rng(seed + 1000)
     qc, tc = c["Tcw_q"], c["Tcw_t"]
     Rc = _rot(qc)
@@ -242,8 +319,8 @@ def make_relocalization_case(n1=1500, n2=2000, seed=61):
     dist = np.linalg.norm(c["world_pos1"].astype(np.float64) - Ow, axis=1)
     # mfMaxDistance = dist * scale^level of the observation that made the point: predicted levels spread over the pyramid
     lvl = c["octave1"].astype(np.int64)                          # near the octave of the feature the point aims at
-    max_d = (dist * 1.2 ** lvl * rng.uniform(0.85, 1.0, n1)).astype(np.float32)
-    min_d = (max_d / np.float32(1.2 ** 7)).astype(np.float32)
+    max_d = (dist * factor ** lvl * rng.uniform(0.85, 1.0, n1)).astype(np.float32)
+    min_d = (max_d / np.float32(factor ** (n_levels - 1))).astype(np.float32)
     far = rng.random(n1) < 0.05
     max_d[far] = (dist[far] * 0.5).astype(np.float32)          # outside the invariance range (too far)
     near = rng.random(n1) < 0.03
@@ -253,7 +330,7 @@ def make_relocalization_case(n1=1500, n2=2000, seed=61):
                 min_dist1=min_d, max_dist1=max_d, angle1=c["angle1"], kp2_xy=c["kp2_xy"], kp2_octave=c["kp2_octave"],
                 kp2_angle=c["kp2_angle"], desc2=c["desc2"], occupied2=(rng.random(n2) < 0.1).astype(np.uint8),
                 grid=c["grid"], Tcw_q=qc, Tcw_t=tc, K=c["K"], scale_factors=c["scale_factors"],
-                log_scale_factor=np.float32(np.log(np.float32(1.2))))
+                log_scale_factor=np.float32(np.log(np.float32(factor))))
 
 
 def relocalization_prepass(case):
@@ -276,12 +353,12 @@ def relocalization_prepass(case):
     return valid.astype(np.uint8), np.where(valid, level, 0).astype(np.int32)
 
 
-def make_fuse_case(n1=2500, n2=2000, seed=91):
+def make_fuse_case(n1=2500, n2=2000, seed=91, camera=None, pyramid=None):
     """Map points of neighbouring key frames projected into a key frame (LocalMapping::SearchInNeighbors -> ORBmatcher::Fuse):
     built on the relocalisation case (same clusters, points behind the camera, invariance ranges) plus normals (some seen
     under more than 60 degrees), points already in the key frame, stereo / mono key-frame features (both chi-square gates)."""
-    c = make_relocalization_case(n1, n2, seed)
-    base = make_projection_case(n1, n2, seed, "none")
+    c = make_relocalization_case(n1, n2, seed, camera=camera, pyramid=pyramid)
+    base = make_projection_case(n1, n2, seed, "none", camera=camera, pyramid=pyramid)
     rng = np.random.default_rng(seed + 2000)
     q, t = c["Tcw_q"], c["Tcw_t"]
     Rc = _rot(q)
@@ -319,20 +396,82 @@ def fuse_prepass(case):
     return valid.astype(np.uint8), np.where(valid, level, 0).astype(np.int32)
 
 
-def make_initialization_case(n1=5000, seed=61, w=synth.KITTI_W, h=synth.KITTI_H, motion=(14.0, -6.0)):
+def make_project_search_case(n1=2500, n2=2000, seed=111, camera=None, pyramid=None):
+    """Camera-frame map points over a key frame (what Fuse(pKF, Scw, ...) and SearchBySim3 hand to the search): the fuse case with
+    the points moved into the camera frame in float64 and rounded once (the product and the oracle both start from these)."""
+    c = make_fuse_case(n1, n2, seed, camera=camera, pyramid=pyramid)
+    valid, level = fuse_prepass(c)
+    R = _rot(c["Tcw_q"]).astype(np.float64)
+    cam = (c["world_pos1"].astype(np.float64) @ R.T + c["Tcw_t"].astype(np.float64)).astype(np.float32)
+    return dict(valid1=valid, cam_pos1=cam, mp_desc1=c["mp_desc1"], level1=level, kp2_xy=c["kp2_xy"], kp2_octave=c["kp2_octave"],
+                desc2=c["desc2"], grid=c["grid"], K=c["K"], scale_factors=c["scale_factors"])
+
+
+def make_sim3_case(n=1500, seed=121, w=synth.KITTI_W, h=synth.KITTI_H, camera=None, pyramid=None):
+    """Two key frames that see the same place (all poses identities, so one common camera frame): KF2's features are KF1's,
+    permuted, moved by a pixel or two and with a few descriptor bits flipped; every feature's map point sits on the ray of its
+    counterpart in the OTHER key frame, so that the two directed searches of SearchBySim3 mostly agree.  Some features have no
+    or a bad map point, some points fall outside their invariance range, some lie behind the camera.
+    camera, pyramid: as for make_projection_case."""
+    rng = np.random.default_rng(seed)
+    cm = _camera(camera, w, h)
+    n_levels, factor, sf = _pyramid(pyramid)
+    K = cm.K
+    x0, y0, x1, y1 = cm.min_x, cm.min_y, cm.max_x, cm.max_y
+    xy1 = np.stack([rng.uniform(x0 + 20, x1 - 20, n), rng.uniform(y0 + 20, y1 - 20, n)], 1).astype(np.float32)
+    oct1 = rng.integers(0, n_levels, n).astype(np.int32)
+    desc1 = synth.descriptors(n, seed)
+    perm = rng.permutation(n)
+    inv = np.argsort(perm)                                   # feature i1 of KF1 <-> feature inv[i1] of KF2
+    xy2 = (xy1[perm] + rng.normal(0, 1.0, (n, 2))).astype(np.float32)
+    oct2 = oct1[perm].copy()
+    desc2 = desc1[perm] ^ np.packbits(rng.random((n, 256)) < 0.03, axis=1, bitorder="little")
+
+    def side(xy_self, octave, desc, xy_other, partner):
+        z = rng.uniform(4, 60, n)
+        z[rng.random(n) < 0.03] *= -1
+        tgt = xy_other[partner] + rng.normal(0, 1.0, (n, 2)) * _aim_spread(octave, sf)[:, None]
+        pos = np.stack([(tgt[:, 0] - K[2]) / K[0] * z, (tgt[:, 1] - K[3]) / K[1] * z, z], 1).astype(np.float32)
+        dist = np.linalg.norm(pos.astype(np.float64), axis=1)
+        lvl = np.clip(octave + rng.integers(0, 2, n), 0, n_levels - 1)   # predicted level = octave or octave + 1: band [l - 1, l] holds the octave
+        max_d = (dist * factor ** lvl * rng.uniform(0.86, 0.99, n)).astype(np.float32)
+        min_d = (max_d / np.float32(factor ** (n_levels - 1))).astype(np.float32)
+        far = rng.random(n) < 0.04
+        max_d[far] = (dist[far] * 0.5).astype(np.float32)
+        normal = -pos / np.maximum(np.linalg.norm(pos, axis=1, keepdims=True), 1e-6) + rng.normal(0, 0.3, pos.shape)
+        normal /= np.linalg.norm(normal, axis=1, keepdims=True)
+        state = rng.choice([0, 1, 2], n, p=[0.12, 0.8, 0.08]).astype(np.uint8)
+        mp_desc = desc ^ np.packbits(rng.random((n, 256)) < 0.02, axis=1, bitorder="little")
+        return dict(kp_xy=xy_self, kp_octave=octave, desc=desc, mp_state=state, mp_pos=pos, mp_normal=(-normal).astype(np.float32),
+                    mp_desc=mp_desc, mp_min_dist=min_d, mp_max_dist=max_d)
+    a1 = side(xy1, oct1, desc1, xy2, inv)
+    a2 = side(xy2, oct2, desc2, xy1, perm)
+    prior = np.where(rng.random(n) < 0.1, inv, -1).astype(np.int32)      # matches found earlier (by SearchByBoW)
+    return dict(a1=a1, a2=a2, K=K, grid=cm.grid(), scale_factors=sf, log_scale_factor=np.float32(np.log(np.float32(factor))),
+                prior12=prior, inv=inv)
+
+
+def make_initialization_case(n1=5000, seed=61, w=synth.KITTI_W, h=synth.KITTI_H, motion=(14.0, -6.0), camera=None, pyramid=None):
     """Two monocular frames: F2's features are F1's moved by `motion` plus noise, descriptors with a few flipped bits;
     vbPrevMatched = F1's positions (Tracking.cc:2493-2495).  Look-alike neighbours make the ratio test bite, and pairs of F1
     features aim at one F2 feature with the later one closer, so that matches are taken over (vMatchedDistance)."""
     rng = np.random.default_rng(seed)
-    xy1 = np.stack([rng.uniform(5, w - 5, n1), rng.uniform(5, h - 5, n1)], 1).astype(np.float32)
-    oct1 = rng.choice(8, n1, p=[0.45, 0.2, 0.1, 0.08, 0.06, 0.05, 0.03, 0.03]).astype(np.int32)
+    cam = _camera(camera, w, h)
+    n_levels = _pyramid(pyramid)[0]
+    x0, y0, x1, y1 = cam.min_x, cam.min_y, cam.max_x, cam.max_y
+    xy1 = np.stack([rng.uniform(x0 + 5, x1 - 5, n1), rng.uniform(y0 + 5, y1 - 5, n1)], 1).astype(np.float32)
+    level_p = [0.45, 0.2, 0.1, 0.08, 0.06, 0.05, 0.03, 0.03]      # level 0 is what the search matches
+    if n_levels != 8:
+        rest = 0.8 ** np.arange(n_levels - 1)
+        level_p = [1.0] if n_levels == 1 else [0.45] + list(0.55 * rest / rest.sum())
+    oct1 = rng.choice(n_levels, n1, p=level_p).astype(np.int32)
     desc1 = synth.descriptors(n1, seed)
     ang1 = rng.uniform(0, 360, n1).astype(np.float32)
     n2 = n1
     perm = rng.permutation(n1)                      # F2 feature j comes from F1 feature perm[j]
     xy2 = (xy1[perm] + np.array(motion, np.float32) + rng.normal(0, 1.5, (n2, 2))).astype(np.float32)
     oct2 = oct1[perm].copy()
-    oct2[rng.random(n2) < 0.1] = 1
+    oct2[rng.random(n2) < 0.1] = min(1, n_levels - 1)
     rate = rng.choice([0.01, 0.04, 0.1, 0.3], n2, p=[0.3, 0.4, 0.2, 0.1])
     desc2 = desc1[perm] ^ np.packbits(rng.random((n2, 256)) < rate[:, None], axis=1, bitorder="little")
     dang = np.where(rng.random(n2) < 0.8, rng.normal(5, 3, n2), rng.uniform(0, 360, n2))
@@ -355,12 +494,11 @@ def make_initialization_case(n1=5000, seed=61, w=synth.KITTI_W, h=synth.KITTI_H,
     xy1[a] = xy1[b] + rng.uniform(-30, 30, (len(a), 2)).astype(np.float32)
     desc2[c] = desc1[b] ^ np.packbits(rng.random((len(a), 256)) < 0.02, axis=1, bitorder="little")
     desc1[a] = desc2[c] ^ np.packbits(rng.random((len(a), 256)) < rng.choice([0.03, 0.08], len(a))[:, None], axis=1, bitorder="little")
-    xy2[:, 0] = np.clip(xy2[:, 0], 1, w - 2)
-    xy2[:, 1] = np.clip(xy2[:, 1], 1, h - 2)
+    xy2[:, 0] = np.clip(xy2[:, 0], x0 + 1, x1 - 2)
+    xy2[:, 1] = np.clip(xy2[:, 1], y0 + 1, y1 - 2)
     prev = xy1.copy()
     prev[rng.random(n1) < 0.01] = np.float32(-500)   # window outside of the grid
-    gw, gh = np.float32(w), np.float32(h)
-    grid = np.array([0, 0, gw, gh, np.float32(64) / gw, np.float32(48) / gh], np.float32)
+    grid = cam.grid()
     return dict(kp1_octave=oct1, kp1_angle=ang1, desc1=desc1, prev_matched=prev, kp2_xy=xy2, kp2_octave=oct2, kp2_angle=ang2,
                 desc2=desc2, grid=grid)
 

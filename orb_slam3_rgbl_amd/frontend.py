@@ -728,7 +728,9 @@ class ORBmatcher:
         out = np.zeros(len(d), np.int32)
         for i, r in enumerate(ratio):
             q = np.float32(libm.logf(float(r))) / lsf
-            n = int(np.ceil(q)) if np.isfinite(q) else (0 if q < 0 else int(mnScaleLevels))
+            # a zero, infinite or NaN distance: the reference converts an infinite or NaN quotient to int, which gives INT_MIN
+            # on x86-64 (cvttsd2si), i.e. level 0 after the clamp - what the oracle and the device's isInFrustum return too
+            n = int(np.ceil(q)) if np.isfinite(q) else 0
             out[i] = min(max(n, 0), int(mnScaleLevels) - 1)
         return out
 

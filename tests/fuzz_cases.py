@@ -5,6 +5,7 @@ bit against the oracle; used by tests/test_fuzz_gpu.py (fixed seeds, `-m gpu`; R
 seeds) and by tools/gpu_random_*_checks.py."""
 import numpy as np
 
+import geometry_checks as gc
 import parity_checks as pc
 from oracle import oracle_py as O
 from orb_slam3_rgbl_amd import frontend as F
@@ -68,21 +69,79 @@ def hamming_case(lib, rng):
 def greedy_search_case(lib, rng):
     """The sequential, blocking searches (SearchByProjection frame-to-frame and key-frame-to-frame, SearchLocalPoints): random
     sizes on both sides of the resolve kernels' LDS limits, every motion / window, dense clusters that make long blocker chains -
-    many rounds of the round-based resolve with real concurrency between the work-items of a round."""
+    many rounds of the round-based resolve with real concurrency between the work-items of a round.  Camera and pyramid come from
+    a generator of their own, seeded by the case's seed: the sizes, thresholds and seeds a test seed draws stay what they were.
+    lib = None: the oracle alone.  These searches give a feature to one point at most, so a frame of n2 features cannot match more
+    than n2 points: the floor is 5 % of n1 where n2 >= n1 / 4 and a fifth of the features (5 % of 4 n2) in a smaller frame."""
     kind = int(rng.integers(0, 3))
     n1 = int(rng.choice([40, 300, 1500, 2000, 3000, 6000, 12500]))
     n2 = int(rng.choice([60, 500, 2000, 3000, 6100, 6200, 9000]))
     seed = int(rng.integers(0, 100000))
+    cam, pyr = draw_geometry(np.random.default_rng(seed + 977))
+    geo = dict(camera=gc.camera(cam), pyramid=pyr)
+    tag = " [%s, %d x %g]" % (cam, pyr[0], pyr[1])
+
+    def floor(n, of):
+        gc.assert_floor(n, min(of, 4 * n2), "greedy search, kind %d, seed %d" % (kind, seed) + tag)
     if kind == 0:
         motion, th = str(rng.choice(["forward", "backward", "none"])), float(rng.choice([7.0, 15.0, 30.0]))
-        n = pc.check_search_by_projection(lib, seed, motion, th, bool(rng.integers(0, 2)), bool(rng.integers(0, 2)), n1=n1, n2=n2)
-        return "SearchByProjection %5d -> %5d %s th %g: %d matches" % (n1, n2, motion, th, n)
+        n = pc.check_search_by_projection(lib, seed, motion, th, bool(rng.integers(0, 2)), bool(rng.integers(0, 2)), n1=n1, n2=n2, **geo)
+        floor(n, n1)
+        return "SearchByProjection %5d -> %5d %s th %g: %d matches" % (n1, n2, motion, th, n) + tag
     if kind == 1:
         th = float(rng.choice([1.0, 3.0, 5.0, 15.0]))
-        n = pc.check_search_local_points(lib, seed, th, float(rng.choice([0.7, 0.8, 0.9])), n1=n1, n2=n2)
-        return "SearchLocalPoints %5d -> %5d th %g: %d matches" % (n1, n2, th, n)
-    n = pc.check_search_by_projection_keyframe(lib, seed, float(rng.choice([3.0, 10.0, 15.0])), int(rng.choice([64, 100, 255])), True, n1=min(n1, 6000), n2=n2)
-    return "SearchByProjection(F, KF) %5d -> %5d: %d matches" % (min(n1, 6000), n2, n)
+        n = pc.check_search_local_points(lib, seed, th, float(rng.choice([0.7, 0.8, 0.9])), n1=n1, n2=n2, **geo)
+        floor(n, n1)
+        return "SearchLocalPoints %5d -> %5d th %g: %d matches" % (n1, n2, th, n) + tag
+    n = pc.check_search_by_projection_keyframe(lib, seed, float(rng.choice([3.0, 10.0, 15.0])), int(rng.choice([64, 100, 255])), True, n1=min(n1, 6000), n2=n2,
+                                               **geo)
+    floor(n, min(n1, 6000))
+    return "SearchByProjection(F, KF) %5d -> %5d: %d matches" % (min(n1, 6000), n2, n) + tag
+
+
+def draw_geometry(rng):
+    return str(rng.choice(gc.CAMERA_NAMES)), gc.PYRAMIDS[int(rng.integers(0, len(gc.PYRAMIDS)))]
+
+
+def point_search_case(lib, rng):
+    """The searches that decide point by point (Fuse, the camera-frame project search behind Fuse(Scw) and SearchBySim3), the greedy
+    SearchByProjection(pKF, Scw) and SearchForInitialization, and ComputeDistinctiveDescriptors: a camera, a pyramid, th / ratio as
+    the reference's callers pass them (LocalMapping.cc, LoopClosing.cc, Tracking.cc), sizes on both sides of kGridLdsN2 and of the
+    resolve kernels' LDS limits.  lib = None: the oracle alone (does every drawn case clear the floor?).
+    A search that gives a feature to one point at most cannot match 5 % of n1 points in a frame of fewer features: such a pair of
+    sizes is drawn again."""
+    kind = int(rng.integers(0, 6))
+    cam, pyr = draw_geometry(rng)
+    seed = int(rng.integers(0, 100000))
+    while True:
+        n1, n2 = int(rng.choice([40, 300, 1500, 3000, 8300])), int(rng.choice([60, 500, 2000, 6200, 8300]))
+        if kind != 3 or 4 * n2 >= n1:
+            break
+    tag = " [%s, %d x %g]" % (cam, pyr[0], pyr[1])
+    if kind == 0:
+        th = float(rng.choice([3.0, 4.0]))     # SearchInNeighbors: the default 3; 4 as in SearchAndFuse
+        found, _ = gc.check_search(lib, gc.fuse(th), cam, pyr, n1, n2, seed)
+        return "Fuse %5d -> %5d th %g: %d matches" % (n1, n2, th, found) + tag
+    if kind == 1:
+        form = int(rng.integers(0, 2))
+        th, maxd = ((4.0, 50), (7.5, 100))[form]
+        found, _ = gc.check_search(lib, gc.project_search(th, form, maxd), cam, pyr, n1, n2, seed)
+        return "project search form %d %5d -> %5d th %g: %d matches" % (form, n1, n2, th, found) + tag
+    if kind == 2:
+        found, _ = gc.check_search(lib, gc.sim3(7.5), cam, pyr, n1, n1, seed)
+        return "SearchBySim3 %5d <-> %5d: %d matches" % (n1, n1, found) + tag
+    if kind == 3:
+        form = int(rng.choice([0, 2]))
+        th, ratio = ((3, 2.5), (8, 1.5), (30, 1.0))[int(rng.integers(0, 3))]   # LoopClosing::FindMatchesByProjection / DetectCommonRegions
+        found, _ = gc.check_search(lib, gc.projection_sim3(th, form, ratio), cam, pyr, n1, n2, seed)
+        return "SearchByProjection(KF, Sim3) form %d %5d -> %5d th %d ratio %g: %d matches" % (form, n1, n2, th, ratio, found) + tag
+    if kind == 4:
+        found, of = gc.check_search(lib, gc.initialization(100, 0.9, True), cam, pyr, n1, n1, seed)
+        return "SearchForInitialization %5d <-> %5d: %d of %d level-0 features" % (n1, n1, found, of) + tag
+    n_points = int(rng.choice([1, 40, 300, 1500]))
+    if lib is None:
+        return "ComputeDistinctiveDescriptors %d points" % n_points
+    return "ComputeDistinctiveDescriptors %d points: %d with a descriptor" % (n_points, pc.check_distinctive_descriptors(lib, seed, n_points))
 
 
 def node_search_case(lib, rng):
@@ -147,4 +206,4 @@ def stereo_case(lib, rng):
 
 
 CASES = {"stereo": stereo_case, "node_search": node_search_case, "extractor": extractor_case, "low_contrast": low_contrast_case, "depth": depth_case, "hamming": hamming_case,
-         "greedy_search": greedy_search_case}
+         "greedy_search": greedy_search_case, "point_search": point_search_case}

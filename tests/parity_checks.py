@@ -9,7 +9,8 @@ from orb_slam3_rgbl_amd import _lib as L
 from orb_slam3_rgbl_amd import frontend as F
 from orb_slam3_rgbl_amd import synth
 from orb_slam3_rgbl_amd.cases import (make_triangulation_case, make_projection_case, make_local_points_case, make_relocalization_case,  # noqa: F401
-                                      relocalization_prepass, make_fuse_case, fuse_prepass, make_initialization_case, _quat, _rot)
+                                      relocalization_prepass, make_fuse_case, fuse_prepass, make_initialization_case, _quat, _rot,
+                                      make_project_search_case, make_sim3_case)
 
 KP_FIELDS = ("x", "y", "size", "angle", "response", "octave", "class_id")
 
@@ -455,24 +456,28 @@ def check_ingest_kitti_bin(lib, method=F.UPS_INVERSE_DILATION, w=620, h=188, n_a
 
 
 # ---- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) -------------------------
-def check_search_by_projection(lib, seed=21, motion="forward", th=7.0, mono=False, check_ori=True, n1=1800, n2=2000):
-    case = make_projection_case(n1, n2, seed, motion)
+def check_search_by_projection(lib, seed=21, motion="forward", th=7.0, mono=False, check_ori=True, n1=1800, n2=2000, camera=None, pyramid=None):
+    case = make_projection_case(n1, n2, seed, motion, camera=camera, pyramid=pyramid)
+    om, on = O.search_by_projection(case, th, mono, check_ori)
+    if lib is None:   # the oracle alone: how many matches the case is worth
+        return on
     mt = F.ORBmatcher(0.9, check_ori, lib=lib)
     m, n = mt.SearchByProjection(case, th, mono)
-    om, on = O.search_by_projection(case, th, mono, check_ori)
     assert n == on and np.array_equal(m, om), "SearchByProjection (seed %d, %s, th %g)" % (seed, motion, th)
     mt.close()
     return n
 
 
-def check_search_by_projection_keyframe(lib, seed=61, th=15.0, orb_dist=100, check_ori=True, n1=1500, n2=2000):
-    case = make_relocalization_case(n1, n2, seed)
+def check_search_by_projection_keyframe(lib, seed=61, th=15.0, orb_dist=100, check_ori=True, n1=1500, n2=2000, camera=None, pyramid=None):
+    case = make_relocalization_case(n1, n2, seed, camera=camera, pyramid=pyramid)
     valid, level = relocalization_prepass(case)
     ovalid, olevel = O.kf_projection_prepass(case)
     assert np.array_equal(valid, ovalid) and np.array_equal(level[valid != 0], olevel[valid != 0]), "relocalisation prepass"
+    om, on = O.search_by_projection_kf(case, th, orb_dist, check_ori)
+    if lib is None:
+        return on
     mt = F.ORBmatcher(0.9, check_ori, lib=lib)
     m, n = mt.SearchByProjectionKeyFrame(dict(case, valid1=valid, level1=level), th, orb_dist)
-    om, on = O.search_by_projection_kf(case, th, orb_dist, check_ori)
     assert n == on and np.array_equal(m, om), "SearchByProjection(Frame, KeyFrame) (seed %d, th %g, ORBdist %d)" % (seed, th, orb_dist)
     mt.close()
     return n
@@ -518,21 +523,26 @@ def check_search_by_projection_edge_cases(lib):
 
 
 # ---- ORBmatcher::SearchByProjection(F, vpMapPoints, th, ...) = Tracking::SearchLocalPoints -------------------------------
-def check_search_local_points(lib, seed=41, th=1.0, nnratio=0.8, n1=3000, n2=2000):
-    case = make_local_points_case(n1, n2, seed)
+def check_search_local_points(lib, seed=41, th=1.0, nnratio=0.8, n1=3000, n2=2000, camera=None, pyramid=None):
+    case = make_local_points_case(n1, n2, seed, camera=camera, pyramid=pyramid)
+    om, on = O.search_local_points(case, th, nnratio)
+    if lib is None:
+        return on
     mt = F.ORBmatcher(nnratio, True, lib=lib)
     m, n = mt.SearchLocalPoints(case, th)
-    om, on = O.search_local_points(case, th, nnratio)
     assert n == on and np.array_equal(m, om), "SearchByProjection(F, vpMapPoints) (seed %d, th %g)" % (seed, th)
     # a dense cluster: more candidates per point than the per-point list holds (window re-scan path)
-    case = make_local_points_case(400, 500, seed + 1)
+    case = make_local_points_case(400, 500, seed + 1, camera=camera, pyramid=pyramid)
     rng = np.random.default_rng(seed)
-    case["kp2_xy"][:60] = np.array([400.0, 200.0], np.float32) + rng.uniform(-4, 4, (60, 2)).astype(np.float32)
-    case["kp2_octave"][:60] = 1
+    centre, lvl = np.array([400.0, 200.0], np.float32), 1
+    if camera is not None or pyramid is not None:   # the middle of the camera's grid, a level of the pyramid
+        centre, lvl = (case["grid"][:2] + case["grid"][2:4]) / np.float32(2), min(1, len(case["scale_factors"]) - 1)
+    case["kp2_xy"][:60] = centre + rng.uniform(-4, 4, (60, 2)).astype(np.float32)
+    case["kp2_octave"][:60] = lvl
     case["desc2"][:60] = case["desc2"][0] ^ np.packbits(rng.random((60, 256)) < 0.03, axis=1, bitorder="little")
     case["uright2"][:60] = -1
-    case["proj1"][:200, :2] = np.array([400.0, 200.0], np.float32) + rng.uniform(-2, 2, (200, 2)).astype(np.float32)
-    case["level1"][:200] = 1
+    case["proj1"][:200, :2] = centre + rng.uniform(-2, 2, (200, 2)).astype(np.float32)
+    case["level1"][:200] = lvl
     case["mp_desc1"][:200] = case["desc2"][0]
     case["valid1"][:200] = 1
     m2, n2_ = mt.SearchLocalPoints(case, 3.0)
@@ -1031,17 +1041,6 @@ def check_distinctive_descriptors(lib, seed=101, n_points=400):
     return int((want >= 0).sum())
 
 
-def make_project_search_case(n1=2500, n2=2000, seed=111):
-    """Camera-frame map points over a key frame (what Fuse(pKF, Scw, ...) and SearchBySim3 hand to the search): the fuse case with
-    the points moved into the camera frame in float64 and rounded once (the product and the oracle both start from these)."""
-    c = make_fuse_case(n1, n2, seed)
-    valid, level = fuse_prepass(c)
-    R = _rot(c["Tcw_q"]).astype(np.float64)
-    cam = (c["world_pos1"].astype(np.float64) @ R.T + c["Tcw_t"].astype(np.float64)).astype(np.float32)
-    return dict(valid1=valid, cam_pos1=cam, mp_desc1=c["mp_desc1"], level1=level, kp2_xy=c["kp2_xy"], kp2_octave=c["kp2_octave"],
-                desc2=c["desc2"], grid=c["grid"], K=c["K"], scale_factors=c["scale_factors"])
-
-
 def check_project_search(lib, seed=111, th=4.0, proj_form=0, max_dist=50, n1=2500, n2=2000):
     case = make_project_search_case(n1, n2, seed)
     mt = F.ORBmatcher(0.75, True, lib=lib)
@@ -1065,49 +1064,6 @@ def camera_prepass(cam_pos, min_dist, max_dist, log_scale_factor, n_levels, norm
         valid &= ~(dot.astype(np.float64) < 0.5 * dist.astype(np.float64))
     level = F.ORBmatcher.PredictScale(dist, max_dist, log_scale_factor, n_levels)
     return valid, np.where(valid, level, 0).astype(np.int32)
-
-
-def make_sim3_case(n=1500, seed=121, w=synth.KITTI_W, h=synth.KITTI_H):
-    """Two key frames that see the same place (all poses identities, so one common camera frame): KF2's features are KF1's,
-    permuted, moved by a pixel or two and with a few descriptor bits flipped; every feature's map point sits on the ray of its
-    counterpart in the OTHER key frame, so that the two directed searches of SearchBySim3 mostly agree.  Some features have no
-    or a bad map point, some points fall outside their invariance range, some lie behind the camera."""
-    rng = np.random.default_rng(seed)
-    K = np.array([718.856, 718.856, 607.1928, 185.2157], np.float32)
-    sf = (1.2 ** np.arange(8)).astype(np.float32)
-    xy1 = np.stack([rng.uniform(20, w - 20, n), rng.uniform(20, h - 20, n)], 1).astype(np.float32)
-    oct1 = rng.integers(0, 8, n).astype(np.int32)
-    desc1 = synth.descriptors(n, seed)
-    perm = rng.permutation(n)
-    inv = np.argsort(perm)                                   # feature i1 of KF1 <-> feature inv[i1] of KF2
-    xy2 = (xy1[perm] + rng.normal(0, 1.0, (n, 2))).astype(np.float32)
-    oct2 = oct1[perm].copy()
-    desc2 = desc1[perm] ^ np.packbits(rng.random((n, 256)) < 0.03, axis=1, bitorder="little")
-
-    def side(xy_self, octave, desc, xy_other, partner):
-        z = rng.uniform(4, 60, n)
-        z[rng.random(n) < 0.03] *= -1
-        tgt = xy_other[partner] + rng.normal(0, 1.0, (n, 2))
-        pos = np.stack([(tgt[:, 0] - K[2]) / K[0] * z, (tgt[:, 1] - K[3]) / K[1] * z, z], 1).astype(np.float32)
-        dist = np.linalg.norm(pos.astype(np.float64), axis=1)
-        lvl = np.clip(octave + rng.integers(0, 2, n), 0, 7)   # predicted level = octave or octave + 1: band [l - 1, l] holds the octave
-        max_d = (dist * 1.2 ** lvl * rng.uniform(0.86, 0.99, n)).astype(np.float32)
-        min_d = (max_d / np.float32(1.2 ** 7)).astype(np.float32)
-        far = rng.random(n) < 0.04
-        max_d[far] = (dist[far] * 0.5).astype(np.float32)
-        normal = -pos / np.maximum(np.linalg.norm(pos, axis=1, keepdims=True), 1e-6) + rng.normal(0, 0.3, pos.shape)
-        normal /= np.linalg.norm(normal, axis=1, keepdims=True)
-        normal = -normal if False else normal
-        state = rng.choice([0, 1, 2], n, p=[0.12, 0.8, 0.08]).astype(np.uint8)
-        mp_desc = desc ^ np.packbits(rng.random((n, 256)) < 0.02, axis=1, bitorder="little")
-        return dict(kp_xy=xy_self, kp_octave=octave, desc=desc, mp_state=state, mp_pos=pos, mp_normal=(-normal).astype(np.float32),
-                    mp_desc=mp_desc, mp_min_dist=min_d, mp_max_dist=max_d)
-    a1 = side(xy1, oct1, desc1, xy2, inv)
-    a2 = side(xy2, oct2, desc2, xy1, perm)
-    gw, gh = np.float32(w), np.float32(h)
-    grid = np.array([0, 0, gw, gh, np.float32(64) / gw, np.float32(48) / gh], np.float32)
-    prior = np.where(rng.random(n) < 0.1, inv, -1).astype(np.int32)      # matches found earlier (by SearchByBoW)
-    return dict(a1=a1, a2=a2, K=K, grid=grid, scale_factors=sf, log_scale_factor=np.float32(np.log(np.float32(1.2))), prior12=prior, inv=inv)
 
 
 def sim3_direction(case, src, dst, already, th):
@@ -1700,3 +1656,247 @@ def check_switches(lib, w=400, h=300, nfeatures=500, batch=8, subset=None):
         assert np.array_equal(desc, odesc) and mono == omono
     ex.close()
     return len(settings)
+
+
+# ---- the grid searches' comparisons, hit by construction --------------------------------------------------------------------
+# Random points never land ON a bound.  Here they do: identity poses, fx = fy = 512, cx = cy = 0, depths 1 and 2, so that
+# fx x / z + cx (Pinhole::project, proj_form 0 / 1, the frame-to-frame overloads) and fx (x (1 / z)) + cx (sim3_mode 2) are exact
+# in fp32 for every fp32 u: x = u z / 512 only moves the exponent.
+BOUNDS_K = np.array([512.0, 512.0, 0.0, 0.0], np.float32)
+# cells of 2 x 2 px, bounds off the origin.  (Small cells: PosInGrid ROUNDS, so a feature within half a cell of the upper bound is
+# in no cell, and a window of radius 2 next to that bound has to reach a feature that is.)
+POW2_GRID = np.array([-8.5, -4.25, 119.5, 91.75, 64 / 128.0, 48 / 96.0], np.float32)
+
+
+def make_bounds_points(grid, radius, seed=7):
+    """Points whose projections sit at {min - 1/8, min, min + 1/8, max - 1/8, max, max + 1/8, centre} of both axes (z = 1: all
+    49 pairs; z = 2: every value of one axis at the centre of the other), one at the principal point, points with z in {+0, -0,
+    +-subnormal, -1} with x = 0 and x != 0, NaN and infinite coordinates.  Around every finite projection eleven features of
+    octave 0: at the projection, at +-(radius - 1/8) and at +-radius (strict '<': rejected) along both axes, at +-(radius - 1/8)
+    along the diagonal; the j-th of them is the point's descriptor with j bits flipped.  Returns dict(cam_pos, uv (NaN: none by construction), desc, kp_xy, kp_desc,
+    kp_owner, index: name -> point)."""
+    f = np.float32
+    rng = np.random.default_rng(seed)
+    e = f(0.125)
+    x0, y0, x1, y1 = (f(v) for v in grid[:4])
+    cu, cv = f(np.round((x0 + x1) / 2 * 8) / 8), f(np.round((y0 + y1) / 2 * 8) / 8)
+    us = [("min-", f(x0 - e)), ("min", x0), ("min+", f(x0 + e)), ("max-", f(x1 - e)), ("max", x1), ("max+", f(x1 + e)), ("mid", cu)]
+    vs = [("min-", f(y0 - e)), ("min", y0), ("min+", f(y0 + e)), ("max-", f(y1 - e)), ("max", y1), ("max+", f(y1 + e)), ("mid", cv)]
+    pts, index = [], {}
+    for nu, u in us:
+        for nv, v in vs:
+            index["u%s,v%s" % (nu, nv)] = len(pts)
+            pts.append((u, v, f(1)))
+    for nu, u in us:
+        index["u%s,vmid,z2" % nu] = len(pts)
+        pts.append((u, cv, f(2)))
+    for nv, v in vs:
+        index["umid,v%s,z2" % nv] = len(pts)
+        pts.append((cu, v, f(2)))
+    index["origin"] = len(pts)
+    pts.append((f(0), f(0), f(1)))
+    n_regular = len(pts)
+    uv = np.array([(u, v) for u, v, _ in pts], np.float32)
+    z = np.array([p[2] for p in pts], np.float32)
+    cam = np.stack([uv[:, 0] * z / f(512), uv[:, 1] * z / f(512), z], 1).astype(np.float32)
+    for form2 in (False, True):   # the construction holds: every projection form gives exactly the intended pixel
+        if form2:
+            invz = f(1) / cam[:, 2]
+            pu, pv = BOUNDS_K[0] * (cam[:, 0] * invz) + BOUNDS_K[2], BOUNDS_K[1] * (cam[:, 1] * invz) + BOUNDS_K[3]
+        else:
+            pu, pv = BOUNDS_K[0] * cam[:, 0] / cam[:, 2] + BOUNDS_K[2], BOUNDS_K[1] * cam[:, 1] / cam[:, 2] + BOUNDS_K[3]
+        assert pu.dtype == np.float32 and np.array_equal(pu, uv[:, 0]) and np.array_equal(pv, uv[:, 1])
+    sub = f(1e-40)
+    assert sub > 0 and sub < np.finfo(np.float32).tiny
+    odd = []
+    for zz in (f(0.0), f(-0.0), sub, f(-sub), f(-1)):
+        for xx in (f(0), f(0.25)):
+            odd.append((xx, f(0), zz))
+    nan, inf = f(np.nan), f(np.inf)
+    odd += [(nan, f(0), f(1)), (f(0), nan, f(1)), (f(0), f(0), nan), (inf, f(0), f(1)), (f(0), f(-inf), f(1)), (f(0), f(0), inf),
+            (nan, nan, nan)]
+    cam = np.concatenate([cam, np.array(odd, np.float32)])
+    uv = np.concatenate([uv, np.full((len(odd), 2), np.nan, np.float32)])
+    desc = rng.integers(0, 256, (len(cam), 32), dtype=np.uint8)
+    for k in range(len(odd)):       # were one of them searched near the principal point, it would find that point's features
+        desc[n_regular + k] = desc[index["origin"]]
+        desc[n_regular + k, 31] ^= np.uint8(1 << (k % 8))
+    r = f(radius)
+    a = f(r - e)
+    # (the diagonal ones: near the upper corner every other feature rounds to grid column 64 or row 48, i.e. lies outside the grid)
+    offs = [(f(0), f(0)), (a, f(0)), (f(-a), f(0)), (f(0), a), (f(0), f(-a)), (r, f(0)), (f(-r), f(0)), (f(0), r), (f(0), f(-r)), (f(-a), f(-a)), (a, a)]
+    kp_xy, kp_desc, owner = [], [], []
+    for i in range(n_regular):
+        for j, (dx, dy) in enumerate(offs):
+            kp_xy.append((f(uv[i, 0] + dx), f(uv[i, 1] + dy)))
+            d = desc[i].copy()
+            for b in range(j):
+                d[b // 8] ^= np.uint8(1 << (b % 8))
+            kp_desc.append(d)
+            owner.append(i)
+    return dict(cam_pos=cam, uv=uv, n_regular=n_regular, desc=desc, kp_xy=np.array(kp_xy, np.float32), kp_desc=np.array(kp_desc, np.uint8),
+                kp_owner=np.array(owner, np.int32), index=index)
+
+
+# (search, radius of its windows at level 0): th and the rest as in bounds_search
+BOUNDS_SEARCHES = (("projection", 7.0), ("projection_keyframe", 10.0), ("fuse", 2.0), ("project_search_form0", 4.0),
+                   ("project_search_form1", 7.5), ("projection_sim3_form0", 8.0), ("projection_sim3_form2", 3.0), ("local_points", 5.0),
+                   ("initialization", 6.0))
+IS_IN_IMAGE_SEARCHES = ("fuse", "project_search_form0", "project_search_form1", "projection_sim3_form0", "projection_sim3_form2")
+
+
+def bounds_search(name, grid, radius, seed=7):
+    """(case, oracle, run, matched): the input of search `name` on make_bounds_points, oracle() -> tuple of result arrays,
+    run(lib) -> the same from the library, matched(results) -> bool per point."""
+    f = np.float32
+    B = make_bounds_points(grid, radius, seed)
+    n1, n2 = len(B["cam_pos"]), len(B["kp_xy"])
+    sf = (1.2 ** np.arange(8)).astype(np.float32)
+    lsf = f(np.log(f(1.2)))
+    q, t = np.array([0, 0, 0, 1], np.float32), np.zeros(3, np.float32)
+    feat = dict(kp2_xy=B["kp_xy"], kp2_octave=np.zeros(n2, np.int32), kp2_angle=np.zeros(n2, np.float32), uright2=np.full(n2, -1, np.float32),
+                desc2=B["kp_desc"], grid=np.asarray(grid, np.float32), K=BOUNDS_K, scale_factors=sf)
+    obs = (np.arange(n1) % 3 != 0).astype(np.uint8)
+    by_feature = lambda res: np.isin(np.arange(n1), res[0][res[0] >= 0])
+    by_point = lambda res: res[0] >= 0
+    # distances: level 0 is predicted from max_dist just below the distance, for the degenerate points with a finite nonzero
+    # distance too (all features are of octave 0: a point predicted higher could never match); a zero, infinite or NaN distance
+    # gets a range that takes anything.  Normals along the ray: the viewing-angle test passes wherever it can be evaluated.
+    with np.errstate(all="ignore"):
+        dist = np.sqrt((B["cam_pos"].astype(np.float64) ** 2).sum(1))
+    regular = np.isfinite(dist) & (dist > 1e-30)
+    safe = np.where(regular, dist, 1.0)
+    max_d = np.where(regular, safe * 0.999, 1e30).astype(np.float32)
+    min_d = np.where(regular, safe * 0.5, 0).astype(np.float32)
+    with np.errstate(all="ignore"):
+        normal = np.where(regular[:, None], B["cam_pos"] / safe[:, None], [0, 0, 1]).astype(np.float32)
+
+    def with_matcher(ratio, ori, call):
+        def run(lib):
+            mt = F.ORBmatcher(ratio, ori, lib=lib)
+            try:
+                return call(mt)
+            finally:
+                mt.close()
+        return run
+    if name == "projection":
+        case = dict(feat, valid1=np.ones(n1, np.uint8), world_pos1=B["cam_pos"], mp_desc1=B["desc"], mp_observed1=obs, octave1=np.zeros(n1, np.int32),
+                    angle1=np.zeros(n1, np.float32), Tcw_q=q, Tcw_t=t, Tlw_q=q, Tlw_t=t, mb=0.5, mbf=256.0)
+        return (case, lambda: (O.search_by_projection(case, radius, False, True)[0],),
+                with_matcher(0.9, True, lambda mt: (mt.SearchByProjection(case, radius, False)[0],)), by_feature)
+    if name == "projection_keyframe":
+        case = dict(feat, has_mp1=np.ones(n1, np.uint8), bad1=np.zeros(n1, np.uint8), found1=np.zeros(n1, np.uint8), world_pos1=B["cam_pos"],
+                    mp_desc1=B["desc"], min_dist1=min_d, max_dist1=max_d, angle1=np.zeros(n1, np.float32), occupied2=np.zeros(n2, np.uint8),
+                    Tcw_q=q, Tcw_t=t, log_scale_factor=lsf)
+        with np.errstate(all="ignore"):
+            valid, level = relocalization_prepass(case)
+        ovalid, olevel = O.kf_projection_prepass(case)
+        assert np.array_equal(valid, ovalid) and np.array_equal(level[valid != 0], olevel[valid != 0]), "bounds case: relocalisation prepass"
+        assert valid[:B["n_regular"]].all() and not level[:B["n_regular"]].any()
+        full = dict(case, valid1=valid, level1=level)
+        return (case, lambda: (O.search_by_projection_kf(case, radius, 100, True)[0],),
+                with_matcher(0.9, True, lambda mt: (mt.SearchByProjectionKeyFrame(full, radius, 100)[0],)), by_feature)
+    if name == "fuse":
+        case = dict(feat, has_mp1=np.ones(n1, np.uint8), bad1=np.zeros(n1, np.uint8), in_kf1=np.zeros(n1, np.uint8), world_pos1=B["cam_pos"],
+                    normal1=normal, mp_desc1=B["desc"], min_dist1=min_d, max_dist1=max_d, Tcw_q=q, Tcw_t=t, Ow=t, bf=f(256.0),
+                    inv_level_sigma2=(f(1) / (sf * sf).astype(np.float32)).astype(np.float32), log_scale_factor=lsf)
+        with np.errstate(all="ignore"):
+            valid, level = fuse_prepass(case)
+        ovalid, olevel = O.fuse_prepass(case)
+        assert np.array_equal(valid, ovalid) and np.array_equal(level[valid != 0], olevel[valid != 0]), "bounds case: fuse prepass"
+        assert valid[:B["n_regular"]].all() and not level[:B["n_regular"]].any()
+        full = dict(case, valid1=valid, level1=level)
+        return (case, lambda: (O.fuse_search(case, radius)[0],), with_matcher(0.6, True, lambda mt: (mt.FuseSearch(full, radius)[0],)), by_point)
+    if name.startswith("project_search") or name.startswith("projection_sim3"):
+        form = int(name[-1])
+        case = dict(feat, valid1=np.ones(n1, np.uint8), cam_pos1=B["cam_pos"], mp_desc1=B["desc"], level1=np.zeros(n1, np.int32))
+        if name.startswith("project_search"):
+            maxd = 50 if form == 0 else 100
+            return (case, lambda: tuple(O.project_search(case, radius, form, maxd)),
+                    with_matcher(0.75, True, lambda mt: tuple(mt.ProjectSearch(case, radius, form, maxd))), by_point)
+        matched2 = (np.arange(n2) % 11 == 5).astype(np.uint8)
+        return (case, lambda: (O.search_by_projection_sim3(case, matched2, radius, form, 75)[0],),
+                with_matcher(0.75, True, lambda mt: (mt.SearchByProjectionSim3(case, matched2, radius, form, 75)[0],)), by_feature)
+    if name == "local_points":
+        # r = 2.5 th (mTrackViewCos > 0.998) resp. 4 th: th so that the radius is `radius` either way
+        cos = np.where(np.arange(n1) % 2 == 0, 0.9995, 0.9).astype(np.float32)
+        proj = np.concatenate([B["uv"], B["uv"][:, :1]], 1).astype(np.float32)
+        k = B["n_regular"]
+        proj[k:k + 6] = [[np.nan, 0, 0], [0, np.nan, 0], [np.inf, 0, 0], [0, -np.inf, 0], [np.nan, np.nan, np.nan], [-np.inf, np.inf, 0]]
+        proj[k + 6:] = 0      # the rest sit at the principal point, behind the regular point there
+        res = []
+        for part, th in ((cos > 0.998, radius / 2.5), (cos <= 0.998, radius / 4.0)):
+            case = dict(feat, valid1=part.astype(np.uint8), proj1=proj, level1=np.zeros(n1, np.int32), view_cos1=cos, mp_desc1=B["desc"],
+                        mp_observed1=obs, blocked2=(np.arange(n2) % 13 == 3).astype(np.uint8))
+            res.append((case, th))
+        return (res, lambda: tuple(O.search_local_points(c, th, 0.8)[0] for c, th in res),
+                with_matcher(0.8, True, lambda mt: tuple(mt.SearchLocalPoints(c, th)[0] for c, th in res)),
+                lambda r: np.isin(np.arange(n1), np.concatenate([r[0][r[0] >= 0], r[1][r[1] >= 0]])))
+    assert name == "initialization"
+    # no bounds test in this search: the windows around the regular projections hang over every border, and some lie wholly outside
+    w = int(radius)
+    gx0, gy0, gx1, gy1 = (f(v) for v in grid[:4])
+    prev = B["uv"].copy()
+    k = B["n_regular"]
+    far = [[gx0 - 3 * w, gy0], [gx1 + w + 1, gy1], [gx0, gy1 + 2 * w], [gx0 - w, gy0 - w], [gx1 + w, gy1 + w], [gx0 - w + f(0.125), gy0],
+           [np.nan, 0], [0, np.inf], [-np.inf, 0], [f(-500), f(-500)]]
+    prev[k:k + len(far)] = np.array(far, np.float32)
+    prev[k + len(far):] = 0
+    case = dict(kp1_octave=np.zeros(n1, np.int32), kp1_angle=np.zeros(n1, np.float32), desc1=B["desc"], prev_matched=prev, kp2_xy=B["kp_xy"],
+                kp2_octave=feat["kp2_octave"], kp2_angle=feat["kp2_angle"], desc2=B["kp_desc"], grid=feat["grid"])
+
+    def oracle():
+        m, p, _ = O.search_for_initialization(case, w, 0.9, True)
+        return m, p.view(np.uint32)
+
+    def call(mt):
+        m, p, _ = mt.SearchForInitialization(case, w)
+        return m, p.view(np.uint32)
+    return case, oracle, with_matcher(0.9, True, call), by_point
+
+
+def check_grid_search_bounds(lib, grid=POW2_GRID, searches=None):
+    """Every search of BOUNDS_SEARCHES on the bounds points for `grid`: the library (lib is not None) against the oracle, and on
+    the oracle's result what the reference's source says about the bounds: the frame-to-frame overloads (ORBmatcher.cc:1715-1718,
+    1918-1921: u < mnMinX || u > mnMaxX skips) search a point ON the upper bound, KeyFrame::IsInImage (KeyFrame.cc:750-753:
+    x >= mnMinX && x < mnMaxX) does not; everybody searches one on the lower bound, nobody one an eighth of a pixel outside."""
+    found = {}
+    for name, radius in BOUNDS_SEARCHES:
+        if searches is not None and name not in searches:
+            continue
+        case, oracle, run, matched = bounds_search(name, grid, radius)
+        want = oracle()
+        if lib is not None:
+            got = run(lib)
+            assert len(got) == len(want)
+            for k, (g, w) in enumerate(zip(got, want)):
+                assert np.array_equal(g, w), "bounds case, %s: result %d differs from the oracle's" % (name, k)
+        B = make_bounds_points(grid, radius)
+        ix, m = B["index"], matched(want)
+        found[name] = int(m.sum())
+        # can a window at the upper bound reach a feature that has a cell?  (the nearest one inside is radius - 1/8 away)
+        reach = all(radius - 0.125 > 0.5 / float(grid[k]) + 0.125 for k in (4, 5))
+        if name in ("local_points", "initialization"):     # no in-image test of their own
+            assert m[ix["umid,vmid"]] and m[ix["umin,vmid"]] and m[ix["umid,vmin"]], name
+            assert not reach or (m[ix["umax,vmid"]] and m[ix["umid,vmax"]]), name
+            continue
+        inclusive = name not in IS_IN_IMAGE_SEARCHES
+        for axis in ("u%s,vmid", "umid,v%s", "u%s,vmid,z2", "umid,v%s,z2"):
+            at = lambda s: m[ix[axis % s]]
+            assert not at("min-") and not at("max+"), "%s searched a point outside the bounds (%s)" % (name, axis)
+            assert at("min") and at("min+") and at("mid"), "%s lost a point inside the bounds (%s)" % (name, axis)
+            assert inclusive or not at("max"), "%s: a point on the upper bound is searched (%s)" % (name, axis)
+            if reach:
+                assert at("max-"), "%s lost a point inside the bounds (%s)" % (name, axis)
+                assert at("max") == inclusive, "%s: a point on the upper bound is %ssearched (%s)" % (name, "" if at("max") else "not ", axis)
+        assert m[ix["umin,vmin"]] and not m[ix["umax+,vmax+"]] and not m[ix["umin-,vmin-"]] and (inclusive or not m[ix["umax,vmax"]]), name
+        # (the corner's only feature with a cell is the diagonal one; Fuse's chi-square gate, 5.99 at level 0, cuts that one off)
+        if reach and not (name == "fuse" and 2 * (radius - 0.125) ** 2 > 5.99):
+            assert m[ix["umax-,vmax-"]] and m[ix["umax,vmax"]] == inclusive, name
+        assert reach or grid is not POW2_GRID
+        # (0, 0, -1) projects onto the principal point, where features are: only the key-frame overload, which has no depth
+        # test (ORBmatcher.cc:1908-1937), searches it; (0.25, 0, -1) projects outside the bounds
+        k = B["n_regular"]
+        assert m[k + 8] == (name == "projection_keyframe"), "%s and the point behind the camera" % name
+        assert not m[k + 9], name
+    return found

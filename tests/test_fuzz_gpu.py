@@ -10,8 +10,9 @@ import pytest
 import fuzz_cases
 
 SEEDS = {"extractor": (1, 2, 3, 4), "low_contrast": (11, 12), "depth": (21, 22, 23, 24), "hamming": (31, 32, 33, 34),
-         "greedy_search": (41, 42, 43, 44, 45, 46), "node_search": (51, 52, 53, 54), "stereo": (61, 62, 63, 66)}
-PER_SEED = {"extractor": 3, "low_contrast": 2, "depth": 3, "hamming": 4, "greedy_search": 4, "node_search": 4, "stereo": 2}
+         "greedy_search": (41, 42, 43, 44, 45, 46), "node_search": (51, 52, 53, 54), "stereo": (61, 62, 63, 66),
+         "point_search": (70, 74, 82, 89)}   # between them: every search of the kind, 8300 on either side
+PER_SEED = {"extractor": 3, "low_contrast": 2, "depth": 3, "hamming": 4, "greedy_search": 4, "node_search": 4, "stereo": 2, "point_search": 4}
 # this seed's first pair has 6007 x 6004 keypoints: the tile loop of k_stereo_match and the tail of k_stereo_filter on real keypoints
 STEREO_BEYOND_ONE_TILE = 63
 
