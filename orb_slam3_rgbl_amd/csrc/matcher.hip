@@ -341,7 +341,69 @@ __device__ __forceinline__ void bf_track_rel_f(float& best, float& second, float
 #endif
 }
 
-__global__ __launch_bounds__(256) void k_hamming_fp4(const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_rows,
+// The scheduling directives of bf_tile_f4 (LLVM SchedGroupMask: VALU 0x2, MFMA 0x8, DS read 0x100); the emulator has no scheduler.
+#ifdef RGBL_EMU
+#define BF_SCHED_FENCE() ((void)0)
+#define BF_SCHED_GROUP(mask, n, id) ((void)0)
+#define BF_PIN(best, second) ((void)0)
+#else
+#define BF_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+#define BF_SCHED_GROUP(mask, n, id) __builtin_amdgcn_sched_group_barrier(mask, n, id)
+// the tracking instructions have no side effects, so nothing orders them against a fence until their values pass through a
+// statement that has some: an empty one on the running pair (never on an accumulator: see bf_track_rel_f)
+#define BF_PIN(best, second) asm volatile("" : "+v"(best), "+v"(second))
+#endif
+constexpr int kBfScaleF4 = 131;  // E8M0: 2^(131 - 127) = 16 per operand
+__device__ __forceinline__ v16f bf_mfma_f4(const v4i& a, const v8i& b, const v16f& c) {
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(v8i{a[0], a[1], a[2], a[3], 0, 0, 0, 0}, b, c, 4, 4, 0, kBfScaleF4, 0, kBfScaleF4);
+}
+// One tile of 32 train rows (fragments a[0..3]) against the wave's two query tiles, as a two-phase software pipeline: a wave is
+// in-order, so its tracking only runs beside its matrix instructions if it stands between them in the instruction stream.
+//   phase A: the four MFMAs of acc0 (queries 0 - 31) for this tile, between them the tracking of acc1 of the PREVIOUS tile;
+//   phase B: the four MFMAs of acc1 (queries 32 - 63) for this tile, between them the tracking of acc0 of this tile.
+// acc1 therefore leaves a tile untracked (the caller keeps it, across stage barriers too, and drains it at the end of a sweep and
+// of the scan).  Each running pair is lowered by 32 once per tile, right before that tile's values meet it.  Only full tiles
+// come here: the partial last stage of a train set is scanned behind the stage loop, where its mask is.
+// kPrefetch: every fragment register is reloaded from frag_next (the next tile of the stage) behind its last MFMA.
+// Fences keep the phases apart, the groups pin MFMA / 8 tracking instructions / MFMA ... inside a phase.  Neither accumulator
+// set is ever copied: acc1 is dead when phase B's first MFMA writes it, acc0 when the next tile's phase A does.
+template <bool kPrefetch>
+__device__ __forceinline__ void bf_tile_f4(const uint8_t* frag_next, v4i (&a)[4], const v8i (&bq)[2][4], const v16f& c_init, v16f& acc0, v16f& acc1,
+                                           float (&best)[2], float (&second)[2], float neg_inf) {
+  best[1] -= 32.f; second[1] -= 32.f;
+  BF_PIN(best[1], second[1]);
+  BF_SCHED_FENCE();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    acc0 = bf_mfma_f4(a[s], bq[0][s], s == 0 ? c_init : acc0);
+#pragma unroll
+    for (int r = 4 * s; r < 4 * s + 4; ++r) bf_track_rel_f(best[1], second[1], acc1[r], neg_inf);
+  }
+#pragma unroll
+  for (int s = 0; s < 4; ++s) { BF_SCHED_GROUP(0x008, 1, 1); BF_SCHED_GROUP(0x002, 8, 1); }
+  BF_PIN(best[1], second[1]);
+  BF_SCHED_FENCE();
+  best[0] -= 32.f; second[0] -= 32.f;
+  BF_PIN(best[0], second[0]);
+  BF_SCHED_FENCE();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    acc1 = bf_mfma_f4(a[s], bq[1][s], s == 0 ? c_init : acc1);
+    if (kPrefetch) a[s] = *reinterpret_cast<const v4i*>(frag_next + s * 32);
+#pragma unroll
+    for (int r = 4 * s; r < 4 * s + 4; ++r) bf_track_rel_f(best[0], second[0], acc0[r], neg_inf);
+  }
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    BF_SCHED_GROUP(0x008, 1, 2);
+    if (kPrefetch) BF_SCHED_GROUP(0x100, 1, 2);
+    BF_SCHED_GROUP(0x002, 8, 2);
+  }
+  BF_PIN(best[0], second[0]);
+  BF_SCHED_FENCE();
+}
+
+__global__ __launch_bounds__(256, 4) void k_hamming_fp4(const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_rows,
                                                      int cap, const int32_t* __restrict__ pair_a,
                                                      const int32_t* __restrict__ pair_b, int32_t* __restrict__ best_idx,
                                                      int32_t* __restrict__ best_dist, int32_t* __restrict__ second_dist,
@@ -361,7 +423,6 @@ __global__ __launch_bounds__(256) void k_hamming_fp4(const uint8_t* __restrict__
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
   const int col = lane & 31, half = lane >> 5;
   const bool wave_has_queries = q_base + wave * 64 < na;
-  constexpr int kScale = 131;  // E8M0: 2^(131 - 127) = 16 per operand
   s_lut[tid] = (uint32_t)bf_expand_fp4((uint32_t)tid)[0];  // the first barrier of the stage loop publishes it
 
   // query fragments: two 32-column tiles, four K steps each
@@ -417,6 +478,19 @@ __global__ __launch_bounds__(256) void k_hamming_fp4(const uint8_t* __restrict__
     }
     tiles_in_sweep = 0;
   };
+  // acc1 is the pending tile of bf_tile_f4: it lives across tiles and stage barriers; before the first tile of a sweep it holds
+  // idle keys, which the tracker ignores (the pair is lowered once more than it has tiles then, while it holds nothing but idle).
+  v16f acc0, acc1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc1[r] = kBfIdleF;
+  auto drain = [&]() {  // track the pending tile on its own (end of a sweep, end of the full stages): phase A without MFMAs
+    best[1] -= 32.f; second[1] -= 32.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bf_track_rel_f(best[1], second[1], acc1[r], neg_inf);
+  };
+  constexpr int kTiles = kBfStageRowsF4 / 32;
+  const uint8_t* tail = nullptr;
+  static_assert(kBfSweep % kBfStageRowsF4 == 0, "a sweep closes at the end of a stage");
   for (int stage = s_begin; stage < n_stages; ++stage) {
     uint8_t* buf = s_rows[stage & 1];
     uint32_t x[kBfStageLoadsF4];
@@ -434,36 +508,59 @@ __global__ __launch_bounds__(256) void k_hamming_fp4(const uint8_t* __restrict__
     }
     __syncthreads();
     if (!wave_has_queries) continue;
-#pragma unroll 1
-    for (int rt = 0; rt < kBfStageRowsF4 / 32; ++rt) {
-      const int row0 = stage * kBfStageRowsF4 + rt * 32;  // first train row of the tile
-      if (row0 >= nb) break;
-      const uint8_t* frag = buf + (rt * 32 + col) * kBfRowBytesF4 + half * 16;
-      v16f acc0 = c_init, acc1 = c_init;
+    const int row_s = stage * kBfStageRowsF4;  // first train row of the stage
+    const uint8_t* frag = buf + col * kBfRowBytesF4 + half * 16;
+    v4i a[4];
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const v4i a4 = *reinterpret_cast<const v4i*>(frag + s * 32);
-        const v8i a = v8i{a4[0], a4[1], a4[2], a4[3], 0, 0, 0, 0};
-        acc0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, bq[0][s], acc0, 4, 4, 0, kScale, 0, kScale);
-        acc1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, bq[1][s], acc1, 4, 4, 0, kScale, 0, kScale);
-      }
-      best[0] -= 32.f; second[0] -= 32.f; best[1] -= 32.f; second[1] -= 32.f;
-      ++tiles_in_sweep;
-      if (row0 + 32 <= nb) {
+    for (int s = 0; s < 4; ++s) {  // in the order the MFMAs take them (the fences keep it), so that the first waits for one read only
+      a[s] = *reinterpret_cast<const v4i*>(frag + s * 32);
+      BF_SCHED_FENCE();
+    }
+    // The partial stage of a train set goes behind the loop.  Leaving a loop that holds a barrier is safe here because a partial
+    // stage is always the last one this launch scans: row_s + kBfStageRowsF4 > nb means stage == all_stages - 1, and n_stages <=
+    // all_stages, so stage == n_stages - 1 and the waves without queries (which `continue` above) meet no further barrier either.
+    if (row_s + kBfStageRowsF4 > nb) { tail = buf; break; }
+    // straight-line tiles, each requests the fragments of the next
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { bf_track_rel_f(best[0], second[0], acc0[r], neg_inf); bf_track_rel_f(best[1], second[1], acc1[r], neg_inf); }
-      } else {  // the last tile of the train set: rows beyond it never win
+    for (int rt = 0; rt < kTiles; ++rt) {
+      if (rt + 1 < kTiles) bf_tile_f4<true>(frag + (rt + 1) * 32 * kBfRowBytesF4, a, bq, c_init, acc0, acc1, best, second, neg_inf);
+      else bf_tile_f4<false>(frag, a, bq, c_init, acc0, acc1, best, second, neg_inf);
+    }
+    tiles_in_sweep += kTiles;
+    if (tiles_in_sweep == kBfSweep / 32) {
+      drain();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const bool live = row0 + (r & 3) + 8 * (r >> 2) + 4 * half < nb;
-          bf_track_rel_f(best[0], second[0], live ? acc0[r] : kBfIdleF, neg_inf);
-          bf_track_rel_f(best[1], second[1], live ? acc1[r] : kBfIdleF, neg_inf);
-        }
-      }
-      if (row0 + 32 - sweep_start == kBfSweep) { close_sweep(sweep_start); sweep_start = row0 + 32; }
+      for (int r = 0; r < 16; ++r) acc1[r] = kBfIdleF;
+      close_sweep(sweep_start);
+      sweep_start = row_s + kBfStageRowsF4;
     }
   }
   if (!wave_has_queries) return;
+  if (tiles_in_sweep > 0) drain();
+  if (tail) {
+    // at most kTiles tiles, the last one masked (rows beyond the train set never win): no barrier follows, nothing is left pending,
+    // so they are tracked where they are computed, with accumulators of their own.  `tail` was set in stage n_stages - 1 (see the
+    // break above), hence the first row below.
+#pragma unroll 1
+    for (int row0 = (n_stages - 1) * kBfStageRowsF4; row0 < nb; row0 += 32, tail += 32 * kBfRowBytesF4) {
+      const uint8_t* frag = tail + col * kBfRowBytesF4 + half * 16;
+      v16f t0 = c_init, t1 = c_init;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const v4i a = *reinterpret_cast<const v4i*>(frag + s * 32);
+        t0 = bf_mfma_f4(a, bq[0][s], t0);
+        t1 = bf_mfma_f4(a, bq[1][s], t1);
+      }
+      best[0] -= 32.f; second[0] -= 32.f; best[1] -= 32.f; second[1] -= 32.f;
+      ++tiles_in_sweep;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bool live = row0 + (r & 3) + 8 * (r >> 2) + 4 * half < nb;
+        bf_track_rel_f(best[0], second[0], live ? t0[r] : kBfIdleF, neg_inf);
+        bf_track_rel_f(best[1], second[1], live ? t1[r] : kBfIdleF, neg_inf);
+      }
+    }
+  }
   if (tiles_in_sweep > 0) close_sweep(sweep_start);
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct) {
