@@ -573,6 +573,75 @@ typedef struct {
 int rgbl_search_triangulation(rgbl_matcher* h, const rgbl_keyframe_view* kf1,
                               const rgbl_keyframe_view* kf2, const rgbl_triangulation_params* prm,
                               int32_t* matches12, int* out_nmatches);
+
+/* void LocalMapping::CreateNewMapPoints() (include/LocalMapping.h, src/LocalMapping.cc:388-712) from its neighbour loop on
+ * (:434-711), without the `new MapPoint` / AddObservation / Atlas part (:694-709), which stays with the caller.  Single-camera
+ * pinhole key frames (mpCamera2 == nullptr, NLeft == -1; the rig branches :505-555 have no form here).
+ * A key frame as the loop reads it: the view of rgbl_search_triangulation plus the per-match block's inputs (:481-691,
+ * GeometricTools::Triangulate src/GeometricTools.cc:47-66, KeyFrame::UnprojectStereo src/KeyFrame.cc:755-772). */
+typedef struct {
+  rgbl_keyframe_view view;
+  const float* depth;          /* mvDepth, n (host pointer also with a resident frame) */
+  const float* kp_xy_raw;      /* mvKeys[i].pt, n x 2, what UnprojectStereo reads; NULL: the view's kp_xy (no distortion) */
+  float Tcw[12];               /* GetPose().matrix3x4(), row-major; mRwc is taken as its rotation transposed */
+  float Ow[3];                 /* GetCameraCenter() = mTwc.translation() */
+  float K[4];                  /* fx, fy, cx, cy */
+  float mb, mbf;
+  const float* scale_factors;  /* mvScaleFactors, n_levels of the params */
+  const float* level_sigma2;   /* mvLevelSigma2 */
+} rgbl_new_points_keyframe;
+
+typedef struct {
+  int n_levels;
+  float ratio_factor;          /* 1.5f * mpCurrentKeyFrame->mfScaleFactor (:428) */
+  int far_points;              /* mbFarPoints */
+  float th_far_points;         /* mThFarPoints */
+  int inertial;                /* mbInertial: 0.9996 instead of 0.9998 (:583) */
+  int monocular;               /* mbMonocular: no baseline test inside the call (:448-460), skip[] carries the median-depth one */
+  int report_rejected;         /* 1: a record for every match, whatever its status; 0: accepted ones (status 1 - 3) only */
+} rgbl_new_points_params;
+
+/* status: 0 no match, 1 accepted triangulated, 2 / 3 accepted stereo point of key frame 1 / 2, 4 low parallax and no stereo
+ * (:601-604), 5 w == 0, 6 UnprojectStereo false, 7 z1 <= 0, 8 z2 <= 0, 9 / 10 reprojection in key frame 1 / 2, 11 dist == 0,
+ * 12 far point, 13 scale consistency.  x3D is zero for 4 - 6. */
+typedef struct {
+  int32_t neighbour, idx1, idx2;
+  float x3D[3];
+  uint8_t status;
+  uint8_t reserved[3];         /* 0 */
+} rgbl_new_point;
+
+/* The per-match block (:481-691) on explicit pairs (idx1[i] of kf1, idx2[i] of kf2): one record per pair, in pair order,
+ * neighbour = 0.  The views' FeatureVectors and descriptors are not read.  Host pointers, synchronous. */
+int rgbl_triangulate_matches(rgbl_matcher* h, const rgbl_new_points_keyframe* kf1, const rgbl_new_points_keyframe* kf2,
+                             const rgbl_new_points_params* prm, int n_pairs, const int32_t* idx1, const int32_t* idx2,
+                             rgbl_new_point* out);
+/* The loop :434-711 in one call: per neighbour kf2[i] the search (tri_prm[i]: F12, epipole, coarse, pKF2's tables;
+ * only_stereo as given; check_orientation must be 0 as LocalMapping.cc:412 has it, else RGBL_ERR_INVALID - the rotation
+ * histogram would be a host pass in the middle of the chain) and the per-match block, chained on the matcher's stream: an
+ * accepted match gives kf1's feature a map point (:701) that the next neighbour's search skips.  One upload, one read-back.
+ * skip (nullable): skip[i] != 0 leaves neighbour i out (the caller's monocular median-depth test, :455-459); with
+ * monocular == 0 a neighbour with |Ow2 - Ow1| < kf2[i].mb is left out as well (:444-451).  matches_per_neighbour[i]
+ * (nullable): -1 for a neighbour left out, else what SearchForTriangulation returned.
+ * out: the records in the reference's order (neighbour, then ascending idx1), *n_out of them.  With report_rejected == 0 there
+ * is at most one per feature of kf1 without a map point, so cap = kf1->view.n always suffices; more than cap records:
+ * RGBL_ERR_CAPACITY with *n_out set, out and has_mappoint1_out untouched.  Every argument error is reported before anything
+ * is launched and leaves all outputs untouched.  The read-back carries cap records whatever *n_out turns out to be (56 KB at
+ * cap = 2000): a caller who knows a smaller bound shortens it.
+ * has_mappoint1_out (nullable, n entries, may be kf1->view.has_mappoint itself): the mask after the call.
+ * The `CheckNewKeyFrames()` poll between two neighbours (:436) has no device form: a caller who wants it splits the neighbours
+ * over several calls and passes has_mappoint1_out on as the next call's kf1->view.has_mappoint.
+ * Host pointers, synchronous. */
+int rgbl_create_new_map_points(rgbl_matcher* h, const rgbl_new_points_keyframe* kf1, int n_neigh,
+                               const rgbl_new_points_keyframe* kf2, const rgbl_triangulation_params* tri_prm,
+                               const uint8_t* skip, const rgbl_new_points_params* prm, rgbl_new_point* out, int cap, int* n_out,
+                               int32_t* matches_per_neighbour, uint8_t* has_mappoint1_out);
+/* rgbl_triangulate_matches evaluated by the HOST build of csrc/newpoint_math.h (no device, no handle): what the tests compose
+ * with the oracle's SearchForTriangulation into the restatement the device is compared with.  The views' resident frames are
+ * not read: kp_xy, kp_octave and uright must be host arrays. */
+int rgbl_triangulate_matches_host(const rgbl_new_points_keyframe* kf1, const rgbl_new_points_keyframe* kf2,
+                                  const rgbl_new_points_params* prm, int n_pairs, const int32_t* idx1, const int32_t* idx2,
+                                  rgbl_new_point* out);
 /* int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, std::vector<MapPoint*>& vpMapPointMatches) (include/ORBmatcher.h:57,
  * src/ORBmatcher.cc:223-425; callers Tracking::TrackReferenceKeyFrame, src/Tracking.cc:2798-2810, and Relocalization).
  * Single-camera frames.  kf: the key-frame (has_mappoint = GetMapPointMatches()[i] != NULL && !isBad(), kp_angle =

@@ -53,6 +53,23 @@ class TriangulationParams(C.Structure):
                 ("coarse", C.c_int), ("check_orientation", C.c_int)]
 
 
+class NewPointsKeyframe(C.Structure):
+    """rgbl_new_points_keyframe (a key frame as LocalMapping::CreateNewMapPoints reads it)."""
+    _fields_ = [("view", KeyframeView), ("depth", C.c_void_p), ("kp_xy_raw", C.c_void_p), ("Tcw", C.c_float * 12),
+                ("Ow", C.c_float * 3), ("K", C.c_float * 4), ("mb", C.c_float), ("mbf", C.c_float),
+                ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p)]
+
+
+class NewPointsParams(C.Structure):
+    _fields_ = [("n_levels", C.c_int), ("ratio_factor", C.c_float), ("far_points", C.c_int), ("th_far_points", C.c_float),
+                ("inertial", C.c_int), ("monocular", C.c_int), ("report_rejected", C.c_int)]
+
+
+# rgbl_new_point
+NEW_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("x3D", "<f4", (3,)), ("status", "u1"),
+                            ("reserved", "u1", (3,))])
+
+
 class ProjectionInput(C.Structure):
     """rgbl_projection_input (ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) as flat arrays)."""
     _fields_ = [("n1", C.c_int), ("valid1", C.c_void_p), ("world_pos1", C.c_void_p), ("mp_desc1", C.c_void_p),
@@ -276,6 +293,12 @@ SYMBOLS = {
     "rgbl_hamming_bf_batch_device": (_I, [_V, _V, _V, _I, _V, _V, _I, _V, _V, _V]),
     "rgbl_search_triangulation": (_I, [_V, C.POINTER(KeyframeView), C.POINTER(KeyframeView),
                                        C.POINTER(TriangulationParams), _V, C.POINTER(_I)]),
+    "rgbl_triangulate_matches": (_I, [_V, C.POINTER(NewPointsKeyframe), C.POINTER(NewPointsKeyframe), C.POINTER(NewPointsParams),
+                                      _I, _V, _V, _V]),
+    "rgbl_triangulate_matches_host": (_I, [C.POINTER(NewPointsKeyframe), C.POINTER(NewPointsKeyframe), C.POINTER(NewPointsParams),
+                                           _I, _V, _V, _V]),
+    "rgbl_create_new_map_points": (_I, [_V, C.POINTER(NewPointsKeyframe), _I, _V, _V, _V, C.POINTER(NewPointsParams), _V, _I,
+                                        C.POINTER(_I), _V, _V]),
     "rgbl_search_by_bow": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_rig": (_I, [_V, _V, _V, _I, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_keyframes": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),

@@ -678,3 +678,158 @@ def make_map_refresh_case(n_points=1500, n_kfs=40, seed=5, obs_counts=None, feat
                 desc0=rng.integers(0, 256, (n_points, 32), dtype=np.uint8), obs_off=obs_off, obs_kf=obs_kf, obs_feat=obs_feat,
                 ref_kf=ref_kf, ref_level=ref_level, kf_n=kf_n.astype(np.int32), kf_desc=kf_desc, kf_octave=kf_octave, kf_xy=kf_xy,
                 kf_center=kf_center, kf_bad=kf_bad, scale_factors=scale, n_levels=n_levels)
+
+
+def make_new_points_case(n=600, n_neigh=10, seed=7, n_nodes=None, th_far_points=None, report_rejected=1, monocular=0, inertial=0):
+    """A key frame and its covisible neighbours for LocalMapping::CreateNewMapPoints: a world of n 3-D points, 4 - 90 m in front
+    of the key frame, seen by every neighbour (about three quarters of them each, shuffled, the rest clutter).  KITTI K and bf;
+    neighbour baselines 0.6 - 1.1 m in ascending order, so that a far point is of low parallax at an early neighbour and
+    triangulates at a later one; pixel noise of 0.5 px times the level's scale factor; about 20 % of a neighbour's pixels are
+    outliers ALONG the epipolar line (a wrong depth on the key frame's ray, a quarter of them beyond infinity, and for the
+    neighbours 4 and 9, which moved ahead, some between the two image planes: the search accepts them, the triangulation lands
+    behind one camera or both, or fails a reprojection test); LiDAR depth (mvDepth, mvuRight = u - bf / depth)
+    on about half the features, a few with depth == 0 and uright >= 0; about 6 % of the octaves break the scale consistency;
+    2 % of the key frame's features are doubles of another one (two idx1 for one idx2).  Descriptors: a world point's own with
+    3 % of the bits flipped per view; the FeatureVector node is a hash of the world point, so the search finds the geometric
+    matches.  With n_neigh >= 4, neighbour 1 is closer than mb (left out by the baseline test), neighbour 2 shares no
+    vocabulary node with the key frame and neighbour 3 is left out by skip[].
+    Returns dict(kf1, neighbours = [dict(kf, F12, ep, coarse, only_stereo)], skip, prm)."""
+    rng = np.random.default_rng(seed)
+    f32 = np.float32
+    w, h = synth.KITTI_W, synth.KITTI_H
+    K = np.array([718.856, 718.856, 607.1928, 185.2157], f32)
+    mbf = f32(386.1448)
+    mb = f32(mbf / K[0])
+    n_levels = 8
+    sf = (1.2 ** np.arange(n_levels)).astype(f32)
+    s2 = (sf * sf).astype(f32)
+    n_nodes = n_nodes or max(2, n // 15)
+    fx, fy, cx, cy = [float(v) for v in K]
+
+    def pose(center, axis, angle):
+        q = _quat(axis, angle)                     # of Rcw, (x, y, z, w): what the reference tier builds its Sophus pose from
+        R = _rot(q)
+        t = -R @ np.asarray(center, np.float64)
+        Tcw = np.concatenate([R, t[:, None]], 1).astype(f32)
+        R32 = Tcw[:, :3].astype(np.float64)
+        Ow = (-R32.T @ Tcw[:, 3].astype(np.float64)).astype(f32)
+        quats[id(Tcw)] = q
+        return Tcw, Ow
+    quats = {}
+
+    def project(Tcw, X):
+        Xc = X @ Tcw[:, :3].astype(np.float64).T + Tcw[:, 3].astype(np.float64)
+        z = Xc[:, 2]
+        with np.errstate(all="ignore"):
+            return np.stack([fx * Xc[:, 0] / z + cx, fy * Xc[:, 1] / z + cy], 1), z
+
+    def flip(desc):
+        bits = np.unpackbits(desc, axis=1)
+        return np.packbits(bits ^ (rng.random(bits.shape) < 0.03).astype(np.uint8), axis=1)
+
+    def csr(key):
+        order = np.argsort(key, kind="stable").astype(np.int32)
+        ids, cnt = np.unique(key, return_counts=True)
+        off = np.zeros(len(ids) + 1, np.int32)
+        off[1:] = np.cumsum(cnt)
+        return ids.astype(np.int32), off, order
+
+    def lidar(xy, z, level):
+        """mvDepth / mvuRight for about half the features; a few stereo features carry depth 0"""
+        m = len(xy)
+        has = rng.random(m) < 0.5
+        depth = np.where(has, z, -1.0).astype(f32)
+        with np.errstate(all="ignore"):
+            ur = np.where(has, xy[:, 0] - float(mbf) / np.where(has, depth, 1.0), -1.0).astype(f32)
+        zero = has & (rng.random(m) < 0.04)
+        depth[zero] = 0.0
+        return depth, ur
+
+    # the key frame: world points from its own pixels and depths
+    Tcw1, Ow1 = pose([3.0, -0.5, 12.0], [0.1, 1.0, 0.05], 0.08)
+    n_dbl = n // 50
+    n_pts = n - n_dbl
+    pix = np.stack([rng.uniform(30, w - 30, n_pts), rng.uniform(30, h - 30, n_pts)], 1)
+    depth_true = np.exp(rng.uniform(np.log(4.0), np.log(90.0), n_pts))
+    Xc = np.stack([(pix[:, 0] - cx) / fx * depth_true, (pix[:, 1] - cy) / fy * depth_true, depth_true], 1)
+    R1 = Tcw1[:, :3].astype(np.float64)
+    X = (Xc - Tcw1[:, 3].astype(np.float64)) @ R1                      # world
+    wid1 = np.concatenate([np.arange(n_pts), rng.integers(0, max(n_pts, 1), n_dbl)]).astype(np.int64) if n_pts else np.zeros(0, np.int64)
+    wid1 = wid1[:n]
+    lvl1 = rng.integers(0, n_levels, len(wid1))
+    base_desc = synth.descriptors(max(n_pts, 1), seed + 1)
+    desc1 = flip(base_desc[wid1[:n_pts]]) if n_pts else np.zeros((0, 32), np.uint8)
+    desc1 = np.concatenate([desc1, desc1[wid1[n_pts:]]]) if n_dbl else desc1     # a double carries the very same descriptor
+    p1, z1 = project(Tcw1, X[wid1]) if len(wid1) else (np.zeros((0, 2)), np.zeros(0))
+    xy1 = (p1 + rng.normal(0, 0.5, p1.shape) * sf[lvl1][:, None]).astype(f32)
+    d1, ur1 = lidar(xy1, z1, lvl1)
+    node_of = (wid1 * 2654435761 % 1000003) % n_nodes
+    id1, off1, f1 = csr(node_of)
+    kf1 = dict(desc=desc1, xy=xy1, octave=lvl1.astype(np.int32), angle=rng.uniform(0, 360, len(wid1)).astype(f32), uright=ur1,
+               has_mp=(rng.random(len(wid1)) < 0.25).astype(np.uint8), node_id=id1, node_off=off1, node_feat=f1, depth=d1,
+               xy_raw=(xy1 + f32(0.25)).astype(f32), Tcw=Tcw1.reshape(-1), Ow=Ow1, q=quats[id(Tcw1)], K=K, mb=mb, mbf=mbf, scale_factors=sf, level_sigma2=s2)
+
+    baselines = np.sort(rng.uniform(0.6, 1.1, n_neigh))
+    neighbours, skip = [], np.zeros(n_neigh, np.uint8)
+    for k in range(n_neigh):
+        special = k if n_neigh >= 4 else -1
+        b = float(rng.uniform(0.3, 0.5)) if special == 1 else float(baselines[k])
+        forward = k % 5 == 4   # the camera moved ahead: the epipole lies in the image
+        direction = np.array([0.1, 0.02, 1.0]) if forward else np.array([np.cos(0.5 * k), 0.15 * np.sin(1.3 * k), 0.6 * np.sin(0.5 * k)])
+        direction /= np.linalg.norm(direction)
+        center = Ow1.astype(np.float64) + b * (R1.T @ direction)
+        Tcw2, Ow2 = pose(center, [0.1, 1.0, 0.05], 0.08 + 0.01 * np.sin(2.0 * k))
+        seen = np.nonzero(rng.random(n_pts) < 0.75)[0]
+        Xs = X[seen].copy()
+        outl = rng.random(len(seen)) < 0.2
+        factor = np.where(rng.random(len(seen)) < 0.25, -rng.uniform(0.5, 4.0, len(seen)), np.exp(rng.uniform(np.log(0.3), np.log(3.0), len(seen))))
+        # a wrong depth on the key frame's ray; a negative one is a pixel beyond the ray's point at infinity
+        if forward:   # and a point between the two centres' planes is in front of the key frame and behind this neighbour
+            near = rng.random(len(seen)) < 0.3
+            factor = np.where(near, rng.uniform(0.1, 0.8, len(seen)) * b / depth_true[seen], factor)
+            outl = outl | near
+        Xs[outl] = Ow1.astype(np.float64) + (X[seen][outl] - Ow1.astype(np.float64)) * factor[outl][:, None]
+        p2, z2 = project(Tcw2, Xs)
+        behind = z2 <= 0
+        if behind.any():   # the mirror image of a point behind the camera: still on the epipolar line, beyond infinity
+            z2 = np.abs(z2)
+        ok = np.isfinite(p2).all(1) & (p2[:, 0] > 5) & (p2[:, 0] < w - 5) & (p2[:, 1] > 5) & (p2[:, 1] < h - 5) & (z2 > 0.05)
+        seen, p2, z2 = seen[ok], p2[ok], z2[ok]
+        n_true = min(len(seen), n)
+        seen, p2, z2 = seen[:n_true], p2[:n_true], z2[:n_true]
+        n_junk = n - n_true
+        wid2 = np.concatenate([seen, np.full(n_junk, -1)]).astype(np.int64)
+        with np.errstate(all="ignore"):
+            shift = np.rint(np.log(np.maximum(z2, 0.1) / depth_true[seen]) / np.log(1.2)).astype(np.int64) if n_true else np.zeros(0, np.int64)
+        lvl_true = np.clip(lvl1[seen] - shift + rng.integers(-1, 2, n_true), 0, n_levels - 1) if n_true else np.zeros(0, np.int64)
+        off_scale = rng.random(n_true) < 0.06
+        lvl_true = np.where(off_scale, (lvl_true + 4) % n_levels, lvl_true)
+        lvl2 = np.concatenate([lvl_true, rng.integers(0, n_levels, n_junk)]).astype(np.int64)
+        xy2 = np.concatenate([p2, np.stack([rng.uniform(5, w - 5, n_junk), rng.uniform(5, h - 5, n_junk)], 1)])
+        xy2 = (xy2 + rng.normal(0, 0.5, xy2.shape) * sf[lvl2][:, None]).astype(f32)
+        zz = np.concatenate([z2, rng.uniform(4, 90, n_junk)])
+        desc2 = np.concatenate([flip(base_desc[seen]) if n_true else np.zeros((0, 32), np.uint8), synth.descriptors(n_junk, seed + 100 + k)])
+        node2 = np.where(wid2 >= 0, (wid2 * 2654435761 % 1000003) % n_nodes, rng.integers(0, n_nodes, n)) + (100000 if special == 2 else 0)
+        perm = rng.permutation(n)
+        xy2, zz, lvl2, desc2, node2 = xy2[perm], zz[perm], lvl2[perm], desc2[perm], node2[perm]
+        d2, ur2 = lidar(xy2, zz, lvl2)
+        id2, off2, f2 = csr(node2)
+        kf2 = dict(desc=desc2, xy=xy2, octave=lvl2.astype(np.int32), angle=rng.uniform(0, 360, n).astype(f32), uright=ur2,
+                   has_mp=(rng.random(n) < 0.25).astype(np.uint8), node_id=id2, node_off=off2, node_feat=f2, depth=d2,
+                   xy_raw=(xy2 - f32(0.125)).astype(f32), Tcw=Tcw2.reshape(-1), Ow=Ow2, q=quats[id(Tcw2)], K=K, mb=mb, mbf=mbf, scale_factors=sf,
+                   level_sigma2=s2)
+        # F12 = K1^-T [t12]x R12 K2^-1 and the epipole project(T2w * Ow1) (ORBmatcher.cc:913-931, Pinhole.cpp:109-112)
+        Ra, ta = Tcw1[:, :3].astype(np.float64), Tcw1[:, 3].astype(np.float64)
+        Rb, tb = Tcw2[:, :3].astype(np.float64), Tcw2[:, 3].astype(np.float64)
+        R12 = Ra @ Rb.T
+        t12 = ta - R12 @ tb
+        Km = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]])
+        tx = np.array([[0, -t12[2], t12[1]], [t12[2], 0, -t12[0]], [-t12[1], t12[0], 0]])
+        F12 = (np.linalg.inv(Km).T @ tx @ R12 @ np.linalg.inv(Km)).astype(f32).reshape(-1)
+        C2 = Rb @ Ow1.astype(np.float64) + tb
+        ep = np.array([fx * C2[0] / C2[2] + cx, fy * C2[1] / C2[2] + cy], f32)
+        neighbours.append(dict(kf=kf2, F12=F12, ep=ep, coarse=0, only_stereo=0))
+        skip[k] = 1 if special == 3 else 0
+    prm = dict(n_levels=n_levels, ratio_factor=float(f32(1.5) * f32(1.2)), far_points=int(th_far_points is not None),
+               th_far_points=float(th_far_points or 0.0), inertial=int(inertial), monocular=int(monocular), report_rejected=int(report_rejected))
+    return dict(kf1=kf1, neighbours=neighbours, skip=skip, prm=prm)

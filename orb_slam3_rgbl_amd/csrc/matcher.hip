@@ -25,6 +25,7 @@
 #include "common.h"
 #include "frustum_math.h"
 #include "logf_glibc.h"
+#include "newpoint_math.h"
 
 namespace rgbl {
 
@@ -734,6 +735,126 @@ __global__ __launch_bounds__(256) void k_search_triangulation(TriDev T) {
   }
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// The per-match block of LocalMapping::CreateNewMapPoints (/root/reference/src/LocalMapping.cc:481-710) behind
+// k_search_triangulation, neighbour after neighbour on one stream (rgbl_create_new_map_points): csrc/newpoint_math.h holds the
+// arithmetic, this kernel the order.  ONE workgroup walks idx2[0 .. n) in tiles in ascending index - the order of
+// vMatchedIndices (ORBmatcher.cc:1138-1144) - a work-item per match; the records leave compacted in that order (ballot and
+// prefix inside the tile, a running base across tiles and, through D.total, across the launches of a chain).  An accepted match
+// sets mask1[idx1] (mpCurrentKeyFrame->AddMapPoint, :701): the next neighbour's k_search_triangulation skips that feature.
+// One workgroup, because the chain is sequential and the order is the workgroup's to keep; with the Jacobi sweeps in fp64 the
+// kernel is nine tenths of a call of KITTI size (fp32 sweeps would take a tenth off) - several workgroups over the
+// list are where a gain would come from.
+struct NewPointsKf {
+  const float *xy, *xy_raw, *ur, *depth;   // mvKeysUn[].pt, mvKeys[].pt, mvuRight, mvDepth
+  const int32_t* oct;
+  const float *scale, *sigma2;             // mvScaleFactors, mvLevelSigma2
+  float Tcw[12], Ow[3], K[4], mb;
+};
+struct NewPointsDev {
+  NewPointsKf k1, k2;
+  NpParams P;
+  int n, n_levels;
+  const int32_t* idx1;   // null: entry i is feature i of key frame 1 (the chain); else explicit pairs (rgbl_triangulate_matches)
+  int32_t* idx2;         // the match of entry i, -1 = none; reset to -1 once read when `reset` (the chain's matches12)
+  int32_t* list;         // scratch, n entries: the matched entries in ascending order
+  int reset, report_rejected, neighbour, cap;
+  uint8_t* mask1;        // nullable
+  rgbl_new_point* out;
+  int32_t* total;        // records so far (all launches of the call)
+  int32_t* per_launch;   // [0] matches, [1] records of this launch
+};
+__device__ __forceinline__ NpSide new_points_side(const NewPointsKf& k, int i, int n_levels) {
+  NpSide S;
+  for (int j = 0; j < 12; ++j) S.Tcw[j] = k.Tcw[j];
+  for (int j = 0; j < 3; ++j) S.Ow[j] = k.Ow[j];
+  for (int j = 0; j < 4; ++j) S.K[j] = k.K[j];
+  S.mb = k.mb;
+  S.u = k.xy[2 * i]; S.v = k.xy[2 * i + 1];
+  S.u_raw = k.xy_raw[2 * i]; S.v_raw = k.xy_raw[2 * i + 1];
+  S.uright = k.ur[i];
+  S.depth = k.depth[i];
+  const int o = imin(imax(k.oct[i], 0), n_levels - 1);   // a resident frame's octaves are not checked on the host
+  S.sigma2 = k.sigma2[o];
+  S.scale = k.scale[o];
+  return S;
+}
+// grid = 1, block = kNewPointsBS.  Two passes: the matched entries are first listed side by side - a tile of entries holds a
+// few dozen matches, and in a wave that holds one every work-item without one idles through the whole per-match block -, then
+// the list is walked densely.
+constexpr int kNewPointsBS = 512, kNewPointsWaves = kNewPointsBS / 64;
+__global__ __launch_bounds__(kNewPointsBS) void k_new_points(NewPointsDev D) {
+  __shared__ int s_cnt[kNewPointsWaves];
+  const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
+  const int base0 = D.total[0];
+  __syncthreads();   // every wave has read D.total before work-item 0 writes it
+  int m = 0;         // matches listed so far
+  for (int t0 = 0; t0 < D.n; t0 += kNewPointsBS) {
+    const int i = t0 + tid;
+    const bool has = i < D.n && D.idx2[i] >= 0;
+    const unsigned long long mh = __ballot(has);
+    if (lane == 0) s_cnt[w] = (int)__popcll(mh);
+    __syncthreads();
+    int before = 0, tile = 0;
+    for (int v = 0; v < kNewPointsWaves; ++v) {
+      before += v < w ? s_cnt[v] : 0;
+      tile += s_cnt[v];
+    }
+    if (has) D.list[m + before + (int)__popcll(mh & lanemask_lt())] = i;
+    m += tile;
+    __syncthreads();   // s_cnt is written again in the next tile; and the list is the workgroup's to read from here on
+  }
+  int base = base0;
+  for (int p0 = 0; p0 < m; p0 += kNewPointsBS) {
+    const int p = p0 + tid;
+    const bool live = p < m;
+    int i1 = 0, i2 = -1;
+    uint8_t st = kNpNone;
+    float x3D[3] = {0.f, 0.f, 0.f};
+    if (live) {
+      const int i = D.list[p];
+      i2 = D.idx2[i];
+      if (D.reset) D.idx2[i] = -1;
+      i1 = D.idx1 ? D.idx1[i] : i;
+      const NpSide S1 = new_points_side(D.k1, i1, D.n_levels), S2 = new_points_side(D.k2, i2, D.n_levels);
+      st = np_check(S1, S2, D.P, x3D);
+    }
+    const bool accepted = st >= kNpTriangulated && st <= kNpStereo2;
+    const bool emit = live && (D.report_rejected || accepted);
+    if (accepted && D.mask1) D.mask1[i1] = 1;
+    const unsigned long long me = __ballot(emit);
+    if (lane == 0) s_cnt[w] = (int)__popcll(me);
+    __syncthreads();
+    int before = 0, tile = 0;
+    for (int v = 0; v < kNewPointsWaves; ++v) {
+      before += v < w ? s_cnt[v] : 0;
+      tile += s_cnt[v];
+    }
+    if (emit) {
+      const int pos = base + before + (int)__popcll(me & lanemask_lt());
+      if (pos < D.cap) {
+        rgbl_new_point r;
+        r.neighbour = D.neighbour; r.idx1 = i1; r.idx2 = i2;
+        r.x3D[0] = x3D[0]; r.x3D[1] = x3D[1]; r.x3D[2] = x3D[2];
+        r.status = st; r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
+        D.out[pos] = r;
+      }
+    }
+    base += tile;
+    __syncthreads();   // s_cnt is written again in the next pass
+  }
+  if (tid == 0) {
+    D.total[0] = base;
+    D.per_launch[0] = m;
+    D.per_launch[1] = base - base0;
+  }
+}
+
+__global__ void k_test_np_cos_parallax(float mb, const float* __restrict__ depth, float* __restrict__ y, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) y[i] = np_cos_parallax_stereo(mb, depth[i]);
+}
 
 // ------------------------------------------------------------------------------------------------
 // ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)
@@ -2196,8 +2317,16 @@ struct SharedNodes {
   bool empty() const { return pa.empty() || a->n == 0 || b->n == 0; }   // nothing to launch
   // inside the call's layout: both sides' per-feature arrays and FeatureVectors (resident or staged), then the pair lists
   int put(HostCall& hc, FeatDst d1, FeatDst d2, NodePairsDev& N) const {
+    RGBL_TRY(put_first(hc, a, d1, N));
+    return put_second(hc, d2, N);
+  }
+  // the two halves of put(): a chain of searches from one first key frame (rgbl_create_new_map_points) stages it once
+  static int put_first(HostCall& hc, const rgbl_keyframe_view* a, FeatDst d1, NodePairsDev& N) {
     RGBL_TRY(put_features(hc, a->device, a->n, a->desc, a->kp_xy, a->kp_octave, a->uright, d1.desc, d1.xy, d1.oct, d1.ur));
     put_feature_vector(hc, a, &N.off1, &N.feat1);
+    return RGBL_OK;
+  }
+  int put_second(HostCall& hc, FeatDst d2, NodePairsDev& N) const {
     RGBL_TRY(put_features(hc, b->device, b->n, b->desc, b->kp_xy, b->kp_octave, b->uright, d2.desc, d2.xy, d2.oct, d2.ur));
     put_feature_vector(hc, b, &N.off2, &N.feat2);
     hc.put(&N.pair_n1, pa.data(), pa.size());
@@ -2236,6 +2365,20 @@ struct RotationFilter {
 // What is left to do once matches12[idx1] (a's feature -> b's, or -1) is filled: count, the rotation check with its bins filled in
 // the order the reference visits idx1 - node by node in merge order, bucket order (ORBmatcher.cc:1083-1096, 1119-1136; 855-865, 886-901) -
 // and *out_nmatches.
+// The launch of one SearchForTriangulation once T's arrays are laid out: the call's parameters, then one workgroup per shared node.
+int enqueue_triangulation(rgbl_matcher* m, hipStream_t s, TriDev& T, const rgbl_triangulation_params* prm, int npairs) {
+  memcpy(T.F, prm->F12, sizeof(T.F));
+  T.ep[0] = prm->epipole[0];
+  T.ep[1] = prm->epipole[1];
+  T.only_stereo = prm->only_stereo;
+  T.coarse = prm->coarse;
+  m->timer.begin("k_search_triangulation", s);
+  hipLaunchKernelGGL(k_search_triangulation, dim3(npairs), dim3(256), 0, s, T);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  return RGBL_OK;
+}
+
 void finish_matches12(const SharedNodes& sn, int32_t* matches12, bool check_orientation, int* out_nmatches) {
   int nmatches = 0;
   for (int i = 0; i < sn.a->n; ++i) nmatches += matches12[i] >= 0;
@@ -2710,19 +2853,240 @@ int rgbl_search_triangulation(rgbl_matcher* m, const rgbl_keyframe_view* k1, con
       hc.mark_result(T.matches12, n1);
       return RGBL_OK;
     }));
-    memcpy(T.F, prm->F12, sizeof(T.F));
-    T.ep[0] = prm->epipole[0];
-    T.ep[1] = prm->epipole[1];
-    T.only_stereo = prm->only_stereo;
-    T.coarse = prm->coarse;
-    m->timer.begin("k_search_triangulation", s);
-    hipLaunchKernelGGL(k_search_triangulation, dim3(sn.npairs()), dim3(256), 0, s, T);
-    m->timer.end(s);
-    RGBL_HIP(hipGetLastError());
+    RGBL_TRY(enqueue_triangulation(m, s, T, prm, sn.npairs()));
     RGBL_TRY(hc.fetch());
     memcpy(matches12, hc.host(T.matches12), sizeof(int32_t) * n1);
   }
   finish_matches12(sn, matches12, prm->check_orientation != 0, out_nmatches);
+  return RGBL_OK;
+}
+
+namespace {
+// What both new-point entries check before anything is queued.  chain: the search reads descriptors, mask and FeatureVector too.
+int check_new_points_kf(const rgbl_matcher* m, const rgbl_new_points_keyframe* k, int n_levels, bool chain, const char* which) {
+  if (!k) { set_error("%s: null key frame", which); return RGBL_ERR_INVALID; }
+  const rgbl_keyframe_view& v = k->view;
+  bool ok = v.n >= 0 && k->scale_factors && k->level_sigma2 && (v.n == 0 || k->depth);
+  if (ok && v.device) ok = v.device->device == m->device && v.device->n == v.n;
+  if (ok && !v.device && v.n > 0) ok = v.kp_xy && v.kp_octave && v.uright && (!chain || v.desc);
+  if (ok && chain) ok = v.n_nodes >= 0 && (v.n == 0 || v.has_mappoint) && (v.n_nodes == 0 || (v.node_id && v.node_off && v.node_feat));
+  if (!ok) { set_error("%s: invalid key frame (null array, negative count, or a resident frame of another size or device)", which); return RGBL_ERR_INVALID; }
+  if (!v.device)
+    for (int i = 0; i < v.n; ++i)
+      if (v.kp_octave[i] < 0 || v.kp_octave[i] >= n_levels) { set_error("%s: octave %d of feature %d outside [0, %d)", which, v.kp_octave[i], i, n_levels); return RGBL_ERR_INVALID; }
+  return RGBL_OK;
+}
+int check_new_points_params(const rgbl_new_points_params* p) {
+  if (!p || p->n_levels < 1 || p->n_levels > kProjMaxLevels) { set_error("new points: n_levels outside [1, %d]", kProjMaxLevels); return RGBL_ERR_INVALID; }
+  return RGBL_OK;
+}
+// inside the call's layout: the per-match block's arrays of one key frame (xy / oct / ur may already be there from the search's layout)
+int put_new_points_kf(HostCall& hc, const rgbl_new_points_keyframe* k, int n_levels, bool features, NewPointsKf& d) {
+  const rgbl_keyframe_view& v = k->view;
+  if (features) RGBL_TRY(put_features(hc, v.device, v.n, nullptr, v.kp_xy, v.kp_octave, v.uright, nullptr, &d.xy, &d.oct, &d.ur));
+  hc.put(&d.depth, k->depth, (size_t)v.n);
+  if (k->kp_xy_raw) hc.put(&d.xy_raw, k->kp_xy_raw, (size_t)v.n * 2); else d.xy_raw = d.xy;
+  hc.put(&d.scale, k->scale_factors, (size_t)n_levels);
+  hc.put(&d.sigma2, k->level_sigma2, (size_t)n_levels);
+  memcpy(d.Tcw, k->Tcw, sizeof(d.Tcw));
+  memcpy(d.Ow, k->Ow, sizeof(d.Ow));
+  memcpy(d.K, k->K, sizeof(d.K));
+  d.mb = k->mb;
+  return RGBL_OK;
+}
+NpParams new_points_params(const rgbl_new_points_keyframe* kf1, const rgbl_new_points_params* prm) {
+  return NpParams{kf1->mbf, prm->ratio_factor, prm->th_far_points, prm->far_points, prm->inertial};
+}
+}  // namespace
+
+int rgbl_triangulate_matches_host(const rgbl_new_points_keyframe* kf1, const rgbl_new_points_keyframe* kf2,
+                                  const rgbl_new_points_params* prm, int n_pairs, const int32_t* idx1, const int32_t* idx2,
+                                  rgbl_new_point* out) {
+  if (!kf1 || !kf2 || !prm || n_pairs < 0 || (n_pairs > 0 && (!idx1 || !idx2 || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  const NpParams P = new_points_params(kf1, prm);
+  auto side = [&](const rgbl_new_points_keyframe* k, int i) {
+    NpSide S;
+    memcpy(S.Tcw, k->Tcw, sizeof(S.Tcw)); memcpy(S.Ow, k->Ow, sizeof(S.Ow)); memcpy(S.K, k->K, sizeof(S.K));
+    S.mb = k->mb;
+    const float* raw = k->kp_xy_raw ? k->kp_xy_raw : k->view.kp_xy;
+    S.u = k->view.kp_xy[2 * i]; S.v = k->view.kp_xy[2 * i + 1]; S.u_raw = raw[2 * i]; S.v_raw = raw[2 * i + 1];
+    S.uright = k->view.uright[i]; S.depth = k->depth[i];
+    const int o = std::min(std::max(k->view.kp_octave[i], 0), prm->n_levels - 1);
+    S.sigma2 = k->level_sigma2[o]; S.scale = k->scale_factors[o];
+    return S;
+  };
+  for (int p = 0; p < n_pairs; ++p) {
+    if (idx1[p] < 0 || idx1[p] >= kf1->view.n || idx2[p] < 0 || idx2[p] >= kf2->view.n) { set_error("pair %d: index out of range", p); return RGBL_ERR_INVALID; }
+    rgbl_new_point r;
+    memset(&r, 0, sizeof(r));
+    r.idx1 = idx1[p]; r.idx2 = idx2[p];
+    r.status = np_check(side(kf1, idx1[p]), side(kf2, idx2[p]), P, r.x3D);
+    out[p] = r;
+  }
+  return RGBL_OK;
+}
+
+int rgbl_triangulate_matches(rgbl_matcher* m, const rgbl_new_points_keyframe* kf1, const rgbl_new_points_keyframe* kf2,
+                             const rgbl_new_points_params* prm, int n_pairs, const int32_t* idx1, const int32_t* idx2,
+                             rgbl_new_point* out) {
+  if (!m || n_pairs < 0 || (n_pairs > 0 && (!idx1 || !idx2 || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  RGBL_TRY(check_new_points_params(prm));
+  RGBL_TRY(check_new_points_kf(m, kf1, prm->n_levels, false, "kf1"));
+  RGBL_TRY(check_new_points_kf(m, kf2, prm->n_levels, false, "kf2"));
+  for (int p = 0; p < n_pairs; ++p)
+    if (idx1[p] < 0 || idx1[p] >= kf1->view.n || idx2[p] < 0 || idx2[p] >= kf2->view.n) { set_error("pair %d: index out of range", p); return RGBL_ERR_INVALID; }
+  if (n_pairs == 0) return RGBL_OK;
+  RGBL_HIP(hipSetDevice(m->device));
+  StreamDrain drain(m->stream);  // error returns included
+  HostCall hc(m);
+  hipStream_t s = hc.s;
+  NewPointsDev D;
+  memset(&D, 0, sizeof(D));
+  RGBL_TRY(hc.begin([&]() -> int {
+    RGBL_TRY(put_new_points_kf(hc, kf1, prm->n_levels, true, D.k1));
+    RGBL_TRY(put_new_points_kf(hc, kf2, prm->n_levels, true, D.k2));
+    hc.put(&D.idx1, idx1, (size_t)n_pairs);
+    const int32_t* d_idx2 = nullptr;
+    hc.put(&d_idx2, idx2, (size_t)n_pairs);
+    D.idx2 = const_cast<int32_t*>(d_idx2);
+    D.total = hc.put_fill<int32_t>(3, 0);
+    D.per_launch = D.total + 1;
+    D.list = hc.scratch<int32_t>((size_t)n_pairs);
+    D.out = hc.result<rgbl_new_point>((size_t)n_pairs);
+    return RGBL_OK;
+  }));
+  D.P = new_points_params(kf1, prm);
+  D.n = n_pairs; D.n_levels = prm->n_levels; D.report_rejected = 1; D.cap = n_pairs;
+  m->timer.begin("k_new_points", s);
+  hipLaunchKernelGGL(k_new_points, dim3(1), dim3(kNewPointsBS), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(hc.fetch());
+  memcpy(out, hc.host(D.out), sizeof(rgbl_new_point) * (size_t)n_pairs);
+  return RGBL_OK;
+}
+
+int rgbl_create_new_map_points(rgbl_matcher* m, const rgbl_new_points_keyframe* kf1, int n_neigh, const rgbl_new_points_keyframe* kf2,
+                               const rgbl_triangulation_params* tri_prm, const uint8_t* skip, const rgbl_new_points_params* prm,
+                               rgbl_new_point* out, int cap, int* n_out, int32_t* matches_per_neighbour, uint8_t* has_mappoint1_out) {
+  if (!m || n_neigh < 0 || cap < 0 || !n_out || (cap > 0 && !out) || (n_neigh > 0 && (!kf2 || !tri_prm))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  RGBL_TRY(check_new_points_params(prm));
+  RGBL_TRY(check_new_points_kf(m, kf1, prm->n_levels, true, "kf1"));
+  for (int i = 0; i < n_neigh; ++i) {
+    RGBL_TRY(check_new_points_kf(m, kf2 + i, prm->n_levels, true, "kf2"));
+    const rgbl_triangulation_params& t = tri_prm[i];
+    if (t.check_orientation != 0) { set_error("neighbour %d: check_orientation has no form in the chain (LocalMapping.cc:412 passes false)", i); return RGBL_ERR_INVALID; }
+    if (t.n_levels != prm->n_levels || !t.scale_factors2 || !t.level_sigma2_2) { set_error("neighbour %d: the search's level tables", i); return RGBL_ERR_INVALID; }
+  }
+  const int n1 = kf1->view.n;
+  // which neighbours run (:444-460), and every merge walk (the searches' shared nodes) before the one upload
+  std::vector<char> runs((size_t)n_neigh, 0);
+  std::vector<SharedNodes> sn;
+  sn.reserve((size_t)n_neigh);
+  bool any = false;
+  for (int i = 0; i < n_neigh; ++i) {
+    sn.emplace_back(&kf1->view, &kf2[i].view);
+    bool left_out = skip && skip[i];
+    if (!left_out && !prm->monocular) {
+      const float baseline = fr_norm(kf2[i].Ow[0] - kf1->Ow[0], kf2[i].Ow[1] - kf1->Ow[1], kf2[i].Ow[2] - kf1->Ow[2]);
+      left_out = baseline < kf2[i].mb;
+    }
+    runs[i] = left_out ? 0 : (sn[i].empty() ? 1 : 2);   // 1: searched, nothing to launch; 2: launched
+    any = any || runs[i] == 2;
+  }
+  int total = 0;
+  std::vector<int32_t> per((size_t)n_neigh, 0);
+  HostCall hc(m);
+  uint8_t* d_mask = nullptr;
+  rgbl_new_point* d_out = nullptr;
+  if (any) {
+    RGBL_HIP(hipSetDevice(m->device));
+    StreamDrain drain(m->stream);  // error returns included
+    hipStream_t s = hc.s;
+    std::vector<TriDev> T((size_t)n_neigh);
+    std::vector<NewPointsDev> D((size_t)n_neigh);
+    TriDev T1;                 // key frame 1's side of every search
+    NewPointsKf K1;
+    int32_t *d_m12 = nullptr, *d_cnt = nullptr, *d_list = nullptr;
+    RGBL_TRY(hc.begin([&]() -> int {
+      RGBL_TRY(SharedNodes::put_first(hc, &kf1->view, {&T1.desc1, &T1.xy1, &K1.oct, &T1.ur1}, T1.fv));
+      K1.xy = T1.xy1; K1.ur = T1.ur1;
+      RGBL_TRY(put_new_points_kf(hc, kf1, prm->n_levels, false, K1));
+      for (int i = 0; i < n_neigh; ++i) {
+        if (runs[i] != 2) continue;
+        memset(&D[i], 0, sizeof(D[i]));
+        T[i] = T1;
+        RGBL_TRY(sn[i].put_second(hc, {&T[i].desc2, &T[i].xy2, &T[i].oct2, &T[i].ur2}, T[i].fv));
+        hc.put(&T[i].mp2, kf2[i].view.has_mappoint, (size_t)kf2[i].view.n);
+        hc.put(&T[i].scale2, tri_prm[i].scale_factors2, (size_t)prm->n_levels);
+        hc.put(&T[i].sigma2, tri_prm[i].level_sigma2_2, (size_t)prm->n_levels);
+        D[i].k2.xy = T[i].xy2; D[i].k2.oct = T[i].oct2; D[i].k2.ur = T[i].ur2;
+        RGBL_TRY(put_new_points_kf(hc, kf2 + i, prm->n_levels, false, D[i].k2));
+      }
+      d_m12 = hc.put_fill<int32_t>((size_t)n1, 0xff);   // all -1; k_new_points leaves it so for the next neighbour
+      // what comes back, side by side: mask, counters, records
+      const uint8_t* mask_up = nullptr;
+      hc.put(&mask_up, kf1->view.has_mappoint, (size_t)n1);
+      d_mask = const_cast<uint8_t*>(mask_up);
+      hc.mark_result(d_mask, (size_t)n1);
+      d_cnt = hc.put_fill<int32_t>((size_t)1 + 2 * (size_t)n_neigh, 0);
+      hc.mark_result(d_cnt, (size_t)1 + 2 * (size_t)n_neigh);
+      d_out = hc.result<rgbl_new_point>((size_t)cap);
+      d_list = hc.scratch<int32_t>((size_t)n1);   // behind everything that travels
+      return RGBL_OK;
+    }));
+    for (int i = 0; i < n_neigh; ++i) {
+      if (runs[i] != 2) continue;
+      T[i].mp1 = d_mask;
+      T[i].matches12 = d_m12;
+      RGBL_TRY(enqueue_triangulation(m, s, T[i], tri_prm + i, sn[i].npairs()));
+      NewPointsDev& d = D[i];
+      d.k1 = K1;
+      d.P = new_points_params(kf1, prm);
+      d.n = n1; d.n_levels = prm->n_levels;
+      d.idx2 = d_m12; d.list = d_list; d.reset = 1; d.report_rejected = prm->report_rejected; d.neighbour = i; d.cap = cap;
+      d.mask1 = d_mask; d.out = d_out; d.total = d_cnt; d.per_launch = d_cnt + 1 + 2 * i;
+      m->timer.begin("k_new_points", s);
+      hipLaunchKernelGGL(k_new_points, dim3(1), dim3(kNewPointsBS), 0, s, d);
+      m->timer.end(s);
+      RGBL_HIP(hipGetLastError());
+    }
+    RGBL_TRY(hc.fetch());
+    const int32_t* cnt = hc.host(d_cnt);
+    total = cnt[0];
+    for (int i = 0; i < n_neigh; ++i) per[i] = cnt[1 + 2 * i];
+  }
+  *n_out = total;
+  if (total > cap) { set_error("new points: %d records, room for %d", total, cap); return RGBL_ERR_CAPACITY; }
+  if (total > 0) memcpy(out, hc.host(d_out), sizeof(rgbl_new_point) * (size_t)total);
+  if (matches_per_neighbour)
+    for (int i = 0; i < n_neigh; ++i) matches_per_neighbour[i] = runs[i] ? per[i] : -1;
+  if (has_mappoint1_out && n1 > 0) {
+    if (any) memcpy(has_mappoint1_out, hc.host(d_mask), (size_t)n1);
+    else if (has_mappoint1_out != kf1->view.has_mappoint) memcpy(has_mappoint1_out, kf1->view.has_mappoint, (size_t)n1);
+  }
+  return RGBL_OK;
+}
+
+// test hooks for csrc/newpoint_math.h: Triangulate on the host, and the stereo parallax cosine on host and device
+int rgbl_test_np_triangulate(const float* xn1, const float* xn2, const float* T1, const float* T2, float* x3D) {
+  return np_triangulate(xn1, xn2, T1, T2, x3D) ? 1 : 0;
+}
+float rgbl_test_np_cos_parallax(float mb, float depth) { return np_cos_parallax_stereo(mb, depth); }
+int rgbl_test_np_cos_parallax_device(float mb, const float* depth, float* y, int n) {
+  if (!depth || !y || n < 1) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  float *dx = nullptr, *dy = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dx), sizeof(float) * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dy), sizeof(float) * (size_t)n);
+  if (e == hipSuccess) e = hipMemcpy(dx, depth, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_test_np_cos_parallax, dim3((n + 255) / 256), dim3(256), 0, 0, mb, (const float*)dx, dy, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(y, dy, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
+  if (dx) (void)hipFree(dx);
+  if (dy) (void)hipFree(dy);
+  if (e != hipSuccess) { set_error("cos parallax test hook: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
   return RGBL_OK;
 }
 

@@ -1119,6 +1119,130 @@ class ORBmatcher:
             return pairs, nm.value, m12
         return call
 
+    @staticmethod
+    def _new_points_kf(kf, keep, out=None):
+        """rgbl_new_points_keyframe of a key-frame dict: the keys of SearchForTriangulation plus depth (mvDepth), xy_raw
+        (mvKeys[].pt, optional), Tcw (3 x 4), Ow, K (fx, fy, cx, cy), mb, mbf, scale_factors, level_sigma2."""
+        k = out if out is not None else L.NewPointsKeyframe()
+        k.view = ORBmatcher._view(kf, keep)
+        for field, key in (("depth", "depth"), ("kp_xy_raw", "xy_raw"), ("scale_factors", "scale_factors"),
+                           ("level_sigma2", "level_sigma2")):
+            if kf.get(key) is None:
+                setattr(k, field, None)
+                continue
+            a = np.ascontiguousarray(kf[key], np.float32)
+            keep.append(a)
+            setattr(k, field, a.ctypes.data)
+        for field, key, cnt in (("Tcw", "Tcw", 12), ("Ow", "Ow", 3), ("K", "K", 4)):
+            v = np.asarray(kf[key], np.float32).reshape(-1)
+            for i in range(cnt):
+                getattr(k, field)[i] = float(v[i])
+        k.mb, k.mbf = float(kf["mb"]), float(kf["mbf"])
+        return k
+
+    @staticmethod
+    def _new_points_params(prm):
+        P = L.NewPointsParams()
+        P.n_levels, P.ratio_factor = int(prm["n_levels"]), float(prm["ratio_factor"])
+        P.far_points, P.th_far_points = int(prm.get("far_points", 0)), float(prm.get("th_far_points", 0.0))
+        P.inertial, P.monocular = int(prm.get("inertial", 0)), int(prm.get("monocular", 0))
+        P.report_rejected = int(prm.get("report_rejected", 0))
+        return P
+
+    def TriangulateMatches(self, kf1, kf2, prm, idx1, idx2, host=False):
+        """The per-match block of LocalMapping::CreateNewMapPoints (LocalMapping.cc:481-691) on explicit pairs: one record
+        (L.NEW_POINT_DTYPE) per pair.  host=True: the same header evaluated by the library's host build (no device)."""
+        keep = []
+        k1, k2, P = self._new_points_kf(kf1, keep), self._new_points_kf(kf2, keep), self._new_points_params(prm)
+        i1, i2 = np.ascontiguousarray(idx1, np.int32), np.ascontiguousarray(idx2, np.int32)
+        out = np.zeros(len(i1), L.NEW_POINT_DTYPE)
+        if host:
+            rc = self.lib.rgbl_triangulate_matches_host(C.byref(k1), C.byref(k2), C.byref(P), len(i1), L.ptr(i1), L.ptr(i2), L.ptr(out))
+        else:
+            rc = self.lib.rgbl_triangulate_matches(self.h, C.byref(k1), C.byref(k2), C.byref(P), len(i1), L.ptr(i1), L.ptr(i2), L.ptr(out))
+        L.check(self.lib, rc)
+        return out
+
+    def CreateNewMapPoints(self, kf1, neighbours, prm, skip=None, cap=None):
+        return self.prepare_CreateNewMapPoints(kf1, neighbours, prm, skip, cap)()
+
+    def prepare_CreateNewMapPoints(self, kf1, neighbours, prm, skip=None, cap=None):
+        """LocalMapping::CreateNewMapPoints from its neighbour loop on (LocalMapping.cc:434-711) in one call.
+        kf1: key-frame dict (see _new_points_kf); neighbours: list of dict(kf=key-frame dict, F12=, ep=, coarse=, only_stereo=)
+        in the order of vpNeighKFs; prm: dict(n_levels, ratio_factor, far_points, th_far_points, inertial, monocular,
+        report_rejected); skip: per neighbour, the caller's monocular median-depth test.  Returns (records, matches per
+        neighbour with -1 for one left out, kf1's has_mp after the call)."""
+        keep = []
+        k1, P = self._new_points_kf(kf1, keep), self._new_points_params(prm)
+        nn = len(neighbours)
+        k2 = (L.NewPointsKeyframe * max(nn, 1))()
+        tp = (L.TriangulationParams * max(nn, 1))()
+        for i, nb in enumerate(neighbours):
+            self._new_points_kf(nb["kf"], keep, k2[i])
+            for j in range(9):
+                tp[i].F12[j] = float(nb["F12"][j])
+            tp[i].epipole[0], tp[i].epipole[1] = float(nb["ep"][0]), float(nb["ep"][1])
+            tp[i].scale_factors2, tp[i].level_sigma2_2, tp[i].n_levels = k2[i].scale_factors, k2[i].level_sigma2, P.n_levels
+            tp[i].only_stereo, tp[i].coarse = int(nb.get("only_stereo", 0)), int(nb.get("coarse", 0))
+            tp[i].check_orientation = int(self.mbCheckOrientation)
+        sk = np.ascontiguousarray(skip, np.uint8) if skip is not None else None
+        n1 = k1.view.n
+        cap = n1 if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), L.NEW_POINT_DTYPE)
+        per = np.zeros(max(nn, 1), np.int32)
+        mask = np.ascontiguousarray(kf1["has_mp"], np.uint8).copy()
+        n_out = C.c_int(0)
+        fn, h = self.lib.rgbl_create_new_map_points, self.h
+        args = (h, C.byref(k1), nn, C.cast(k2, C.c_void_p), C.cast(tp, C.c_void_p), L.ptr(sk), C.byref(P), L.ptr(out), cap,
+                C.byref(n_out), L.ptr(per), L.ptr(mask))
+
+        def call(_keep=(keep, k2, tp, sk)):   # the closure owns the input arrays
+            L.check(self.lib, fn(*args))
+            return out[:n_out.value], per[:nn], mask
+        call.out, call.mask = out, mask   # what an error return must leave untouched (tests)
+        return call
+
+    @staticmethod
+    def new_points_left_out(kf1, neighbours, prm, skip, i):
+        """LocalMapping.cc:444-460 for neighbour i: the caller's skip[], or (not monocular) a baseline below pKF2->mb, in fp32"""
+        if skip is not None and skip[i]:
+            return True
+        if prm.get("monocular", 0):
+            return False
+        kf2 = neighbours[i]["kf"]
+        d = np.asarray(kf2["Ow"], np.float32) - np.asarray(kf1["Ow"], np.float32)
+        sq = np.float32(d[0] * d[0])
+        sq = np.float32(sq + np.float32(d[1] * d[1]))
+        sq = np.float32(sq + np.float32(d[2] * d[2]))
+        return bool(np.float32(np.sqrt(sq)) < np.float32(kf2["mb"]))
+
+    def CreateNewMapPointsRestatement(self, search, kf1, neighbours, prm, skip=None, chained=True, block=None):
+        """The loop of LocalMapping.cc:434-711 restated neighbour by neighbour on the host: search(kf1 with the mask so far, nb)
+        -> matches12 is SearchForTriangulation (the tests hand in the oracle's, tools/new_points_bench.py the device's single
+        call), then the per-match block by the host build of csrc/newpoint_math.h (block(i, idx1, idx2) -> records; default
+        TriangulateMatches(host=True)), then the has_mappoint feedback of :701.  chained=False: every neighbour searches with
+        the mask the call started from.  Returns what CreateNewMapPoints returns."""
+        mask = np.ascontiguousarray(kf1["has_mp"], np.uint8).copy()
+        start = mask.copy()
+        if block is None:
+            def block(i, idx1, idx2):
+                return self.TriangulateMatches(kf1, neighbours[i]["kf"], prm, idx1, idx2, host=True)
+        recs, per = [], []
+        for i, nb in enumerate(neighbours):
+            if self.new_points_left_out(kf1, neighbours, prm, skip, i):
+                per.append(-1)
+                continue
+            m12 = search(dict(kf1, has_mp=mask.copy() if chained else start), nb)
+            idx1 = np.nonzero(m12 >= 0)[0].astype(np.int32)
+            r = block(i, idx1, np.ascontiguousarray(m12[idx1], np.int32))
+            r["neighbour"] = i
+            acc = (r["status"] >= 1) & (r["status"] <= 3)
+            mask[idx1[acc]] = 1
+            recs.append((r if prm.get("report_rejected", 0) else r[acc]).copy())
+            per.append(len(idx1))
+        recs = np.concatenate(recs) if recs else np.zeros(0, L.NEW_POINT_DTYPE)
+        return recs, np.array(per, np.int32), mask
+
     def profile(self, enable):
         L.check(self.lib, self.lib.rgbl_matcher_profile(self.h, int(enable)))
 

@@ -33,9 +33,13 @@
 
 // rgbl_shim::device_frame_of (a Frame / KeyFrame's resident copy, if its class has the member) lives in LocalMap.h
 
+namespace rgbl_shim { struct NewPointsAccess; }   // NewMapPoints.h: reaches Flat / Flatten and the handle of a matcher it is given
+
 namespace ORB_SLAM3 {
 
 class ORBmatcher {
+  friend struct rgbl_shim::NewPointsAccess;
+
  public:
   ORBmatcher(float nnratio = 0.6, bool checkOri = true, int device = 0) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {
     // the reference constructs this class on the stack in every call (Tracking.cc:2890 ...): the device handle comes from
