@@ -120,6 +120,8 @@ struct rgbl_extractor {
   ResizeTab *d_xtab = nullptr, *d_ytab = nullptr;
   ResizeGroup* d_xgroups = nullptr;  // k_resize_linear: one record per 4 output columns (index xtab_off / 4 + group)
   int32_t* d_xsxa = nullptr;         // first source byte of the group's 8-byte window, -1 = byte path
+  ResizePair* d_xpairs = nullptr;    // k_resize_linear: one record per 8 output columns (index xtab_off / 4 + pair: a level has at most as many pairs as groups)
+  int32_t* d_xwin = nullptr;         // first source byte of the pair's 12-byte window, -1 = the two groups on their own records
   uint8_t* d_rootx = nullptr;
   int8_t* d_pattern = nullptr;
   // ---- device buffers
@@ -443,6 +445,42 @@ int upload_tables(rgbl_extractor* e) {
         sxas[G] = ok ? sxa : -1;
       }
     }
+    // pairs of groups on one 12-byte window: group 0 on the words (0, 1), group 1 on the words (1, 2).  The window starts as
+    // far right as both groups and the row's end allow; where no start serves both (scale factors above ~1.4, and the last
+    // pair of a row whose taps reach the row's last four bytes) the pair is left to its groups' records.  Both taps of a
+    // column, sofs and sofs + 1, must lie inside the window, also where sofs + 1 == sw carries the weight 0 (the byte path
+    // clamps that index; the group builder above asks the same), so such a pair is never given a window.  A level with an odd
+    // number of groups ends in a pair of one group: only that group has to fit, the other half repeats its last column and
+    // lands in the padding of the row.
+    std::vector<ResizePair> pairs(groups.size());
+    std::vector<int32_t> wins(groups.size(), -1);
+    memset(pairs.data(), 0, sizeof(ResizePair) * pairs.size());
+    for (int l = 1; l < L; ++l) {
+      const int sw = e->geom[l - 1].w;
+      const size_t g0 = e->geom[l].xtab_off / 4, g1 = (l + 1 < L ? e->geom[l + 1].xtab_off : xt.size()) / 4;
+      const int ng = (int)(g1 - g0);
+      for (int P = 0; 2 * P < ng; ++P) {
+        const ResizeTab* X = xt.data() + 4 * g0 + 8 * (size_t)P;
+        const int n = std::min(8, 4 * ng - 8 * P);
+        int hi = sw - 12, lo = 0;   // the window's first byte lies in lo .. hi
+        for (int i = 0; i < n; ++i) {
+          hi = std::min(hi, (int)X[i].sofs - 4 * (i >> 2));
+          lo = std::max(lo, (int)X[i].sofs + 1 - 4 * (i >> 2) - 7);
+        }
+        ResizePair& R = pairs[g0 + P];
+        for (int i = 0; i < 8; ++i) {
+          const ResizeTab& T = X[std::min(i, n - 1)];
+          const uint32_t o = (uint32_t)std::min(std::max((int)T.sofs - hi - 4 * (i >> 2), 0), 6);
+          R.sel[i] = o | (0x0cu << 8) | ((o + 1) << 16) | (0x0cu << 24);
+          R.w[i] = (uint32_t)(uint16_t)T.a0 | ((uint32_t)(uint16_t)T.a1 << 16);
+        }
+        wins[g0 + P] = hi >= lo ? hi : -1;
+      }
+    }
+    RGBL_TRY(dev_alloc(e, &e->d_xpairs, pairs.size()));
+    RGBL_TRY(dev_alloc(e, &e->d_xwin, wins.size()));
+    RGBL_HIP(hipMemcpy(e->d_xpairs, pairs.data(), sizeof(ResizePair) * pairs.size(), hipMemcpyHostToDevice));
+    RGBL_HIP(hipMemcpy(e->d_xwin, wins.data(), sizeof(int32_t) * wins.size(), hipMemcpyHostToDevice));
     RGBL_TRY(dev_alloc(e, &e->d_xgroups, groups.size()));
     RGBL_TRY(dev_alloc(e, &e->d_xsxa, sxas.size()));
     RGBL_HIP(hipMemcpy(e->d_xgroups, groups.data(), sizeof(ResizeGroup) * groups.size(), hipMemcpyHostToDevice));
@@ -754,9 +792,10 @@ int enqueue_extract(rgbl_extractor* e, const uint8_t* d_imgs, int batch, int str
     const int spitch = (l == 1) ? stride : p.pitch;
     const size_t sframe = (l == 1) ? frame_stride : e->pyr_frame;
     e->timer.begin("k_resize_linear", st);
-    const int rtx = (g.w + 4 * kResizeLanes - 1) / (4 * kResizeLanes), rty = (g.h + 4 * kResizeRows - 1) / (4 * kResizeRows);
+    const int rtx = (g.w + 8 * kResizeLanes - 1) / (8 * kResizeLanes), rty = (g.h + 4 * kResizeRows - 1) / (4 * kResizeRows);
     hipLaunchKernelGGL(k_resize_linear, xcd_grid(e->sw.xcd_map, rtx * rty, batch), dim3(kResizeWG), 0, st, src, spitch, sframe, p.w, p.h, e->d_pyr + g.img_off, g.pitch, e->pyr_frame, g.w, g.h,
-                     e->d_xtab + g.xtab_off, e->d_xgroups + g.xtab_off / 4, e->d_xsxa + g.xtab_off / 4, e->d_ytab + g.ytab_off, rtx);
+                     e->d_xtab + g.xtab_off, e->d_xgroups + g.xtab_off / 4, e->d_xsxa + g.xtab_off / 4, e->d_xpairs + g.xtab_off / 4,
+                     e->d_xwin + g.xtab_off / 4, e->d_ytab + g.ytab_off, rtx);
     e->timer.end(st);
   };
   const bool lapping = lap1 >= 19 && lap1 >= lap0;  // keypoint x is always >= 19: nothing can fall into [lap0, lap1] otherwise

@@ -77,55 +77,50 @@ __device__ __forceinline__ int key_y(uint32_t k) { return (int)((k >> 12) & 0xff
 __device__ __forceinline__ int key_s(uint32_t k) { return (int)(k >> 24); }
 
 // ------------------------------------------------------------------------------------------------
-// cv::resize(INTER_LINEAR, CV_8UC1): 11-bit fixed-point bilinear, each work-item makes 4 output pixels of one
-// row.  The 4 outputs read a short run of source pixels (about 6 at scale 1.2) from two rows: those are fetched
-// as two 32-bit words per row (8 bytes from the first source column) instead of 16 byte loads; the coefficient
-// table entries of the 4 columns are one 32-byte read.  grid = (ceil(dw / (4 kResizeLanes)), ceil(dh / 16), B), block = kResizeLanes x 4.
+// cv::resize(INTER_LINEAR, CV_8UC1): 11-bit fixed-point bilinear, each work-item makes 8 output pixels (two groups of 4) of
+// kResizeRows rows.  The 8 outputs read a short run of source pixels (about 11 at scale 1.2) from two rows: those are
+// fetched as ONE 12-byte window per source row (three words from the window's first byte) instead of 20 byte loads; the
+// selectors and weights of the 8 columns are one 64-byte record.  grid = xcd_grid(ceil(dw / (8 kResizeLanes)) *
+// ceil(dh / (4 kResizeRows)), B), block = kResizeLanes x 4.
 __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t* p) {
   uint32_t v;
   __builtin_memcpy(&v, p, 4);  // level 0 may have an odd row stride: gfx950 global loads need no alignment
   return v;
 }
 
-constexpr int kResizeRows = 4;  // output rows per work-item (1 / 2 / 4 measured: 4 is 6 % ahead of 1 on the whole step)
-// A workgroup covers kResizeLanes * 4 output columns x 16 rows.  With 64 lanes per row (256 columns) the last workgroup
-// column of a level is mostly empty (1034 columns = 4.04 workgroups: 83 % of the launched lanes work over the 7 levels);
-// 32 lanes per row leave 92 % (0.595 -> 0.575 ms; 16 lanes per row: 0.58).
-constexpr int kResizeLanes = 32, kResizeWG = kResizeLanes * 4;
+constexpr int kResizeRows = 4;  // output rows per work-item (2 rows: 1.02 instead of 0.95 ms over the 7 levels, docs/history/r14_measured.md)
+// A workgroup covers kResizeLanes * 8 output columns x 16 rows: 16 lanes per row are the 128 columns that 32 lanes of 4
+// columns were (wider workgroups leave the last workgroup column of a level mostly empty: 1034 columns = 4.04 workgroups of
+// 256 columns, 83 % of the launched lanes working over the 7 levels against 92 %; 32 lanes per row: 1.04 ms).
+constexpr int kResizeLanes = 16, kResizeWG = kResizeLanes * 4;
 // One group of 4 output columns, prepared by the host: the 8-byte source window (pulled back at the end of a row so that it
 // stays inside it), per column the v_perm_b32 selector that pulls its two taps out of the window as two 16-bit halves and
 // the two 11-bit weights packed the same way (one v_dot2_u32_u16 per source row and column).  sxa < 0: the taps of the
 // group do not fit 8 bytes (scale factors above ~1.7) or the source is narrower than 8 px - byte path.
 struct ResizeGroup { uint32_t sel[4], w[4]; };
 static_assert(sizeof(ResizeGroup) == 32, "two 16-byte loads per group");
+// Two adjacent groups (8 output columns) on ONE 12-byte source window (words 0 1 2 from its first byte, pulled back at the
+// end of a row so that it stays inside it): the first group's selectors address the word pair (0, 1), the second group's
+// the pair (1, 2) - at the scale 1.2 the second group's taps lie in the bytes 4 .. 10 - so the kernel selects no registers.
+// The window's first byte is < 0 where the taps of a group do not fit its pair (scale factors above ~1.4, the last pair of
+// a row where the pulled-back window leaves them outside, sources narrower than 12 px): the work-item then runs its two
+// groups on their ResizeGroup records, byte path included.
+struct ResizePair { uint32_t sel[8], w[8]; };
+static_assert(sizeof(ResizePair) == 64, "four 16-byte loads per pair");
 
-__global__ __launch_bounds__(kResizeWG) void k_resize_linear(const uint8_t* __restrict__ src, int spitch,
-                                                       size_t sframe, int sw, int sh,
-                                                       uint8_t* __restrict__ dst, int dpitch, size_t dframe,
-                                                       int dw, int dh, const ResizeTab* __restrict__ xtab,
-                                                       const ResizeGroup* __restrict__ xgroups, const int32_t* __restrict__ xsxa,
-                                                       const ResizeTab* __restrict__ ytab, int tiles_x) {
-  // grid = xcd_grid(tiles_x * tiles_y, B) (common.h)
-  const int tx = threadIdx.x % kResizeLanes, ty = threadIdx.x / kResizeLanes;
-  const int tile_y = xcd_item() / tiles_x, tile_x = xcd_item() - tile_y * tiles_x;
-  const int dx0 = (tile_x * kResizeLanes + tx) * 4;
-  const int dy0 = (tile_y * 4 + ty) * kResizeRows;
-  if (dy0 >= dh || dx0 >= dw) return;
-  const uint8_t* S = src + (size_t)xcd_frame() * sframe;
-  uint8_t* D = dst + (size_t)xcd_frame() * dframe + (size_t)dy0 * dpitch;
-  // the group's record and the row table are requested before either is used (one round trip, not two); the x table is
+// one group of 4 output columns x kResizeRows rows on its 8-byte windows (or byte by byte): dx0 < dw, dy0 < dh
+__device__ __forceinline__ void resize_group(const uint8_t* __restrict__ S, int spitch, int sw, int sh, uint8_t* __restrict__ D, int dpitch,
+                                             int dw, int dh, int dx0, int dy0, const ResizeTab (&ry)[kResizeRows],
+                                             const ResizeTab* __restrict__ xtab, const ResizeGroup* __restrict__ xgroups,
+                                             const int32_t* __restrict__ xsxa) {
+  // the group's record and its window are requested before either is used (one round trip, not two); the x table is
   // padded to a multiple of 4 entries per level with copies of the last entry
   const int sxa = xsxa[dx0 >> 2];
   const uint4* g4 = reinterpret_cast<const uint4*>(xgroups + (dx0 >> 2));
   const uint4 gs = g4[0], gw = g4[1];
-  // the kResizeRows rows' vertical taps; rows past the image repeat the last one (computed, not stored)
-  ResizeTab ry[kResizeRows];
-#pragma unroll
-  for (int r = 0; r < kResizeRows; ++r) ry[r] = ytab[imin(dy0 + r, dh - 1)];
   if (sxa >= 0) {
-    // all 4 kResizeRows source windows are requested before the first one is used: a wave keeps 4 KB in flight, the
-    // kernel is bound by the round trips per byte otherwise (one row per work-item ran at 1.2 TB/s).  The last (partial)
-    // group of a row takes this path too and stores a full word (the level's row pitch is 64-byte aligned).
+    // all 4 kResizeRows source windows are requested before the first one is used.  The last (partial) group of a row takes
+    // this path too and stores a full word (the level's row pitch is 64-byte aligned).
     uint32_t r0l[kResizeRows], r0h[kResizeRows], r1l[kResizeRows], r1h[kResizeRows];
 #pragma unroll
     for (int r = 0; r < kResizeRows; ++r) {
@@ -186,6 +181,64 @@ __global__ __launch_bounds__(kResizeWG) void k_resize_linear(const uint8_t* __re
     } else {
       for (int i = 0; dx0 + i < dw; ++i) Dr[dx0 + i] = (uint8_t)(out >> (8 * i));
     }
+  }
+}
+
+__global__ __launch_bounds__(kResizeWG) void k_resize_linear(const uint8_t* __restrict__ src, int spitch,
+                                                       size_t sframe, int sw, int sh,
+                                                       uint8_t* __restrict__ dst, int dpitch, size_t dframe,
+                                                       int dw, int dh, const ResizeTab* __restrict__ xtab,
+                                                       const ResizeGroup* __restrict__ xgroups, const int32_t* __restrict__ xsxa,
+                                                       const ResizePair* __restrict__ xpairs, const int32_t* __restrict__ xwin,
+                                                       const ResizeTab* __restrict__ ytab, int tiles_x) {
+  // grid = xcd_grid(tiles_x * tiles_y, B) (common.h)
+  const int tx = threadIdx.x % kResizeLanes, ty = threadIdx.x / kResizeLanes;
+  const int tile_y = xcd_item() / tiles_x, tile_x = xcd_item() - tile_y * tiles_x;
+  const int dx0 = (tile_x * kResizeLanes + tx) * 8;
+  const int dy0 = (tile_y * 4 + ty) * kResizeRows;
+  if (dy0 >= dh || dx0 >= dw) return;
+  const uint8_t* S = src + (size_t)xcd_frame() * sframe;
+  uint8_t* D = dst + (size_t)xcd_frame() * dframe + (size_t)dy0 * dpitch;
+  // the pair's window, its record and the row table are requested before any of them is used
+  const int wa = xwin[dx0 >> 3];
+  const uint4* p4 = reinterpret_cast<const uint4*>(xpairs + (dx0 >> 3));
+  const uint4 ps0 = p4[0], ps1 = p4[1], pw0 = p4[2], pw1 = p4[3];
+  // the kResizeRows rows' vertical taps; rows past the image repeat the last one (computed, not stored)
+  ResizeTab ry[kResizeRows];
+#pragma unroll
+  for (int r = 0; r < kResizeRows; ++r) ry[r] = ytab[imin(dy0 + r, dh - 1)];
+  if (wa < 0) {
+    resize_group(S, spitch, sw, sh, D, dpitch, dw, dh, dx0, dy0, ry, xtab, xgroups, xsxa);
+    if (dx0 + 4 < dw) resize_group(S, spitch, sw, sh, D, dpitch, dw, dh, dx0 + 4, dy0, ry, xtab, xgroups, xsxa);
+    return;
+  }
+  // all 2 kResizeRows source windows are requested before the first one is used: a wave keeps 6 KB in flight, the kernel is
+  // bound by the round trips per byte otherwise.  The last (partial) pair of a row takes this path too where its window fits
+  // and stores both words (the level's row pitch is 64-byte aligned; the record of a group past the row repeats the last column).
+  uint32_t r0[kResizeRows][3], r1[kResizeRows][3];
+#pragma unroll
+  for (int r = 0; r < kResizeRows; ++r) {
+    const int sy0 = imin(imax(ry[r].sofs, 0), sh - 1), sy1 = imin(imax(ry[r].sofs + 1, 0), sh - 1);
+    __builtin_memcpy(r0[r], S + (size_t)sy0 * spitch + wa, 12);
+    __builtin_memcpy(r1[r], S + (size_t)sy1 * spitch + wa, 12);
+  }
+  const uint32_t sel[8] = {ps0.x, ps0.y, ps0.z, ps0.w, ps1.x, ps1.y, ps1.z, ps1.w};
+  const uint32_t wt[8] = {pw0.x, pw0.y, pw0.z, pw0.w, pw1.x, pw1.y, pw1.z, pw1.w};
+#pragma unroll
+  for (int r = 0; r < kResizeRows; ++r) {
+    const int b0 = ry[r].a0, b1 = ry[r].a1;
+    uint32_t out[2] = {0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int g = i >> 2;  // group g reads the words g, g + 1
+      const int h0 = (int)udot2(perm_bytes(r0[r][g + 1], r0[r][g], sel[i]), wt[i], 0u);  // p00 a0 + p01 a1
+      const int h1 = (int)udot2(perm_bytes(r1[r][g + 1], r1[r][g], sel[i]), wt[i], 0u);
+      const int v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+      out[g] |= (uint32_t)(v & 0xff) << (8 * (i & 3));
+    }
+    uint2 o;
+    o.x = out[0]; o.y = out[1];
+    if (dy0 + r < dh) *reinterpret_cast<uint2*>(D + (size_t)r * dpitch + dx0) = o;  // dpitch and dx0 are multiples of 8
   }
 }
 
@@ -770,15 +823,15 @@ __global__ __launch_bounds__(256) void k_compact_cells(const CellGroup* __restri
 
 // ------------------------------------------------------------------------------------------------
 // 7x7 Gaussian, sigma 2, OpenCV's 8.8 fixed-point kernel {18,34,48,56,48,34,18}; BORDER_REFLECT_101.
-// Tile = 128 x 32 outputs per workgroup.  Pass 1 reads the source rows straight from HBM as three 32-bit
-// words per 4 pixels and leaves the horizontal sums (exact 16-bit 8.8 values) in LDS; pass 2 gives every
-// work-item a 4 x 4 output block: five 16-byte LDS reads, four 32-bit stores.
-// grid = (tiles per frame over all levels, B), block = 256.
+// Tile = 128 x 32 outputs per workgroup.  Pass 1 reads the source rows straight from HBM as one 16-byte
+// request per 8 pixels and leaves the horizontal sums (exact 16-bit 8.8 values) in LDS; pass 2 gives every
+// work-item a 4 x 4 output block: five 16-byte LDS reads, one 128-bit store.
+// grid = xcd_grid(tiles of the launch, B) (common.h), block = BS (128; 256 with RGBL_GAUSS_BS=256).
 constexpr int kBlurTW = 128, kBlurTH = 32;
 struct BlurTiles { int tile_off[kMaxLevels + 1]; int tiles_x[kMaxLevels]; };
 
-// The filter runs on the VALU's integer dot products.  Horizontal: a work-item owns 4 output columns of two rows; the
-// seven taps of an output are two v_dot4_u32_u8 over byte-aligned windows (v_alignbyte_b32) of the row's three words with
+// The filter runs on the VALU's integer dot products.  Horizontal: a work-item owns 8 output columns of two rows; the
+// seven taps of an output are two v_dot4_u32_u8 over byte-aligned windows (v_alignbyte_b32) of the row's four words with
 // the weights {18,34,48,56} / {48,34,18,0}.  The exact 16-bit sums of the two rows share a word (row pair j = rows 2j,
 // 2j + 1), so the vertical pass is four v_dot2_u32_u16 per output over five such words, the rounding constant being the
 // initial accumulator: even output rows take the weights (18,34)(48,56)(48,34)(18,0), odd ones (0,18)(34,48)(56,48)(34,18).
@@ -802,6 +855,7 @@ __global__ __launch_bounds__(BS) void k_gauss7(const GaussTile* __restrict__ til
                                                     const uint8_t* __restrict__ pyr, size_t pyr_frame,
                                                     uint8_t* __restrict__ blur, size_t blur_frame, int tile_begin) {
   constexpr int kPairs = (kBlurTH + 6) / 2;       // 19 row pairs
+  constexpr int kGroups = kBlurTW / 8;            // 16 groups of 8 columns
   __shared__ uint32_t s_p[kPairs * kBlurTW];      // [pair][column]: sum of row 2j | sum of row 2j + 1 << 16
   const int f = xcd_frame();
   const int tid = threadIdx.x, bx = xcd_item() + tile_begin;
@@ -812,65 +866,62 @@ __global__ __launch_bounds__(BS) void k_gauss7(const GaussTile* __restrict__ til
   const int W = T.w, H = T.h;
   const uint32_t kWA = 18u | (34u << 8) | (48u << 16) | (56u << 24), kWB = 48u | (34u << 8) | (18u << 16);
 
-  // one row pair x four columns: seven-tap sums of both rows from their three words each, stored as one 128-bit LDS write
-  auto h_sums = [&](const uint32_t (&w)[2][3], int j, int cg) {
-    uint32_t hs[2][4];
+  // eight columns of one row: the seven-tap sums of the outputs x .. x + 7 from the row's four words (pixels x - 4 .. x + 11)
+  auto h_row = [&](const uint32_t (&w)[4], uint32_t (&hs)[8]) {
 #pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {  // output x + i: pixels x+i-3 .. x+i+3 = bytes i+1 .. i+7 of the 12
-        const uint32_t lo = i == 3 ? w[rr][1] : align_bytes(w[rr][1], w[rr][0], i + 1);
-        const uint32_t hi = i == 3 ? w[rr][2] : align_bytes(w[rr][2], w[rr][1], i + 1);
-        hs[rr][i] = udot4(lo, kWA, udot4(hi, kWB, 0u));
-      }
+    for (int i = 0; i < 8; ++i) {  // output x + i: pixels x+i-3 .. x+i+3 = bytes i+1 .. i+7 of the 16 (byte 15 meets the zero weight)
+      const int k = i >> 2, s = (i & 3) + 1;
+      const uint32_t lo = s == 4 ? w[k + 1] : align_bytes(w[k + 1], w[k], s);
+      const uint32_t hi = s == 4 ? w[k + 2] : align_bytes(w[k + 2], w[k + 1], s);
+      hs[i] = udot4(lo, kWA, udot4(hi, kWB, 0u));
     }
-    uint4 v;
-    v.x = hs[0][0] | (hs[1][0] << 16); v.y = hs[0][1] | (hs[1][1] << 16);
-    v.z = hs[0][2] | (hs[1][2] << 16); v.w = hs[0][3] | (hs[1][3] << 16);
-    *reinterpret_cast<uint4*>(&s_p[j * kBlurTW + 4 * cg]) = v;
   };
-  // interior column groups: all six words requested before the first use.  The groups that touch the left or right border
-  // of the level are left to a second, compacted pass - inside this loop two lanes per wave would drag the other 62 through
-  // the byte-wise path in every iteration of every tile in the first and last tile column.
+  // interior column groups, one row pair x eight columns per task: ONE 16-byte request per row (x - 4 .. x + 11 lies inside
+  // the row: 4-byte aligned on the levels >= 1, of any alignment on the caller's image), both requested before the first use;
+  // the sums leave as two 128-bit LDS writes.  The groups that touch the left or right border of the level are left to a
+  // second, compacted pass - inside this loop two lanes per wave would drag the other 62 through the byte-wise path in every
+  // iteration of every tile in the first and last tile column.
   const bool rows_inside = y0 >= 3 && y0 + kBlurTH + 3 <= H;
-  for (int task = tid; task < kPairs * 32; task += BS) {
-    const int j = task >> 5, cg = task & 31;
-    const int x = x0 + 4 * cg;
-    if (x < 4 || x + 8 > W) continue;
+  for (int task = tid; task < kPairs * kGroups; task += BS) {
+    const int j = task / kGroups, cg = task % kGroups;
+    const int x = x0 + 8 * cg;
+    if (x < 4 || x + 12 > W) continue;
     // tiles whose rows y0 - 3 .. y0 + 34 all exist (every tile but the first and last tile row of a level) skip the reflection
     int ya = y0 + 2 * j - 3, yb = ya + 1;
     if (!rows_inside) { ya = reflect101(ya, H); yb = reflect101(yb, H); }   // uniform
-    const uint8_t* row0 = img + __umul24((uint32_t)ya, (uint32_t)pitch) + x;
-    const uint8_t* row1 = img + __umul24((uint32_t)yb, (uint32_t)pitch) + x;
-    uint32_t w[2][3];
-    w[0][0] = load_u32_unaligned(row0 - 4); w[0][1] = load_u32_unaligned(row0); w[0][2] = load_u32_unaligned(row0 + 4);
-    w[1][0] = load_u32_unaligned(row1 - 4); w[1][1] = load_u32_unaligned(row1); w[1][2] = load_u32_unaligned(row1 + 4);
-    h_sums(w, j, cg);
+    uint4 q0, q1;
+    __builtin_memcpy(&q0, img + __umul24((uint32_t)ya, (uint32_t)pitch) + x - 4, 16);
+    __builtin_memcpy(&q1, img + __umul24((uint32_t)yb, (uint32_t)pitch) + x - 4, 16);
+    const uint32_t w0[4] = {q0.x, q0.y, q0.z, q0.w}, w1[4] = {q1.x, q1.y, q1.z, q1.w};
+    uint32_t h0[8], h1[8];
+    h_row(w0, h0);
+    h_row(w1, h1);
+    uint4* dst = reinterpret_cast<uint4*>(&s_p[j * kBlurTW + 8 * cg]);
+    dst[0] = make_uint4(h0[0] | (h1[0] << 16), h0[1] | (h1[1] << 16), h0[2] | (h1[2] << 16), h0[3] | (h1[3] << 16));
+    dst[1] = make_uint4(h0[4] | (h1[4] << 16), h0[5] | (h1[5] << 16), h0[6] | (h1[6] << 16), h0[7] | (h1[7] << 16));
   }
-  // border column groups of this tile: group 0 of the first tile column, and the groups with x + 8 > W (at most two)
+  // border column groups of this tile: group 0 of the first tile column, and the groups with x + 12 > W (at most two).  One
+  // ROW x eight columns per task (15 byte loads; a row pair per task would hold 30 in flight and cost the kernel two waves
+  // per SIMD in registers); a row's sums are the low or the high halves of its pair's words.
   {
-    const int cg_last = imin(31, (W - 1 - x0) >> 2);                    // last group that holds a pixel of the level
-    const int cg_r0 = imax(0, imin(cg_last + 1, ((W - 8 - x0) >> 2) + 1));  // first group with x + 8 > W (W >= 8 always)
-    const int n_right = (x0 + 4 * cg_r0 + 8 > W) ? cg_last - cg_r0 + 1 : 0;
-    const int n_left = (x0 == 0 && cg_r0 > 0) ? 1 : 0;                  // x = 0 < 4 (when it is not a right-border group too)
+    const int cg_last = imin(kGroups - 1, (W - 1 - x0) >> 3);              // last group that holds a pixel of the level
+    const int cg_r0 = imax(0, imin(cg_last + 1, ((W - 12 - x0) >> 3) + 1));  // first group with x + 12 > W (arithmetic shift: floor)
+    const int n_right = (x0 + 8 * cg_r0 + 12 > W) ? cg_last - cg_r0 + 1 : 0;
+    const int n_left = (x0 == 0 && cg_r0 > 0) ? 1 : 0;                     // x = 0 < 4 (when it is not a right-border group too)
     const int n_edge = n_left + n_right;
-    for (int task = tid; task < kPairs * n_edge; task += BS) {
-      const int j = task / n_edge, e = task - j * n_edge;
+    uint16_t* s_h = reinterpret_cast<uint16_t*>(s_p);
+    for (int task = tid; task < 2 * kPairs * n_edge; task += BS) {
+      const int r = task / n_edge, e = task - r * n_edge;                  // r = row y0 - 3 + r of the 38
       const int cg = e < n_left ? 0 : cg_r0 + (e - n_left);
-      const int x = x0 + 4 * cg;
-      uint32_t w[2][3];
+      const int x = x0 + 8 * cg;
+      const uint32_t ro = __umul24((uint32_t)reflect101(y0 + r - 3, H), (uint32_t)pitch);
+      uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-      for (int rr = 0; rr < 2; ++rr) {
-        const uint8_t* row = img + __umul24((uint32_t)reflect101(y0 + 2 * j + rr - 3, H), (uint32_t)pitch);
-        w[rr][0] = w[rr][1] = w[rr][2] = 0;
+      for (int k = 0; k < 15; ++k) w[k >> 2] |= (uint32_t)img[ro + (uint32_t)reflect101(x - 4 + k, W)] << (8 * (k & 3));
+      uint32_t hs[8];
+      h_row(w, hs);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          w[rr][0] |= (uint32_t)row[reflect101(x - 4 + k, W)] << (8 * k);
-          w[rr][1] |= (uint32_t)row[reflect101(x + k, W)] << (8 * k);
-          w[rr][2] |= (uint32_t)row[reflect101(x + 4 + k, W)] << (8 * k);
-        }
-      }
-      h_sums(w, j, cg);
+      for (int i = 0; i < 8; ++i) s_h[2 * ((r >> 1) * kBlurTW + 8 * cg + i) + (r & 1)] = (uint16_t)hs[i];
     }
   }
   __syncthreads();
