@@ -974,6 +974,63 @@ int rgbl_frustum_cull(rgbl_matcher* h, const rgbl_track_local_input* in, uint8_t
 int rgbl_track_local_points(rgbl_matcher* h, const rgbl_track_local_input* in, uint8_t* in_view, rgbl_frustum_record* rec,
                             int* n_to_match, int32_t* match2, int* out_nmatches);
 
+/* int Optimizer::PoseOptimization(Frame* pFrame) (include/Optimizer.h, src/Optimizer.cc:814-1114): the motion-only bundle
+ * adjustment Tracking runs after every search (src/Tracking.cc:2779, :2943, :3005 / :3011, :3748-3779), one workgroup per
+ * frame.  Single-camera pinhole frames (pFrame->mpCamera2 == nullptr, Pinhole): monocular edges (uright < 0, :866-893) and
+ * stereo / RGB-L edges (uright >= 0, :894-927) mixed; the rig branch (:930-991), KannalaBrandt8 and the inertial variants
+ * (:4491, :4875) have no form here.  csrc/poseopt_math.h restates the function and the parts of g2o it runs, and says what is
+ * pinned (control flow, the quirks, the summation order) and what is not (Eigen's LDLT, libm's sin / cos). */
+typedef struct {
+  int n;                       /* pFrame->N */
+  const int32_t* mp_index;     /* per feature: index of pFrame->mvpMapPoints[i] in the map side below, -1 = no map point */
+  int n_points;                /* entries of the map side */
+  /* map side, form 1 (pool == NULL): host array */
+  const float* world_pos;      /* pMP->GetWorldPos(), 3 floats per point */
+  /* map side, form 2: slots of a pool on the matcher's device (the call holds the pool's mutex for its duration) */
+  rgbl_map_points* pool;
+  const int32_t* slot;         /* n_points slots in [0, capacity) */
+  /* frame side: host arrays, or the resident frame (the three arrays are then not read) */
+  const float* kp_xy;          /* mvKeysUn[i].pt, n x 2 */
+  const int32_t* kp_octave;    /* mvKeysUn[i].octave */
+  const float* uright;         /* mvuRight */
+  const rgbl_device_frame* device;
+  float Tcw_q[4];              /* GetPose().unit_quaternion(): x, y, z, w */
+  float Tcw_t[3];              /* GetPose().translation() */
+  float K[4];                  /* fx, fy, cx, cy (:916-919; the Pinhole's mvParameters for a monocular edge) */
+  float bf;                    /* mbf */
+  const float* inv_level_sigma2; /* mvInvLevelSigma2, n_levels entries */
+  int n_levels;                /* 1 .. 16 */
+} rgbl_pose_opt_input;
+/* per round of :1006-1104 (rounds of them were run; the others are 0) */
+typedef struct {
+  int32_t iterations[4];       /* Levenberg iterations of the round's optimize() (0: no active edge) */
+  int32_t active[4];           /* edges on level 0 when the round began */
+  double chi2[4];              /* the robust chi2 of the active edges when optimize() returned (0 without iteration) */
+  int32_t rounds, reserved;
+  double Tcw_q[4], Tcw_t[3];   /* the vertex estimate in double, before :1109-1110 cast it to float */
+} rgbl_pose_opt_diag;
+typedef struct {
+  float Tcw_q[4], Tcw_t[3];    /* what :1107-1111 hands to SetPose, x y z w; the input pose, bit for bit, when result is 0 because
+                                  there are fewer than 3 correspondences (:996-997) */
+  uint8_t* outlier;            /* mvbOutlier, n bytes, written only where mp_index >= 0 */
+  int result;                  /* the reference's return value: nInitialCorrespondences - nBad */
+  rgbl_pose_opt_diag diag;
+} rgbl_pose_opt_output;
+/* One frame (replaces Optimizer.cc:814-1114).  Host pointers, synchronous, one upload and one read-back.
+ * RGBL_ERR_INVALID, before anything is launched and with every output untouched: mp_index outside [-1, n_points); a slot
+ * outside the pool; an octave outside [0, n_levels) on a feature with a map point (host arrays; a resident frame's octaves
+ * are clamped on the device, the host does not hold them); a frame whose size is not n, or a frame or pool on another device
+ * than the matcher; a pose, K or bf that is not finite; n_levels outside 1 .. 16; more than 65535 features. */
+int rgbl_pose_optimization(rgbl_matcher* h, const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out);
+/* B independent frames (the candidates of Tracking::Relocalization, :3748-3779, or an offline pipeline), each with its own
+ * pose, K and bf, in ONE launch: the correspondences are packed back to back behind an offsets array, workgroup b runs
+ * problem b.  One upload, one read-back.  A problem with n = 0 or fewer than 3 correspondences is valid (result 0).  Problems
+ * that name a pool must name the same one.  Errors as above: nothing is launched and no problem's output is written. */
+int rgbl_pose_optimization_batch(rgbl_matcher* h, int n_problems, const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out);
+/* rgbl_pose_optimization evaluated by the HOST build of csrc/poseopt_math.h (no device, no handle): the same bits.  The
+ * frame and map sides must be host arrays (device and pool NULL). */
+int rgbl_pose_optimization_host(const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out);
+
 /* ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>& vbPrevMatched, vector<int>& vnMatches12,
  * int windowSize)    /root/reference/include/ORBmatcher.h:72, src/ORBmatcher.cc:648-763 (Tracking::MonocularInitialization,
  * src/Tracking.cc:2526; not on the RGB-L / stereo path - built so that every search routine of ORBmatcher has a device form).

@@ -70,6 +70,24 @@ NEW_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4
                             ("reserved", "u1", (3,))])
 
 
+class PoseOptInput(C.Structure):
+    """rgbl_pose_opt_input (a Frame as Optimizer::PoseOptimization reads it)."""
+    _fields_ = [("n", C.c_int), ("mp_index", C.c_void_p), ("n_points", C.c_int), ("world_pos", C.c_void_p), ("pool", C.c_void_p),
+                ("slot", C.c_void_p), ("kp_xy", C.c_void_p), ("kp_octave", C.c_void_p), ("uright", C.c_void_p),
+                ("device", C.c_void_p), ("Tcw_q", C.c_float * 4), ("Tcw_t", C.c_float * 3), ("K", C.c_float * 4), ("bf", C.c_float),
+                ("inv_level_sigma2", C.c_void_p), ("n_levels", C.c_int)]
+
+
+class PoseOptDiag(C.Structure):
+    _fields_ = [("iterations", C.c_int32 * 4), ("active", C.c_int32 * 4), ("chi2", C.c_double * 4), ("rounds", C.c_int32),
+                ("reserved", C.c_int32), ("Tcw_q", C.c_double * 4), ("Tcw_t", C.c_double * 3)]
+
+
+class PoseOptOutput(C.Structure):
+    _fields_ = [("Tcw_q", C.c_float * 4), ("Tcw_t", C.c_float * 3), ("outlier", C.c_void_p), ("result", C.c_int),
+                ("diag", PoseOptDiag)]
+
+
 class ProjectionInput(C.Structure):
     """rgbl_projection_input (ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) as flat arrays)."""
     _fields_ = [("n1", C.c_int), ("valid1", C.c_void_p), ("world_pos1", C.c_void_p), ("mp_desc1", C.c_void_p),
@@ -299,6 +317,9 @@ SYMBOLS = {
                                            _I, _V, _V, _V]),
     "rgbl_create_new_map_points": (_I, [_V, C.POINTER(NewPointsKeyframe), _I, _V, _V, _V, C.POINTER(NewPointsParams), _V, _I,
                                         C.POINTER(_I), _V, _V]),
+    "rgbl_pose_optimization": (_I, [_V, C.POINTER(PoseOptInput), C.POINTER(PoseOptOutput)]),
+    "rgbl_pose_optimization_batch": (_I, [_V, _I, _V, _V]),
+    "rgbl_pose_optimization_host": (_I, [C.POINTER(PoseOptInput), C.POINTER(PoseOptOutput)]),
     "rgbl_search_by_bow": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_rig": (_I, [_V, _V, _V, _I, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_keyframes": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),

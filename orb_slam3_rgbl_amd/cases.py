@@ -833,3 +833,64 @@ def make_new_points_case(n=600, n_neigh=10, seed=7, n_nodes=None, th_far_points=
     prm = dict(n_levels=n_levels, ratio_factor=float(f32(1.5) * f32(1.2)), far_points=int(th_far_points is not None),
                th_far_points=float(th_far_points or 0.0), inertial=int(inertial), monocular=int(monocular), report_rejected=int(report_rejected))
     return dict(kf1=kf1, neighbours=neighbours, skip=skip, prm=prm)
+
+
+def make_pose_opt_case(n=2000, matched=300, seed=3, mono_share=0.2, outlier_share=0.1, n_levels=8, scale_factor=1.2,
+                       rot_noise=0.01, trans_noise=0.15, pixel_noise=1.0):
+    """A frame as Optimizer::PoseOptimization reads it (Optimizer.cc:814-1114), deterministic by seed: `matched` of the n features
+    have a map point 4 - 60 m in front of a KITTI camera (stored as float), octaves 0 .. n_levels - 1, pixel noise proportional to
+    the level's sigma, a planted share of gross outliers (+-40 px), a share of monocular features (uright = -1), and an entry
+    pose that is the planted one perturbed by about rot_noise rad and trans_noise m.
+    Keys: the frame dict of frontend.ORBmatcher.PoseOptimization (mp_index, world_pos, xy, octave, uright, q, t, K, bf,
+    inv_level_sigma2) plus the plant: q_true, t_true, planted_outlier (per feature)."""
+    rng = np.random.default_rng(seed)
+    cam = _kitti_camera()
+    fx, fy, cx, cy = [float(v) for v in cam.K]
+    bf = float(np.float32(cam.mbf))
+    sf = np.array([scale_factor ** i for i in range(n_levels)], np.float32)
+    inv_sigma2 = (np.float32(1.0) / (sf * sf)).astype(np.float32)
+    axis = rng.normal(size=3)
+    q_true = _quat(axis, rng.uniform(0.0, 0.3))
+    t_true = rng.uniform(-2.0, 2.0, 3).astype(np.float32)
+    R = _rot(q_true)
+    matched = min(matched, n)
+    feat = np.sort(rng.choice(n, matched, replace=False)) if matched else np.zeros(0, np.int64)
+    # points in the camera frame, then to the world: Xw = R^T (Xc - t)
+    z = rng.uniform(4.0, 60.0, matched)
+    u = rng.uniform(20.0, cam.w - 20.0, matched)
+    v = rng.uniform(20.0, cam.h - 20.0, matched)
+    Xc = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], 1)
+    Xw = ((Xc - t_true.astype(np.float64)) @ R).astype(np.float32)
+    order = rng.permutation(matched)               # the map side is not in feature order
+    world_pos = np.zeros((matched, 3), np.float32)
+    world_pos[order] = Xw
+    mp_index = np.full(n, -1, np.int32)
+    mp_index[feat] = order
+    octave = rng.integers(0, n_levels, n).astype(np.int32)
+    xy = np.stack([rng.uniform(0, cam.w, n), rng.uniform(0, cam.h, n)], 1).astype(np.float32)
+    uright = np.full(n, -1.0, np.float32)
+    # observations of the float points under the planted pose
+    Pc = Xw.astype(np.float64) @ R.T + t_true.astype(np.float64)
+    pu, pv = fx * Pc[:, 0] / Pc[:, 2] + cx, fy * Pc[:, 1] / Pc[:, 2] + cy
+    pr = pu - bf / Pc[:, 2]
+    sig = sf[octave[feat]].astype(np.float64) * pixel_noise
+    noise = rng.normal(size=(matched, 3)) * sig[:, None]
+    gross = rng.random(matched) < outlier_share
+    noise[gross, :2] += rng.choice([-40.0, 40.0], (int(gross.sum()), 2))
+    mono = rng.random(matched) < mono_share
+    xy[feat] = np.stack([pu + noise[:, 0], pv + noise[:, 1]], 1).astype(np.float32)
+    ur = (pr + noise[:, 0] + 0.5 * noise[:, 2]).astype(np.float32)
+    uright[feat] = np.where(mono | (ur < 0), np.float32(-1.0), ur)
+    planted = np.zeros(n, np.uint8)
+    planted[feat] = gross
+    # the entry pose
+    dq = _quat(rng.normal(size=3), rot_noise)
+    a, b = dq.astype(np.float64), q_true.astype(np.float64)
+    q = np.array([a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1], a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2],
+                  a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0], a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2]])
+    q = (q / np.linalg.norm(q)).astype(np.float32)
+    d = rng.normal(size=3)
+    t = (t_true + trans_noise * d / np.linalg.norm(d)).astype(np.float32)
+    return dict(mp_index=mp_index, world_pos=world_pos, xy=xy, octave=octave, uright=uright, q=q, t=t,
+                K=np.array([fx, fy, cx, cy], np.float32), bf=np.float32(bf), inv_level_sigma2=inv_sigma2, n_levels=n_levels,
+                q_true=q_true, t_true=t_true, planted_outlier=planted)

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -26,6 +27,7 @@
 #include "frustum_math.h"
 #include "logf_glibc.h"
 #include "newpoint_math.h"
+#include "poseopt_math.h"
 
 namespace rgbl {
 
@@ -854,6 +856,140 @@ __global__ __launch_bounds__(kNewPointsBS) void k_new_points(NewPointsDev D) {
 __global__ void k_test_np_cos_parallax(float mb, const float* __restrict__ depth, float* __restrict__ y, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) y[i] = np_cos_parallax_stereo(mb, depth[i]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Optimizer::PoseOptimization (src/Optimizer.cc:814-1114): k_pose_opt, one workgroup of 256 work-items per problem.  The
+// algorithm is po_optimize of csrc/poseopt_math.h, run by every work-item: the scalar state (pose, lambda, the 6 x 6 solve,
+// the update) is computed redundantly and identically, the edges are spread over the lanes (edge k on lane k mod 256).  No
+// communication between workgroups, no atomics; the barriers of PoDevLanes::reduce are the only synchronisation and every
+// work-item reaches every one of them (all branches around them depend on reduced values only).  Every loop is bounded by
+// 4 rounds x 10 iterations x 10 trials.
+struct PoseOptProblem {
+  const float* xy;       // the frame's mvKeysUn (resident or staged)
+  const int32_t* oct;
+  const float* ur;
+  const float* wpos;     // world positions: the call's staged array or the pool's
+  const float* sigma;    // mvInvLevelSigma2
+  int edge_off, m, n_levels;
+  float q[4], t[3], K[4], bf;
+};
+struct PoseOptDev {
+  const PoseOptProblem* prob;
+  const int32_t* feat;   // per correspondence (all problems back to back): the feature ...
+  const int32_t* point;  // ... and its row of wpos
+  double* chi2;          // the state of the edges beyond 8 per lane
+  uint8_t* level;        // every edge's level: the result, and the state of the edges beyond 8 per lane (starts 0)
+  float* pose;           // 8 floats per problem: q, t
+  int32_t* ret;
+  PoDiag* diag;
+};
+
+__device__ __forceinline__ PoEdge pose_opt_edge(const PoseOptProblem& pb, const PoseOptDev& D, int k) {
+  const int f = D.feat[pb.edge_off + k], p = D.point[pb.edge_off + k];
+  PoEdge e;
+  e.Xw[0] = pb.wpos[3 * (size_t)p]; e.Xw[1] = pb.wpos[3 * (size_t)p + 1]; e.Xw[2] = pb.wpos[3 * (size_t)p + 2];
+  e.obs[0] = pb.xy[2 * f]; e.obs[1] = pb.xy[2 * f + 1]; e.obs[2] = pb.ur[f];
+  const int oc = pb.oct[f], o = oc < 0 ? 0 : (oc >= pb.n_levels ? pb.n_levels - 1 : oc);   // host arrays are checked before the launch
+  e.info = pb.sigma[o];
+  e.stereo = e.obs[2] >= 0.0f ? 1 : 0;   // !(mvuRight[i] < 0) (:866)
+  e.level = 0;
+  e.chi2 = 0.0;
+  return e;
+}
+
+constexpr int kPoTreeLds = kPoLanes - 64;   // the partial sums of lanes 64 .. 255
+struct PoDevLanes {
+  PoEdge r[kPoRegEdges];   // edges tid, tid + 256, ... in registers
+  double acc[kPoSums];
+  const PoseOptProblem* pb;
+  const PoseOptDev* D;
+  double (*red)[kPoTreeLds];
+  double* bc;
+  int tid, m;
+  __device__ void zero() {
+#pragma unroll
+    for (int c = 0; c < kPoSums; ++c) acc[c] = 0.0;
+  }
+  template <class F> __device__ void each(F f) {
+#pragma unroll
+    for (int j = 0; j < kPoRegEdges; ++j)
+      if (tid + kPoLanes * j < m) f(r[j], acc);
+    for (int k = tid + kPoLanes * kPoRegEdges; k < m; k += kPoLanes) {   // beyond 2048 correspondences: global memory
+      PoEdge e = pose_opt_edge(*pb, *D, k);
+      e.chi2 = D->chi2[pb->edge_off + k];
+      e.level = D->level[pb->edge_off + k];
+      f(e, acc);
+      D->chi2[pb->edge_off + k] = e.chi2;
+      D->level[pb->edge_off + k] = e.level;
+    }
+  }
+  // v[i] = v[i] + v[i + s]: lanes 64 .. 255 put their sums into LDS and wave 0 forms (v[i] + v[i + 128]) + (v[i + 64] + v[i + 192]),
+  // which is what s = 128 and s = 64 leave in lane i < 64; s = 32 .. 1 run inside wave 0 (lane i reads lane i + s; lanes >= s
+  // compute values nobody reads), all sums side by side so that the cross-lane reads overlap; lane 0's sums go to every
+  // work-item through LDS.  Two barriers.
+  template <int N> __device__ void reduce(double* S) {
+    if (tid >= 64) {
+#pragma unroll
+      for (int c = 0; c < N; ++c) red[c][tid - 64] = acc[c];
+    }
+    __syncthreads();
+    if (tid < 64) {
+      double v[N];
+#pragma unroll
+      for (int c = 0; c < N; ++c) v[c] = (acc[c] + red[c][tid + 64]) + (red[c][tid] + red[c][tid + 128]);
+#pragma unroll
+      for (int s = 32; s >= 1; s >>= 1) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) v[c] = v[c] + __shfl_down(v[c], (unsigned)s);
+      }
+      if (tid == 0) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) bc[c] = v[c];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < N; ++c) S[c] = bc[c];
+  }
+};
+
+__global__ __launch_bounds__(kPoLanes) void k_pose_opt(PoseOptDev D) {
+  __shared__ double s_red[kPoSums][kPoTreeLds];   // 42 KB
+  __shared__ double s_bc[kPoSums];
+  const PoseOptProblem& pb = D.prob[blockIdx.x];
+  PoDevLanes G;
+  G.pb = &pb; G.D = &D; G.red = s_red; G.bc = s_bc; G.tid = (int)threadIdx.x; G.m = pb.m;
+#pragma unroll
+  for (int j = 0; j < kPoRegEdges; ++j) {
+    const int k = G.tid + kPoLanes * j;
+    if (k < pb.m) G.r[j] = pose_opt_edge(pb, D, k);
+  }
+  const PoCam C = {(double)pb.K[0], (double)pb.K[1], (double)pb.K[2], (double)pb.K[3], (double)pb.bf};
+  const PoPose entry = po_pose_from_float(pb.q, pb.t);
+  PoPose out;
+  PoDiag diag;
+  const int ret = po_optimize(G, C, entry, pb.m, out, diag);
+#pragma unroll
+  for (int j = 0; j < kPoRegEdges; ++j) {
+    const int k = G.tid + kPoLanes * j;
+    if (k < pb.m) D.level[pb.edge_off + k] = G.r[j].level;
+  }
+  if (threadIdx.x == 0) {
+    float* o = D.pose + 8 * (size_t)blockIdx.x;
+    for (int i = 0; i < 4; ++i) o[i] = (float)out.q[i];
+    for (int i = 0; i < 3; ++i) o[4 + i] = (float)out.t[i];
+    o[7] = 0.0f;
+    D.ret[blockIdx.x] = ret;
+    D.diag[blockIdx.x] = diag;
+  }
+}
+
+// test hook: the header's sin / cos and the fp64 quotient and square root on the device (op 0: sin, 1: cos, 2: x / y, 3: sqrt)
+__global__ void k_test_po_math(int op, const double* __restrict__ x, const double* __restrict__ y, double* __restrict__ z, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  z[i] = op == 0 ? po_sin(x[i]) : op == 1 ? po_cos(x[i]) : op == 2 ? x[i] / y[i] : sqrt(x[i]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3895,6 +4031,189 @@ int rgbl_frustum_cull(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t
 int rgbl_track_local_points(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t* in_view, rgbl_frustum_record* rec,
                             int* n_to_match, int32_t* match2, int* out_nmatches) {
   return track_local_core(m, in, in_view, rec, n_to_match, true, match2, out_nmatches);
+}
+
+// ---- Optimizer::PoseOptimization (src/Optimizer.cc:814-1114) ---------------------------------------------------------
+namespace {
+// everything that can be refused is refused here, before anything is staged, launched or written; counts the correspondences
+int check_pose_opt_input(const rgbl_pose_opt_input* in, int b, bool host_only, int* n_corr) {
+  *n_corr = 0;
+  if (in->n < 0 || in->n > 65535 || in->n_points < 0 || (in->n > 0 && !in->mp_index)) { set_error("pose optimisation %d: n outside [0, 65535], n_points < 0 or no mp_index", b); return RGBL_ERR_INVALID; }
+  if (in->n_levels < 1 || in->n_levels > kProjMaxLevels || !in->inv_level_sigma2) { set_error("pose optimisation %d: n_levels outside [1, %d] or no inv_level_sigma2", b, kProjMaxLevels); return RGBL_ERR_INVALID; }
+  bool finite = std::isfinite(in->bf);
+  for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(in->Tcw_q[i]) && std::isfinite(in->K[i]);
+  for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(in->Tcw_t[i]);
+  if (!finite) { set_error("pose optimisation %d: the pose, K or bf is not finite", b); return RGBL_ERR_INVALID; }
+  if (host_only && (in->device || in->pool)) { set_error("pose optimisation %d: the host build reads host arrays only", b); return RGBL_ERR_INVALID; }
+  if (in->device ? in->device->n != in->n : (in->n > 0 && (!in->kp_xy || !in->kp_octave || !in->uright))) {
+    set_error("pose optimisation %d: the frame side is either kp_xy, kp_octave, uright or a resident frame of n features", b);
+    return RGBL_ERR_INVALID;
+  }
+  if (in->n_points > 0 && (in->pool ? !in->slot : !in->world_pos)) { set_error("pose optimisation %d: the map side is either world_pos or a pool with slot", b); return RGBL_ERR_INVALID; }
+  int m = 0;
+  for (int i = 0; i < in->n; ++i) {
+    const int p = in->mp_index[i];
+    if (p < -1 || p >= in->n_points) { set_error("pose optimisation %d: mp_index[%d] = %d outside [-1, %d)", b, i, p, in->n_points); return RGBL_ERR_INVALID; }
+    if (p < 0) continue;
+    ++m;
+    if (!in->device && (in->kp_octave[i] < 0 || in->kp_octave[i] >= in->n_levels)) { set_error("pose optimisation %d: octave %d of feature %d outside [0, %d)", b, in->kp_octave[i], i, in->n_levels); return RGBL_ERR_INVALID; }
+  }
+  *n_corr = m;
+  return RGBL_OK;
+}
+// what :869 / :897 and :1107-1113 leave in the caller's arrays, from the level of every correspondence
+void write_pose_opt_output(const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out, const float pose[7], const uint8_t* level, int ret,
+                           const PoDiag& diag) {
+  const bool untouched = diag.rounds == 0;   // fewer than 3 correspondences: the pose is not written (:996-997)
+  memcpy(out->Tcw_q, untouched ? in->Tcw_q : pose, sizeof(out->Tcw_q));
+  memcpy(out->Tcw_t, untouched ? in->Tcw_t : pose + 4, sizeof(out->Tcw_t));
+  if (out->outlier) {
+    int k = 0;
+    for (int i = 0; i < in->n; ++i)
+      if (in->mp_index[i] >= 0) out->outlier[i] = level[k++];
+  }
+  out->result = ret;
+  static_assert(sizeof(PoDiag) == sizeof(rgbl_pose_opt_diag), "PoDiag is rgbl_pose_opt_diag");
+  memcpy(&out->diag, &diag, sizeof(diag));
+}
+}  // namespace
+
+int rgbl_pose_optimization_host(const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out) {
+  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  int m = 0;
+  RGBL_TRY(check_pose_opt_input(in, 0, true, &m));
+  std::vector<PoEdge> edges((size_t)m);
+  int k = 0;
+  for (int i = 0; i < in->n; ++i) {
+    const int p = in->mp_index[i];
+    if (p < 0) continue;
+    PoEdge& e = edges[(size_t)k++];
+    for (int c = 0; c < 3; ++c) e.Xw[c] = in->world_pos[3 * (size_t)p + c];
+    e.obs[0] = in->kp_xy[2 * i]; e.obs[1] = in->kp_xy[2 * i + 1]; e.obs[2] = in->uright[i];
+    e.info = in->inv_level_sigma2[in->kp_octave[i]];
+    e.stereo = e.obs[2] >= 0.0f ? 1 : 0;
+    e.level = 0;
+    e.chi2 = 0.0;
+  }
+  std::vector<PoHostLanes> lanes(1, PoHostLanes(edges.data(), m));   // 57 KB: not on the stack
+  const PoCam C = {(double)in->K[0], (double)in->K[1], (double)in->K[2], (double)in->K[3], (double)in->bf};
+  PoPose T;
+  PoDiag diag;
+  const int ret = po_optimize(lanes[0], C, po_pose_from_float(in->Tcw_q, in->Tcw_t), m, T, diag);
+  float pose[7];
+  for (int i = 0; i < 4; ++i) pose[i] = (float)T.q[i];
+  for (int i = 0; i < 3; ++i) pose[4 + i] = (float)T.t[i];
+  std::vector<uint8_t> level((size_t)m);
+  for (int i = 0; i < m; ++i) level[(size_t)i] = edges[(size_t)i].level;
+  write_pose_opt_output(in, out, pose, level.data(), ret, diag);
+  return RGBL_OK;
+}
+
+int rgbl_pose_optimization_batch(rgbl_matcher* m, int n_problems, const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out) {
+  if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  const int B = n_problems;
+  std::vector<int> off((size_t)B + 1, 0);
+  rgbl_map_points* pool = nullptr;
+  for (int b = 0; b < B; ++b) {
+    int mb = 0;
+    RGBL_TRY(check_pose_opt_input(in + b, b, false, &mb));
+    if (off[(size_t)b] > INT_MAX - mb) { set_error("pose optimisation: more than 2^31 correspondences in one call"); return RGBL_ERR_INVALID; }
+    off[(size_t)b + 1] = off[(size_t)b] + mb;
+    if (in[b].device && in[b].device->device != m->device) { set_error("pose optimisation %d: the frame is on device %d, the matcher on %d", b, in[b].device->device, m->device); return RGBL_ERR_INVALID; }
+    if (in[b].pool) {
+      if (pool && pool != in[b].pool) { set_error("pose optimisation %d: the problems of one call share one pool", b); return RGBL_ERR_INVALID; }
+      pool = in[b].pool;
+      if (pool->device != m->device) { set_error("pose optimisation %d: the pool is on device %d, the matcher on %d", b, pool->device, m->device); return RGBL_ERR_INVALID; }
+    }
+  }
+  if (B == 0) return RGBL_OK;
+  const int M = off[(size_t)B];
+  std::unique_lock<std::mutex> pool_lock;
+  if (pool) {
+    pool_lock = std::unique_lock<std::mutex>(pool->mu);
+    for (int b = 0; b < B; ++b)
+      if (in[b].pool)
+        for (int i = 0; i < in[b].n_points; ++i)
+          if (in[b].slot[i] < 0 || in[b].slot[i] >= pool->cap) { set_error("pose optimisation %d: slot %d outside [0, %d)", b, in[b].slot[i], pool->cap); return RGBL_ERR_INVALID; }
+  }
+  // the correspondences of all problems back to back: feature, and row of the problem's world positions
+  std::vector<int32_t> feat((size_t)M), point((size_t)M);
+  for (int b = 0; b < B; ++b) {
+    int k = off[(size_t)b];
+    for (int i = 0; i < in[b].n; ++i) {
+      const int p = in[b].mp_index[i];
+      if (p < 0) continue;
+      feat[(size_t)k] = i;
+      point[(size_t)k] = in[b].pool ? in[b].slot[p] : p;
+      ++k;
+    }
+  }
+  RGBL_HIP(hipSetDevice(m->device));
+  StreamDrain drain(m->stream);  // error returns included; declared behind pool_lock: the stream is drained before the pool is released
+  HostCall hc(m);
+  hipStream_t s = hc.s;
+  std::vector<PoseOptProblem> prob((size_t)B);
+  PoseOptDev D;
+  memset(&D, 0, sizeof(D));
+  RGBL_TRY(hc.begin([&]() -> int {
+    for (int b = 0; b < B; ++b) {
+      PoseOptProblem& P = prob[(size_t)b];
+      memset(&P, 0, sizeof(P));
+      const rgbl_pose_opt_input& I = in[b];
+      RGBL_TRY(put_features(hc, I.device, I.n, nullptr, I.kp_xy, I.kp_octave, I.uright, nullptr, &P.xy, &P.oct, &P.ur));
+      if (I.pool) P.wpos = pool->d_wpos; else hc.put(&P.wpos, I.world_pos, (size_t)I.n_points * 3);
+      hc.put(&P.sigma, I.inv_level_sigma2, (size_t)I.n_levels);
+      P.edge_off = off[(size_t)b]; P.m = off[(size_t)b + 1] - off[(size_t)b]; P.n_levels = I.n_levels;
+      memcpy(P.q, I.Tcw_q, sizeof(P.q)); memcpy(P.t, I.Tcw_t, sizeof(P.t)); memcpy(P.K, I.K, sizeof(P.K));
+      P.bf = I.bf;
+    }
+    hc.put(&D.feat, feat.data(), (size_t)M);
+    hc.put(&D.point, point.data(), (size_t)M);
+    D.prob = hc.stage<PoseOptProblem>((size_t)B, [&](PoseOptProblem* dst) { memcpy(dst, prob.data(), sizeof(PoseOptProblem) * (size_t)B); });
+    D.level = hc.put_fill<uint8_t>((size_t)M, 0);   // what comes back, side by side
+    hc.mark_result(D.level, (size_t)M);
+    D.pose = hc.result<float>((size_t)B * 8);
+    D.ret = hc.result<int32_t>((size_t)B);
+    D.diag = hc.result<PoDiag>((size_t)B);
+    D.chi2 = hc.scratch<double>((size_t)M);
+    return RGBL_OK;
+  }));
+  m->timer.begin("k_pose_opt", s);
+  hipLaunchKernelGGL(k_pose_opt, dim3((unsigned)B), dim3(kPoLanes), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(hc.fetch());
+  for (int b = 0; b < B; ++b)
+    write_pose_opt_output(in + b, out + b, hc.host(D.pose) + 8 * (size_t)b, hc.host(D.level) + off[(size_t)b], hc.host(D.ret)[b], hc.host(D.diag)[b]);
+  return RGBL_OK;
+}
+
+int rgbl_pose_optimization(rgbl_matcher* m, const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out) {
+  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  return rgbl_pose_optimization_batch(m, 1, in, out);
+}
+
+// test hooks for csrc/poseopt_math.h: op 0 sin, 1 cos, 2 x / y, 3 sqrt - on the host, and compiled for the device
+double rgbl_test_po_math(int op, double x, double y) { return op == 0 ? po_sin(x) : op == 1 ? po_cos(x) : op == 2 ? x / y : sqrt(x); }
+int rgbl_test_po_math_device(int op, const double* x, const double* y, double* z, int n) {
+  if (!x || !y || !z || n < 1 || op < 0 || op > 3) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  double *dx = nullptr, *dy = nullptr, *dz = nullptr;
+  const size_t bytes = sizeof(double) * (size_t)n;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dx), bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dy), bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dz), bytes);
+  if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_test_po_math, dim3((n + 255) / 256), dim3(256), 0, 0, op, (const double*)dx, (const double*)dy, dz, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(z, dz, bytes, hipMemcpyDeviceToHost);
+  if (dx) (void)hipFree(dx);
+  if (dy) (void)hipFree(dy);
+  if (dz) (void)hipFree(dz);
+  if (e != hipSuccess) { set_error("poseopt math test hook: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
+  return RGBL_OK;
 }
 
 // test hooks (tests/test_logf_glibc.py): the restatement on the host, and the same function compiled for the device

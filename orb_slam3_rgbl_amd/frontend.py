@@ -1163,6 +1163,85 @@ class ORBmatcher:
         L.check(self.lib, rc)
         return out
 
+    @staticmethod
+    def _pose_opt_input(fr, keep, out=None):
+        """rgbl_pose_opt_input of a frame dict: mp_index (per feature, -1 = none), world_pos (points x 3) or pool (MapPointPool)
+        + slot, xy / octave / uright or device (DeviceFrame), q (x y z w), t, K (fx fy cx cy), bf, inv_level_sigma2."""
+        P = out if out is not None else L.PoseOptInput()
+
+        def arr(key, dt):
+            if fr.get(key) is None:
+                return None
+            keep.append(np.ascontiguousarray(fr[key], dt))
+            return keep[-1].ctypes.data
+        mp = np.ascontiguousarray(fr["mp_index"], np.int32)
+        keep.append(mp)
+        P.n, P.mp_index = len(mp), mp.ctypes.data
+        pool = fr.get("pool")
+        P.pool = pool.h if pool is not None else None
+        P.world_pos, P.slot = arr("world_pos", np.float32), arr("slot", np.int32)
+        P.n_points = int(fr["n_points"]) if fr.get("n_points") is not None else (
+            len(fr["slot"]) if pool is not None else len(np.asarray(fr["world_pos"]).reshape(-1, 3)))
+        P.kp_xy, P.kp_octave, P.uright = arr("xy", np.float32), arr("octave", np.int32), arr("uright", np.float32)
+        P.device = _dev(fr, "device")
+        for field, key, cnt in (("Tcw_q", "q", 4), ("Tcw_t", "t", 3), ("K", "K", 4)):
+            v = np.asarray(fr[key], np.float32).reshape(-1)
+            for i in range(cnt):
+                getattr(P, field)[i] = v[i]
+        P.bf = np.float32(fr["bf"])
+        P.inv_level_sigma2 = arr("inv_level_sigma2", np.float32)
+        P.n_levels = int(fr.get("n_levels", len(fr["inv_level_sigma2"])))
+        return P
+
+    @staticmethod
+    def _pose_opt_result(O, outlier):
+        d = O.diag
+        return dict(q=np.array(O.Tcw_q, np.float32), t=np.array(O.Tcw_t, np.float32), outlier=outlier, result=int(O.result),
+                    rounds=int(d.rounds), iterations=np.array(d.iterations, np.int32), active=np.array(d.active, np.int32),
+                    chi2=np.array(d.chi2, np.float64), q64=np.array(d.Tcw_q, np.float64), t64=np.array(d.Tcw_t, np.float64))
+
+    def prepare_PoseOptimizationBatch(self, frames, host=False, outlier_fill=0):
+        """Optimizer::PoseOptimization (Optimizer.cc:814-1114) of every frame dict in one launch; the call returns one dict per
+        frame: q, t (what SetPose receives), outlier (mvbOutlier, `outlier_fill` where there is no map point), result (the
+        reference's return value) and the diagnostics rounds / iterations / active / chi2."""
+        keep = []
+        B = len(frames)
+        I, O = (L.PoseOptInput * max(B, 1))(), (L.PoseOptOutput * max(B, 1))()
+        outl = []
+        for b, fr in enumerate(frames):
+            self._pose_opt_input(fr, keep, I[b])
+            outl.append(np.full(I[b].n, outlier_fill, np.uint8))
+            O[b].outlier = outl[b].ctypes.data
+        lib, h = self.lib, self.h
+
+        def call(_keep=keep):
+            if host:
+                for b in range(B):
+                    L.check(lib, lib.rgbl_pose_optimization_host(C.byref(I[b]), C.byref(O[b])))
+            else:
+                L.check(lib, lib.rgbl_pose_optimization_batch(h, B, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)))
+            return [self._pose_opt_result(O[b], outl[b]) for b in range(B)]
+
+        def c_call(_keep=keep):   # the C call alone (what tools/pose_opt_bench.py times): the results stay in the structs
+            L.check(lib, lib.rgbl_pose_optimization_batch(h, B, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)))
+        call.c_call = c_call
+        return call
+
+    def PoseOptimizationBatch(self, frames, host=False, outlier_fill=0):
+        return self.prepare_PoseOptimizationBatch(frames, host, outlier_fill)()
+
+    def PoseOptimization(self, frame, host=False, outlier_fill=0):
+        """One frame through rgbl_pose_optimization (host=True: rgbl_pose_optimization_host, the header's host build)."""
+        keep = []
+        I, O = self._pose_opt_input(frame, keep), L.PoseOptOutput()
+        outl = np.full(I.n, outlier_fill, np.uint8)
+        O.outlier = outl.ctypes.data
+        if host:
+            L.check(self.lib, self.lib.rgbl_pose_optimization_host(C.byref(I), C.byref(O)))
+        else:
+            L.check(self.lib, self.lib.rgbl_pose_optimization(self.h, C.byref(I), C.byref(O)))
+        return self._pose_opt_result(O, outl)
+
     def CreateNewMapPoints(self, kf1, neighbours, prm, skip=None, cap=None):
         return self.prepare_CreateNewMapPoints(kf1, neighbours, prm, skip, cap)()
 
@@ -1584,3 +1663,15 @@ def frustum_restatement(case):
                 level = 0 if not c >= 0 else (n_levels - 1 if c >= n_levels else int(c))
             rec["level"][i] = level
     return seen.astype(np.uint8), rec, stage
+
+
+def pose_optimization_host(frame, lib=None, outlier_fill=0):
+    """rgbl_pose_optimization_host: Optimizer::PoseOptimization by the host build of csrc/poseopt_math.h (no device, no handle);
+    the result dict of ORBmatcher.PoseOptimization."""
+    lib = lib or L.load()
+    keep = []
+    I, O = ORBmatcher._pose_opt_input(frame, keep), L.PoseOptOutput()
+    outl = np.full(I.n, outlier_fill, np.uint8)
+    O.outlier = outl.ctypes.data
+    L.check(lib, lib.rgbl_pose_optimization_host(C.byref(I), C.byref(O)))
+    return ORBmatcher._pose_opt_result(O, outl)
