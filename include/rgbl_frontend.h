@@ -1031,6 +1031,65 @@ int rgbl_pose_optimization_batch(rgbl_matcher* h, int n_problems, const rgbl_pos
  * frame and map sides must be host arrays (device and pool NULL). */
 int rgbl_pose_optimization_host(const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out);
 
+/* Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc): the RANSAC over 3-point Horn solutions that
+ * LoopClosing::DetectCommonRegionsFromBoW runs per candidate (src/LoopClosing.cc:698-710), ALL hypotheses of a call at once.
+ * One call is what one or more calls of Sim3Solver::iterate (:149-294) compute: ComputeSim3 (:311-412) and CheckInliers
+ * (:415-439) for every sample triple, then the rule by which the reference's loop stops (:192-209 / :265-287) as a scan over
+ * the inlier counts.  Pinhole cameras (Pinhole::project, src/CameraModels/Pinhole.cpp:43-49).  csrc/sim3_math.h restates the
+ * arithmetic and says what is pinned (fp32 / fp64 as the reference, SO3f::exp, the control flow) and what is not (the eigen
+ * decomposition, atan2, Eigen's evaluation order).  The constructor's bookkeeping (:35-121), SetRansacParameters (:123-147)
+ * and the drawing of the samples (:172-186) stay with the caller. */
+typedef struct {
+  int n;                       /* N = mvX3Dc1.size(), 0 .. 65535 */
+  /* the points, form 1 (pool == NULL): camera frames, mvX3Dc1 / mvX3Dc2 (:107, :110), n x 3 */
+  const float* x1c;
+  const float* x2c;
+  /* form 2: slots of a pool on the matcher's device and the two key-frame poses; the device forms Rcw * Xw + tcw in fp32 from
+   * the resident positions (the call holds the pool's mutex for its duration) */
+  rgbl_map_points* pool;
+  const int32_t* slot1;        /* n slots in [0, capacity): pMP1 */
+  const int32_t* slot2;        /* pMP2 */
+  float Rcw1[9], tcw1[3];      /* pKF1->GetRotation() (row-major), GetTranslation() (:61-62); read in form 2 only */
+  float Rcw2[9], tcw2[3];      /* pKF2's (:63-64) */
+  const float* max_err1;       /* mvnMaxError1: 9.210 * sigma2 of the key point's level (:99) as the reference stores it - a
+                                  std::vector<size_t>, so truncated to an integer -, n entries */
+  const float* max_err2;       /* mvnMaxError2 (:100) */
+  float K1[4], K2[4];          /* pCamera1 / pCamera2: fx, fy, cx, cy */
+  int fix_scale;               /* mbFixScale */
+  int min_inliers;             /* mRansacMinInliers */
+  int best_inliers;            /* mnBestInliers on entry (0 for a fresh solver) */
+  int n_hyp;                   /* iterations this call may run: min(nIterations, mRansacMaxIts - mnIterations); 0 .. 2^20 */
+  const int32_t* samples;      /* n_hyp x 3 indices into 0 .. n-1 in the order drawn (:175-186), distinct inside a triple */
+} rgbl_sim3_input;
+typedef struct {
+  int selected;                /* the hypothesis the loop holds when it ends (the last k with c[k] >= the best so far), -1: none */
+  int converged;               /* 1: the scan stopped at a c[k] > min_inliers (:201 / :274) */
+  int n_inliers;               /* c[selected]: the new mnBestInliers; 0 without a selection */
+  int iterations_run;          /* k + 1 at the stop, n_hyp if the scan ran through: what mnIterations grows by */
+  float T12[16];               /* mBestT12, row-major; with R12, t12, s12 and inlier written only when selected >= 0 */
+  float R12[9];                /* mBestRotation, row-major */
+  float t12[3];                /* mBestTranslation */
+  float s12;                   /* mBestScale */
+  uint8_t* inlier;             /* mvbBestInliers, n bytes (NULL: not wanted) */
+  int32_t* counts;             /* optional diagnostics: mnInliersi of every hypothesis, n_hyp entries (NULL: not wanted) */
+  float* T12_all;              /* optional diagnostics: mT12i of every hypothesis, n_hyp x 16 (NULL: not wanted) */
+} rgbl_sim3_output;
+/* One problem.  Host pointers, synchronous, one upload, two launches on one stream, one read-back.  A problem with n < 3,
+ * n < min_inliers (:155-159) or n_hyp == 0 is valid: selected = -1 and nothing else is written.  Otherwise selected,
+ * converged, n_inliers and iterations_run are always written, and so are counts and T12_all where given.
+ * RGBL_ERR_INVALID, before anything is launched and with every output untouched: n outside [0, 65535] or n_hyp outside
+ * [0, 2^20] (SetRansacParameters' default mRansacMaxIts is 300); a sample index outside [0, n) or repeated in its triple
+ * (n >= 3); K, a threshold or (form 2) a pose that is not finite; a slot outside the pool, or a pool on another device than
+ * the matcher; a missing array. */
+int rgbl_sim3_ransac(rgbl_matcher* h, const rgbl_sim3_input* in, rgbl_sim3_output* out);
+/* B independent problems (the candidates of one DetectCommonRegionsFromBoW pass): one upload, one launch pair, one
+ * read-back.  Problems that name a pool must name the same one.  Errors as above, and n_problems outside [0, 32767] (the
+ * problem is a grid dimension): nothing is launched and no problem's output is written. */
+int rgbl_sim3_ransac_batch(rgbl_matcher* h, int n_problems, const rgbl_sim3_input* in, rgbl_sim3_output* out);
+/* rgbl_sim3_ransac evaluated by the HOST build of csrc/sim3_math.h (no device, no handle): the same bits.  The points must be
+ * host arrays (pool NULL). */
+int rgbl_sim3_ransac_host(const rgbl_sim3_input* in, rgbl_sim3_output* out);
+
 /* ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>& vbPrevMatched, vector<int>& vnMatches12,
  * int windowSize)    /root/reference/include/ORBmatcher.h:72, src/ORBmatcher.cc:648-763 (Tracking::MonocularInitialization,
  * src/Tracking.cc:2526; not on the RGB-L / stereo path - built so that every search routine of ORBmatcher has a device form).

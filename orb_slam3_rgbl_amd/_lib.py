@@ -88,6 +88,21 @@ class PoseOptOutput(C.Structure):
                 ("diag", PoseOptDiag)]
 
 
+class Sim3Input(C.Structure):
+    """rgbl_sim3_input (one Sim3Solver problem: the correspondences, the cameras and the drawn sample triples)."""
+    _fields_ = [("n", C.c_int), ("x1c", C.c_void_p), ("x2c", C.c_void_p), ("pool", C.c_void_p), ("slot1", C.c_void_p),
+                ("slot2", C.c_void_p), ("Rcw1", C.c_float * 9), ("tcw1", C.c_float * 3), ("Rcw2", C.c_float * 9),
+                ("tcw2", C.c_float * 3), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p), ("K1", C.c_float * 4),
+                ("K2", C.c_float * 4), ("fix_scale", C.c_int), ("min_inliers", C.c_int), ("best_inliers", C.c_int),
+                ("n_hyp", C.c_int), ("samples", C.c_void_p)]
+
+
+class Sim3Output(C.Structure):
+    _fields_ = [("selected", C.c_int), ("converged", C.c_int), ("n_inliers", C.c_int), ("iterations_run", C.c_int),
+                ("T12", C.c_float * 16), ("R12", C.c_float * 9), ("t12", C.c_float * 3), ("s12", C.c_float),
+                ("inlier", C.c_void_p), ("counts", C.c_void_p), ("T12_all", C.c_void_p)]
+
+
 class ProjectionInput(C.Structure):
     """rgbl_projection_input (ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) as flat arrays)."""
     _fields_ = [("n1", C.c_int), ("valid1", C.c_void_p), ("world_pos1", C.c_void_p), ("mp_desc1", C.c_void_p),
@@ -320,6 +335,9 @@ SYMBOLS = {
     "rgbl_pose_optimization": (_I, [_V, C.POINTER(PoseOptInput), C.POINTER(PoseOptOutput)]),
     "rgbl_pose_optimization_batch": (_I, [_V, _I, _V, _V]),
     "rgbl_pose_optimization_host": (_I, [C.POINTER(PoseOptInput), C.POINTER(PoseOptOutput)]),
+    "rgbl_sim3_ransac": (_I, [_V, C.POINTER(Sim3Input), C.POINTER(Sim3Output)]),
+    "rgbl_sim3_ransac_batch": (_I, [_V, _I, _V, _V]),
+    "rgbl_sim3_ransac_host": (_I, [C.POINTER(Sim3Input), C.POINTER(Sim3Output)]),
     "rgbl_search_by_bow": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_rig": (_I, [_V, _V, _V, _I, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_keyframes": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),

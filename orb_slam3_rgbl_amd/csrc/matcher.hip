@@ -28,6 +28,7 @@
 #include "logf_glibc.h"
 #include "newpoint_math.h"
 #include "poseopt_math.h"
+#include "sim3_math.h"
 
 namespace rgbl {
 
@@ -990,6 +991,176 @@ __global__ void k_test_po_math(int op, const double* __restrict__ x, const doubl
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   z[i] = op == 0 ? po_sin(x[i]) : op == 1 ? po_cos(x[i]) : op == 2 ? x[i] / y[i] : sqrt(x[i]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Sim3Solver (src/Sim3Solver.cc): every hypothesis of a call at once.  The arithmetic is csrc/sim3_math.h.
+//   k_sim3_hypotheses  grid (groups of 4 hypotheses, problem), 256 work-items: one wave per hypothesis.  The workgroup stages
+//                      the problem's correspondences once in LDS (12 floats each: X1c, X2c, both own-image projections, both
+//                      thresholds; problems beyond kS3LdsPoints read global memory and recompute them).  The closed form is
+//                      wave-uniform: every lane computes it, no broadcast, no divergent branch.  A lane then takes every 64th
+//                      correspondence; a chunk's count is a ballot and a population count, the ballot word is the chunk's
+//                      part of the hypothesis's bit mask.  No atomics, no floating-point reduction.
+//   k_sim3_select      one workgroup per problem: wave 0 runs the selection scan 64 hypotheses at a time (a prefix maximum and
+//                      two ballots per chunk), then all work-items expand the selected mask into bytes.
+// Both run on the call's stream, one behind the other; no workgroup waits for another.
+constexpr int kS3LdsPoints = 1024;   // 48 KB of LDS
+constexpr int kS3HypPerGroup = 4;
+struct Sim3Problem {
+  const float *x1, *x2;            // form 1: the staged camera-frame points
+  const float* wpos;               // form 2: the pool's positions ...
+  const int32_t *slot1, *slot2;    // ... and the slots
+  const float *e1, *e2;            // the thresholds
+  const int32_t* samples;
+  int n, n_hyp;                    // n_hyp = 0: the problem is not run
+  int hyp_off, word_off, words, inl_off;
+  int fix_scale, min_inliers, best_inliers, pool_form;
+  float K1[4], K2[4], Rcw1[9], tcw1[3], Rcw2[9], tcw2[3];
+};
+struct Sim3HypOut {
+  int32_t count;
+  float T12[16], R[9], t[3], s;
+};
+struct Sim3Result {
+  S3Selection sel;
+  float T12[16], R[9], t[3], s;
+};
+struct Sim3Dev {
+  const Sim3Problem* prob;
+  Sim3HypOut* hyp;             // all problems' hypotheses back to back
+  unsigned long long* mask;    // per hypothesis `words` 64-bit words
+  Sim3Result* res;
+  uint8_t* inlier;             // all problems' flags back to back
+};
+
+__device__ __forceinline__ S3Point sim3_point(const Sim3Problem& pb, int i) {
+  float a[3], b[3];
+  if (pb.pool_form) {
+    s3_transform(pb.Rcw1, pb.tcw1, pb.wpos + 3 * (size_t)pb.slot1[i], a);   // Sim3Solver.cc:107
+    s3_transform(pb.Rcw2, pb.tcw2, pb.wpos + 3 * (size_t)pb.slot2[i], b);   // :110
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { a[c] = pb.x1[3 * (size_t)i + c]; b[c] = pb.x2[3 * (size_t)i + c]; }
+  }
+  return s3_point(a, b, pb.K1, pb.K2, pb.e1[i], pb.e2[i]);
+}
+
+__global__ __launch_bounds__(256) void k_sim3_hypotheses(Sim3Dev D) {
+  __shared__ float s_pt[12][kS3LdsPoints];
+  const Sim3Problem& pb = D.prob[blockIdx.y];
+  if ((int)blockIdx.x * kS3HypPerGroup >= pb.n_hyp) return;   // the whole workgroup, before the barrier
+  const int tid = (int)threadIdx.x, n = pb.n;
+  const bool lds = n <= kS3LdsPoints;
+  if (lds) {
+    for (int i = tid; i < n; i += 256) {
+      const S3Point p = sim3_point(pb, i);
+      s_pt[0][i] = p.x1[0]; s_pt[1][i] = p.x1[1]; s_pt[2][i] = p.x1[2];
+      s_pt[3][i] = p.x2[0]; s_pt[4][i] = p.x2[1]; s_pt[5][i] = p.x2[2];
+      s_pt[6][i] = p.p1[0]; s_pt[7][i] = p.p1[1]; s_pt[8][i] = p.p2[0]; s_pt[9][i] = p.p2[1];
+      s_pt[10][i] = p.e1; s_pt[11][i] = p.e2;
+    }
+  }
+  __syncthreads();
+  const int lane = tid & 63, h = (int)blockIdx.x * kS3HypPerGroup + (tid >> 6);
+  if (h >= pb.n_hyp) return;   // a whole wave; no barrier follows
+  auto point = [&](int i) {
+    if (!lds) return sim3_point(pb, i);
+    S3Point p;
+    p.x1[0] = s_pt[0][i]; p.x1[1] = s_pt[1][i]; p.x1[2] = s_pt[2][i];
+    p.x2[0] = s_pt[3][i]; p.x2[1] = s_pt[4][i]; p.x2[2] = s_pt[5][i];
+    p.p1[0] = s_pt[6][i]; p.p1[1] = s_pt[7][i]; p.p2[0] = s_pt[8][i]; p.p2[1] = s_pt[9][i];
+    p.e1 = s_pt[10][i]; p.e2 = s_pt[11][i];
+    return p;
+  };
+  float P1[9], P2[9];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const S3Point p = point(pb.samples[3 * (size_t)h + k]);   // checked by the host: inside [0, n)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { P1[3 * k + c] = p.x1[c]; P2[3 * k + c] = p.x2[c]; }
+  }
+  S3Hyp H;
+  s3_compute_sim3(P1, P2, pb.fix_scale, H);
+  unsigned long long* mask = D.mask + (size_t)pb.word_off + (size_t)h * (size_t)pb.words;
+  int count = 0;
+  for (int c = 0; c < pb.words; ++c) {   // wave-uniform
+    const int i = c * 64 + lane;
+    bool in = false;
+    if (i < n) in = s3_is_inlier(H, pb.K1, pb.K2, point(i));
+    const unsigned long long w = __ballot(in);
+    count += __popcll(w);
+    if (lane == 0) mask[c] = w;
+  }
+  if (lane == 0) {
+    Sim3HypOut& o = D.hyp[(size_t)pb.hyp_off + (size_t)h];
+    o.count = count;
+    s3_T12(H, o.T12);
+    for (int k = 0; k < 9; ++k) o.R[k] = H.R[k];
+    for (int k = 0; k < 3; ++k) o.t[k] = H.t[k];
+    o.s = H.s;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_sim3_select(Sim3Dev D) {
+  __shared__ S3Selection s_sel;
+  const Sim3Problem& pb = D.prob[blockIdx.x];
+  if (pb.n_hyp == 0) return;   // the whole workgroup
+  const int tid = (int)threadIdx.x;
+  const Sim3HypOut* hyp = D.hyp + (size_t)pb.hyp_off;
+  if (tid < 64) {
+    // s3_select, 64 hypotheses at a time: before hypothesis k the best is max(b, c[0 .. k-1])
+    int b = pb.best_inliers, held = -1, conv = 0, iters = pb.n_hyp;
+    for (int base = 0; base < pb.n_hyp && !conv; base += 64) {   // wave-uniform
+      const int k = base + tid;
+      const bool valid = k < pb.n_hyp;
+      const int c = valid ? hyp[k].count : -1;
+      int m = c;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(m, (unsigned)d);
+        if (tid >= d && o > m) m = o;
+      }
+      const int ex = __shfl_up(m, 1u);
+      const int before = (tid == 0 || b > ex) ? b : ex;
+      const bool upd = valid && c >= before;
+      const bool stop = upd && c > pb.min_inliers;
+      const unsigned long long su = __ballot(stop);
+      unsigned long long uu = __ballot(upd);
+      if (su) {
+        const int first = __ffsll((long long)su) - 1;
+        uu &= (2ull << first) - 1ull;
+        conv = 1;
+        iters = base + first + 1;
+      }
+      if (uu) {
+        const int last = 63 - __clzll((long long)uu);
+        held = base + last;
+        b = __shfl(c, last);
+      }
+    }
+    if (tid == 0) {
+      S3Selection sel;
+      sel.selected = held; sel.converged = conv; sel.n_inliers = held >= 0 ? b : 0; sel.iterations = iters;
+      s_sel = sel;
+    }
+  }
+  __syncthreads();
+  const S3Selection sel = s_sel;
+  if (tid == 0) {
+    Sim3Result& r = D.res[blockIdx.x];
+    r.sel = sel;
+    if (sel.selected >= 0) {
+      const Sim3HypOut& o = hyp[sel.selected];
+      for (int k = 0; k < 16; ++k) r.T12[k] = o.T12[k];
+      for (int k = 0; k < 9; ++k) r.R[k] = o.R[k];
+      for (int k = 0; k < 3; ++k) r.t[k] = o.t[k];
+      r.s = o.s;
+    }
+  }
+  if (sel.selected >= 0) {
+    const unsigned long long* mask = D.mask + (size_t)pb.word_off + (size_t)sel.selected * (size_t)pb.words;
+    for (int i = tid; i < pb.n; i += 256) D.inlier[(size_t)pb.inl_off + i] = (uint8_t)((mask[i >> 6] >> (i & 63)) & 1ull);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4191,6 +4362,194 @@ int rgbl_pose_optimization_batch(rgbl_matcher* m, int n_problems, const rgbl_pos
 int rgbl_pose_optimization(rgbl_matcher* m, const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out) {
   if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
   return rgbl_pose_optimization_batch(m, 1, in, out);
+}
+
+// ---- Sim3Solver (src/Sim3Solver.cc) ------------------------------------------------------------------------------------
+namespace {
+constexpr int kS3MaxHyp = 1 << 20;
+// a problem the reference leaves at once (:155-159), or that has nothing to run
+inline bool sim3_skipped(const rgbl_sim3_input* in) { return in->n < 3 || in->n < in->min_inliers || in->n_hyp == 0; }
+// everything that can be refused without the pool is refused here, before anything is staged, launched or written
+int check_sim3_input(const rgbl_sim3_input* in, int b, bool host_only) {
+  if (in->n < 0 || in->n > 65535 || in->n_hyp < 0 || in->n_hyp > kS3MaxHyp) { set_error("sim3 %d: n outside [0, 65535] or n_hyp outside [0, %d]", b, kS3MaxHyp); return RGBL_ERR_INVALID; }
+  if (host_only && in->pool) { set_error("sim3 %d: the host build reads host arrays only", b); return RGBL_ERR_INVALID; }
+  if (in->n > 0 && (in->pool ? (!in->slot1 || !in->slot2) : (!in->x1c || !in->x2c))) { set_error("sim3 %d: the points are either x1c, x2c or a pool with slot1, slot2", b); return RGBL_ERR_INVALID; }
+  if (in->n > 0 && (!in->max_err1 || !in->max_err2)) { set_error("sim3 %d: no max_err1 / max_err2", b); return RGBL_ERR_INVALID; }
+  bool finite = true;
+  for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(in->K1[i]) && std::isfinite(in->K2[i]);
+  if (in->pool) {
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(in->Rcw1[i]) && std::isfinite(in->Rcw2[i]);
+    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(in->tcw1[i]) && std::isfinite(in->tcw2[i]);
+  }
+  for (int i = 0; i < in->n; ++i) finite = finite && std::isfinite(in->max_err1[i]) && std::isfinite(in->max_err2[i]);
+  if (!finite) { set_error("sim3 %d: K, a pose or a threshold is not finite", b); return RGBL_ERR_INVALID; }
+  if (in->n >= 3 && in->n_hyp > 0) {
+    if (!in->samples) { set_error("sim3 %d: no samples", b); return RGBL_ERR_INVALID; }
+    for (int k = 0; k < in->n_hyp; ++k) {
+      const int32_t* s = in->samples + 3 * (size_t)k;
+      if (s[0] < 0 || s[0] >= in->n || s[1] < 0 || s[1] >= in->n || s[2] < 0 || s[2] >= in->n || s[0] == s[1] || s[0] == s[2] || s[1] == s[2]) {
+        set_error("sim3 %d: sample %d = (%d, %d, %d) is not three distinct indices in [0, %d)", b, k, s[0], s[1], s[2], in->n);
+        return RGBL_ERR_INVALID;
+      }
+    }
+  }
+  return RGBL_OK;
+}
+void write_sim3_output(const rgbl_sim3_input* in, rgbl_sim3_output* out, const Sim3Result& r, const uint8_t* inlier, const Sim3HypOut* hyp) {
+  out->selected = r.sel.selected; out->converged = r.sel.converged; out->n_inliers = r.sel.n_inliers; out->iterations_run = r.sel.iterations;
+  if (r.sel.selected >= 0) {
+    memcpy(out->T12, r.T12, sizeof(out->T12)); memcpy(out->R12, r.R, sizeof(out->R12)); memcpy(out->t12, r.t, sizeof(out->t12));
+    out->s12 = r.s;
+    if (out->inlier && in->n) memcpy(out->inlier, inlier, (size_t)in->n);
+  }
+  for (int k = 0; k < in->n_hyp; ++k) {
+    if (out->counts) out->counts[k] = hyp[k].count;
+    if (out->T12_all) memcpy(out->T12_all + 16 * (size_t)k, hyp[k].T12, sizeof(hyp[k].T12));
+  }
+}
+}  // namespace
+
+int rgbl_sim3_ransac_host(const rgbl_sim3_input* in, rgbl_sim3_output* out) {
+  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  RGBL_TRY(check_sim3_input(in, 0, true));
+  if (sim3_skipped(in)) { out->selected = -1; return RGBL_OK; }
+  const int n = in->n, words = (n + 63) / 64;
+  std::vector<S3Point> pts((size_t)n);
+  for (int i = 0; i < n; ++i) pts[(size_t)i] = s3_point(in->x1c + 3 * (size_t)i, in->x2c + 3 * (size_t)i, in->K1, in->K2, in->max_err1[i], in->max_err2[i]);
+  std::vector<Sim3HypOut> hyp((size_t)in->n_hyp);
+  std::vector<int32_t> counts((size_t)in->n_hyp);
+  std::vector<uint64_t> mask((size_t)in->n_hyp * (size_t)words, 0);
+  for (int h = 0; h < in->n_hyp; ++h) {
+    float P1[9], P2[9];
+    for (int k = 0; k < 3; ++k) {
+      const S3Point& p = pts[(size_t)in->samples[3 * (size_t)h + k]];
+      for (int c = 0; c < 3; ++c) { P1[3 * k + c] = p.x1[c]; P2[3 * k + c] = p.x2[c]; }
+    }
+    S3Hyp H;
+    s3_compute_sim3(P1, P2, in->fix_scale, H);
+    int count = 0;
+    for (int i = 0; i < n; ++i)
+      if (s3_is_inlier(H, in->K1, in->K2, pts[(size_t)i])) { mask[(size_t)h * words + (i >> 6)] |= (uint64_t)1 << (i & 63); ++count; }
+    Sim3HypOut& o = hyp[(size_t)h];
+    o.count = counts[(size_t)h] = count;
+    s3_T12(H, o.T12);
+    memcpy(o.R, H.R, sizeof(o.R)); memcpy(o.t, H.t, sizeof(o.t));
+    o.s = H.s;
+  }
+  Sim3Result r;
+  memset(&r, 0, sizeof(r));
+  r.sel = s3_select(counts.data(), in->n_hyp, in->best_inliers, in->min_inliers);
+  std::vector<uint8_t> inl((size_t)n, 0);
+  if (r.sel.selected >= 0) {
+    const Sim3HypOut& o = hyp[(size_t)r.sel.selected];
+    memcpy(r.T12, o.T12, sizeof(r.T12)); memcpy(r.R, o.R, sizeof(r.R)); memcpy(r.t, o.t, sizeof(r.t));
+    r.s = o.s;
+    for (int i = 0; i < n; ++i) inl[(size_t)i] = (uint8_t)((mask[(size_t)r.sel.selected * words + (i >> 6)] >> (i & 63)) & 1u);
+  }
+  write_sim3_output(in, out, r, inl.data(), hyp.data());
+  return RGBL_OK;
+}
+
+int rgbl_sim3_ransac_batch(rgbl_matcher* m, int n_problems, const rgbl_sim3_input* in, rgbl_sim3_output* out) {
+  if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  const int B = n_problems;
+  if (B > 32767) { set_error("sim3: more than 32767 problems in one call"); return RGBL_ERR_INVALID; }
+  rgbl_map_points* pool = nullptr;
+  // offsets of the problems that run: hypotheses, mask words, flags
+  std::vector<int> hyp_off((size_t)B + 1, 0), inl_off((size_t)B + 1, 0);
+  std::vector<size_t> word_off((size_t)B + 1, 0);
+  int max_hyp = 0;
+  for (int b = 0; b < B; ++b) {
+    RGBL_TRY(check_sim3_input(in + b, b, false));
+    if (in[b].pool) {
+      if (pool && pool != in[b].pool) { set_error("sim3 %d: the problems of one call share one pool", b); return RGBL_ERR_INVALID; }
+      pool = in[b].pool;
+      if (pool->device != m->device) { set_error("sim3 %d: the pool is on device %d, the matcher on %d", b, pool->device, m->device); return RGBL_ERR_INVALID; }
+    }
+    const bool run = !sim3_skipped(in + b);
+    const int nh = run ? in[b].n_hyp : 0, nn = run ? in[b].n : 0;
+    if (hyp_off[(size_t)b] > INT_MAX - nh) { set_error("sim3: more than 2^31 hypotheses in one call"); return RGBL_ERR_INVALID; }
+    hyp_off[(size_t)b + 1] = hyp_off[(size_t)b] + nh;
+    inl_off[(size_t)b + 1] = inl_off[(size_t)b] + nn;   // at most 65535 each: B < 2^15 problems fit an int
+    word_off[(size_t)b + 1] = word_off[(size_t)b] + (size_t)nh * (size_t)((nn + 63) / 64);
+    max_hyp = std::max(max_hyp, nh);
+  }
+  if (word_off[(size_t)B] > (size_t)INT_MAX) { set_error("sim3: more than 2^31 mask words in one call"); return RGBL_ERR_INVALID; }
+  std::unique_lock<std::mutex> pool_lock;
+  if (pool) {
+    pool_lock = std::unique_lock<std::mutex>(pool->mu);
+    for (int b = 0; b < B; ++b)
+      if (in[b].pool)
+        for (int i = 0; i < in[b].n; ++i)
+          if (in[b].slot1[i] < 0 || in[b].slot1[i] >= pool->cap || in[b].slot2[i] < 0 || in[b].slot2[i] >= pool->cap) {
+            set_error("sim3 %d: slots (%d, %d) of correspondence %d outside [0, %d)", b, in[b].slot1[i], in[b].slot2[i], i, pool->cap);
+            return RGBL_ERR_INVALID;
+          }
+  }
+  const int H = hyp_off[(size_t)B];
+  if (H == 0) {   // nothing to run (B == 0 included)
+    for (int b = 0; b < B; ++b) out[b].selected = -1;
+    return RGBL_OK;
+  }
+  RGBL_HIP(hipSetDevice(m->device));
+  StreamDrain drain(m->stream);  // error returns included; declared behind pool_lock: the stream is drained before the pool is released
+  HostCall hc(m);
+  hipStream_t s = hc.s;
+  std::vector<Sim3Problem> prob((size_t)B);
+  Sim3Dev D;
+  memset(&D, 0, sizeof(D));
+  bool diag = false;
+  for (int b = 0; b < B; ++b) diag = diag || out[b].counts || out[b].T12_all;
+  RGBL_TRY(hc.begin([&]() -> int {
+    for (int b = 0; b < B; ++b) {
+      Sim3Problem& P = prob[(size_t)b];
+      memset(&P, 0, sizeof(P));
+      const rgbl_sim3_input& I = in[b];
+      if (sim3_skipped(&I)) continue;   // n_hyp = 0: no workgroup touches it
+      if (I.pool) {
+        P.pool_form = 1; P.wpos = pool->d_wpos;
+        hc.put(&P.slot1, I.slot1, (size_t)I.n);
+        hc.put(&P.slot2, I.slot2, (size_t)I.n);
+        memcpy(P.Rcw1, I.Rcw1, sizeof(P.Rcw1)); memcpy(P.tcw1, I.tcw1, sizeof(P.tcw1));
+        memcpy(P.Rcw2, I.Rcw2, sizeof(P.Rcw2)); memcpy(P.tcw2, I.tcw2, sizeof(P.tcw2));
+      } else {
+        hc.put(&P.x1, I.x1c, (size_t)I.n * 3);
+        hc.put(&P.x2, I.x2c, (size_t)I.n * 3);
+      }
+      hc.put(&P.e1, I.max_err1, (size_t)I.n);
+      hc.put(&P.e2, I.max_err2, (size_t)I.n);
+      hc.put(&P.samples, I.samples, (size_t)I.n_hyp * 3);
+      P.n = I.n; P.n_hyp = I.n_hyp; P.words = (I.n + 63) / 64;
+      P.hyp_off = hyp_off[(size_t)b]; P.word_off = (int)word_off[(size_t)b]; P.inl_off = inl_off[(size_t)b];
+      P.fix_scale = I.fix_scale ? 1 : 0; P.min_inliers = I.min_inliers; P.best_inliers = I.best_inliers;
+      memcpy(P.K1, I.K1, sizeof(P.K1)); memcpy(P.K2, I.K2, sizeof(P.K2));
+    }
+    D.prob = hc.stage<Sim3Problem>((size_t)B, [&](Sim3Problem* dst) { memcpy(dst, prob.data(), sizeof(Sim3Problem) * (size_t)B); });
+    D.res = hc.result<Sim3Result>((size_t)B);   // what comes back, side by side
+    D.inlier = hc.result<uint8_t>((size_t)inl_off[(size_t)B]);
+    D.hyp = diag ? hc.result<Sim3HypOut>((size_t)H) : hc.scratch<Sim3HypOut>((size_t)H);
+    D.mask = hc.scratch<unsigned long long>(word_off[(size_t)B]);
+    return RGBL_OK;
+  }));
+  m->timer.begin("k_sim3_hypotheses", s);
+  hipLaunchKernelGGL(k_sim3_hypotheses, dim3((unsigned)((max_hyp + kS3HypPerGroup - 1) / kS3HypPerGroup), (unsigned)B), dim3(256), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  m->timer.begin("k_sim3_select", s);
+  hipLaunchKernelGGL(k_sim3_select, dim3((unsigned)B), dim3(256), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(hc.fetch());
+  for (int b = 0; b < B; ++b) {
+    if (sim3_skipped(in + b)) { out[b].selected = -1; continue; }
+    write_sim3_output(in + b, out + b, hc.host(D.res)[b], hc.host(D.inlier) + inl_off[(size_t)b], hc.host(D.hyp) + hyp_off[(size_t)b]);
+  }
+  return RGBL_OK;
+}
+
+int rgbl_sim3_ransac(rgbl_matcher* m, const rgbl_sim3_input* in, rgbl_sim3_output* out) {
+  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  return rgbl_sim3_ransac_batch(m, 1, in, out);
 }
 
 // test hooks for csrc/poseopt_math.h: op 0 sin, 1 cos, 2 x / y, 3 sqrt - on the host, and compiled for the device

@@ -1242,6 +1242,97 @@ class ORBmatcher:
             L.check(self.lib, self.lib.rgbl_pose_optimization(self.h, C.byref(I), C.byref(O)))
         return self._pose_opt_result(O, outl)
 
+    @staticmethod
+    def _sim3_input(pr, keep, out=None):
+        """rgbl_sim3_input of a problem dict: x1c / x2c (n x 3 camera frames) or pool (MapPointPool) + slot1 / slot2 + Rcw1, tcw1,
+        Rcw2, tcw2; max_err1, max_err2, K1, K2 (fx fy cx cy), fix_scale, min_inliers, best_inliers (default 0), samples (n_hyp x 3)."""
+        P = out if out is not None else L.Sim3Input()
+
+        def arr(key, dt):
+            if pr.get(key) is None:
+                return None
+            keep.append(np.ascontiguousarray(pr[key], dt))
+            return keep[-1].ctypes.data
+        pool = pr.get("pool")
+        P.pool = pool.h if pool is not None else None
+        P.x1c, P.x2c = arr("x1c", np.float32), arr("x2c", np.float32)
+        P.slot1, P.slot2 = arr("slot1", np.int32), arr("slot2", np.int32)
+        P.max_err1, P.max_err2 = arr("max_err1", np.float32), arr("max_err2", np.float32)
+        P.n = int(pr["n"]) if pr.get("n") is not None else len(np.asarray(pr["max_err1"]).reshape(-1))
+        for field, cnt in (("Rcw1", 9), ("tcw1", 3), ("Rcw2", 9), ("tcw2", 3), ("K1", 4), ("K2", 4)):
+            if pr.get(field) is None:
+                continue
+            v = np.asarray(pr[field], np.float32).reshape(-1)
+            for i in range(cnt):
+                getattr(P, field)[i] = v[i]
+        P.fix_scale, P.min_inliers, P.best_inliers = int(pr["fix_scale"]), int(pr["min_inliers"]), int(pr.get("best_inliers", 0))
+        P.samples = arr("samples", np.int32)
+        P.n_hyp = int(pr["n_hyp"]) if pr.get("n_hyp") is not None else (0 if pr.get("samples") is None else len(np.asarray(pr["samples"]).reshape(-1, 3)))
+        return P
+
+    @staticmethod
+    def _sim3_buffers(I, O, fill=0, diag=True):
+        """the caller's arrays of one rgbl_sim3_output, pre-filled with `fill` so that what a call leaves untouched can be seen"""
+        inl = np.full(I.n, fill, np.uint8)
+        counts = np.full(I.n_hyp, fill, np.int32) if diag else None
+        T_all = np.full((I.n_hyp, 16), fill, np.float32) if diag else None
+        O.inlier = inl.ctypes.data
+        O.counts = counts.ctypes.data if diag else None
+        O.T12_all = T_all.ctypes.data if diag else None
+        return inl, counts, T_all
+
+    @staticmethod
+    def _sim3_result(O, bufs):
+        inl, counts, T_all = bufs
+        return dict(selected=int(O.selected), converged=int(O.converged), n_inliers=int(O.n_inliers), iterations_run=int(O.iterations_run),
+                    T12=np.array(O.T12, np.float32).reshape(4, 4), R12=np.array(O.R12, np.float32).reshape(3, 3),
+                    t12=np.array(O.t12, np.float32), s12=np.float32(O.s12), inlier=inl, counts=counts, T12_all=T_all)
+
+    def prepare_Sim3RansacBatch(self, problems, host=False, diag=True, fill=0):
+        """Sim3Solver (Sim3Solver.cc) for every problem dict in one upload, one launch pair and one read-back; the call returns
+        one dict per problem: selected, converged, n_inliers, iterations_run, T12 (4 x 4), R12, t12, s12, inlier (n bytes) and,
+        with diag, counts (n_hyp) and T12_all (n_hyp x 16).  With selected = -1 the transformation and the flags are not
+        written; for a problem that is not run (n < 3, n < min_inliers, no hypothesis) nothing but selected is."""
+        keep = []
+        B = len(problems)
+        I, O = (L.Sim3Input * max(B, 1))(), (L.Sim3Output * max(B, 1))()
+        bufs = []
+        for b, pr in enumerate(problems):
+            self._sim3_input(pr, keep, I[b])
+            bufs.append(self._sim3_buffers(I[b], O[b], fill, diag))
+        lib, h = self.lib, self.h
+
+        def call(_keep=keep):
+            if host:
+                for b in range(B):
+                    L.check(lib, lib.rgbl_sim3_ransac_host(C.byref(I[b]), C.byref(O[b])))
+            else:
+                L.check(lib, lib.rgbl_sim3_ransac_batch(h, B, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)))
+            return [self._sim3_result(O[b], bufs[b]) for b in range(B)]
+
+        def c_call(_keep=keep):   # the C call alone (what tools/sim3_bench.py times): the results stay in the structs
+            L.check(lib, lib.rgbl_sim3_ransac_batch(h, B, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)))
+
+        def c_call_host(_keep=keep):
+            for b in range(B):
+                L.check(lib, lib.rgbl_sim3_ransac_host(C.byref(I[b]), C.byref(O[b])))
+        call.c_call, call.c_call_host = c_call, c_call_host
+        return call
+
+    def Sim3RansacBatch(self, problems, host=False, diag=True, fill=0):
+        return self.prepare_Sim3RansacBatch(problems, host, diag, fill)()
+
+    def Sim3Ransac(self, problem, host=False, diag=True, fill=0):
+        """One problem through rgbl_sim3_ransac (host=True: rgbl_sim3_ransac_host, the header's host build)."""
+        keep = []
+        I, O = self._sim3_input(problem, keep), L.Sim3Output()
+        bufs = self._sim3_buffers(I, O, fill, diag)
+        if host:
+            L.check(self.lib, self.lib.rgbl_sim3_ransac_host(C.byref(I), C.byref(O)))
+        else:
+            L.check(self.lib, self.lib.rgbl_sim3_ransac(self.h, C.byref(I), C.byref(O)))
+        return self._sim3_result(O, bufs)
+
     def CreateNewMapPoints(self, kf1, neighbours, prm, skip=None, cap=None):
         return self.prepare_CreateNewMapPoints(kf1, neighbours, prm, skip, cap)()
 
@@ -1675,3 +1766,14 @@ def pose_optimization_host(frame, lib=None, outlier_fill=0):
     O.outlier = outl.ctypes.data
     L.check(lib, lib.rgbl_pose_optimization_host(C.byref(I), C.byref(O)))
     return ORBmatcher._pose_opt_result(O, outl)
+
+
+def sim3_ransac_host(problem, lib=None, diag=True, fill=0):
+    """rgbl_sim3_ransac_host: Sim3Solver by the host build of csrc/sim3_math.h (no device, no handle); the result dict of
+    ORBmatcher.Sim3Ransac."""
+    lib = lib or L.load()
+    keep = []
+    I, O = ORBmatcher._sim3_input(problem, keep), L.Sim3Output()
+    bufs = ORBmatcher._sim3_buffers(I, O, fill, diag)
+    L.check(lib, lib.rgbl_sim3_ransac_host(C.byref(I), C.byref(O)))
+    return ORBmatcher._sim3_result(O, bufs)
