@@ -56,12 +56,14 @@ typedef struct {
 typedef struct rgbl_extractor rgbl_extractor;
 
 typedef struct {
-  int nfeatures;       /* ORBextractor.nFeatures   */
+  int nfeatures;       /* ORBextractor.nFeatures: every level's share + 24 <= 65535 (positions in the quad-tree's node list travel in
+                        * 16 bits; one level: nfeatures <= 65511), RGBL_ERR_INVALID beyond */
   float scale_factor;  /* ORBextractor.scaleFactor */
   int nlevels;         /* ORBextractor.nLevels (<= 16) */
   int ini_th_fast;     /* ORBextractor.iniThFAST   */
   int min_th_fast;     /* ORBextractor.minThFAST   */
-  int width, height;   /* image size this handle is built for (<= 4096 x 4096) */
+  int width, height;   /* image size this handle is built for (64 .. 4096 each: a quad-tree node's x travels in 12 bits of its sort
+                        * key; every level at least one 35-px detection cell and at most 16 quad-tree roots wide) */
   int max_batch;       /* frames per batched call (>= 1) */
 } rgbl_extractor_cfg;
 
@@ -389,7 +391,10 @@ int rgbl_structuring_element(int shape, int kw, int kh, uint8_t* out);
  * (DepthModule.h:62, DepthModule.cc:50-79).  cloud = the 4 x n CV_32F matrix of
  * Examples/RGB-L/rgbl_kitti.cc:151-185 (rows x,y,z,1; `ld` floats between rows).  kp_xy = k pairs
  * (pt.x, pt.y) of mvKeys, kpun_x = pt.x of mvKeysUn.  Outputs mvDepth / mvuRight (k floats each) and,
- * if non-NULL, RawDepthMap / ProcessedDepthMap (h*w floats each). */
+ * if non-NULL, RawDepthMap / ProcessedDepthMap (h*w floats each).
+ * Any n up to max_points is taken.  Inverse dilation without the maps reads the points' depths through the index map, whose
+ * entries are generation << 20 | point index + 1: scans of up to 2^20 - 2 points; from 2^20 - 1 points on the call goes through
+ * the raw map as if the maps had been asked for (same results). */
 int rgbl_depth_compute(rgbl_depth* h, const float* cloud, int n, int ld, int w, int h_,
                        const float* kp_xy, const float* kpun_x, int k, float* out_depth,
                        float* out_uright, float* out_raw, float* out_processed);
@@ -483,7 +488,8 @@ int rgbl_matcher_profile_samples(rgbl_matcher* h, int kernel, float* ms, int cap
 int rgbl_descriptor_distance(const uint8_t* a, const uint8_t* b);
 
 /* Hamming brute force: for every row of A the best and second-best row of B, selection rule of
- * ORBmatcher.cc:283-304 (strict '<': the first minimum wins; distances start at 256, idx at -1).
+ * ORBmatcher.cc:283-304 (strict '<': the first minimum wins; distances start at 256, idx at -1 - so a row at distance 256, a
+ * complement, is never the best).  nb <= 65535: a train row's index travels in 16 bits (RGBL_ERR_INVALID beyond, nothing written).
  * Host pointers, synchronous.  second_dist may be NULL. */
 int rgbl_hamming_bf(rgbl_matcher* h, const uint8_t* desc_a, int na, const uint8_t* desc_b, int nb,
                     int32_t* best_idx, int32_t* best_dist, int32_t* second_dist);
@@ -498,7 +504,7 @@ int rgbl_stereo_fisheye_matches(rgbl_matcher* h, const uint8_t* desc_left, int n
                                 int n_right, int mono_right, int32_t* left_to_right, int32_t* best_dist, int32_t* second_dist);
 /* Device batch over frame pairs: descriptors of frame f live at d_desc + f*cap*32 with d_n[f] rows
  * (the layout rgbl_extract_batch_device() writes).  Pair p matches frame pair_a[p] (queries) against
- * frame pair_b[p] (train); outputs for pair p start at p*cap. */
+ * frame pair_b[p] (train); outputs for pair p start at p*cap.  cap 1 .. 65535 (RGBL_ERR_INVALID beyond). */
 int rgbl_hamming_bf_batch_device(rgbl_matcher* h, const uint8_t* d_desc, const int32_t* d_n, int cap,
                                  const int32_t* d_pair_a, const int32_t* d_pair_b, int n_pairs,
                                  int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_second_dist);
@@ -513,7 +519,7 @@ int rgbl_hamming_bf_batch_device(rgbl_matcher* h, const uint8_t* d_desc, const i
  * these four arrays are then not read.  Optionally the FeatureVector's CSR arrays as well.  A frame object is filled by one
  * thread at a time; once filled it may be read by any number of concurrent matcher calls. */
 typedef struct rgbl_device_frame rgbl_device_frame;
-int rgbl_device_frame_create(int device, int capacity /* features */, rgbl_device_frame** out);
+int rgbl_device_frame_create(int device, int capacity /* features, 1 .. 65535: the matchers' 16-bit feature indices */, rgbl_device_frame** out);
 void rgbl_device_frame_destroy(rgbl_device_frame* f);
 /* n <= capacity features from host arrays; uright may be NULL (monocular: all -1).  Synchronous. */
 int rgbl_device_frame_upload(rgbl_device_frame* f, int n, const uint8_t* desc, const float* kp_xy, const int32_t* kp_octave,
@@ -647,7 +653,9 @@ int rgbl_triangulate_matches_host(const rgbl_new_points_keyframe* kf1, const rgb
  * Single-camera frames.  kf: the key-frame (has_mappoint = GetMapPointMatches()[i] != NULL && !isBad(), kp_angle =
  * mvKeysUn[i].angle, FeatureVector as CSR); frame: F.mDescriptors, kp_angle = F.mvKeys[i].angle, F.mFeatVec (the other
  * fields of the view are not read).  match_f (frame->n entries): index of the key-frame feature whose map point ends up
- * in vpMapPointMatches[i], or -1.  Host pointers, synchronous. */
+ * in vpMapPointMatches[i], or -1.  Host pointers, synchronous.
+ * All three SearchByBoW entry points: a vocabulary node the two sets share may hold at most 16384 features of the second set (the
+ * frame; kf2) - a bucket position indexes one byte of LDS each; RGBL_ERR_INVALID beyond, before match_f / match12 is written. */
 int rgbl_search_by_bow(rgbl_matcher* h, const rgbl_keyframe_view* kf, const rgbl_keyframe_view* frame, float nnratio,
                        int check_orientation, int32_t* match_f, int* out_nmatches);
 /* The same for a two-camera frame (F.Nleft != -1: the fisheye rig; src/ORBmatcher.cc:298-326 and 357-386).  frame_n_left =

@@ -889,7 +889,7 @@ int rgbl_extractor_create(const rgbl_extractor_cfg* cfg, int device, rgbl_extrac
   if (cfg->nlevels < 1 || cfg->nlevels > kMaxLevels || cfg->nfeatures < 1 || cfg->scale_factor < 1.0f ||
       cfg->width < 64 || cfg->height < 64 || cfg->width > 4096 || cfg->height > 4096 || cfg->max_batch < 1 ||
       cfg->min_th_fast < 1 || cfg->ini_th_fast < cfg->min_th_fast || cfg->ini_th_fast > 255) {
-    set_error("invalid extractor configuration");
+    set_error("invalid extractor configuration (1 .. %d levels, images of 64 x 64 .. 4096 x 4096: a quad-tree node's x travels in 12 bits of its sort key)", kMaxLevels);
     return RGBL_ERR_INVALID;
   }
   if (rgbl_device_count() <= device || device < 0) {

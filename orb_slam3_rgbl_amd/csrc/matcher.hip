@@ -67,6 +67,8 @@ __device__ __forceinline__ int desc_dist(const Desc256& a, const Desc256& b) { r
 // second-best is the second smallest word, whose distance part is the second smallest distance counted with
 // multiplicity.  The four partial results are merged through LDS with the same two operations.
 // grid = (ceil(cap/64), n_pairs), block = 256.  Requires train counts < 65536.
+// (All three scans: a key of distance 256 - a complement - orders below kNone but is no match: the selection starts at 256 with
+// strict '<', so the index written for it is -1.)
 __device__ __forceinline__ void bf_track(uint32_t& best, uint32_t& second, uint32_t cur) {
   // best <= second always: the new second is the median of (best, cur, second) - one v_med3_u32 instead of max + min
 #ifdef RGBL_EMU
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(256) void k_hamming_bf(const uint8_t* __restrict__ 
       second = second < hi ? second : hi;
     }
     const size_t o = (size_t)p * cap + i;
-    best_idx[o] = best == kNone ? -1 : (int32_t)(best & 0xffffu);
+    best_idx[o] = best >= (256u << 16) ? -1 : (int32_t)(best & 0xffffu);
     best_dist[o] = (int32_t)(best >> 16);
     if (second_dist) second_dist[o] = (int32_t)(second >> 16);
   }
@@ -288,7 +290,7 @@ __global__ __launch_bounds__(256) void k_hamming_mfma(const uint8_t* __restrict_
     const int qi = q_base + wave * 64 + ct * 32 + col;
     if (half == 0 && qi < na) {
       const size_t o = (size_t)p * cap + qi;
-      best_idx[o] = out_best[ct] == kNone ? -1 : (int32_t)(out_best[ct] & 0xffffu);
+      best_idx[o] = out_best[ct] >= (256u << 16) ? -1 : (int32_t)(out_best[ct] & 0xffffu);
       best_dist[o] = (int32_t)(out_best[ct] >> 16);
       if (second_dist) second_dist[o] = (int32_t)(out_second[ct] >> 16);
     }
@@ -578,7 +580,7 @@ __global__ __launch_bounds__(256, 4) void k_hamming_fp4(const uint8_t* __restric
         o[0] = out_best[ct]; o[1] = out_second[ct];
       } else {
         const size_t o = (size_t)p * cap + qi;
-        best_idx[o] = out_best[ct] == kNone ? -1 : (int32_t)(out_best[ct] & 0xffffu);
+        best_idx[o] = out_best[ct] >= (256u << 16) ? -1 : (int32_t)(out_best[ct] & 0xffffu);
         best_dist[o] = (int32_t)(out_best[ct] >> 16);
         if (second_dist) second_dist[o] = (int32_t)(out_second[ct] >> 16);
       }
@@ -597,7 +599,7 @@ __global__ __launch_bounds__(256) void k_hamming_merge(const uint32_t* __restric
     const uint32_t* o = partial + ((size_t)sp * na + qi) * 2;
     bf_merge(b, s2, o[0], o[1]);
   }
-  best_idx[qi] = b == kNone ? -1 : (int32_t)(b & 0xffffu);
+  best_idx[qi] = b >= (256u << 16) ? -1 : (int32_t)(b & 0xffffu);
   best_dist[qi] = (int32_t)(b >> 16);
   if (second_dist) second_dist[qi] = (int32_t)(s2 >> 16);
 }
@@ -2990,7 +2992,7 @@ int rgbl_hamming_bf_batch_device(rgbl_matcher* m, const uint8_t* d_desc, const i
                                  const int32_t* d_pair_b, int n_pairs, int32_t* d_best_idx, int32_t* d_best_dist,
                                  int32_t* d_second_dist) {
   if (!m || !d_desc || !d_n || !d_pair_a || !d_pair_b || !d_best_idx || !d_best_dist || cap < 1 || cap > 65535 || n_pairs < 0) {
-    set_error("invalid argument");
+    set_error("invalid argument (cap 1 .. 65535: a train row's index travels in 16 bits)");
     return RGBL_ERR_INVALID;
   }
   if (n_pairs == 0) return RGBL_OK;
@@ -3014,7 +3016,7 @@ int rgbl_hamming_bf_batch_device(rgbl_matcher* m, const uint8_t* d_desc, const i
 int rgbl_hamming_bf(rgbl_matcher* m, const uint8_t* desc_a, int na, const uint8_t* desc_b, int nb, int32_t* best_idx,
                     int32_t* best_dist, int32_t* second_dist) {
   if (!m || na < 0 || nb < 0 || nb > 65535 || (na > 0 && (!desc_a || !best_idx || !best_dist)) || (nb > 0 && !desc_b)) {
-    set_error("invalid argument");
+    set_error("invalid argument (at most 65535 train descriptors: a train row's index travels in 16 bits)");
     return RGBL_ERR_INVALID;
   }
   if (na == 0) return RGBL_OK;
@@ -3488,11 +3490,11 @@ int greedy_search(rgbl_matcher* m, hipStream_t s, ProjDev& P, const rgbl_device_
 }
 
 int projection_core(rgbl_matcher* m, const ProjHost& in, int32_t* match2, int* out_nmatches) {
-  *out_nmatches = 0;
   const int n1 = in.n1, n2 = in.n2;
+  RGBL_TRY(check_point_count(n1));  // before anything is written: a refused call leaves the outputs as they were
+  *out_nmatches = 0;
   for (int i = 0; i < n2; ++i) match2[i] = -1;
   if (n1 == 0 || n2 == 0) return RGBL_OK;
-  RGBL_TRY(check_point_count(n1));
   RGBL_TRY(check_levels(in.valid1, in.oct1, n1, in.n_levels, "octave out of range"));
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
@@ -4904,16 +4906,24 @@ int rgbl_bow_transform_frame(rgbl_vocabulary* v, const rgbl_device_frame* frame,
 // device part of both SearchByBoW overloads over the shared nodes `sn` of (kf, fr): match1[idx1] = feature of `fr` taken by
 // key-frame feature idx1 (or -1), match2 the inverse; a caller passes nullptr for the one it does not want, and has filled the
 // other with -1
+// a second-set feature's bucket position indexes BowLds::taken (and travels in the low 16 bits of the search key): the entry points
+// refuse a larger bucket before they write anything
+static int check_bow_buckets(const SharedNodes& sn) {
+  const rgbl_keyframe_view* fr = sn.b;
+  if (sn.empty()) return RGBL_OK;
+  for (int p = 0; p < sn.npairs(); ++p)
+    if (fr->node_off[sn.pb[p] + 1] - fr->node_off[sn.pb[p]] > kBowBucket) {
+      set_error("SearchByBoW: a vocabulary node holds more than %d features of the second set", kBowBucket);
+      return RGBL_ERR_INVALID;
+    }
+  return RGBL_OK;
+}
+
 static int bow_core(rgbl_matcher* m, const SharedNodes& sn, float nnratio, bool second_needs_mp, int max_best, int n_left2,
                     int32_t* match1, int32_t* match2) {
   const rgbl_keyframe_view *kf = sn.a, *fr = sn.b;
   const int n1 = kf->n, n2 = fr->n, npairs = sn.npairs();
   if (sn.empty()) return RGBL_OK;
-  for (int p = 0; p < npairs; ++p)
-    if (fr->node_off[sn.pb[p] + 1] - fr->node_off[sn.pb[p]] > kBowBucket) {
-      set_error("SearchByBoW: a vocabulary node holds more than %d features of the second set", kBowBucket);
-      return RGBL_ERR_CAPACITY;
-    }
   RGBL_HIP(hipSetDevice(m->device));
   StreamDrain drain(m->stream);  // error returns included
   HostCall hc(m);
@@ -4962,10 +4972,12 @@ int rgbl_search_by_bow_rig(rgbl_matcher* m, const rgbl_keyframe_view* kf, const 
     set_error("invalid argument");
     return RGBL_ERR_INVALID;
   }
+  const SharedNodes sn(kf, fr);
+  RGBL_TRY(check_bow_buckets(sn));
   *out_nmatches = 0;
   const int n2 = fr->n;
   for (int i = 0; i < n2; ++i) match_f[i] = -1;
-  RGBL_TRY(bow_core(m, SharedNodes(kf, fr), nnratio, false, 50 /* <= TH_LOW */, frame_n_left, nullptr, match_f));
+  RGBL_TRY(bow_core(m, sn, nnratio, false, 50 /* <= TH_LOW */, frame_n_left, nullptr, match_f));
   int nmatches = 0;
   for (int i = 0; i < n2; ++i) nmatches += match_f[i] >= 0;
   if (check_orientation) {
@@ -4983,9 +4995,10 @@ int rgbl_search_by_bow_rig(rgbl_matcher* m, const rgbl_keyframe_view* kf, const 
 int rgbl_search_by_bow_keyframes(rgbl_matcher* m, const rgbl_keyframe_view* kf1, const rgbl_keyframe_view* kf2, float nnratio,
                                  int check_orientation, int32_t* match12, int* out_nmatches) {
   if (!m || !kf1 || !kf2 || !match12 || !out_nmatches || kf1->n < 0 || kf2->n < 0) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  const SharedNodes sn(kf1, kf2);
+  RGBL_TRY(check_bow_buckets(sn));
   *out_nmatches = 0;
   for (int i = 0; i < kf1->n; ++i) match12[i] = -1;
-  const SharedNodes sn(kf1, kf2);
   RGBL_TRY(bow_core(m, sn, nnratio, true, 49 /* < TH_LOW */, -1, match12, nullptr));
   finish_matches12(sn, match12, check_orientation != 0, out_nmatches);
   return RGBL_OK;

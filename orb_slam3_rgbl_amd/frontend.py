@@ -826,6 +826,9 @@ class ORBmatcher:
         return best
 
     def ProjectSearch(self, case, th, proj_form, max_dist):
+        return self.prepare_ProjectSearch(case, th, proj_form, max_dist)()
+
+    def prepare_ProjectSearch(self, case, th, proj_form, max_dist):
         """The per-point search of Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (proj_form 0, max_dist TH_LOW) and of both
         directions of SearchBySim3 (proj_form 1, max_dist TH_HIGH): case has valid1, cam_pos1 (points already in the key
         frame's camera frame), mp_desc1, level1, kp2_xy, kp2_octave, desc2, grid[6], K[4], scale_factors.
@@ -851,10 +854,17 @@ class ORBmatcher:
         P.device2 = _dev(case, "device2")
         best = np.zeros(P.n1, np.int32)
         dist = np.zeros(P.n1, np.int32)
-        L.check(self.lib, self.lib.rgbl_project_search(self.h, C.byref(P), L.ptr(best), L.ptr(dist)))
-        return best, dist
+        fn, h, pP, pb, pd = self.lib.rgbl_project_search, self.h, C.byref(P), L.ptr(best), L.ptr(dist)
+
+        def call(_keep=keep):
+            L.check(self.lib, fn(h, pP, pb, pd))
+            return best, dist
+        return call
 
     def SearchByProjectionSim3(self, case, matched2, th, proj_form, max_dist):
+        return self.prepare_SearchByProjectionSim3(case, matched2, th, proj_form, max_dist)()
+
+    def prepare_SearchByProjectionSim3(self, case, matched2, th, proj_form, max_dist):
         """The greedy search of ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (proj_form 0) and of
         its vpPointsKFs overload (proj_form 2), max_dist = floor(TH_LOW * ratioHamming); case as for ProjectSearch, matched2 =
         vpMatched[i] != NULL on entry.  Returns (point index stored in vpMatched[i2] by the call or -1, nmatches)."""
@@ -880,8 +890,12 @@ class ORBmatcher:
         m2 = np.ascontiguousarray(matched2, np.uint8)
         match = np.zeros(P.n2, np.int32)
         n = C.c_int(0)
-        L.check(self.lib, self.lib.rgbl_search_by_projection_sim3(self.h, C.byref(P), L.ptr(m2), L.ptr(match), C.byref(n)))
-        return match, n.value
+        fn, h, pP, pb, pm, pn = self.lib.rgbl_search_by_projection_sim3, self.h, C.byref(P), L.ptr(m2), L.ptr(match), C.byref(n)
+
+        def call(_keep=keep):
+            L.check(self.lib, fn(h, pP, pb, pm, pn))
+            return match, n.value
+        return call
 
     def SearchLocalPoints(self, pts, th):
         """Tracking::SearchLocalPoints.  pts with the map points themselves (world_pos1 ..., or pool + slot1; cases.make_local_map_case):

@@ -191,6 +191,59 @@ def check_errors(lib, mt):
     same(mt.PoseOptimization(base), F.pose_optimization_host(base, lib), "after the refused calls")
 
 
+# ---- n <= 65535: an edge names its feature in 16 bits ------------------------------------------------------------------------
+N_MAX = 65535
+PER_FEATURE = ("mp_index", "xy", "octave", "uright", "planted_outlier")
+
+
+def limit_case(matched=30000, seed=3):
+    """N_MAX features, `matched` with a map point; the last feature (65534) carries an edge, and so does one with bit 15 set"""
+    case = cases.make_pose_opt_case(N_MAX, matched, seed=seed)
+    mp = case["mp_index"]
+    if mp[N_MAX - 1] < 0:
+        i = int(np.nonzero(mp >= 0)[0][matched // 2])
+        for k in PER_FEATURE:
+            case[k][[i, N_MAX - 1]] = case[k][[N_MAX - 1, i]]
+    assert mp[N_MAX - 1] >= 0 and (mp[32768:N_MAX - 1] >= 0).any() and int((mp >= 0).sum()) == matched
+    return case
+
+
+def check_limit(lib, mt):
+    case = limit_case()
+    want = F.pose_optimization_host(case, lib, outlier_fill=7)
+    assert want["rounds"] == 4 and want["active"][0] == 30000 and want["result"] > 20000, want
+    assert want["outlier"][N_MAX - 1] != 7 and (want["outlier"][case["mp_index"] < 0] == 7).all()
+    same(mt.PoseOptimization(case, outlier_fill=7), want, "%d features" % N_MAX)
+    # the other value of the last edge's flag: its observation moved 40 px away
+    far = dict(case, xy=case["xy"].copy())
+    far["xy"][N_MAX - 1] += np.float32(40.0 if not want["outlier"][N_MAX - 1] else 0.0)
+    want2 = F.pose_optimization_host(far, lib, outlier_fill=7)
+    assert want2["outlier"][N_MAX - 1] == 1
+    same(mt.PoseOptimization(far, outlier_fill=7), want2, "%d features, the last edge an outlier" % N_MAX)
+    return want["result"]
+
+
+def check_limit_refused(lib, mt):
+    """n = 65536 (refused before an array is read): RGBL_ERR_INVALID that names 65535, nothing written, by all three entry points"""
+    base = cases.make_pose_opt_case(60, 40, seed=31)
+    for entry in ("single", "batch", "host"):
+        keep = []
+        I, O = (L.PoseOptInput * 2)(), (L.PoseOptOutput * 2)()
+        outl = [np.full(60, 9, np.uint8), np.full(60, 9, np.uint8)]
+        for b in range(2):
+            F.ORBmatcher._pose_opt_input(base, keep, I[b])
+            C.memset(C.byref(O[b]), 0x5a, C.sizeof(L.PoseOptOutput))
+            O[b].outlier = outl[b].ctypes.data
+        I[1].n = N_MAX + 1
+        before = [bytes(O[0]), bytes(O[1])]
+        rc = {"single": lambda: lib.rgbl_pose_optimization(mt.h, C.byref(I[1]), C.byref(O[1])),
+              "batch": lambda: lib.rgbl_pose_optimization_batch(mt.h, 2, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)),
+              "host": lambda: lib.rgbl_pose_optimization_host(C.byref(I[1]), C.byref(O[1]))}[entry]()
+        assert rc == L.ERR_INVALID and b"65535" in lib.rgbl_last_error(), (entry, rc, lib.rgbl_last_error())
+        assert [bytes(O[0]), bytes(O[1])] == before and (outl[0] == 9).all() and (outl[1] == 9).all(), entry
+    same(mt.PoseOptimization(base), F.pose_optimization_host(base, lib), "after the refused calls")
+
+
 def check_threads(lib, rounds=4):
     """the call next to other matcher calls from other threads, every thread on a handle of its own"""
     case = cases.make_pose_opt_case(600, 400, seed=41)

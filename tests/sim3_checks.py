@@ -214,6 +214,7 @@ def check_errors(lib, mt):
            "threshold inf": broken("max_err1", 0, np.inf),
            "n too large": dict(base, n=65536),
            "n_hyp negative": dict(base, n_hyp=-1),
+           "n_hyp too large": dict(base, n_hyp=N_HYP_MAX + 1),
            "no points": dict({k: v for k, v in base.items() if k != "x2c"}),
            "no thresholds": dict({k: v for k, v in base.items() if k != "max_err1"}, n=40),
            "slot outside the pool": sc.pool_problem(case, pool, np.arange(40, dtype=np.int32), np.zeros(40, np.int32)),
@@ -227,7 +228,7 @@ def check_errors(lib, mt):
             bufs = []
             for b in range(2):
                 C.memset(C.byref(O[b]), 0x5a, C.sizeof(L.Sim3Output))
-                n, nh = min(max(I[b].n, 0), 40), max(I[b].n_hyp, 0)
+                n, nh = min(max(I[b].n, 0), 40), min(max(I[b].n_hyp, 0), 5)
                 bufs.append((np.full(n, 9, np.uint8), np.full(nh, 9, np.int32), np.full((nh, 16), 9, np.float32)))
                 O[b].inlier, O[b].counts, O[b].T12_all = [a.ctypes.data for a in bufs[b]]
             before = [bytes(O[0]), bytes(O[1])]
@@ -236,6 +237,8 @@ def check_errors(lib, mt):
             else:
                 rc = lib.rgbl_sim3_ransac(mt.h, C.byref(I[1]), C.byref(O[1]))
             assert rc == L.ERR_INVALID, (what, batch, rc)
+            if what in ("n too large", "n_hyp too large"):
+                assert b"65535" in lib.rgbl_last_error() and b"%d" % N_HYP_MAX in lib.rgbl_last_error(), lib.rgbl_last_error()
             assert [bytes(O[0]), bytes(O[1])] == before, (what, batch)
             assert all((a == 9).all() for bb in bufs for a in bb), (what, batch)
             if not batch:   # the host build refuses the same things (and every pool)
@@ -257,6 +260,54 @@ def check_errors(lib, mt):
     for p in (pool, pool2, pool3):
         p.close()
     same(mt.Sim3Ransac(base), F.sim3_ransac_host(base, lib), "after the refused calls")
+
+
+# ---- n <= 65535 correspondences, n_hyp <= 2^20 hypotheses ---------------------------------------------------------------------
+N_MAX, N_HYP_MAX = 65535, 1 << 20
+PER_POINT = ("x1c", "x2c", "max_err1", "max_err2", "planted_outlier", "Xw1", "Xw2")
+
+
+def limit_n_problem(lib):
+    """N_MAX correspondences; the selected hypothesis counts correspondences 32768 and 65534 (the last) as inliers, and the
+    first sample names both.  Returns (problem, the host build's result)."""
+    case = sized_case(N_MAX, 20, False, seed=7)
+    good = np.nonzero(case["planted_outlier"] == 0)[0]
+    for at, k in ((N_MAX - 1, 10), (32768, 11)):
+        if case["planted_outlier"][at]:
+            for key in PER_POINT:
+                case[key][[at, good[k]]] = case[key][[good[k], at]]
+    case["samples"][0] = (N_MAX - 1, 32768, int(good[12]))
+    pr = sc.problem(case, min_inliers=N_MAX)      # runs through: the best of the twenty is selected
+    want = F.sim3_ransac_host(pr, lib, fill=FILL)
+    assert want["selected"] >= 0 and want["iterations_run"] == 20 and want["n_inliers"] >= floor_of(N_MAX), want["n_inliers"]
+    assert want["inlier"][N_MAX - 1] == 1 and want["inlier"][32768] == 1 and want["counts"][0] > 0
+    return pr, want
+
+
+def floor_of(of):
+    return -(-of // 20)      # 5 %, as geometry_checks.FLOOR
+
+
+def check_limit_n(lib, mt):
+    pr, want = limit_n_problem(lib)
+    same(mt.Sim3Ransac(pr, fill=FILL), want, "%d correspondences" % N_MAX)
+    return want["n_inliers"]
+
+
+def check_limit_hyp(lib, mt, n=20):
+    """N_HYP_MAX hypotheses of n correspondences, run through; the best triple once more as the last hypothesis: the later one wins
+    a tie, so the selection is hypothesis 2^20 - 1"""
+    case = sized_case(n, 1, False, seed=11, outlier_share=0.2)
+    rng = np.random.default_rng(5)
+    samples = np.ascontiguousarray(rng.permuted(np.tile(np.arange(n, dtype=np.int32), (N_HYP_MAX, 1)), axis=1)[:, :3])
+    pr = sc.problem(case, samples=samples, n_hyp=N_HYP_MAX, min_inliers=n)
+    first = F.sim3_ransac_host(pr, lib)
+    samples[-1] = samples[int(np.argmax(first["counts"]))]
+    want = F.sim3_ransac_host(pr, lib, fill=FILL)
+    assert want["selected"] == N_HYP_MAX - 1 and want["iterations_run"] == N_HYP_MAX and want["converged"] == 0, want["selected"]
+    assert want["n_inliers"] == want["counts"].max() >= 3 and (want["counts"][N_HYP_MAX // 2:] > 3).any()
+    same(mt.Sim3Ransac(pr, fill=FILL), want, "%d hypotheses" % N_HYP_MAX)
+    return want["n_inliers"]
 
 
 def check_threads(lib, rounds=4):

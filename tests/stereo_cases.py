@@ -648,6 +648,30 @@ def case_host_sizes(lib, dev):
     return 8
 
 
+# ---- 65535 keypoints in a view: the lane merge keeps the right index in 16 bits (the refusals: case_argument_errors) ---------
+LIMIT = 65535
+
+
+def case_limit(lib, dev, side):
+    """side "right": 65535 right keypoints, the intended matches at right indices 65534 (the last), 32768 and 32767; side "left":
+    65535 left keypoints of which the last and number 32768 own an intended match"""
+    r = rig(lib, "bands")
+    rng = np.random.default_rng(LIMIT + len(side))
+    g = rng.permutation(r.good())
+    if side == "right":
+        n_left, n_right = 130, LIMIT
+        placed = {j: (i, 0.0, int(rng.integers(0, 9)), int(rng.integers(0, 256))) for i, j in enumerate((LIMIT - 1, 32768, 32767, 0, 2048, 40000))}
+    else:
+        n_left, n_right = LIMIT, 2049
+        placed = {j: (i, 0.0, int(rng.integers(0, 9)), int(rng.integers(0, 256))) for i, j in ((LIMIT - 1, 2048), (32768, 37), (0, 0))}
+    kl, dl = lefts_from(r, g, n_left)
+    kr, dr = right_set(r, kl, dl, n_right, placed, rng)
+    our, odp = r.match(kl, dl, kr, dr, what="limit, %s" % side)
+    for j, p in placed.items():
+        assert_matched(r, kl, kr, our, odp, p[0], j, "limit, %s" % side)
+    return int((odp > 0).sum())
+
+
 # ---- batch entry point ------------------------------------------------------------------------------------------------
 BATCH_CAP = 2200
 BATCHES = {5: [(BATCH_CAP, 40), (0, 7), (1, 2049), (130, 0), (2100, BATCH_CAP)], 3: [(65, 2049), (0, 5), (BATCH_CAP, 33)], 1: [(130, 2051)]}

@@ -121,21 +121,103 @@ def check_ties_and_extremes(lib):
     assert (bi[0], bd[0], sd[0]) == (0, 0, 256)
     bi, bd, sd = ms.check(a[:1], np.concatenate([comp[:1], a[:1]]), "256 then 0")
     assert (bi[0], bd[0], sd[0]) == (1, 0, 256)
+    # nothing but complements: the selection starts at 256 with a strict '<', so there is no best row
+    for nb in (1, 2, 33, 97):
+        bi, bd, sd = ms.check(a[:1], np.repeat(comp[:1], nb, 0), "256 only")
+        assert (bi[0], bd[0], sd[0]) == (-1, 256, 256)
     # an empty train set
     bi, bd, sd = ms.check(a, np.zeros((0, 32), np.uint8), "empty")
     assert (bi == -1).all() and (bd == 256).all() and (sd == 256).all()
     ms.close()
 
 
-def check_batch_device(lib, dev):
-    """rgbl_hamming_bf_batch_device: three pairs of unequal n in one launch."""
+# ---- the 16-bit train index: nb = 65535 is the most a call accepts (tests/limit_cases.py) ------------------------------------
+LIMIT_NB = 65535
+LAST, TOP_BIT = LIMIT_NB - 1, 32768
+
+
+def limit_near_rows(a, seed=7):
+    """LIMIT_NB _near rows in which query 0 has its only exact copy in the last row and query 1 in row 32768 (_near alone leaves
+    every exact copy at a low index: the lowest one wins)"""
+    b = _near(a, LIMIT_NB, seed)
+    for q, row in ((0, LAST), (1, TOP_BIT)):
+        same = (b == a[q]).all(1)
+        b[same, 5] ^= np.uint8(0x10)
+        b[row] = a[q]
+    return b
+
+
+def limit_directed(a0):
+    """(what, train rows, expected (best index, best distance, second distance) of the one query a0[0]) at nb = LIMIT_NB"""
+    far = np.bitwise_not(a0[:1])
+    for best_row, second_row in ((LAST, TOP_BIT), (TOP_BIT, LAST)):
+        t = np.repeat(far, LIMIT_NB, 0)
+        t[best_row] = a0[0]
+        t[second_row] = a0[0]
+        t[second_row, 3] ^= 0x21
+        yield "best in row %d, second in row %d" % (best_row, second_row), t, (best_row, 0, 2)
+    t = np.repeat(far, LIMIT_NB, 0)
+    t[TOP_BIT - 1] = a0[0]
+    t[LAST] = a0[0]
+    yield "a tie between rows 32767 and 65534", t, (TOP_BIT - 1, 0, 0)
+    # distance 256 in every row, the last one included: the key 256 << 16 | 0xfffe is one below kNone = 256 << 16 | 0xffff
+    # (no row is nearer than 256, where the selection starts: there is no best row)
+    yield "complements only", np.repeat(far, LIMIT_NB, 0), (-1, 256, 256)
+    # ... and 256 as the runner-up's distance: the best in the last row at 255
+    t = np.repeat(far, LIMIT_NB, 0)
+    t[LAST, 0] ^= 1
+    yield "255 in row 65534 among complements", t, (LAST, 255, 256)
+
+
+def check_limit_rows(lib, first_only=False):
+    """nb = LIMIT_NB.  first_only: one query row and the first directed case (what the emulator tier can afford)."""
+    ms = _Matchers(lib)
+    a = _desc(65, 13)
+    cases_ = list(limit_directed(a))
+    for what, t, expect in cases_[:1] if first_only else cases_:
+        bi, bd, sd = ms.check(a[:1], t, what)
+        if expect is not None:
+            assert (bi[0], bd[0], sd[0]) == expect, (what, bi[0], bd[0], sd[0])
+    if not first_only:
+        b = limit_near_rows(a)
+        bi, bd, sd = ms.check(a, b, "near rows at the limit")
+        assert (bi[0], bd[0]) == (LAST, 0) and (bi[1], bd[1]) == (TOP_BIT, 0), (bi[:2], bd[:2])
+    ms.close()
+
+
+def check_limit_refused(lib):
+    """nb = 65536: RGBL_ERR_INVALID, the outputs keep the caller's pattern, the handle still works"""
+    m = F.ORBmatcher(0.6, False, lib=lib)
+    a = _desc(3, 17)
+    b = np.zeros((LIMIT_NB + 1, 32), np.uint8)
+    out = [np.full(3, -7, np.int32) for _ in range(3)]
+    rc = lib.rgbl_hamming_bf(m.h, L.ptr(a), 3, L.ptr(b), LIMIT_NB + 1, L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]))
+    assert rc == L.ERR_INVALID and b"65535" in lib.rgbl_last_error(), (rc, lib.rgbl_last_error())
+    assert all((o == -7).all() for o in out)
+    # the batch entry point tests cap before it touches a pointer
+    one = C.c_void_p(a.ctypes.data)
+    rc = lib.rgbl_hamming_bf_batch_device(m.h, one, one, LIMIT_NB + 1, one, one, 1, one, one, one)
+    assert rc == L.ERR_INVALID and b"65535" in lib.rgbl_last_error(), (rc, lib.rgbl_last_error())
+    t = _near(a, 40, 3)
+    for g, w in zip(m.BruteForce(a, t), O.hamming_bf(a, t)):
+        assert np.array_equal(g, w)
+    m.close()
+
+
+def check_batch_device_at_limit(lib, dev):
+    """rgbl_hamming_bf_batch_device with cap = 65535: one pair whose train frame is full (d_n = 65535), one the other way round"""
+    a = _desc(65, 13)
+    check_batch_device(lib, dev, n=(65, LIMIT_NB), pairs=((0, 1), (1, 0)), cap=LIMIT_NB, frames=[a, limit_near_rows(a)],
+                       expect={0: ((0, LAST), (1, TOP_BIT))})
+
+
+def check_batch_device(lib, dev, n=(65, 257, 33, 130), pairs=((0, 1), (1, 2), (3, 0)), cap=300, frames=None, expect=None):
+    """rgbl_hamming_bf_batch_device: three pairs of unequal n in one launch.  expect: {pair: ((query, best index), ...)}"""
     import torch
-    n = (65, 257, 33, 130)
-    pairs = ((0, 1), (1, 2), (3, 0))
-    cap = 300
-    frames = [_desc(n[0], 70)]
-    for k in (1, 2, 3):
-        frames.append(_near(frames[0], n[k], 70 + k))
+    if frames is None:
+        frames = [_desc(n[0], 70)]
+        for k in (1, 2, 3):
+            frames.append(_near(frames[0], n[k], 70 + k))
     desc = np.zeros((len(n), cap, 32), np.uint8)
     for k, f in enumerate(frames):
         desc[k, : n[k]] = f
@@ -154,6 +236,8 @@ def check_batch_device(lib, dev):
         want = O.hamming_bf(frames[fa], frames[fb])
         for g, w, name in zip(got, want, ("best index", "best distance", "second distance")):
             assert np.array_equal(g[k, : n[fa]], w), "pair %d: %s differs" % (k, name)
+        for q, row in (expect or {}).get(k, ()):
+            assert want[0][q] == row, (k, q, want[0][q])
     m.close()
 
 
@@ -174,6 +258,10 @@ def test_emu_ties_and_extremes(emu_lib):
 def test_emu_batch_device(emu_lib):
     import torch
     check_batch_device(emu_lib, torch.device("cpu"))
+
+
+def test_emu_train_set_of_65536_rows_is_refused(emu_lib):
+    check_limit_refused(emu_lib)
 
 
 # ---- the device ---------------------------------------------------------------------------------------------------
@@ -197,3 +285,8 @@ def test_gpu_ties_and_extremes(gpu_lib):
 def test_gpu_batch_device(gpu_lib):
     import torch
     check_batch_device(gpu_lib, torch.device("cuda", 0))
+
+
+@pytest.mark.gpu
+def test_gpu_train_set_of_65536_rows_is_refused(gpu_lib):
+    check_limit_refused(gpu_lib)

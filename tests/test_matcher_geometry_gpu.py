@@ -1,7 +1,8 @@
 """The grid-walking matcher searches beyond the KITTI camera and the (8, 1.2) pyramid on the hardware, against the oracle: the
 matrix of tests/test_matcher_geometry_emu.py at the emulator tier's size and at one that crosses the kernels' LDS forms
 (kGridLdsN2 = 8192 features; kResolveLdsN1 = 8192 points, kResolveLdsN2 = 6144 features), the points placed on the bounds, and
-the EuRoC grid through resident frames.  Nothing in these kernels changes behaviour between 8300 and the 65535 limit."""
+the EuRoC grid through resident frames.  The sizes at the library's limits - 65535 features, 2^20 - 1 points, one past each - are
+in tests/test_limits_gpu.py and tests/test_limits_emu.py (cases: tests/limit_cases.py)."""
 import pytest
 
 import geometry_checks as gc
