@@ -1098,6 +1098,79 @@ int rgbl_sim3_ransac_batch(rgbl_matcher* h, int n_problems, const rgbl_sim3_inpu
  * host arrays (pool NULL). */
 int rgbl_sim3_ransac_host(const rgbl_sim3_input* in, rgbl_sim3_output* out);
 
+/* int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+ * const bool bFixScale, Eigen::Matrix<double,7,7>& mAcumHessian, const bool bAllPoints) (include/Optimizer.h,
+ * src/Optimizer.cc:2115-2381): the 7-dof refinement LoopClosing runs per candidate (src/LoopClosing.cc:556, :767), one
+ * workgroup per candidate.  Pinhole cameras.  csrc/sim3opt_math.h restates the function and the parts of g2o it runs - the
+ * numeric Jacobians of base_binary_edge.hpp included - and says what is pinned (control flow, the quirks, the summation
+ * order) and what is not (Eigen's LDLT, libm's exp / sin / cos).  mAcumHessian is zeros on return (:2356): the caller
+ * writes them. */
+typedef struct {
+  int n;                       /* vpMatches1.size() == pKF1->N */
+  const int32_t* mp1_index;    /* per feature of pKF1: pKF1->GetMapPointMatches()[i] in the point set below, -1 = null */
+  const int32_t* match_index;  /* vpMatches1[i] in the point set, -1 = null */
+  const int32_t* i2;           /* get<0>(vpMatches1[i]->GetIndexInKeyFrame(pKF2)), -1 .. n2-1; read where match_index >= 0 */
+  const int32_t* track_level2; /* the level of the inverse edge where i2 < 0, in [0, n_levels2).  :2280 names mnTrackScaleLevel, but hands it to
+                                  cv::KeyPoint as the SIZE: as compiled with OpenCV the octave is 0, which is what
+                                  shim/Sim3Optimizer.h passes and tests/golden/sim3_opt records */
+  int n_points;                /* entries of the point set */
+  const uint8_t* bad;          /* isBad() of every point */
+  /* map side, form 1 (pool == NULL): host array */
+  const float* world_pos;      /* GetWorldPos(), 3 floats per point */
+  /* map side, form 2: slots of a pool on the matcher's device (the call holds the pool's mutex for its duration) */
+  rgbl_map_points* pool;
+  const int32_t* slot;         /* n_points slots in [0, capacity) */
+  float Rcw1[9], tcw1[3];      /* pKF1->GetRotation() (row-major), GetTranslation() (:2129-2130) */
+  float Rcw2[9], tcw2[3];      /* pKF2's (:2131-2132) */
+  /* key frame 1: host arrays, or the resident frame (the two arrays are then not read) */
+  const float* kp1_xy;         /* pKF1->mvKeysUn[i].pt, n x 2 */
+  const int32_t* kp1_octave;
+  const rgbl_device_frame* device1;
+  int n2;                      /* pKF2->N */
+  const float* kp2_xy;         /* pKF2->mvKeysUn, n2 x 2 */
+  const int32_t* kp2_octave;
+  const rgbl_device_frame* device2;
+  const float* inv_level_sigma2_1; /* pKF1->mvInvLevelSigma2, n_levels1 entries */
+  int n_levels1;               /* 1 .. 16 */
+  const float* inv_level_sigma2_2;
+  int n_levels2;
+  float K1[4], K2[4];          /* pCamera1 / pCamera2: fx, fy, cx, cy */
+  double q[4], t[3], s;        /* g2oS12 as g2o::Sim3 holds it: r (x y z w), t, s; never normalised */
+  float th2;
+  int fix_scale;               /* bFixScale */
+  int all_points;              /* bAllPoints */
+} rgbl_sim3_opt_input;
+typedef struct {
+  int32_t n_correspondences, n_bad_mps, n_in_kf2, n_out_kf2, n_without_mp; /* the counters of :2159-2163 */
+  int32_t n_bad;               /* pairs dropped after the first optimize() (:2311) */
+  int32_t iterations[2];       /* Levenberg iterations of the two optimize() calls (0: no edge, or not run) */
+  int32_t active[2];           /* edge pairs in the graph when each began */
+  double chi2[2];              /* the (robust) chi2 when each returned */
+  int32_t rounds, reserved;    /* optimize() calls reached: 1 when the function returns at :2349 */
+} rgbl_sim3_opt_diag;
+typedef struct {
+  int result;                  /* the reference's return value: nIn, or 0 */
+  double q[4], t[3], s;        /* g2oS12 on return: the input estimate, bit for bit, when the function returns at :2349 */
+  uint8_t* cleared;            /* n bytes (NULL: not wanted): 1 where the reference sets vpMatches1[idx] = NULL (:2323, :2369), 0
+                                  where the pair stays; written only where an edge pair existed */
+  rgbl_sim3_opt_diag diag;
+} rgbl_sim3_opt_output;
+/* One candidate (replaces Optimizer.cc:2115-2381).  Host pointers, synchronous, one upload, one launch, one read-back.  A
+ * problem with no edge pair at all is valid: result 0 and no iteration.
+ * RGBL_ERR_INVALID, before anything is launched and with every output untouched: mp1_index / match_index outside
+ * [-1, n_points); i2 outside [-1, n2); an octave (host arrays; a resident frame's octaves are clamped on the device) or
+ * track_level2 outside [0, n_levels) on a pair that reaches the depth test of :2235; a pose, K, th2 or estimate that is not
+ * finite; n or n2 above 65535; n_levels outside 1 .. 16; a slot outside the pool; a frame of another size, or a frame or pool
+ * on another device than the matcher; a missing array. */
+int rgbl_optimize_sim3(rgbl_matcher* h, const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out);
+/* B independent candidates (one DetectCommonRegionsFromBoW pass, LoopClosing.cc:690-800): one upload, one launch, one
+ * read-back; workgroup b runs problem b.  Problems that name a pool must name the same one.  Errors as above, and n_problems
+ * outside [0, 32767]: nothing is launched and no problem's output is written. */
+int rgbl_optimize_sim3_batch(rgbl_matcher* h, int n_problems, const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out);
+/* rgbl_optimize_sim3 evaluated by the HOST build of csrc/sim3opt_math.h (no device, no handle): the same bits.  Both key
+ * frames and the map side must be host arrays (device1, device2 and pool NULL). */
+int rgbl_optimize_sim3_host(const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out);
+
 /* ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>& vbPrevMatched, vector<int>& vnMatches12,
  * int windowSize)    /root/reference/include/ORBmatcher.h:72, src/ORBmatcher.cc:648-763 (Tracking::MonocularInitialization,
  * src/Tracking.cc:2526; not on the RGB-L / stereo path - built so that every search routine of ORBmatcher has a device form).

@@ -103,6 +103,30 @@ class Sim3Output(C.Structure):
                 ("inlier", C.c_void_p), ("counts", C.c_void_p), ("T12_all", C.c_void_p)]
 
 
+class Sim3OptInput(C.Structure):
+    """rgbl_sim3_opt_input (two key frames, the matches and the entry estimate as Optimizer::OptimizeSim3 reads them)."""
+    _fields_ = [("n", C.c_int), ("mp1_index", C.c_void_p), ("match_index", C.c_void_p), ("i2", C.c_void_p),
+                ("track_level2", C.c_void_p), ("n_points", C.c_int), ("bad", C.c_void_p), ("world_pos", C.c_void_p),
+                ("pool", C.c_void_p), ("slot", C.c_void_p), ("Rcw1", C.c_float * 9), ("tcw1", C.c_float * 3),
+                ("Rcw2", C.c_float * 9), ("tcw2", C.c_float * 3), ("kp1_xy", C.c_void_p), ("kp1_octave", C.c_void_p),
+                ("device1", C.c_void_p), ("n2", C.c_int), ("kp2_xy", C.c_void_p), ("kp2_octave", C.c_void_p),
+                ("device2", C.c_void_p), ("inv_level_sigma2_1", C.c_void_p), ("n_levels1", C.c_int),
+                ("inv_level_sigma2_2", C.c_void_p), ("n_levels2", C.c_int), ("K1", C.c_float * 4), ("K2", C.c_float * 4),
+                ("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("th2", C.c_float), ("fix_scale", C.c_int),
+                ("all_points", C.c_int)]
+
+
+class Sim3OptDiag(C.Structure):
+    _fields_ = [("n_correspondences", C.c_int32), ("n_bad_mps", C.c_int32), ("n_in_kf2", C.c_int32), ("n_out_kf2", C.c_int32),
+                ("n_without_mp", C.c_int32), ("n_bad", C.c_int32), ("iterations", C.c_int32 * 2), ("active", C.c_int32 * 2),
+                ("chi2", C.c_double * 2), ("rounds", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Sim3OptOutput(C.Structure):
+    _fields_ = [("result", C.c_int), ("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("cleared", C.c_void_p),
+                ("diag", Sim3OptDiag)]
+
+
 class ProjectionInput(C.Structure):
     """rgbl_projection_input (ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) as flat arrays)."""
     _fields_ = [("n1", C.c_int), ("valid1", C.c_void_p), ("world_pos1", C.c_void_p), ("mp_desc1", C.c_void_p),
@@ -338,6 +362,9 @@ SYMBOLS = {
     "rgbl_sim3_ransac": (_I, [_V, C.POINTER(Sim3Input), C.POINTER(Sim3Output)]),
     "rgbl_sim3_ransac_batch": (_I, [_V, _I, _V, _V]),
     "rgbl_sim3_ransac_host": (_I, [C.POINTER(Sim3Input), C.POINTER(Sim3Output)]),
+    "rgbl_optimize_sim3": (_I, [_V, C.POINTER(Sim3OptInput), C.POINTER(Sim3OptOutput)]),
+    "rgbl_optimize_sim3_batch": (_I, [_V, _I, _V, _V]),
+    "rgbl_optimize_sim3_host": (_I, [C.POINTER(Sim3OptInput), C.POINTER(Sim3OptOutput)]),
     "rgbl_search_by_bow": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_rig": (_I, [_V, _V, _V, _I, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_keyframes": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),

@@ -29,6 +29,7 @@
 #include "newpoint_math.h"
 #include "poseopt_math.h"
 #include "sim3_math.h"
+#include "sim3opt_math.h"
 
 namespace rgbl {
 
@@ -993,6 +994,203 @@ __global__ void k_test_po_math(int op, const double* __restrict__ x, const doubl
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   z[i] = op == 0 ? po_sin(x[i]) : op == 1 ? po_cos(x[i]) : op == 2 ? x[i] / y[i] : sqrt(x[i]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Optimizer::OptimizeSim3 (src/Optimizer.cc:2115-2381): k_sim3_opt, one workgroup of 256 work-items per problem, after
+// k_pose_opt.  The algorithm is so_optimize of csrc/sim3opt_math.h, run by every work-item: the scalar state (estimate, lambda,
+// the 7 x 7 solve, the update) is computed redundantly and identically, the edge pairs are spread over the lanes (pair k on
+// lane k mod 256).  The host hands over the CANDIDATES (the features that pass :2169-2233); the workgroup forms P3D2c, applies
+// the float test of :2235 and numbers the survivors in ascending feature index with a ballot scan, 256 candidates at a time
+// (at most 256 chunks).  The 30 transforms of a linearisation are computed by work-items 0 .. 14 and kept in LDS.  No
+// communication between workgroups, no atomics; every work-item reaches every barrier (all branches around them depend on
+// reduced values only).  The optimiser's loops are bounded by (5 + 10) iterations x 10 trials.
+struct Sim3OptProblem {
+  const float *xy1, *xy2;        // mvKeysUn of both key frames (resident or staged)
+  const int32_t *oct1, *oct2;
+  const float* wpos;             // world positions: the call's staged array or the pool's
+  const float *sig1, *sig2;      // mvInvLevelSigma2 of both
+  int cand_off, n_cand, n_levels1, n_levels2, fix_scale;
+  float th2;
+  float Rcw1[9], tcw1[3], Rcw2[9], tcw2[3], K1[4], K2[4];
+  SoSim3 entry;
+  SoDiag diag;                   // the host's counters (n_bad_mps, n_without_mp); the others are the kernel's
+};
+struct Sim3OptOut {
+  SoSim3 est;
+  SoDiag diag;
+  int32_t ret, reserved;
+};
+struct Sim3OptDev {
+  const Sim3OptProblem* prob;
+  const int32_t *feat, *p1, *p2, *i2, *lvl2;   // per candidate (all problems back to back): feature, rows of wpos, i2, mnTrackScaleLevel
+  int32_t* corr;       // per correspondence k of a problem (at cand_off + k): its candidate
+  double* chi;         // the state of the pairs beyond 8 per lane: chi12, chi21 ...
+  uint8_t* state;      // ... and gone | cleared << 1
+  uint8_t* cleared;    // per candidate: the result (2: no edge pair)
+  Sim3OptOut* out;
+};
+
+__device__ __forceinline__ int clamp_level(int o, int n_levels) { return o < 0 ? 0 : (o >= n_levels ? n_levels - 1 : o); }   // host arrays are checked before the launch
+
+__device__ __forceinline__ bool sim3_opt_edge(const Sim3OptProblem& pb, const Sim3OptDev& D, int c, SoEdge& e) {
+  const int g = pb.cand_off + c, f = D.feat[g], i2 = D.i2[g];
+  const float info1 = pb.sig1[clamp_level(pb.oct1[f], pb.n_levels1)];
+  const float info2 = pb.sig2[clamp_level(i2 >= 0 ? pb.oct2[i2] : D.lvl2[g], pb.n_levels2)];
+  return so_make_edge(pb.Rcw1, pb.tcw1, pb.Rcw2, pb.tcw2, pb.wpos + 3 * (size_t)D.p1[g], pb.wpos + 3 * (size_t)D.p2[g], pb.xy1 + 2 * (size_t)f,
+                      info1, i2 >= 0, pb.xy2 + 2 * (size_t)(i2 >= 0 ? i2 : 0), info2, e);
+}
+
+constexpr int kSoTreeLds = kSoLanes - 64;   // the partial sums of lanes 64 .. 255
+// A pair's twelve floats are used as doubles in every pass over the edges.  Left alone, the compiler converts them once and
+// keeps the doubles for the whole kernel: 24 more registers per pair.  An empty statement the value passes through makes the
+// conversion belong to the pass.
+#ifdef RGBL_EMU
+#define SO_OPAQUE(x) ((void)0)
+#else
+#define SO_OPAQUE(x) asm volatile("" : "+v"(x))
+#endif
+struct SoDevLanes {
+  SoEdge r[kSoRegEdges];   // pairs tid, tid + 256, ... in registers
+  double acc[kSoSums];
+  const Sim3OptProblem* pb;
+  const Sim3OptDev* D;
+  double (*red)[kSoTreeLds];
+  double* bc;
+  SoSim3* T;
+  int tid, m;
+  __device__ void zero() {
+#pragma unroll
+    for (int c = 0; c < kSoSums; ++c) acc[c] = 0.0;
+  }
+  template <class F> __device__ void each(F f) {
+#pragma unroll
+    for (int j = 0; j < kSoRegEdges; ++j) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) { SO_OPAQUE(r[j].X1[c]); SO_OPAQUE(r[j].X2[c]); }
+      SO_OPAQUE(r[j].obs1[0]); SO_OPAQUE(r[j].obs1[1]); SO_OPAQUE(r[j].obs2[0]); SO_OPAQUE(r[j].obs2[1]);
+      SO_OPAQUE(r[j].info1); SO_OPAQUE(r[j].info2);
+      if (tid + kSoLanes * j < m) f(r[j], acc);
+    }
+    for (int k = tid + kSoLanes * kSoRegEdges; k < m; k += kSoLanes) {   // beyond 2048 correspondences: global memory
+      const size_t g = (size_t)pb->cand_off + (size_t)k;
+      SoEdge e;
+      sim3_opt_edge(*pb, *D, D->corr[g], e);
+      e.chi12 = D->chi[2 * g]; e.chi21 = D->chi[2 * g + 1];
+      e.gone = D->state[g] & 1; e.cleared = D->state[g] >> 1;
+      f(e, acc);
+      D->chi[2 * g] = e.chi12; D->chi[2 * g + 1] = e.chi21;
+      D->state[g] = (uint8_t)(e.gone | (e.cleared << 1));
+    }
+  }
+  // PoDevLanes::reduce: lanes 64 .. 255 through LDS, wave 0 below with cross-lane reads, lane 0's sums to everyone through
+  // LDS.  The system's 36 sums stay in bc[0 .. 35] for the trials' solves; the single sum goes through bc[36].
+  template <int N> __device__ void reduce(double* dst) {
+    if (tid >= 64) {
+#pragma unroll
+      for (int c = 0; c < N; ++c) red[c][tid - 64] = acc[c];
+    }
+    __syncthreads();
+    if (tid < 64) {
+      double v[N];
+#pragma unroll
+      for (int c = 0; c < N; ++c) v[c] = (acc[c] + red[c][tid + 64]) + (red[c][tid] + red[c][tid + 128]);
+#pragma unroll
+      for (int s = 32; s >= 1; s >>= 1) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) v[c] = v[c] + __shfl_down(v[c], (unsigned)s);
+      }
+      if (tid == 0) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) dst[c] = v[c];
+      }
+    }
+    __syncthreads();
+  }
+  __device__ const double* reduce_system() { reduce<kSoSums>(bc); return bc; }
+  __device__ double reduce_one() { reduce<1>(bc + kSoSums); return bc[kSoSums]; }
+  // work-item j < 14 forms perturbed estimate j and its inverse, work-item 14 the estimate's inverse; the readers of the
+  // previous linearisation are behind the barriers of the reductions in between
+  __device__ const SoSim3* transforms(const SoSim3& S, bool fix_scale) {
+    if (tid < 14) {
+      const SoSim3 P = so_perturbed(S, tid, fix_scale);
+      T[2 + tid] = P;
+      T[16 + tid] = so_inverse(P);
+    } else if (tid == 14) {
+      T[0] = S;
+      T[1] = so_inverse(S);
+    }
+    __syncthreads();
+    return T;
+  }
+};
+
+__global__ __launch_bounds__(kSoLanes) void k_sim3_opt(Sim3OptDev D) {
+  __shared__ double s_red[kSoSums][kSoTreeLds];   // 54 KB
+  __shared__ double s_bc[kSoSums + 1];
+  __shared__ SoSim3 s_T[kSoTransforms];           // 1920 B
+  __shared__ int s_cnt[4][2];
+  const Sim3OptProblem& pb = D.prob[blockIdx.x];
+  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  // :2235 and the numbering of the correspondences
+  int m = 0, n_in = 0;
+  for (int c0 = 0; c0 < pb.n_cand; c0 += kSoLanes) {   // uniform
+    const int c = c0 + tid;
+    bool keep = false, in2 = false;
+    if (c < pb.n_cand) {
+      float X2[3];
+      s3_transform(pb.Rcw2, pb.tcw2, pb.wpos + 3 * (size_t)D.p2[pb.cand_off + c], X2);
+      keep = !(X2[2] < 0.0f);
+      in2 = keep && D.i2[pb.cand_off + c] >= 0;
+    }
+    const unsigned long long bk = __ballot(keep), bi = __ballot(in2);
+    if (lane == 0) { s_cnt[wave][0] = __popcll(bk); s_cnt[wave][1] = __popcll(bi); }
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      if (w < wave) before += s_cnt[w][0];
+      total += s_cnt[w][0];
+      n_in += s_cnt[w][1];
+    }
+    if (keep) D.corr[pb.cand_off + m + before + __popcll(bk & ((1ull << lane) - 1ull))] = c;   // < cand_off + n_cand
+    m += total;
+    __syncthreads();
+  }
+  SoDevLanes G;
+  G.pb = &pb; G.D = &D; G.red = s_red; G.bc = s_bc; G.T = s_T; G.tid = tid; G.m = m;
+#pragma unroll
+  for (int j = 0; j < kSoRegEdges; ++j) {
+    const int k = tid + kSoLanes * j;
+    if (k < m) sim3_opt_edge(pb, D, D.corr[pb.cand_off + k], G.r[j]);
+  }
+  for (int k = tid + kSoLanes * kSoRegEdges; k < m; k += kSoLanes) D.state[pb.cand_off + k] = 0;
+  const SoCam C1 = {(double)pb.K1[0], (double)pb.K1[1], (double)pb.K1[2], (double)pb.K1[3]};
+  const SoCam C2 = {(double)pb.K2[0], (double)pb.K2[1], (double)pb.K2[2], (double)pb.K2[3]};
+  SoSim3 est;
+  SoDiag diag = pb.diag;
+  diag.n_correspondences = m; diag.n_in_kf2 = n_in; diag.n_out_kf2 = m - n_in;
+  const int ret = so_optimize(G, C1, C2, pb.entry, m, pb.th2, pb.fix_scale != 0, est, diag);
+#pragma unroll
+  for (int j = 0; j < kSoRegEdges; ++j) {
+    const int k = tid + kSoLanes * j;
+    if (k < m) D.cleared[pb.cand_off + D.corr[pb.cand_off + k]] = G.r[j].cleared;
+  }
+  for (int k = tid + kSoLanes * kSoRegEdges; k < m; k += kSoLanes)
+    D.cleared[pb.cand_off + D.corr[pb.cand_off + k]] = D.state[pb.cand_off + k] >> 1;
+  if (tid == 0) {
+    Sim3OptOut& o = D.out[blockIdx.x];
+    o.est = est;
+    o.diag = diag;
+    o.ret = ret;
+    o.reserved = 0;
+  }
+}
+
+// test hook: the header's exp on the device
+__global__ void k_test_so_exp(const double* __restrict__ x, double* __restrict__ z, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) z[i] = so_exp(x[i]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4552,6 +4750,221 @@ int rgbl_sim3_ransac_batch(rgbl_matcher* m, int n_problems, const rgbl_sim3_inpu
 int rgbl_sim3_ransac(rgbl_matcher* m, const rgbl_sim3_input* in, rgbl_sim3_output* out) {
   if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
   return rgbl_sim3_ransac_batch(m, 1, in, out);
+}
+
+// ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:2115-2381) --------------------------------------------------------------
+namespace {
+struct Sim3OptCand { int32_t feat, p1, p2, i2, lvl2; };
+// Everything that can be refused without the pool is refused here, before anything is staged, launched or written.  Runs
+// :2167-2233: counts nBadMPs and nMatchWithoutMP and lists the candidates, the features that reach the depth test of :2235.
+int check_sim3_opt_input(const rgbl_sim3_opt_input* in, int b, bool host_only, std::vector<Sim3OptCand>* cand, SoDiag* diag) {
+  memset(diag, 0, sizeof(*diag));
+  if (in->n < 0 || in->n > 65535 || in->n2 < 0 || in->n2 > 65535 || in->n_points < 0) { set_error("sim3 optimisation %d: n or n2 outside [0, 65535], or n_points < 0", b); return RGBL_ERR_INVALID; }
+  if (in->n > 0 && (!in->mp1_index || !in->match_index || !in->i2 || !in->track_level2)) { set_error("sim3 optimisation %d: no mp1_index, match_index, i2 or track_level2", b); return RGBL_ERR_INVALID; }
+  if (in->n_levels1 < 1 || in->n_levels1 > kProjMaxLevels || in->n_levels2 < 1 || in->n_levels2 > kProjMaxLevels || !in->inv_level_sigma2_1 || !in->inv_level_sigma2_2) {
+    set_error("sim3 optimisation %d: n_levels outside [1, %d] or no inv_level_sigma2", b, kProjMaxLevels);
+    return RGBL_ERR_INVALID;
+  }
+  bool finite = std::isfinite(in->th2) && std::isfinite(in->s);
+  for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(in->K1[i]) && std::isfinite(in->K2[i]) && std::isfinite(in->q[i]);
+  for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(in->Rcw1[i]) && std::isfinite(in->Rcw2[i]);
+  for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(in->tcw1[i]) && std::isfinite(in->tcw2[i]) && std::isfinite(in->t[i]);
+  if (!finite) { set_error("sim3 optimisation %d: a pose, K, th2 or the estimate is not finite", b); return RGBL_ERR_INVALID; }
+  if (host_only && (in->device1 || in->device2 || in->pool)) { set_error("sim3 optimisation %d: the host build reads host arrays only", b); return RGBL_ERR_INVALID; }
+  if (in->device1 ? in->device1->n != in->n : (in->n > 0 && (!in->kp1_xy || !in->kp1_octave))) {
+    set_error("sim3 optimisation %d: key frame 1 is either kp1_xy, kp1_octave or a resident frame of n features", b);
+    return RGBL_ERR_INVALID;
+  }
+  if (in->device2 ? in->device2->n != in->n2 : (in->n2 > 0 && (!in->kp2_xy || !in->kp2_octave))) {
+    set_error("sim3 optimisation %d: key frame 2 is either kp2_xy, kp2_octave or a resident frame of n2 features", b);
+    return RGBL_ERR_INVALID;
+  }
+  if (in->n_points > 0 && (!in->bad || (in->pool ? !in->slot : !in->world_pos))) { set_error("sim3 optimisation %d: no bad flags, or the map side is neither world_pos nor a pool with slot", b); return RGBL_ERR_INVALID; }
+  for (int i = 0; i < in->n; ++i) {
+    const int p1 = in->mp1_index[i], p2 = in->match_index[i];
+    if (p1 < -1 || p1 >= in->n_points || p2 < -1 || p2 >= in->n_points) { set_error("sim3 optimisation %d: mp1_index / match_index of feature %d = (%d, %d) outside [-1, %d)", b, i, p1, p2, in->n_points); return RGBL_ERR_INVALID; }
+    if (p2 < 0) continue;                                                 // :2169
+    const int i2 = in->i2[i];
+    if (i2 < -1 || i2 >= in->n2) { set_error("sim3 optimisation %d: i2 of feature %d = %d outside [-1, %d)", b, i, i2, in->n2); return RGBL_ERR_INVALID; }
+    if (p1 < 0) { ++diag->n_without_mp; continue; }                       // :2209-2227
+    if (in->bad[p1] || in->bad[p2]) { ++diag->n_bad_mps; continue; }      // :2203-2207
+    if (i2 < 0 && !in->all_points) continue;                              // :2229
+    // the levels are checked on every pair that reaches the depth test
+    if (!in->device1 && (in->kp1_octave[i] < 0 || in->kp1_octave[i] >= in->n_levels1)) { set_error("sim3 optimisation %d: octave %d of feature %d outside [0, %d)", b, in->kp1_octave[i], i, in->n_levels1); return RGBL_ERR_INVALID; }
+    if (i2 < 0 ? (in->track_level2[i] < 0 || in->track_level2[i] >= in->n_levels2)
+               : (!in->device2 && (in->kp2_octave[i2] < 0 || in->kp2_octave[i2] >= in->n_levels2))) {
+      set_error("sim3 optimisation %d: the level of feature %d's match outside [0, %d)", b, i, in->n_levels2);
+      return RGBL_ERR_INVALID;
+    }
+    cand->push_back(Sim3OptCand{i, p1, p2, i2, in->track_level2[i]});
+  }
+  return RGBL_OK;
+}
+inline SoSim3 sim3_opt_entry(const rgbl_sim3_opt_input* in) {
+  SoSim3 S;
+  memcpy(S.q, in->q, sizeof(S.q)); memcpy(S.t, in->t, sizeof(S.t));
+  S.s = in->s;
+  return S;
+}
+// `flag` per candidate: 0 / 1 the pair's cleared flag, 2 no pair
+void write_sim3_opt_output(const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out, const Sim3OptCand* cand, int n_cand, const uint8_t* flag,
+                           const SoSim3& est, int ret, const SoDiag& diag) {
+  out->result = ret;
+  memcpy(out->q, est.q, sizeof(out->q)); memcpy(out->t, est.t, sizeof(out->t));
+  out->s = est.s;
+  if (out->cleared)
+    for (int c = 0; c < n_cand; ++c)
+      if (flag[c] != 2) out->cleared[cand[c].feat] = flag[c];
+  static_assert(sizeof(SoDiag) == sizeof(rgbl_sim3_opt_diag), "SoDiag is rgbl_sim3_opt_diag");
+  memcpy(&out->diag, &diag, sizeof(diag));
+}
+}  // namespace
+
+int rgbl_optimize_sim3_host(const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out) {
+  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  std::vector<Sim3OptCand> cand;
+  SoDiag diag;
+  RGBL_TRY(check_sim3_opt_input(in, 0, true, &cand, &diag));
+  const int nc = (int)cand.size();
+  std::vector<SoEdge> edges;
+  std::vector<int> edge_cand;
+  for (int c = 0; c < nc; ++c) {
+    const Sim3OptCand& k = cand[(size_t)c];
+    SoEdge e;
+    const float info1 = in->inv_level_sigma2_1[in->kp1_octave[k.feat]];
+    const float info2 = in->inv_level_sigma2_2[k.i2 >= 0 ? in->kp2_octave[k.i2] : k.lvl2];
+    if (!so_make_edge(in->Rcw1, in->tcw1, in->Rcw2, in->tcw2, in->world_pos + 3 * (size_t)k.p1, in->world_pos + 3 * (size_t)k.p2,
+                      in->kp1_xy + 2 * (size_t)k.feat, info1, k.i2 >= 0, k.i2 >= 0 ? in->kp2_xy + 2 * (size_t)k.i2 : nullptr, info2, e))
+      continue;
+    edges.push_back(e);
+    edge_cand.push_back(c);
+    if (k.i2 >= 0) ++diag.n_in_kf2; else ++diag.n_out_kf2;
+  }
+  const int m = (int)edges.size();
+  diag.n_correspondences = m;
+  std::vector<SoHostLanes> lanes(1, SoHostLanes(edges.data(), m));   // 75 KB: not on the stack
+  const SoCam C1 = {(double)in->K1[0], (double)in->K1[1], (double)in->K1[2], (double)in->K1[3]};
+  const SoCam C2 = {(double)in->K2[0], (double)in->K2[1], (double)in->K2[2], (double)in->K2[3]};
+  SoSim3 est;
+  const int ret = so_optimize(lanes[0], C1, C2, sim3_opt_entry(in), m, in->th2, in->fix_scale != 0, est, diag);
+  std::vector<uint8_t> flag((size_t)nc, 2);
+  for (int k = 0; k < m; ++k) flag[(size_t)edge_cand[(size_t)k]] = edges[(size_t)k].cleared;
+  write_sim3_opt_output(in, out, cand.data(), nc, flag.data(), est, ret, diag);
+  return RGBL_OK;
+}
+
+int rgbl_optimize_sim3_batch(rgbl_matcher* m, int n_problems, const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out) {
+  if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  const int B = n_problems;
+  if (B > 32767) { set_error("sim3 optimisation: more than 32767 problems in one call"); return RGBL_ERR_INVALID; }
+  std::vector<int> off((size_t)B + 1, 0);   // at most 65535 candidates each: B < 2^15 problems fit an int
+  std::vector<Sim3OptCand> cand;
+  std::vector<SoDiag> diag((size_t)B);
+  rgbl_map_points* pool = nullptr;
+  for (int b = 0; b < B; ++b) {
+    RGBL_TRY(check_sim3_opt_input(in + b, b, false, &cand, &diag[(size_t)b]));
+    off[(size_t)b + 1] = (int)cand.size();
+    for (const rgbl_device_frame* fr : {in[b].device1, in[b].device2})
+      if (fr && fr->device != m->device) { set_error("sim3 optimisation %d: a frame is on device %d, the matcher on %d", b, fr->device, m->device); return RGBL_ERR_INVALID; }
+    if (in[b].pool) {
+      if (pool && pool != in[b].pool) { set_error("sim3 optimisation %d: the problems of one call share one pool", b); return RGBL_ERR_INVALID; }
+      pool = in[b].pool;
+      if (pool->device != m->device) { set_error("sim3 optimisation %d: the pool is on device %d, the matcher on %d", b, pool->device, m->device); return RGBL_ERR_INVALID; }
+    }
+  }
+  if (B == 0) return RGBL_OK;
+  const int M = off[(size_t)B];
+  std::unique_lock<std::mutex> pool_lock;
+  if (pool) {
+    pool_lock = std::unique_lock<std::mutex>(pool->mu);
+    for (int b = 0; b < B; ++b)
+      if (in[b].pool)
+        for (int i = 0; i < in[b].n_points; ++i)
+          if (in[b].slot[i] < 0 || in[b].slot[i] >= pool->cap) { set_error("sim3 optimisation %d: slot %d outside [0, %d)", b, in[b].slot[i], pool->cap); return RGBL_ERR_INVALID; }
+  }
+  // the candidates of all problems back to back
+  std::vector<int32_t> feat((size_t)M), p1((size_t)M), p2((size_t)M), i2((size_t)M), lvl2((size_t)M);
+  for (int b = 0; b < B; ++b)
+    for (int c = off[(size_t)b]; c < off[(size_t)b + 1]; ++c) {
+      const Sim3OptCand& k = cand[(size_t)c];
+      feat[(size_t)c] = k.feat; i2[(size_t)c] = k.i2; lvl2[(size_t)c] = k.lvl2;
+      p1[(size_t)c] = in[b].pool ? in[b].slot[k.p1] : k.p1;
+      p2[(size_t)c] = in[b].pool ? in[b].slot[k.p2] : k.p2;
+    }
+  RGBL_HIP(hipSetDevice(m->device));
+  StreamDrain drain(m->stream);  // error returns included; declared behind pool_lock: the stream is drained before the pool is released
+  HostCall hc(m);
+  hipStream_t s = hc.s;
+  std::vector<Sim3OptProblem> prob((size_t)B);
+  Sim3OptDev D;
+  memset(&D, 0, sizeof(D));
+  RGBL_TRY(hc.begin([&]() -> int {
+    for (int b = 0; b < B; ++b) {
+      Sim3OptProblem& P = prob[(size_t)b];
+      memset(&P, 0, sizeof(P));
+      const rgbl_sim3_opt_input& I = in[b];
+      RGBL_TRY(put_features(hc, I.device1, I.n, nullptr, I.kp1_xy, I.kp1_octave, nullptr, nullptr, &P.xy1, &P.oct1, nullptr));
+      RGBL_TRY(put_features(hc, I.device2, I.n2, nullptr, I.kp2_xy, I.kp2_octave, nullptr, nullptr, &P.xy2, &P.oct2, nullptr));
+      if (I.pool) P.wpos = pool->d_wpos; else hc.put(&P.wpos, I.world_pos, (size_t)I.n_points * 3);
+      hc.put(&P.sig1, I.inv_level_sigma2_1, (size_t)I.n_levels1);
+      hc.put(&P.sig2, I.inv_level_sigma2_2, (size_t)I.n_levels2);
+      P.cand_off = off[(size_t)b]; P.n_cand = off[(size_t)b + 1] - off[(size_t)b];
+      P.n_levels1 = I.n_levels1; P.n_levels2 = I.n_levels2; P.fix_scale = I.fix_scale ? 1 : 0; P.th2 = I.th2;
+      memcpy(P.Rcw1, I.Rcw1, sizeof(P.Rcw1)); memcpy(P.tcw1, I.tcw1, sizeof(P.tcw1));
+      memcpy(P.Rcw2, I.Rcw2, sizeof(P.Rcw2)); memcpy(P.tcw2, I.tcw2, sizeof(P.tcw2));
+      memcpy(P.K1, I.K1, sizeof(P.K1)); memcpy(P.K2, I.K2, sizeof(P.K2));
+      P.entry = sim3_opt_entry(&I);
+      P.diag = diag[(size_t)b];
+    }
+    hc.put(&D.feat, feat.data(), (size_t)M);
+    hc.put(&D.p1, p1.data(), (size_t)M);
+    hc.put(&D.p2, p2.data(), (size_t)M);
+    hc.put(&D.i2, i2.data(), (size_t)M);
+    hc.put(&D.lvl2, lvl2.data(), (size_t)M);
+    D.prob = hc.stage<Sim3OptProblem>((size_t)B, [&](Sim3OptProblem* dst) { memcpy(dst, prob.data(), sizeof(Sim3OptProblem) * (size_t)B); });
+    D.cleared = hc.put_fill<uint8_t>((size_t)M, 2);   // what comes back, side by side
+    hc.mark_result(D.cleared, (size_t)M);
+    D.out = hc.result<Sim3OptOut>((size_t)B);
+    D.corr = hc.scratch<int32_t>((size_t)M);
+    D.chi = hc.scratch<double>((size_t)M * 2);
+    D.state = hc.scratch<uint8_t>((size_t)M);
+    return RGBL_OK;
+  }));
+  m->timer.begin("k_sim3_opt", s);
+  hipLaunchKernelGGL(k_sim3_opt, dim3((unsigned)B), dim3(kSoLanes), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(hc.fetch());
+  for (int b = 0; b < B; ++b) {
+    const Sim3OptOut& o = hc.host(D.out)[b];
+    write_sim3_opt_output(in + b, out + b, cand.data() + off[(size_t)b], off[(size_t)b + 1] - off[(size_t)b], hc.host(D.cleared) + off[(size_t)b], o.est, o.ret, o.diag);
+  }
+  return RGBL_OK;
+}
+
+int rgbl_optimize_sim3(rgbl_matcher* m, const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out) {
+  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  return rgbl_optimize_sim3_batch(m, 1, in, out);
+}
+
+// test hooks for csrc/sim3opt_math.h: so_exp on the host, and compiled for the device
+double rgbl_test_so_exp(double x) { return so_exp(x); }
+int rgbl_test_so_exp_device(const double* x, double* z, int n) {
+  if (!x || !z || n < 1) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  double *dx = nullptr, *dz = nullptr;
+  const size_t bytes = sizeof(double) * (size_t)n;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dx), bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dz), bytes);
+  if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_test_so_exp, dim3((n + 255) / 256), dim3(256), 0, 0, (const double*)dx, dz, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(z, dz, bytes, hipMemcpyDeviceToHost);
+  if (dx) (void)hipFree(dx);
+  if (dz) (void)hipFree(dz);
+  if (e != hipSuccess) { set_error("sim3opt math test hook: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
+  return RGBL_OK;
 }
 
 // test hooks for csrc/poseopt_math.h: op 0 sin, 1 cos, 2 x / y, 3 sqrt - on the host, and compiled for the device

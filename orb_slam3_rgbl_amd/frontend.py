@@ -1347,6 +1347,104 @@ class ORBmatcher:
             L.check(self.lib, self.lib.rgbl_sim3_ransac(self.h, C.byref(I), C.byref(O)))
         return self._sim3_result(O, bufs)
 
+    @staticmethod
+    def _sim3_opt_input(cs, keep, out=None):
+        """rgbl_sim3_opt_input of a case dict: mp1_index, match_index, i2, track_level2 (per feature of key frame 1), bad and
+        world_pos (points x 3) or pool (MapPointPool) + slot, Rcw1, tcw1, Rcw2, tcw2, xy1 / octave1 or device1 (DeviceFrame),
+        xy2 / octave2 or device2, inv_level_sigma2_1 / _2, K1, K2, the entry estimate R (3 x 3; or q, x y z w), t, s, th2,
+        fix_scale, all_points.  R becomes a quaternion as g2o::Sim3(Matrix3d, ...) makes it (LoopClosing.cc:746)."""
+        P = out if out is not None else L.Sim3OptInput()
+
+        def arr(key, dt):
+            if cs.get(key) is None:
+                return None
+            keep.append(np.ascontiguousarray(cs[key], dt))
+            return keep[-1].ctypes.data
+        P.mp1_index, P.match_index = arr("mp1_index", np.int32), arr("match_index", np.int32)
+        P.i2, P.track_level2 = arr("i2", np.int32), arr("track_level2", np.int32)
+        P.n = int(cs["n"]) if cs.get("n") is not None else len(np.asarray(cs["match_index"]).reshape(-1))
+        pool = cs.get("pool")
+        P.pool = pool.h if pool is not None else None
+        P.bad, P.world_pos, P.slot = arr("bad", np.uint8), arr("world_pos", np.float32), arr("slot", np.int32)
+        P.n_points = int(cs["n_points"]) if cs.get("n_points") is not None else len(np.asarray(cs["bad"]).reshape(-1))
+        P.kp1_xy, P.kp1_octave = arr("xy1", np.float32), arr("octave1", np.int32)
+        P.kp2_xy, P.kp2_octave = arr("xy2", np.float32), arr("octave2", np.int32)
+        P.device1, P.device2 = _dev(cs, "device1"), _dev(cs, "device2")
+        P.n2 = int(cs["n2"])
+        P.inv_level_sigma2_1, P.inv_level_sigma2_2 = arr("inv_level_sigma2_1", np.float32), arr("inv_level_sigma2_2", np.float32)
+        P.n_levels1 = int(cs.get("n_levels1", len(cs["inv_level_sigma2_1"])))
+        P.n_levels2 = int(cs.get("n_levels2", len(cs["inv_level_sigma2_2"])))
+        for field, cnt in (("Rcw1", 9), ("tcw1", 3), ("Rcw2", 9), ("tcw2", 3), ("K1", 4), ("K2", 4)):
+            v = np.asarray(cs[field], np.float32).reshape(-1)
+            for i in range(cnt):
+                getattr(P, field)[i] = v[i]
+        q = np.asarray(cs["q"], np.float64) if cs.get("q") is not None else quat_from_matrix(cs["R"])
+        t = np.asarray(cs["t"], np.float64)
+        for i in range(4):
+            P.q[i] = q[i]
+        for i in range(3):
+            P.t[i] = t[i]
+        P.s, P.th2 = float(cs["s"]), np.float32(cs["th2"])
+        P.fix_scale, P.all_points = int(cs["fix_scale"]), int(cs["all_points"])
+        return P
+
+    @staticmethod
+    def _sim3_opt_result(O, cleared):
+        d = O.diag
+        out = dict(result=int(O.result), q=np.array(O.q, np.float64), t=np.array(O.t, np.float64), s=float(O.s), cleared=cleared,
+                   iterations=np.array(d.iterations, np.int32), active=np.array(d.active, np.int32),
+                   chi2=np.array(d.chi2, np.float64), rounds=int(d.rounds))
+        for k in ("n_correspondences", "n_bad_mps", "n_in_kf2", "n_out_kf2", "n_without_mp", "n_bad"):
+            out[k] = int(getattr(d, k))
+        return out
+
+    def prepare_OptimizeSim3Batch(self, problems, host=False, cleared_fill=0):
+        """Optimizer::OptimizeSim3 (Optimizer.cc:2115-2381) of every case dict in one upload, one launch and one read-back; the
+        call returns one dict per problem: result (nIn, or 0), q (x y z w) / t / s (g2oS12 on return), cleared (n bytes, 1 where
+        vpMatches1[i] becomes NULL, `cleared_fill` where no edge pair existed), the counters of the set-up loop and the
+        diagnostics n_bad / iterations / active / chi2 / rounds."""
+        keep = []
+        B = len(problems)
+        I, O = (L.Sim3OptInput * max(B, 1))(), (L.Sim3OptOutput * max(B, 1))()
+        clr = []
+        for b, cs in enumerate(problems):
+            self._sim3_opt_input(cs, keep, I[b])
+            clr.append(np.full(I[b].n, cleared_fill, np.uint8))
+            O[b].cleared = clr[b].ctypes.data
+        lib, h = self.lib, self.h
+
+        def call(_keep=keep):
+            if host:
+                for b in range(B):
+                    L.check(lib, lib.rgbl_optimize_sim3_host(C.byref(I[b]), C.byref(O[b])))
+            else:
+                L.check(lib, lib.rgbl_optimize_sim3_batch(h, B, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)))
+            return [self._sim3_opt_result(O[b], clr[b]) for b in range(B)]
+
+        def c_call(_keep=keep):   # the C call alone (what tools/sim3_opt_bench.py times): the results stay in the structs
+            L.check(lib, lib.rgbl_optimize_sim3_batch(h, B, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)))
+
+        def c_call_host(_keep=keep):
+            for b in range(B):
+                L.check(lib, lib.rgbl_optimize_sim3_host(C.byref(I[b]), C.byref(O[b])))
+        call.c_call, call.c_call_host = c_call, c_call_host
+        return call
+
+    def OptimizeSim3Batch(self, problems, host=False, cleared_fill=0):
+        return self.prepare_OptimizeSim3Batch(problems, host, cleared_fill)()
+
+    def OptimizeSim3(self, case, host=False, cleared_fill=0):
+        """One candidate through rgbl_optimize_sim3 (host=True: rgbl_optimize_sim3_host, the header's host build)."""
+        keep = []
+        I, O = self._sim3_opt_input(case, keep), L.Sim3OptOutput()
+        clr = np.full(I.n, cleared_fill, np.uint8)
+        O.cleared = clr.ctypes.data
+        if host:
+            L.check(self.lib, self.lib.rgbl_optimize_sim3_host(C.byref(I), C.byref(O)))
+        else:
+            L.check(self.lib, self.lib.rgbl_optimize_sim3(self.h, C.byref(I), C.byref(O)))
+        return self._sim3_opt_result(O, clr)
+
     def CreateNewMapPoints(self, kf1, neighbours, prm, skip=None, cap=None):
         return self.prepare_CreateNewMapPoints(kf1, neighbours, prm, skip, cap)()
 
@@ -1791,3 +1889,43 @@ def sim3_ransac_host(problem, lib=None, diag=True, fill=0):
     bufs = ORBmatcher._sim3_buffers(I, O, fill, diag)
     L.check(lib, lib.rgbl_sim3_ransac_host(C.byref(I), C.byref(O)))
     return ORBmatcher._sim3_result(O, bufs)
+
+
+def quat_from_matrix(R):
+    """Quaterniond(Matrix3d) as Eigen assigns it, in the arithmetic of csrc/poseopt_math.h (po_quat_from_matrix): x y z w"""
+    m = np.asarray(R, np.float64).reshape(9)
+    q = np.zeros(4, np.float64)
+    t = (m[0] + m[4]) + m[8]
+    if t > 0.0:
+        t = np.sqrt(t + 1.0)
+        q[3] = 0.5 * t
+        t = 0.5 / t
+        q[0], q[1], q[2] = (m[7] - m[5]) * t, (m[2] - m[6]) * t, (m[3] - m[1]) * t
+    elif not m[4] > m[0] and not m[8] > m[0]:
+        t = np.sqrt(((m[0] - m[4]) - m[8]) + 1.0)
+        q[0] = 0.5 * t
+        t = 0.5 / t
+        q[3], q[1], q[2] = (m[7] - m[5]) * t, (m[3] + m[1]) * t, (m[6] + m[2]) * t
+    elif m[4] > m[0] and not m[8] > m[4]:
+        t = np.sqrt(((m[4] - m[8]) - m[0]) + 1.0)
+        q[1] = 0.5 * t
+        t = 0.5 / t
+        q[3], q[2], q[0] = (m[2] - m[6]) * t, (m[7] + m[5]) * t, (m[1] + m[3]) * t
+    else:
+        t = np.sqrt(((m[8] - m[0]) - m[4]) + 1.0)
+        q[2] = 0.5 * t
+        t = 0.5 / t
+        q[3], q[0], q[1] = (m[3] - m[1]) * t, (m[2] + m[6]) * t, (m[5] + m[7]) * t
+    return q
+
+
+def optimize_sim3_host(case, lib=None, cleared_fill=0):
+    """rgbl_optimize_sim3_host: Optimizer::OptimizeSim3 by the host build of csrc/sim3opt_math.h (no device, no handle); the
+    result dict of ORBmatcher.OptimizeSim3."""
+    lib = lib or L.load()
+    keep = []
+    I, O = ORBmatcher._sim3_opt_input(case, keep), L.Sim3OptOutput()
+    clr = np.full(I.n, cleared_fill, np.uint8)
+    O.cleared = clr.ctypes.data
+    L.check(lib, lib.rgbl_optimize_sim3_host(C.byref(I), C.byref(O)))
+    return ORBmatcher._sim3_opt_result(O, clr)
