@@ -1,0 +1,189 @@
+// lm_math.h — the part of g2o that Optimizer::PoseOptimization (csrc/poseopt_math.h, 6 unknowns) and Optimizer::OptimizeSim3
+// (csrc/sim3opt_math.h, 7 unknowns) both run, in ONE place for host and device: the layout of a reduced system, the dense
+// solve, OptimizationAlgorithmLevenberg::solve and the lanes' summation order, restated from
+//   Thirdparty/g2o/g2o/core/{optimization_algorithm_levenberg,sparse_optimizer}.cpp, solvers/linear_solver_dense.h
+// All arithmetic is fp64, no contraction.  OptimizeSim3 calls lm_levenberg; po_optimize carries that loop written out (it says why).
+//
+// What is NOT pinned: Eigen's LDLT with its pivoting, replaced by lm_solve (LDL^T without pivoting).  Deviations that follow
+// from the solver and are kept on purpose, for both optimisers:
+//   - a pivot that is not finite and > 0 counts as a failed factorisation (LDLT::isPositive() also accepts zero pivots);
+//   - after a failed factorisation g2o's x keeps whatever it held (uninitialised memory before the first success); here x is
+//     the caller's, starts as zeros on entry and persists across failed factorisations, trials, iterations and rounds.
+// Quirks of g2o's Levenberg that ARE kept, for both:
+//   - a failed factorisation gives tempChi = DBL_MAX, which passes g2o_isfinite: with an infinite currentChi rho is +inf and
+//     the step - the x of the last successful solve, or zeros - is ACCEPTED;
+//   - the edges keep the chi2 of the last TRIED step, even a rejected one (pop() restores the vertex, not the edges' errors).
+//
+// Summation order (host, emulator and GPU agree bit for bit).  Edge k, in ascending feature index, belongs to lane k mod 256;
+// a lane adds its edges in ascending k; the 256 partial sums are combined by the fixed tree v[i] = v[i] + v[i + s] for
+// s = 128, 64, ..., 1.  This holds for every sum of a system and for every single sum.  LmHostLanes below is the host's
+// execution of it, lm_tree_reduce of csrc/matcher.hip the workgroup's.
+#pragma once
+#include <float.h>
+#include <math.h>
+#include <stdint.h>
+
+#ifndef RGBL_HD
+#if defined(__HIPCC__)
+#define RGBL_HD __host__ __device__ inline
+#else
+#define RGBL_HD inline
+#endif
+#endif
+
+namespace rgbl {
+
+constexpr int kLmLanes = 256;   // work-items of one problem
+constexpr int kLmTrials = 10;   // _maxTrialsAfterFailure (optimization_algorithm_levenberg.cpp:46)
+
+// A reduced system of N unknowns: H's upper triangle row by row, then b, then the robust chi2.
+template <int N> struct LmSystem {
+  static constexpr int kB = N * (N + 1) / 2, kChi = kB + N, kSums = kChi + 1;
+  static constexpr int diag(int j) { return j * N - j * (j - 1) / 2; }   // H[j][j]: rows of N, N - 1, ... entries lie before it
+};
+
+// (H + lambda I) x = b by LDL^T without pivoting; Hu = the upper triangle row by row.  False, x untouched, when a pivot is not
+// finite and > 0 (linear_solver_dense.h:107-109: LDLT::isPositive() false).
+template <int N> RGBL_HD bool lm_solve(const double* Hu, double lambda, const double* b, double* x) {
+  double L[N][N], D[N], y[N];
+  int k = 0;
+  #pragma unroll
+  for (int j = 0; j < N; ++j)
+    #pragma unroll
+    for (int c = j; c < N; ++c, ++k) L[c][j] = Hu[k] + (c == j ? lambda : 0.0);   // lower triangle of the symmetric matrix
+  #pragma unroll
+  for (int j = 0; j < N; ++j) {
+    double d = L[j][j];
+    #pragma unroll
+    for (int p = 0; p < j; ++p) d = d - L[j][p] * L[j][p] * D[p];
+    if (!(d > 0.0 && d <= DBL_MAX)) return false;
+    D[j] = d;
+    #pragma unroll
+    for (int i = j + 1; i < N; ++i) {
+      double v = L[i][j];
+      #pragma unroll
+      for (int p = 0; p < j; ++p) v = v - L[i][p] * L[j][p] * D[p];
+      L[i][j] = v / d;
+    }
+  }
+  #pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double v = b[i];
+    #pragma unroll
+    for (int p = 0; p < i; ++p) v = v - L[i][p] * y[p];
+    y[i] = v;
+  }
+  #pragma unroll
+  for (int i = 0; i < N; ++i) y[i] = y[i] / D[i];
+  #pragma unroll
+  for (int i = N - 1; i >= 0; --i) {
+    double v = y[i];
+    #pragma unroll
+    for (int p = i + 1; p < N; ++p) v = v - L[p][i] * x[p];
+    x[i] = v;
+  }
+  return true;
+}
+
+// SparseOptimizer::optimize(max_it) (sparse_optimizer.cpp:376-414) with OptimizationAlgorithmLevenberg::solve
+// (optimization_algorithm_levenberg.cpp:61-169) on one vertex of N unknowns.
+//   G, the lanes, owns the problem's edges and the partial sums (LmSystem<N>::kSums per lane):
+//     G.zero()             every lane's partial sums = 0
+//     G.each(f)            f(Edge&, double* acc) for the caller's edges in ascending k (host: every lane in turn)
+//     G.reduce_system(buf) the fixed tree over all sums; returns where they stay readable until the next reduce_system():
+//                          the caller's buf (kSums doubles) or storage of G's own (k_sim3_opt: LDS)
+//     G.reduce_one()       the fixed tree over sum 0
+//   M, the optimiser's model, owns the estimate:
+//     M.linearise(G)       G.zero() and one pass that adds every active edge's H, b and robust chi2 at the current estimate
+//     M.trial(G, x)        forms the trial estimate from x (and may write x: OptimizeSim3's quirk 8); G.zero() and one pass that adds every active edge's robust chi2
+//                          there to sum 0
+//     M.accept()           the trial estimate becomes the current one
+// On the device every work-item runs this function; the scalar state (lambda, x, ...) is computed redundantly and identically
+// by all of them, so the only synchronisation is inside G.  Every loop is bounded: max_it x kLmTrials trials.
+// *iterations = the solve() calls, *chi = the Levenberg currentChi on return (0 for max_it < 1).
+template <int N, class Lanes, class Model>
+RGBL_HD void lm_levenberg(Lanes& G, Model& M, int max_it, double* x, int* iterations, double* chi) {
+  typedef LmSystem<N> Sys;
+  double lambda = 0.0, ni = 2.0, currentChi = 0.0;
+  int lmBad = 0, iters = 0;
+  double sums[Sys::kSums];
+  for (int it = 0; it < max_it; ++it) {
+    M.linearise(G);
+    const double* S = G.reduce_system(sums);
+    currentChi = S[Sys::kChi];
+    const double iniChi = currentChi;
+    double tempChi = currentChi;
+    if (it == 0) {                  // computeLambdaInit (:171-185): _tau = 1e-5
+      double maxDiagonal = 0.0;
+      for (int j = 0; j < N; ++j) { const double a = fabs(S[Sys::diag(j)]); maxDiagonal = a > maxDiagonal ? a : maxDiagonal; }   // std::max(fabs, max)
+      lambda = 1e-5 * maxDiagonal;
+      ni = 2.0;
+      lmBad = 0;
+    }
+    double rho = 0.0;
+    int qmax = 0;
+    do {
+      const bool ok = lm_solve<N>(S, lambda, S + Sys::kB, x);
+      M.trial(G, x);
+      tempChi = G.reduce_one();
+      if (!ok) tempChi = DBL_MAX;
+      rho = currentChi - tempChi;
+      double scale = 0.0;           // computeScale (:187-194)
+      for (int j = 0; j < N; ++j) scale += x[j] * (lambda * x[j] + S[Sys::kB + j]);
+      scale += 1e-3;
+      rho /= scale;
+      if (rho > 0.0 && tempChi >= -DBL_MAX && tempChi <= DBL_MAX) {   // g2o_isfinite
+        const double c = 2.0 * rho - 1.0;
+        double alpha = 1.0 - c * c * c;
+        alpha = (2.0 / 3.0 < alpha) ? 2.0 / 3.0 : alpha;                      // std::min(alpha, _goodStepUpperScale)
+        const double scaleFactor = (1.0 / 3.0 < alpha) ? alpha : 1.0 / 3.0;   // std::max(_goodStepLowerScale, alpha)
+        lambda *= scaleFactor;
+        ni = 2.0;
+        currentChi = tempChi;
+        M.accept();                 // discardTop
+      } else {
+        lambda *= ni;
+        ni *= 2.0;                  // pop: the estimate stays; the edges keep the errors of the rejected step
+      }
+      ++qmax;
+    } while (rho < 0.0 && qmax < kLmTrials);
+    ++iters;
+    if (qmax == kLmTrials || rho == 0.0) break;   // Terminate
+    if ((iniChi - currentChi) * 1e3 < iniChi) ++lmBad; else lmBad = 0;   // :157-166
+    if (lmBad >= 3) break;
+  }
+  *iterations = iters;
+  *chi = currentChi;
+}
+
+// The host's execution of the lanes: the partial sums of all 256 lanes side by side, the tree written out.
+template <class Edge, int Sums> struct LmHostLanes {
+  Edge* e;
+  int m;
+  double part[kLmLanes][Sums];
+  LmHostLanes(Edge* edges, int count) : e(edges), m(count) {}
+  void zero() {
+    for (int l = 0; l < kLmLanes; ++l)
+      for (int c = 0; c < Sums; ++c) part[l][c] = 0.0;
+  }
+  template <class F> void each(F f) {
+    for (int l = 0; l < kLmLanes; ++l)
+      for (int k = l; k < m; k += kLmLanes) f(e[k], part[l]);
+  }
+  void tree(int count) {
+    for (int s = kLmLanes / 2; s >= 1; s >>= 1)
+      for (int i = 0; i < s; ++i)
+        for (int c = 0; c < count; ++c) part[i][c] = part[i][c] + part[i + s][c];
+  }
+  const double* reduce_system(double* S) {
+    tree(Sums);
+    for (int c = 0; c < Sums; ++c) S[c] = part[0][c];
+    return S;
+  }
+  double reduce_one() {
+    tree(1);
+    return part[0][0];
+  }
+};
+
+}  // namespace rgbl

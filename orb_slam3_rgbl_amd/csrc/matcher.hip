@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -866,7 +867,7 @@ __global__ void k_test_np_cos_parallax(float mb, const float* __restrict__ depth
 // Optimizer::PoseOptimization (src/Optimizer.cc:814-1114): k_pose_opt, one workgroup of 256 work-items per problem.  The
 // algorithm is po_optimize of csrc/poseopt_math.h, run by every work-item: the scalar state (pose, lambda, the 6 x 6 solve,
 // the update) is computed redundantly and identically, the edges are spread over the lanes (edge k on lane k mod 256).  No
-// communication between workgroups, no atomics; the barriers of PoDevLanes::reduce are the only synchronisation and every
+// communication between workgroups, no atomics; the barriers of lm_tree_reduce are the only synchronisation and every
 // work-item reaches every one of them (all branches around them depend on reduced values only).  Every loop is bounded by
 // 4 rounds x 10 iterations x 10 trials.
 struct PoseOptProblem {
@@ -902,13 +903,41 @@ __device__ __forceinline__ PoEdge pose_opt_edge(const PoseOptProblem& pb, const 
   return e;
 }
 
-constexpr int kPoTreeLds = kPoLanes - 64;   // the partial sums of lanes 64 .. 255
+// The workgroup's execution of csrc/lm_math.h's fixed tree v[i] = v[i] + v[i + s] over the first N sums of every lane's acc:
+// lanes 64 .. 255 put their sums into LDS and wave 0 forms (v[i] + v[i + 128]) + (v[i + 64] + v[i + 192]), which is what s = 128
+// and s = 64 leave in lane i < 64; s = 32 .. 1 run inside wave 0 (lane i reads lane i + s; lanes >= s compute values nobody
+// reads), all sums side by side so that the cross-lane reads overlap; lane 0 writes the result to dst (LDS), where every
+// work-item reads it.  Two barriers.
+constexpr int kLmTreeLds = kLmLanes - 64;   // the partial sums of lanes 64 .. 255
+template <int N> __device__ __forceinline__ void lm_tree_reduce(const double* acc, double (*red)[kLmTreeLds], double* dst, int tid) {
+  if (tid >= 64) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) red[c][tid - 64] = acc[c];
+  }
+  __syncthreads();
+  if (tid < 64) {
+    double v[N];
+#pragma unroll
+    for (int c = 0; c < N; ++c) v[c] = (acc[c] + red[c][tid + 64]) + (red[c][tid] + red[c][tid + 128]);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+#pragma unroll
+      for (int c = 0; c < N; ++c) v[c] = v[c] + __shfl_down(v[c], (unsigned)s);
+    }
+    if (tid == 0) {
+#pragma unroll
+      for (int c = 0; c < N; ++c) dst[c] = v[c];
+    }
+  }
+  __syncthreads();
+}
+
 struct PoDevLanes {
   PoEdge r[kPoRegEdges];   // edges tid, tid + 256, ... in registers
   double acc[kPoSums];
   const PoseOptProblem* pb;
   const PoseOptDev* D;
-  double (*red)[kPoTreeLds];
+  double (*red)[kLmTreeLds];
   double* bc;
   int tid, m;
   __device__ void zero() {
@@ -928,38 +957,19 @@ struct PoDevLanes {
       D->level[pb->edge_off + k] = e.level;
     }
   }
-  // v[i] = v[i] + v[i + s]: lanes 64 .. 255 put their sums into LDS and wave 0 forms (v[i] + v[i + 128]) + (v[i + 64] + v[i + 192]),
-  // which is what s = 128 and s = 64 leave in lane i < 64; s = 32 .. 1 run inside wave 0 (lane i reads lane i + s; lanes >= s
-  // compute values nobody reads), all sums side by side so that the cross-lane reads overlap; lane 0's sums go to every
-  // work-item through LDS.  Two barriers.
-  template <int N> __device__ void reduce(double* S) {
-    if (tid >= 64) {
+  // every work-item copies the system's 28 sums from bc to registers (the trials' solves read them there: measured against
+  // reading them from LDS, docs/history/r15_measured.md), so the single sum can go through bc[0]
+  __device__ const double* reduce_system(double* S) {
+    lm_tree_reduce<kPoSums>(acc, red, bc, tid);
 #pragma unroll
-      for (int c = 0; c < N; ++c) red[c][tid - 64] = acc[c];
-    }
-    __syncthreads();
-    if (tid < 64) {
-      double v[N];
-#pragma unroll
-      for (int c = 0; c < N; ++c) v[c] = (acc[c] + red[c][tid + 64]) + (red[c][tid] + red[c][tid + 128]);
-#pragma unroll
-      for (int s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-        for (int c = 0; c < N; ++c) v[c] = v[c] + __shfl_down(v[c], (unsigned)s);
-      }
-      if (tid == 0) {
-#pragma unroll
-        for (int c = 0; c < N; ++c) bc[c] = v[c];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < N; ++c) S[c] = bc[c];
+    for (int c = 0; c < kPoSums; ++c) S[c] = bc[c];
+    return S;
   }
+  __device__ double reduce_one() { lm_tree_reduce<1>(acc, red, bc, tid); return bc[0]; }
 };
 
 __global__ __launch_bounds__(kPoLanes) void k_pose_opt(PoseOptDev D) {
-  __shared__ double s_red[kPoSums][kPoTreeLds];   // 42 KB
+  __shared__ double s_red[kPoSums][kLmTreeLds];   // 42 KB
   __shared__ double s_bc[kPoSums];
   const PoseOptProblem& pb = D.prob[blockIdx.x];
   PoDevLanes G;
@@ -1041,7 +1051,6 @@ __device__ __forceinline__ bool sim3_opt_edge(const Sim3OptProblem& pb, const Si
                       info1, i2 >= 0, pb.xy2 + 2 * (size_t)(i2 >= 0 ? i2 : 0), info2, e);
 }
 
-constexpr int kSoTreeLds = kSoLanes - 64;   // the partial sums of lanes 64 .. 255
 // A pair's twelve floats are used as doubles in every pass over the edges.  Left alone, the compiler converts them once and
 // keeps the doubles for the whole kernel: 24 more registers per pair.  An empty statement the value passes through makes the
 // conversion belong to the pass.
@@ -1055,7 +1064,7 @@ struct SoDevLanes {
   double acc[kSoSums];
   const Sim3OptProblem* pb;
   const Sim3OptDev* D;
-  double (*red)[kSoTreeLds];
+  double (*red)[kLmTreeLds];
   double* bc;
   SoSim3* T;
   int tid, m;
@@ -1083,32 +1092,9 @@ struct SoDevLanes {
       D->state[g] = (uint8_t)(e.gone | (e.cleared << 1));
     }
   }
-  // PoDevLanes::reduce: lanes 64 .. 255 through LDS, wave 0 below with cross-lane reads, lane 0's sums to everyone through
-  // LDS.  The system's 36 sums stay in bc[0 .. 35] for the trials' solves; the single sum goes through bc[36].
-  template <int N> __device__ void reduce(double* dst) {
-    if (tid >= 64) {
-#pragma unroll
-      for (int c = 0; c < N; ++c) red[c][tid - 64] = acc[c];
-    }
-    __syncthreads();
-    if (tid < 64) {
-      double v[N];
-#pragma unroll
-      for (int c = 0; c < N; ++c) v[c] = (acc[c] + red[c][tid + 64]) + (red[c][tid] + red[c][tid + 128]);
-#pragma unroll
-      for (int s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-        for (int c = 0; c < N; ++c) v[c] = v[c] + __shfl_down(v[c], (unsigned)s);
-      }
-      if (tid == 0) {
-#pragma unroll
-        for (int c = 0; c < N; ++c) dst[c] = v[c];
-      }
-    }
-    __syncthreads();
-  }
-  __device__ const double* reduce_system() { reduce<kSoSums>(bc); return bc; }
-  __device__ double reduce_one() { reduce<1>(bc + kSoSums); return bc[kSoSums]; }
+  // the system's 36 sums stay in bc[0 .. 35] for the trials' solves; the single sum goes through bc[36]
+  __device__ const double* reduce_system(double*) { lm_tree_reduce<kSoSums>(acc, red, bc, tid); return bc; }
+  __device__ double reduce_one() { lm_tree_reduce<1>(acc, red, bc + kSoSums, tid); return bc[kSoSums]; }
   // work-item j < 14 forms perturbed estimate j and its inverse, work-item 14 the estimate's inverse; the readers of the
   // previous linearisation are behind the barriers of the reductions in between
   __device__ const SoSim3* transforms(const SoSim3& S, bool fix_scale) {
@@ -1126,7 +1112,7 @@ struct SoDevLanes {
 };
 
 __global__ __launch_bounds__(kSoLanes) void k_sim3_opt(Sim3OptDev D) {
-  __shared__ double s_red[kSoSums][kSoTreeLds];   // 54 KB
+  __shared__ double s_red[kSoSums][kLmTreeLds];   // 54 KB
   __shared__ double s_bc[kSoSums + 1];
   __shared__ SoSim3 s_T[kSoTransforms];           // 1920 B
   __shared__ int s_cnt[4][2];
@@ -2900,6 +2886,31 @@ void finish_matches12(const SharedNodes& sn, int32_t* matches12, bool check_orie
   }
   *out_nmatches = nmatches;
 }
+
+// The element-wise device test hooks (rgbl_test_*_device): every array of `in` (n elements each) goes to the device,
+// launch(d_in, d_out, grid, block) runs one work-item per element on the null stream, d_out comes back as `out`.  The device
+// arrays are freed on every path.
+template <class T, class Launch> int elementwise_device_hook(std::initializer_list<const T*> in, T* out, int n, Launch launch) {
+  const size_t bytes = sizeof(T) * (size_t)n;
+  std::vector<T*> d(in.size() + 1, nullptr);   // the inputs, then the output
+  hipError_t e = hipSuccess;
+  for (T*& p : d)
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p), bytes);
+  size_t k = 0;
+  for (const T* h : in) {
+    if (e == hipSuccess) e = hipMemcpy(d[k], h, bytes, hipMemcpyHostToDevice);
+    ++k;
+  }
+  if (e == hipSuccess) {
+    launch(d.data(), d.back(), dim3((unsigned)((n + 255) / 256)), dim3(256));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, d.back(), bytes, hipMemcpyDeviceToHost);
+  for (T* p : d)
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess) { set_error("device test hook: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
+  return RGBL_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3582,19 +3593,9 @@ int rgbl_test_np_triangulate(const float* xn1, const float* xn2, const float* T1
 float rgbl_test_np_cos_parallax(float mb, float depth) { return np_cos_parallax_stereo(mb, depth); }
 int rgbl_test_np_cos_parallax_device(float mb, const float* depth, float* y, int n) {
   if (!depth || !y || n < 1) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  float *dx = nullptr, *dy = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dx), sizeof(float) * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dy), sizeof(float) * (size_t)n);
-  if (e == hipSuccess) e = hipMemcpy(dx, depth, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_test_np_cos_parallax, dim3((n + 255) / 256), dim3(256), 0, 0, mb, (const float*)dx, dy, n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(y, dy, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
-  if (dx) (void)hipFree(dx);
-  if (dy) (void)hipFree(dy);
-  if (e != hipSuccess) { set_error("cos parallax test hook: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
-  return RGBL_OK;
+  return elementwise_device_hook<float>({depth}, y, n, [&](float* const* d, float* dy, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_test_np_cos_parallax, grid, block, 0, 0, mb, (const float*)d[0], dy, n);
+  });
 }
 
 // what the two greedy, best-only projection matchers (Frame-to-Frame and key-frame-to-Frame) hand to the kernels
@@ -4404,6 +4405,42 @@ int rgbl_track_local_points(rgbl_matcher* m, const rgbl_track_local_input* in, u
   return track_local_core(m, in, in_view, rec, n_to_match, true, match2, out_nmatches);
 }
 
+namespace {
+// The prologue of the batch entry points whose problems read resident frames and a map-point pool: the problems of one call
+// share one pool, pool and frames are on the matcher's device, and the pool is locked while its slots are range-checked and
+// until the call returns.  An entry point declares its PoolCall FIRST, then - after lock() - StreamDrain, then HostCall:
+// destruction runs backwards, so the stream is drained (error returns included) before the pool is released.
+struct PoolCall {
+  const rgbl_matcher* m;
+  const char *what, *frame;   // the entry point and a resident frame as the error texts name them
+  rgbl_map_points* pool = nullptr;
+  std::unique_lock<std::mutex> held;
+  PoolCall(const rgbl_matcher* matcher, const char* name, const char* frame_name) : m(matcher), what(name), frame(frame_name) {}
+  // problem b reads pool `p` and the resident `frames` (null: host arrays)
+  int note(rgbl_map_points* p, std::initializer_list<const rgbl_device_frame*> frames, int b) {
+    for (const rgbl_device_frame* fr : frames)
+      if (fr && fr->device != m->device) {
+        set_error("%s %d: %s is on device %d, the matcher on %d", what, b, frame, fr->device, m->device);
+        return RGBL_ERR_INVALID;
+      }
+    if (!p) return RGBL_OK;
+    if (pool && pool != p) { set_error("%s %d: the problems of one call share one pool", what, b); return RGBL_ERR_INVALID; }
+    pool = p;
+    if (pool->device != m->device) { set_error("%s %d: the pool is on device %d, the matcher on %d", what, b, pool->device, m->device); return RGBL_ERR_INVALID; }
+    return RGBL_OK;
+  }
+  // locks the pool; under the lock, check(b) asks holds() for every slot problem b names (none if it does not read the pool)
+  // and returns RGBL_OK, or sets the error text of the first slot outside and returns RGBL_ERR_INVALID
+  int lock(int B, const std::function<int(int)>& check) {
+    if (!pool) return RGBL_OK;
+    held = std::unique_lock<std::mutex>(pool->mu);
+    for (int b = 0; b < B; ++b) RGBL_TRY(check(b));
+    return RGBL_OK;
+  }
+  bool holds(int slot) const { return slot >= 0 && slot < pool->cap; }
+};
+}  // namespace
+
 // ---- Optimizer::PoseOptimization (src/Optimizer.cc:814-1114) ---------------------------------------------------------
 namespace {
 // everything that can be refused is refused here, before anything is staged, launched or written; counts the correspondences
@@ -4466,7 +4503,7 @@ int rgbl_pose_optimization_host(const rgbl_pose_opt_input* in, rgbl_pose_opt_out
     e.level = 0;
     e.chi2 = 0.0;
   }
-  std::vector<PoHostLanes> lanes(1, PoHostLanes(edges.data(), m));   // 57 KB: not on the stack
+  std::vector<LmHostLanes<PoEdge, kPoSums>> lanes(1, LmHostLanes<PoEdge, kPoSums>(edges.data(), m));   // 57 KB: not on the stack
   const PoCam C = {(double)in->K[0], (double)in->K[1], (double)in->K[2], (double)in->K[3], (double)in->bf};
   PoPose T;
   PoDiag diag;
@@ -4484,29 +4521,22 @@ int rgbl_pose_optimization_batch(rgbl_matcher* m, int n_problems, const rgbl_pos
   if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
   const int B = n_problems;
   std::vector<int> off((size_t)B + 1, 0);
-  rgbl_map_points* pool = nullptr;
+  PoolCall pc(m, "pose optimisation", "the frame");
   for (int b = 0; b < B; ++b) {
     int mb = 0;
     RGBL_TRY(check_pose_opt_input(in + b, b, false, &mb));
     if (off[(size_t)b] > INT_MAX - mb) { set_error("pose optimisation: more than 2^31 correspondences in one call"); return RGBL_ERR_INVALID; }
     off[(size_t)b + 1] = off[(size_t)b] + mb;
-    if (in[b].device && in[b].device->device != m->device) { set_error("pose optimisation %d: the frame is on device %d, the matcher on %d", b, in[b].device->device, m->device); return RGBL_ERR_INVALID; }
-    if (in[b].pool) {
-      if (pool && pool != in[b].pool) { set_error("pose optimisation %d: the problems of one call share one pool", b); return RGBL_ERR_INVALID; }
-      pool = in[b].pool;
-      if (pool->device != m->device) { set_error("pose optimisation %d: the pool is on device %d, the matcher on %d", b, pool->device, m->device); return RGBL_ERR_INVALID; }
-    }
+    RGBL_TRY(pc.note(in[b].pool, {in[b].device}, b));
   }
   if (B == 0) return RGBL_OK;
   const int M = off[(size_t)B];
-  std::unique_lock<std::mutex> pool_lock;
-  if (pool) {
-    pool_lock = std::unique_lock<std::mutex>(pool->mu);
-    for (int b = 0; b < B; ++b)
-      if (in[b].pool)
-        for (int i = 0; i < in[b].n_points; ++i)
-          if (in[b].slot[i] < 0 || in[b].slot[i] >= pool->cap) { set_error("pose optimisation %d: slot %d outside [0, %d)", b, in[b].slot[i], pool->cap); return RGBL_ERR_INVALID; }
-  }
+  const rgbl_map_points* pool = pc.pool;
+  RGBL_TRY(pc.lock(B, [&](int b) -> int {
+    for (int i = 0; in[b].pool && i < in[b].n_points; ++i)
+      if (!pc.holds(in[b].slot[i])) { set_error("pose optimisation %d: slot %d outside [0, %d)", b, in[b].slot[i], pool->cap); return RGBL_ERR_INVALID; }
+    return RGBL_OK;
+  }));
   // the correspondences of all problems back to back: feature, and row of the problem's world positions
   std::vector<int32_t> feat((size_t)M), point((size_t)M);
   for (int b = 0; b < B; ++b) {
@@ -4520,7 +4550,7 @@ int rgbl_pose_optimization_batch(rgbl_matcher* m, int n_problems, const rgbl_pos
     }
   }
   RGBL_HIP(hipSetDevice(m->device));
-  StreamDrain drain(m->stream);  // error returns included; declared behind pool_lock: the stream is drained before the pool is released
+  StreamDrain drain(m->stream);  // behind pc (PoolCall)
   HostCall hc(m);
   hipStream_t s = hc.s;
   std::vector<PoseOptProblem> prob((size_t)B);
@@ -4654,18 +4684,14 @@ int rgbl_sim3_ransac_batch(rgbl_matcher* m, int n_problems, const rgbl_sim3_inpu
   if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
   const int B = n_problems;
   if (B > 32767) { set_error("sim3: more than 32767 problems in one call"); return RGBL_ERR_INVALID; }
-  rgbl_map_points* pool = nullptr;
+  PoolCall pc(m, "sim3", "a frame");
   // offsets of the problems that run: hypotheses, mask words, flags
   std::vector<int> hyp_off((size_t)B + 1, 0), inl_off((size_t)B + 1, 0);
   std::vector<size_t> word_off((size_t)B + 1, 0);
   int max_hyp = 0;
   for (int b = 0; b < B; ++b) {
     RGBL_TRY(check_sim3_input(in + b, b, false));
-    if (in[b].pool) {
-      if (pool && pool != in[b].pool) { set_error("sim3 %d: the problems of one call share one pool", b); return RGBL_ERR_INVALID; }
-      pool = in[b].pool;
-      if (pool->device != m->device) { set_error("sim3 %d: the pool is on device %d, the matcher on %d", b, pool->device, m->device); return RGBL_ERR_INVALID; }
-    }
+    RGBL_TRY(pc.note(in[b].pool, {}, b));
     const bool run = !sim3_skipped(in + b);
     const int nh = run ? in[b].n_hyp : 0, nn = run ? in[b].n : 0;
     if (hyp_off[(size_t)b] > INT_MAX - nh) { set_error("sim3: more than 2^31 hypotheses in one call"); return RGBL_ERR_INVALID; }
@@ -4675,24 +4701,22 @@ int rgbl_sim3_ransac_batch(rgbl_matcher* m, int n_problems, const rgbl_sim3_inpu
     max_hyp = std::max(max_hyp, nh);
   }
   if (word_off[(size_t)B] > (size_t)INT_MAX) { set_error("sim3: more than 2^31 mask words in one call"); return RGBL_ERR_INVALID; }
-  std::unique_lock<std::mutex> pool_lock;
-  if (pool) {
-    pool_lock = std::unique_lock<std::mutex>(pool->mu);
-    for (int b = 0; b < B; ++b)
-      if (in[b].pool)
-        for (int i = 0; i < in[b].n; ++i)
-          if (in[b].slot1[i] < 0 || in[b].slot1[i] >= pool->cap || in[b].slot2[i] < 0 || in[b].slot2[i] >= pool->cap) {
-            set_error("sim3 %d: slots (%d, %d) of correspondence %d outside [0, %d)", b, in[b].slot1[i], in[b].slot2[i], i, pool->cap);
-            return RGBL_ERR_INVALID;
-          }
-  }
+  const rgbl_map_points* pool = pc.pool;
+  RGBL_TRY(pc.lock(B, [&](int b) -> int {
+    for (int i = 0; in[b].pool && i < in[b].n; ++i)
+      if (!pc.holds(in[b].slot1[i]) || !pc.holds(in[b].slot2[i])) {
+        set_error("sim3 %d: slots (%d, %d) of correspondence %d outside [0, %d)", b, in[b].slot1[i], in[b].slot2[i], i, pool->cap);
+        return RGBL_ERR_INVALID;
+      }
+    return RGBL_OK;
+  }));
   const int H = hyp_off[(size_t)B];
   if (H == 0) {   // nothing to run (B == 0 included)
     for (int b = 0; b < B; ++b) out[b].selected = -1;
     return RGBL_OK;
   }
   RGBL_HIP(hipSetDevice(m->device));
-  StreamDrain drain(m->stream);  // error returns included; declared behind pool_lock: the stream is drained before the pool is released
+  StreamDrain drain(m->stream);  // behind pc (PoolCall)
   HostCall hc(m);
   hipStream_t s = hc.s;
   std::vector<Sim3Problem> prob((size_t)B);
@@ -4860,28 +4884,20 @@ int rgbl_optimize_sim3_batch(rgbl_matcher* m, int n_problems, const rgbl_sim3_op
   std::vector<int> off((size_t)B + 1, 0);   // at most 65535 candidates each: B < 2^15 problems fit an int
   std::vector<Sim3OptCand> cand;
   std::vector<SoDiag> diag((size_t)B);
-  rgbl_map_points* pool = nullptr;
+  PoolCall pc(m, "sim3 optimisation", "a frame");
   for (int b = 0; b < B; ++b) {
     RGBL_TRY(check_sim3_opt_input(in + b, b, false, &cand, &diag[(size_t)b]));
     off[(size_t)b + 1] = (int)cand.size();
-    for (const rgbl_device_frame* fr : {in[b].device1, in[b].device2})
-      if (fr && fr->device != m->device) { set_error("sim3 optimisation %d: a frame is on device %d, the matcher on %d", b, fr->device, m->device); return RGBL_ERR_INVALID; }
-    if (in[b].pool) {
-      if (pool && pool != in[b].pool) { set_error("sim3 optimisation %d: the problems of one call share one pool", b); return RGBL_ERR_INVALID; }
-      pool = in[b].pool;
-      if (pool->device != m->device) { set_error("sim3 optimisation %d: the pool is on device %d, the matcher on %d", b, pool->device, m->device); return RGBL_ERR_INVALID; }
-    }
+    RGBL_TRY(pc.note(in[b].pool, {in[b].device1, in[b].device2}, b));
   }
   if (B == 0) return RGBL_OK;
   const int M = off[(size_t)B];
-  std::unique_lock<std::mutex> pool_lock;
-  if (pool) {
-    pool_lock = std::unique_lock<std::mutex>(pool->mu);
-    for (int b = 0; b < B; ++b)
-      if (in[b].pool)
-        for (int i = 0; i < in[b].n_points; ++i)
-          if (in[b].slot[i] < 0 || in[b].slot[i] >= pool->cap) { set_error("sim3 optimisation %d: slot %d outside [0, %d)", b, in[b].slot[i], pool->cap); return RGBL_ERR_INVALID; }
-  }
+  const rgbl_map_points* pool = pc.pool;
+  RGBL_TRY(pc.lock(B, [&](int b) -> int {
+    for (int i = 0; in[b].pool && i < in[b].n_points; ++i)
+      if (!pc.holds(in[b].slot[i])) { set_error("sim3 optimisation %d: slot %d outside [0, %d)", b, in[b].slot[i], pool->cap); return RGBL_ERR_INVALID; }
+    return RGBL_OK;
+  }));
   // the candidates of all problems back to back
   std::vector<int32_t> feat((size_t)M), p1((size_t)M), p2((size_t)M), i2((size_t)M), lvl2((size_t)M);
   for (int b = 0; b < B; ++b)
@@ -4892,7 +4908,7 @@ int rgbl_optimize_sim3_batch(rgbl_matcher* m, int n_problems, const rgbl_sim3_op
       p2[(size_t)c] = in[b].pool ? in[b].slot[k.p2] : k.p2;
     }
   RGBL_HIP(hipSetDevice(m->device));
-  StreamDrain drain(m->stream);  // error returns included; declared behind pool_lock: the stream is drained before the pool is released
+  StreamDrain drain(m->stream);  // behind pc (PoolCall)
   HostCall hc(m);
   hipStream_t s = hc.s;
   std::vector<Sim3OptProblem> prob((size_t)B);
@@ -4951,62 +4967,27 @@ int rgbl_optimize_sim3(rgbl_matcher* m, const rgbl_sim3_opt_input* in, rgbl_sim3
 double rgbl_test_so_exp(double x) { return so_exp(x); }
 int rgbl_test_so_exp_device(const double* x, double* z, int n) {
   if (!x || !z || n < 1) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
-  double *dx = nullptr, *dz = nullptr;
-  const size_t bytes = sizeof(double) * (size_t)n;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dx), bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dz), bytes);
-  if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_test_so_exp, dim3((n + 255) / 256), dim3(256), 0, 0, (const double*)dx, dz, n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(z, dz, bytes, hipMemcpyDeviceToHost);
-  if (dx) (void)hipFree(dx);
-  if (dz) (void)hipFree(dz);
-  if (e != hipSuccess) { set_error("sim3opt math test hook: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
-  return RGBL_OK;
+  return elementwise_device_hook<double>({x}, z, n, [&](double* const* d, double* dz, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_test_so_exp, grid, block, 0, 0, (const double*)d[0], dz, n);
+  });
 }
 
 // test hooks for csrc/poseopt_math.h: op 0 sin, 1 cos, 2 x / y, 3 sqrt - on the host, and compiled for the device
 double rgbl_test_po_math(int op, double x, double y) { return op == 0 ? po_sin(x) : op == 1 ? po_cos(x) : op == 2 ? x / y : sqrt(x); }
 int rgbl_test_po_math_device(int op, const double* x, const double* y, double* z, int n) {
   if (!x || !y || !z || n < 1 || op < 0 || op > 3) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
-  double *dx = nullptr, *dy = nullptr, *dz = nullptr;
-  const size_t bytes = sizeof(double) * (size_t)n;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dx), bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dy), bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dz), bytes);
-  if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_test_po_math, dim3((n + 255) / 256), dim3(256), 0, 0, op, (const double*)dx, (const double*)dy, dz, n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(z, dz, bytes, hipMemcpyDeviceToHost);
-  if (dx) (void)hipFree(dx);
-  if (dy) (void)hipFree(dy);
-  if (dz) (void)hipFree(dz);
-  if (e != hipSuccess) { set_error("poseopt math test hook: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
-  return RGBL_OK;
+  return elementwise_device_hook<double>({x, y}, z, n, [&](double* const* d, double* dz, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_test_po_math, grid, block, 0, 0, op, (const double*)d[0], (const double*)d[1], dz, n);
+  });
 }
 
 // test hooks (tests/test_logf_glibc.py): the restatement on the host, and the same function compiled for the device
 float rgbl_test_logf(float x) { return rgbl::logf_glibc(x); }
 int rgbl_test_logf_device(const float* x, float* y, int n) {
   if (!x || !y || n < 1) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  float *d_x = nullptr, *d_y = nullptr;
-  RGBL_HIP(hipMalloc(reinterpret_cast<void**>(&d_x), sizeof(float) * (size_t)n));
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_y), sizeof(float) * (size_t)n);
-  if (e == hipSuccess) e = hipMemcpy(d_x, x, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_test_logf, dim3((n + 255) / 256), dim3(256), 0, 0, (const float*)d_x, d_y, n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(y, d_y, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
-  (void)hipFree(d_x);
-  if (d_y) (void)hipFree(d_y);
-  if (e != hipSuccess) { set_error("logf test hook: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
-  return RGBL_OK;
+  return elementwise_device_hook<float>({x}, y, n, [&](float* const* d, float* dy, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_test_logf, grid, block, 0, 0, (const float*)d[0], dy, n);
+  });
 }
 
 int rgbl_search_for_initialization(rgbl_matcher* m, const rgbl_initialization_input* in, float* prev_matched, int32_t* matches12,

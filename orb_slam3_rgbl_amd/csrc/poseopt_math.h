@@ -14,11 +14,8 @@
 // difference stays at 1.1e-16, which next to a zero of the function is up to 11 ulp of the result.
 //
 // What is NOT pinned (as for every Eigen evaluation order in this project): the order of Eigen's small fixed-size products -
-// written here left to right -, Eigen's LDLT with its pivoting, replaced by po_solve6 (LDL^T without pivoting), and libm's
-// sin / cos.  Deviations that follow from the solver and are kept on purpose:
-//   - a pivot that is not finite and > 0 counts as a failed factorisation (LDLT::isPositive() also accepts zero pivots);
-//   - after a failed factorisation g2o's x keeps whatever it held (uninitialised memory before the first success); here x
-//     starts as zeros on entry and persists across trials, iterations and rounds.
+// written here left to right -, Eigen's LDLT with its pivoting, replaced by lm_solve<6>, and libm's sin / cos.  The solver's
+// failed-pivot rule, the x that persists and g2o's Levenberg with the quirks it keeps are stated once, in csrc/lm_math.h.
 //
 // Quirks of the reference that ARE kept:
 //   1. every round restarts from the ENTRY pose (:1008-1009 read pFrame->GetPose(), not written before :1111);
@@ -33,31 +30,18 @@
 //   9. information() * _error is the full matrix product, zeros included: a non-finite error row makes the chi2 NaN, and NaN
 //      is not `> threshold`, so such an edge counts as an inlier.
 //
-// Summation order (part of this header: host, emulator and GPU agree bit for bit).  The correspondences are numbered in
-// ascending feature index, k = 0 .. m-1; edge k belongs to lane k mod 256; a lane adds its edges in ascending k; the 256
-// partial sums are combined by the fixed tree v[i] = v[i] + v[i + s] for s = 128, 64, ..., 1.  This holds for the 21 + 6
-// entries of H and b and for every chi2 sum.  Edges on level 1 (outliers) are SKIPPED: a lane's partial sum does not see them.
+// Summation order: csrc/lm_math.h's (edge k on lane k mod 256, ascending k, the fixed tree), for the 21 + 6 entries of H and b
+// and for every chi2 sum.  Edges on level 1 (outliers) are SKIPPED: a lane's partial sum does not see them.
 #pragma once
-#include <float.h>
-#include <math.h>
-#include <stdint.h>
-
-#ifndef RGBL_HD
-#if defined(__HIPCC__)
-#define RGBL_HD __host__ __device__ inline
-#else
-#define RGBL_HD inline
-#endif
-#endif
+#include "lm_math.h"
 
 namespace rgbl {
 
-constexpr int kPoLanes = 256;      // work-items of one problem
+constexpr int kPoLanes = kLmLanes;
 constexpr int kPoRegEdges = 8;     // edges a lane keeps in registers
 constexpr int kPoRounds = 4;       // Optimizer.cc:1006
 constexpr int kPoIterations = 10;  // its[] (:1003)
-constexpr int kPoTrials = 10;      // _maxTrialsAfterFailure (optimization_algorithm_levenberg.cpp:46)
-constexpr int kPoSums = 28;        // upper triangle of H (21), b (6), the robust chi2 (1)
+constexpr int kPoSums = LmSystem<6>::kSums;   // 28: upper triangle of H (21), b (6), the robust chi2 (1)
 
 // ---- sin / cos -------------------------------------------------------------------------------------------------------
 // fdlibm's __kernel_sin / __kernel_cos (the msun forms) on [-pi/4, pi/4] with a tail y
@@ -307,38 +291,6 @@ RGBL_HD void po_edge_accumulate(PoEdge& e, const PoCam& C, const PoPose& T, bool
   acc[27] = acc[27] + rho0;
 }
 
-// (H + lambda I) x = b by LDL^T without pivoting; Hu = the upper triangle row by row.  False, x untouched, when a pivot is not
-// finite and > 0 (linear_solver_dense.h:107-109: LDLT::isPositive() false).
-RGBL_HD bool po_solve6(const double Hu[21], double lambda, const double b[6], double x[6]) {
-  double L[6][6], D[6], y[6];
-  int k = 0;
-  for (int j = 0; j < 6; ++j)
-    for (int c = j; c < 6; ++c, ++k) L[c][j] = Hu[k] + (c == j ? lambda : 0.0);   // lower triangle of the symmetric matrix
-  for (int j = 0; j < 6; ++j) {
-    double d = L[j][j];
-    for (int p = 0; p < j; ++p) d = d - L[j][p] * L[j][p] * D[p];
-    if (!(d > 0.0 && d <= DBL_MAX)) return false;
-    D[j] = d;
-    for (int i = j + 1; i < 6; ++i) {
-      double v = L[i][j];
-      for (int p = 0; p < j; ++p) v = v - L[i][p] * L[j][p] * D[p];
-      L[i][j] = v / d;
-    }
-  }
-  for (int i = 0; i < 6; ++i) {
-    double v = b[i];
-    for (int p = 0; p < i; ++p) v = v - L[i][p] * y[p];
-    y[i] = v;
-  }
-  for (int i = 0; i < 6; ++i) y[i] = y[i] / D[i];
-  for (int i = 5; i >= 0; --i) {
-    double v = y[i];
-    for (int p = i + 1; p < 6; ++p) v = v - L[p][i] * x[p];
-    x[i] = v;
-  }
-  return true;
-}
-
 // what the tests compare besides pose, flags and count
 struct PoDiag {
   int32_t iterations[kPoRounds];   // solve() calls of the round's optimize() (0: no active edge)
@@ -349,12 +301,33 @@ struct PoDiag {
 };
 
 // ---- the four rounds -------------------------------------------------------------------------------------------------------
-// Written once for both execution models.  `G` owns the problem's edges and the partial sums:
-//   G.zero()                        every lane's 28 partial sums = 0
-//   G.each(f)                       f(PoEdge&, double acc[28]) for the caller's edges in ascending k (host: every lane in turn)
-//   G.reduce<count>(S)              the fixed tree over the first `count` sums; S is the same on every lane afterwards
-// On the device every work-item runs this function; all scalar state (pose, lambda, x, ...) is computed redundantly and
-// identically by all of them, so the only synchronisation is inside G.reduce.  Every loop is bounded: 4 x 10 x 10 trials.
+// The model lm_levenberg<6> runs: the vertex estimate and the two passes over the edges.
+struct PoModel {
+  const PoCam& C;
+  PoPose T, Tt;   // the estimate, and the one of the trial (written by trial, read by accept)
+  bool robust;
+  RGBL_HD PoModel(const PoCam& cam, const PoPose& estimate, bool robust_kernel) : C(cam), T(estimate), robust(robust_kernel) {}
+  template <class Lanes> RGBL_HD void linearise(Lanes& G) {
+    G.zero();
+    G.each([&](PoEdge& e, double* acc) { if (!e.level) po_edge_accumulate(e, C, T, robust, acc); });
+  }
+  template <class Lanes> RGBL_HD void trial(Lanes& G, const double* x) {
+    Tt = po_oplus(x, T);
+    G.zero();
+    G.each([&](PoEdge& e, double* acc) {
+      if (e.level) return;
+      double P[3], err[3];
+      e.chi2 = po_edge_error(e, C, Tt, P, err);
+      acc[0] = acc[0] + po_edge_rho(e, robust);
+    });
+  }
+  RGBL_HD void accept() { T = Tt; }
+};
+
+// Written once for both execution models.  `G` owns the problem's edges and the partial sums: the lanes of csrc/lm_math.h
+// (zero, each, reduce_system, reduce_one) with kPoSums sums.  On the device every work-item runs this function; all scalar
+// state is computed redundantly and identically by all of them, so the only synchronisation is inside G's reductions.  Every
+// loop is bounded: 4 x 10 x 10 trials.
 // Returns nInitialCorrespondences - nBad (:1113); `out` is the vertex estimate.
 template <class Lanes>
 RGBL_HD int po_optimize(Lanes& G, const PoCam& C, const PoPose& entry, int n_corr, PoPose& out, PoDiag& D) {
@@ -365,75 +338,58 @@ RGBL_HD int po_optimize(Lanes& G, const PoCam& C, const PoPose& entry, int n_cor
   for (int i = 0; i < 3; ++i) D.t[i] = entry.t[i];
   if (n_corr < 3) return 0;   // :996-997
   double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  double S[kPoSums];
   int nBad = 0;
   for (int round = 0; round < kPoRounds; ++round) {
-    PoPose T = entry;                 // quirk 1
-    const bool robust = round < 3;    // quirk 4: setRobustKernel(0) at it == 2 acts from round 3 on
+    PoModel M(C, entry, round < 3);   // quirk 1; quirk 4: setRobustKernel(0) at it == 2 acts from round 3 on
     const int n_active = n_corr - nBad;
     int iters = 0;
     double currentChi = 0.0;
     if (n_active > 0) {               // quirk 8
-      double lambda = 0.0, ni = 2.0;
+      // lm_levenberg<6>(G, M, kPoIterations, x, &iters, &currentChi) of csrc/lm_math.h WRITTEN OUT (comments there; a change
+      // there belongs here too): called, the same loop costs k_pose_opt 0.3 - 0.7 % on the MI355X (docs/history/r15_measured.md)
+      typedef LmSystem<6> Sys;
+      double lambda = 0.0, ni = 2.0, sums[kPoSums];
       int lmBad = 0;
-      for (int it = 0; it < kPoIterations; ++it) {   // SparseOptimizer::optimize (sparse_optimizer.cpp:376-414)
-        // OptimizationAlgorithmLevenberg::solve (optimization_algorithm_levenberg.cpp:61-169)
-        G.zero();
-        G.each([&](PoEdge& e, double* acc) { if (!e.level) po_edge_accumulate(e, C, T, robust, acc); });
-        G.template reduce<kPoSums>(S);
-        currentChi = S[27];
+      for (int it = 0; it < kPoIterations; ++it) {
+        M.linearise(G);
+        const double* S = G.reduce_system(sums);
+        currentChi = S[Sys::kChi];
         const double iniChi = currentChi;
-        double tempChi = currentChi;
-        if (it == 0) {                // computeLambdaInit (:171-185): _tau = 1e-5
-          double maxDiagonal = 0.0;
-          const int diag[6] = {0, 6, 11, 15, 18, 20};
-          for (int j = 0; j < 6; ++j) { const double a = fabs(S[diag[j]]); maxDiagonal = a > maxDiagonal ? a : maxDiagonal; }   // std::max(fabs, max)
-          lambda = 1e-5 * maxDiagonal;
-          ni = 2.0;
-          lmBad = 0;
-        }
-        double rho = 0.0;
+        double tempChi = currentChi, rho = 0.0;
         int qmax = 0;
+        if (it == 0) {
+          double maxDiagonal = 0.0;
+          for (int j = 0; j < 6; ++j) { const double a = fabs(S[Sys::diag(j)]); maxDiagonal = a > maxDiagonal ? a : maxDiagonal; }
+          lambda = 1e-5 * maxDiagonal; ni = 2.0; lmBad = 0;
+        }
         do {
-          const bool ok = po_solve6(S, lambda, S + 21, x);
-          const PoPose Tt = po_oplus(x, T);
-          G.zero();
-          G.each([&](PoEdge& e, double* acc) {
-            if (e.level) return;
-            double P[3], err[3];
-            e.chi2 = po_edge_error(e, C, Tt, P, err);
-            acc[0] = acc[0] + po_edge_rho(e, robust);
-          });
-          double chi[1];
-          G.template reduce<1>(chi);
-          tempChi = chi[0];
+          const bool ok = lm_solve<6>(S, lambda, S + Sys::kB, x);
+          M.trial(G, x);
+          tempChi = G.reduce_one();
           if (!ok) tempChi = DBL_MAX;
           rho = currentChi - tempChi;
-          double scale = 0.0;         // computeScale (:187-194)
-          for (int j = 0; j < 6; ++j) scale += x[j] * (lambda * x[j] + S[21 + j]);
-          scale += 1e-3;
-          rho /= scale;
-          if (rho > 0.0 && tempChi >= -DBL_MAX && tempChi <= DBL_MAX) {   // g2o_isfinite
+          double scale = 0.0;
+          for (int j = 0; j < 6; ++j) scale += x[j] * (lambda * x[j] + S[Sys::kB + j]);
+          scale += 1e-3; rho /= scale;
+          if (rho > 0.0 && tempChi >= -DBL_MAX && tempChi <= DBL_MAX) {
             const double c = 2.0 * rho - 1.0;
             double alpha = 1.0 - c * c * c;
-            alpha = (2.0 / 3.0 < alpha) ? 2.0 / 3.0 : alpha;              // std::min(alpha, _goodStepUpperScale)
-            const double scaleFactor = (1.0 / 3.0 < alpha) ? alpha : 1.0 / 3.0;   // std::max(_goodStepLowerScale, alpha)
-            lambda *= scaleFactor;
-            ni = 2.0;
-            currentChi = tempChi;
-            T = Tt;                   // discardTop
+            alpha = (2.0 / 3.0 < alpha) ? 2.0 / 3.0 : alpha;
+            const double scaleFactor = (1.0 / 3.0 < alpha) ? alpha : 1.0 / 3.0;
+            lambda *= scaleFactor; ni = 2.0;
+            currentChi = tempChi; M.accept();
           } else {
-            lambda *= ni;
-            ni *= 2.0;                // pop: T stays; the edges keep the errors of the rejected step (quirk 2)
+            lambda *= ni; ni *= 2.0;
           }
           ++qmax;
-        } while (rho < 0.0 && qmax < kPoTrials);
+        } while (rho < 0.0 && qmax < kLmTrials);
         ++iters;
-        if (qmax == kPoTrials || rho == 0.0) break;   // Terminate
-        if ((iniChi - currentChi) * 1e3 < iniChi) ++lmBad; else lmBad = 0;   // :157-166
+        if (qmax == kLmTrials || rho == 0.0) break;
+        if ((iniChi - currentChi) * 1e3 < iniChi) ++lmBad; else lmBad = 0;
         if (lmBad >= 3) break;
       }
     }
+    const PoPose& T = M.T;
     // Optimizer.cc:1014-1100
     G.zero();
     G.each([&](PoEdge& e, double* acc) {
@@ -445,9 +401,7 @@ RGBL_HD int po_optimize(Lanes& G, const PoCam& C, const PoPose& entry, int n_cor
       e.level = chi2 > (e.stereo ? 7.815f : 5.991f) ? 1 : 0;
       acc[0] = acc[0] + (double)e.level;
     });
-    double bad[1];
-    G.template reduce<1>(bad);
-    nBad = (int)bad[0];
+    nBad = (int)G.reduce_one();
     D.iterations[round] = iters; D.active[round] = n_active; D.chi2[round] = currentChi;
     D.rounds = round + 1;
     out = T;
@@ -457,27 +411,5 @@ RGBL_HD int po_optimize(Lanes& G, const PoCam& C, const PoPose& entry, int n_cor
   }
   return n_corr - nBad;
 }
-
-// The host's execution of the lanes: the partial sums of all 256 lanes side by side, the tree written out.
-struct PoHostLanes {
-  PoEdge* e;
-  int m;
-  double part[kPoLanes][kPoSums];
-  PoHostLanes(PoEdge* edges, int count) : e(edges), m(count) {}
-  void zero() {
-    for (int l = 0; l < kPoLanes; ++l)
-      for (int c = 0; c < kPoSums; ++c) part[l][c] = 0.0;
-  }
-  template <class F> void each(F f) {
-    for (int l = 0; l < kPoLanes; ++l)
-      for (int k = l; k < m; k += kPoLanes) f(e[k], part[l]);
-  }
-  template <int count> void reduce(double* S) {
-    for (int s = kPoLanes / 2; s >= 1; s >>= 1)
-      for (int i = 0; i < s; ++i)
-        for (int c = 0; c < count; ++c) part[i][c] = part[i][c] + part[i + s][c];
-    for (int c = 0; c < count; ++c) S[c] = part[0][c];
-  }
-};
 
 }  // namespace rgbl

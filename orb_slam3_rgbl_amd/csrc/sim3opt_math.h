@@ -19,12 +19,12 @@
 // they are computed once per linearisation (G.transforms) and an edge pair costs 30 map-and-project evaluations.
 //
 // What is NOT pinned: the order of Eigen's small fixed-size products - written here left to right -, Eigen's LDLT with its
-// pivoting, replaced by so_solve7 (LDL^T without pivoting; a pivot that is not finite and > 0 counts as a failed
-// factorisation, x then keeps what it held: zeros on entry, persisting across trials, iterations and rounds), libm's
-// exp / sin / cos, and BlockSolverX's dynamic-size products (the 7 x 7 system is formed directly).
+// pivoting, replaced by lm_solve<7>, libm's exp / sin / cos, and BlockSolverX's dynamic-size products (the 7 x 7 system is
+// formed directly).  The solver's failed-pivot rule, the x that persists and g2o's Levenberg with the quirks it keeps are
+// stated once, in csrc/lm_math.h.
 //
 // Quirks of the reference that ARE kept:
-//   1. round 1's classification reads the chi2 of the last TRIED step, even a rejected one (:2320; quirk 2 of poseopt_math.h);
+//   1. round 1's classification reads the chi2 of the last TRIED step, even a rejected one (:2320; lm_math.h);
 //   2. chi2() > th2 compares a double with the float th2 (:2320, :2367);
 //   3. nCorrespondences - nBad < 10 returns 0 at :2349: the matches cleared so far stay cleared, g2oS12 is NOT written;
 //   4. nMoreIterations is 10 if any pair was dropped, else 5; round 2 starts from the estimate round 1 left, lambda is
@@ -40,23 +40,20 @@
 //   9. a round without edges runs no iteration;
 //  10. no quaternion is ever normalised (sim3.h has no normalisation);
 //  11. mAcumHessian comes back as zeros (:2356 zeroes it, nothing adds to it): the callers write the zeros.
-//  12. tempChi = DBL_MAX after a failed factorisation passes g2o_isfinite: with an infinite currentChi (a non-finite
-//      information) rho is +inf and the step - the x of the last successful solve, or zeros - is ACCEPTED.
+//  12. tempChi = DBL_MAX after a failed factorisation passes g2o_isfinite (lm_math.h): with an infinite currentChi (a
+//      non-finite information) rho is +inf and the step - the x of the last successful solve, or zeros - is ACCEPTED.
 //
-// Summation order (part of this header: host, emulator and GPU agree bit for bit).  Correspondence k, in ascending feature
-// index, belongs to lane k mod 256; a lane adds its pairs in ascending k, e12 before e21; the 256 partial sums are combined
-// by the fixed tree v[i] = v[i] + v[i + s] for s = 128, 64, ..., 1.  28 + 7 + 1 sums: H's upper triangle row by row, b, the
-// robust chi2.  Dropped pairs are skipped: a lane's partial sum does not see them.
+// Summation order: csrc/lm_math.h's (pair k on lane k mod 256, ascending k, the fixed tree), e12 before e21, for the 28 + 7 + 1
+// sums.  Dropped pairs are skipped: a lane's partial sum does not see them.
 #pragma once
 #include "poseopt_math.h"
 #include "sim3_math.h"
 
 namespace rgbl {
 
-constexpr int kSoLanes = 256;      // work-items of one problem
+constexpr int kSoLanes = kLmLanes;
 constexpr int kSoRegEdges = 8;     // edge pairs a lane keeps in registers
-constexpr int kSoTrials = 10;      // _maxTrialsAfterFailure
-constexpr int kSoSums = 36;        // upper triangle of H (28), b (7), the robust chi2 (1)
+constexpr int kSoSums = LmSystem<7>::kSums;   // 36: upper triangle of H (28), b (7), the robust chi2 (1)
 constexpr int kSoTransforms = 30;  // S, S^-1, the 14 perturbed estimates, their 14 inverses
 
 // ---- exp ---------------------------------------------------------------------------------------------------------------
@@ -281,49 +278,6 @@ RGBL_HD void so_edge_accumulate(SoEdge& e, const SoCam& C1, const SoCam& C2, con
   e.chi21 = so_accumulate_one(e.obs2, e.X1, (double)e.info2, C2, T[1], T + 16, robust, delta, acc);
 }
 
-// (H + lambda I) x = b by LDL^T without pivoting; Hu = the upper triangle row by row.  False, x untouched, when a pivot is not
-// finite and > 0 (po_solve6's rule).
-RGBL_HD bool so_solve7(const double Hu[28], double lambda, const double b[7], double x[7]) {
-  double L[7][7], D[7], y[7];
-  int k = 0;
-  #pragma unroll
-  for (int j = 0; j < 7; ++j)
-    #pragma unroll
-    for (int c = j; c < 7; ++c, ++k) L[c][j] = Hu[k] + (c == j ? lambda : 0.0);
-  #pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    double d = L[j][j];
-    #pragma unroll
-    for (int p = 0; p < j; ++p) d = d - L[j][p] * L[j][p] * D[p];
-    if (!(d > 0.0 && d <= DBL_MAX)) return false;
-    D[j] = d;
-    #pragma unroll
-    for (int i = j + 1; i < 7; ++i) {
-      double v = L[i][j];
-      #pragma unroll
-      for (int p = 0; p < j; ++p) v = v - L[i][p] * L[j][p] * D[p];
-      L[i][j] = v / d;
-    }
-  }
-  #pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    double v = b[i];
-    #pragma unroll
-    for (int p = 0; p < i; ++p) v = v - L[i][p] * y[p];
-    y[i] = v;
-  }
-  #pragma unroll
-  for (int i = 0; i < 7; ++i) y[i] = y[i] / D[i];
-  #pragma unroll
-  for (int i = 6; i >= 0; --i) {
-    double v = y[i];
-    #pragma unroll
-    for (int p = i + 1; p < 7; ++p) v = v - L[p][i] * x[p];
-    x[i] = v;
-  }
-  return true;
-}
-
 // what the tests compare besides the estimate, the flags and the count; the first six are rgbl_sim3_opt_diag's counters
 struct SoDiag {
   int32_t n_correspondences, n_bad_mps, n_in_kf2, n_out_kf2, n_without_mp, n_bad;
@@ -334,76 +288,43 @@ struct SoDiag {
 };
 
 // ---- the optimiser -----------------------------------------------------------------------------------------------------
-// `G` owns the problem's edge pairs, the partial sums and the transforms of a linearisation:
-//   G.zero(), G.each(f)           as in poseopt_math.h, with kSoSums sums
-//   G.reduce_system()             the fixed tree over all kSoSums sums; the result is held by G (device: LDS) until the next call
-//   G.reduce_one()                the fixed tree over sum 0
+// `G` owns the problem's edge pairs, the partial sums and the transforms of a linearisation: the lanes of csrc/lm_math.h
+// (zero, each, reduce_system, reduce_one) with kSoSums sums, and
 //   G.transforms(S, fix_scale)    the kSoTransforms transforms at S, the same for every lane (device: LDS)
-// SparseOptimizer::optimize(max_it) with OptimizationAlgorithmLevenberg as po_optimize restates it, on the 7-dof vertex.
-template <class Lanes>
-RGBL_HD void so_levenberg(Lanes& G, const SoCam& C1, const SoCam& C2, SoSim3& S, bool robust, double delta, bool fix_scale, int max_it,
-                          double x[7], int* iterations, double* chi) {
-  double lambda = 0.0, ni = 2.0, currentChi = 0.0;
-  int lmBad = 0, iters = 0;
-  for (int it = 0; it < max_it; ++it) {
+// The model lm_levenberg<7> runs: the 7-dof vertex estimate and the two passes over the edge pairs.
+struct SoModel {
+  const SoCam &C1, &C2;
+  SoSim3& S;    // the estimate (the caller's)
+  SoSim3 St;    // the one of the trial (written by trial, read by accept)
+  bool robust, fix_scale;
+  double delta;
+  RGBL_HD SoModel(const SoCam& c1, const SoCam& c2, SoSim3& estimate, bool robust_kernel, bool fix, double d)
+      : C1(c1), C2(c2), S(estimate), robust(robust_kernel), fix_scale(fix), delta(d) {}
+  template <class Lanes> RGBL_HD void linearise(Lanes& G) {
     const SoSim3* T = G.transforms(S, fix_scale);
     G.zero();
     G.each([&](SoEdge& e, double* acc) { if (!e.gone) so_edge_accumulate(e, C1, C2, T, robust, delta, acc); });
-    const double* Sm = G.reduce_system();
-    currentChi = Sm[35];
-    const double iniChi = currentChi;
-    double tempChi = currentChi;
-    if (it == 0) {                  // computeLambdaInit: _tau = 1e-5
-      double maxDiagonal = 0.0;
-      const int diag[7] = {0, 7, 13, 18, 22, 25, 27};
-      for (int j = 0; j < 7; ++j) { const double a = fabs(Sm[diag[j]]); maxDiagonal = a > maxDiagonal ? a : maxDiagonal; }
-      lambda = 1e-5 * maxDiagonal;
-      ni = 2.0;
-      lmBad = 0;
-    }
-    double rho = 0.0;
-    int qmax = 0;
-    do {
-      const bool ok = so_solve7(Sm, lambda, Sm + 28, x);
-      if (fix_scale) x[6] = 0.0;    // quirk 8: oplusImpl writes the zero into the solver's x
-      const SoSim3 St = so_oplus(x, S, fix_scale);
-      const SoSim3 Sti = so_inverse(St);
-      G.zero();
-      G.each([&](SoEdge& e, double* acc) {
-        if (e.gone) return;
-        so_edge_errors(e, C1, C2, St, Sti);
-        acc[0] = acc[0] + so_rho(e.chi12, robust, delta);
-        acc[0] = acc[0] + so_rho(e.chi21, robust, delta);
-      });
-      tempChi = G.reduce_one();
-      if (!ok) tempChi = DBL_MAX;
-      rho = currentChi - tempChi;
-      double scale = 0.0;           // computeScale
-      for (int j = 0; j < 7; ++j) scale += x[j] * (lambda * x[j] + Sm[28 + j]);
-      scale += 1e-3;
-      rho /= scale;
-      if (rho > 0.0 && tempChi >= -DBL_MAX && tempChi <= DBL_MAX) {
-        const double c = 2.0 * rho - 1.0;
-        double alpha = 1.0 - c * c * c;
-        alpha = (2.0 / 3.0 < alpha) ? 2.0 / 3.0 : alpha;
-        const double scaleFactor = (1.0 / 3.0 < alpha) ? alpha : 1.0 / 3.0;
-        lambda *= scaleFactor;
-        ni = 2.0;
-        currentChi = tempChi;
-        S = St;
-      } else {
-        lambda *= ni;
-        ni *= 2.0;                  // the edges keep the errors of the rejected step (quirk 1)
-      }
-      ++qmax;
-    } while (rho < 0.0 && qmax < kSoTrials);
-    ++iters;
-    if (qmax == kSoTrials || rho == 0.0) break;
-    if ((iniChi - currentChi) * 1e3 < iniChi) ++lmBad; else lmBad = 0;
-    if (lmBad >= 3) break;
   }
-  *iterations = iters;
-  *chi = currentChi;
+  template <class Lanes> RGBL_HD void trial(Lanes& G, double* x) {
+    if (fix_scale) x[6] = 0.0;    // quirk 8: oplusImpl writes the zero into the solver's x
+    St = so_oplus(x, S, fix_scale);
+    const SoSim3 Sti = so_inverse(St);
+    G.zero();
+    G.each([&](SoEdge& e, double* acc) {
+      if (e.gone) return;
+      so_edge_errors(e, C1, C2, St, Sti);
+      acc[0] = acc[0] + so_rho(e.chi12, robust, delta);
+      acc[0] = acc[0] + so_rho(e.chi21, robust, delta);
+    });
+  }
+  RGBL_HD void accept() { S = St; }
+};
+// SparseOptimizer::optimize(max_it) on the 7-dof vertex: S is the estimate on entry and on return.
+template <class Lanes>
+RGBL_HD void so_levenberg(Lanes& G, const SoCam& C1, const SoCam& C2, SoSim3& S, bool robust, double delta, bool fix_scale, int max_it,
+                          double x[7], int* iterations, double* chi) {
+  SoModel M(C1, C2, S, robust, fix_scale, delta);
+  lm_levenberg<7>(G, M, max_it, x, iterations, chi);
 }
 
 // Optimizer.cc:2306-2380.  D's six counters are the caller's (the set-up); n_corr = nCorrespondences.  Returns nIn, or 0;
@@ -449,35 +370,10 @@ RGBL_HD int so_optimize(Lanes& G, const SoCam& C1, const SoCam& C2, const SoSim3
   return nIn;
 }
 
-// The host's execution of the lanes.
-struct SoHostLanes {
-  SoEdge* e;
-  int m;
-  double part[kSoLanes][kSoSums], sys[kSoSums];
+// The host's execution of the lanes: csrc/lm_math.h's, and the transforms.
+struct SoHostLanes : LmHostLanes<SoEdge, kSoSums> {
   SoSim3 T[kSoTransforms];
-  SoHostLanes(SoEdge* edges, int count) : e(edges), m(count) {}
-  void zero() {
-    for (int l = 0; l < kSoLanes; ++l)
-      for (int c = 0; c < kSoSums; ++c) part[l][c] = 0.0;
-  }
-  template <class F> void each(F f) {
-    for (int l = 0; l < kSoLanes; ++l)
-      for (int k = l; k < m; k += kSoLanes) f(e[k], part[l]);
-  }
-  void tree(int count) {
-    for (int s = kSoLanes / 2; s >= 1; s >>= 1)
-      for (int i = 0; i < s; ++i)
-        for (int c = 0; c < count; ++c) part[i][c] = part[i][c] + part[i + s][c];
-  }
-  const double* reduce_system() {
-    tree(kSoSums);
-    for (int c = 0; c < kSoSums; ++c) sys[c] = part[0][c];
-    return sys;
-  }
-  double reduce_one() {
-    tree(1);
-    return part[0][0];
-  }
+  using LmHostLanes::LmHostLanes;
   const SoSim3* transforms(const SoSim3& S, bool fix_scale) {
     T[0] = S;
     T[1] = so_inverse(S);

@@ -28,6 +28,15 @@ def test_every_size_against_the_host_build(gpu_lib, mt, matched, kind):
     pc.check_size(gpu_lib, mt, matched, kind)
 
 
+def test_every_size_gives_the_recorded_bits(mt):
+    """the device against tests/golden/pose_opt/host_bits.json (what the host build gave when it was recorded), not against the
+    host build next to it: a change that moves both together fails here"""
+    import host_bits as hb
+    want = hb.recorded("pose_opt")
+    for name, case, _ in hb.pose_size_cases():
+        assert hb.pose_record(mt.PoseOptimization(case, outlier_fill=hb.FILL)) == want[name], name
+
+
 def test_every_correspondence_an_outlier_after_round_0(gpu_lib, mt):
     pc.check_all_outliers(gpu_lib, mt)
 

@@ -28,6 +28,15 @@ def test_every_size_against_the_host_build(gpu_lib, mt, matched, fix_scale):
     oc.check_size(gpu_lib, mt, matched, fix_scale)
 
 
+def test_every_size_gives_the_recorded_bits(mt):
+    """the device against tests/golden/sim3_opt/host_bits.json (what the host build gave when it was recorded), not against the
+    host build next to it: a change that moves both together fails here"""
+    import host_bits as hb
+    want = hb.recorded("sim3_opt")
+    for name, case, _ in hb.sim3_size_cases():
+        assert hb.sim3_record(mt.OptimizeSim3(case, cleared_fill=hb.FILL)) == want[name], name
+
+
 def test_point_on_and_behind_the_camera_plane(gpu_lib, mt):
     oc.check_degenerate_depth(gpu_lib, mt)
 
