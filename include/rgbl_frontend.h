@@ -1098,6 +1098,83 @@ int rgbl_sim3_ransac_batch(rgbl_matcher* h, int n_problems, const rgbl_sim3_inpu
  * host arrays (pool NULL). */
 int rgbl_sim3_ransac_host(const rgbl_sim3_input* in, rgbl_sim3_output* out);
 
+/* MLPnPsolver (include/MLPnPsolver.h, src/MLPnPsolver.cpp): the RANSAC over 6-point MLPnP solutions that
+ * Tracking::Relocalization runs per candidate key frame (src/Tracking.cc:3690-3717), ALL hypotheses of a call at once, for
+ * pinhole cameras without covariance information (covs(1), use_cov == false).  One call is what one call of
+ * MLPnPsolver::iterate (:100-223) computes: computePose (:356-658) and CheckInliers (:262-293) for every sample, then the loop's
+ * stop rule as a scan over the inlier counts.  Refine (:295-353) is what the reference COMPILES to: it never copies the pose it
+ * computes into mRi / mti, so its CheckInliers sees the current hypothesis again; it succeeds iff that hypothesis has more than
+ * min_inliers inliers, and iterate then returns that hypothesis (csrc/mlpnp_math.h, ml_scan).  The recomputed pose has no
+ * observable effect and is not computed.  Batched, it covers the candidates of one pass of the
+ * loop at Tracking.cc:3703.  csrc/mlpnp_math.h restates the arithmetic and says what is pinned and what is not.  The
+ * constructor's bookkeeping (:55-97) is done here from the frame and the map side; SetRansacParameters (:225-260) and the
+ * drawing of the samples (:128-140) stay with the caller.  N below = the number of features with mp_index >= 0: the
+ * correspondences, in ascending feature index. */
+typedef struct {
+  int n;                       /* vpMapPointMatches.size() = F.N, 0 .. 65535 */
+  const int32_t* mp_index;     /* per feature: index of vpMapPointMatches[i] in the map side below, -1 = none (or isBad) */
+  int n_points;                /* entries of the map side */
+  /* map side, form 1 (pool == NULL): host array */
+  const float* world_pos;      /* pMP->GetWorldPos(), 3 floats per point (:84-86) */
+  /* map side, form 2: slots of a pool on the matcher's device (the call holds the pool's mutex for its duration) */
+  rgbl_map_points* pool;
+  const int32_t* slot;         /* n_points slots in [0, capacity) */
+  /* frame side: host arrays, or the resident frame (the two arrays are then not read) */
+  const float* kp_xy;          /* F.mvKeysUn[i].pt, n x 2 (:72-74) */
+  const int32_t* kp_octave;    /* F.mvKeysUn[i].octave (:75) */
+  const rgbl_device_frame* device;
+  float K[4];                  /* the Pinhole's fx, fy, cx, cy */
+  const float* level_sigma2;   /* F.mvLevelSigma2, n_levels entries */
+  int n_levels;                /* 1 .. 16 */
+  float th2;                   /* SetRansacParameters' th2: mvMaxError[i] = sigma2 * th2 (:259) */
+  int min_inliers;             /* mRansacMinInliers AFTER SetRansacParameters (:237-242), >= 6 */
+  int best_inliers;            /* mnBestInliers on entry (0 for a fresh solver) */
+  const uint8_t* best_mask;    /* mvbBestInliers on entry, N bytes; not read when best_inliers == 0 */
+  float best_Tcw[16];          /* mBestTcw on entry, row-major */
+  int n_hyp;                   /* iterations this call runs unless it succeeds earlier: max(mRansacMaxIts - mnIterations,
+                                  nIterations) (the `||` of :115); 0 .. 2^20 */
+  const int32_t* samples;      /* n_hyp x 6 indices into the correspondences 0 .. N-1 in the order drawn, distinct in a set */
+} rgbl_mlpnp_input;
+typedef struct {
+  int found;                   /* iterate's return value */
+  int no_more;                 /* bNoMore: 1 when the call ran through all n_hyp, or N < min_inliers */
+  int n_inliers;               /* nInliers (0 when not found) */
+  int iterations_run;          /* what mnIterations grows by: k + 1 at a successful Refine, else n_hyp */
+  float Tcw[16];               /* Tout, row-major: hypothesis k's pose in float after a successful Refine (mRefinedTcw as compiled),
+                                  mBestTcw after a run-through, identity when not found */
+  uint8_t* inlier;             /* vbInliers, n bytes per FEATURE (through mvKeyPointIndices); written when found (NULL: not wanted) */
+  int best_inliers;            /* the new mnBestInliers */
+  uint8_t* best_mask;          /* the new mvbBestInliers, N bytes; written when the new best_inliers > 0 (NULL: not wanted) */
+  float best_Tcw[16];          /* the new mBestTcw */
+  int refines;                 /* diagnostics: how often the reference would have called Refine (the qualifying hypotheses up to the stop) */
+  int32_t* counts;             /* optional diagnostics: mnInliersi of every hypothesis, n_hyp entries (NULL: not wanted) */
+  double* Tcw_all;             /* optional diagnostics: [R | t] of every hypothesis in fp64, n_hyp x 12 row-major (NULL: not wanted) */
+  int32_t* gn_path;            /* TEST DIAGNOSTICS, not a stable part of the interface - the encoding may change with the header: per
+                                  hypothesis the Gauss-Newton updates + 8 (left at the break rule), + 16 (the stop rule), + 32 (a failed
+                                  solve or non-finite step), n_hyp entries (NULL: not wanted).  The tests need it to tell which
+                                  hypotheses took the model's path */
+} rgbl_mlpnp_output;
+/* One problem.  Host pointers, synchronous, one upload, two launches on one stream, one read-back.  Valid inputs that compute
+ * nothing, as :106-110 does: N < min_inliers gives no_more = 1, found = 0; n_hyp == 0 gives found = 0, no_more = 0; in both the
+ * state goes from the input to the output unchanged, Tcw is the identity, counts / Tcw_all / gn_path are not written.
+ * RGBL_ERR_INVALID, before anything is launched and with every output untouched: n outside [0, 65535]; n_hyp outside
+ * [0, 2^20]; a sample outside [0, N) or repeated in its set; N < 6 with n_hyp > 0 and N >= min_inliers; min_inliers < 6;
+ * mp_index outside [-1, n_points); a slot outside the pool; a pool or frame on another device than the matcher, or a frame
+ * whose size is not n; an octave outside [0, n_levels) on a feature with a map point (host arrays; a resident frame's octaves
+ * are clamped on the device); n_levels outside 1 .. 16; a K, th2 or sigma2 that is not finite; best_inliers < 0, or > 0 with a
+ * best_mask that is missing or does not hold exactly best_inliers (>= 6) ones; a missing array; more than 2^26 mask words in
+ * the call, i.e. the sum over the problems of n_hyp x ceil(N / 64) (512 MB of device scratch: 2^20 hypotheses of up to 4096
+ * correspondences, or 65535 correspondences with up to 65536 hypotheses - each maximum alone is inside, both at once are not).
+ * Beyond the checks a call can fail with RGBL_ERR_HIP when the device cannot hold its arena; nothing is written then either. */
+int rgbl_mlpnp_ransac(rgbl_matcher* h, const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out);
+/* B independent problems (the candidates of one pass of the loop at Tracking.cc:3703): one upload, one launch pair, one
+ * read-back.  Problems that name a pool must name the same one.  Errors as above, and n_problems outside [0, 32767] (the
+ * problem is a grid dimension): nothing is launched and no problem's output is written. */
+int rgbl_mlpnp_ransac_batch(rgbl_matcher* h, int n_problems, const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out);
+/* rgbl_mlpnp_ransac evaluated by the HOST build of csrc/mlpnp_math.h (no device, no handle): the same bits.  Frame and map
+ * side must be host arrays (device and pool NULL). */
+int rgbl_mlpnp_ransac_host(const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out);
+
 /* int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
  * const bool bFixScale, Eigen::Matrix<double,7,7>& mAcumHessian, const bool bAllPoints) (include/Optimizer.h,
  * src/Optimizer.cc:2115-2381): the 7-dof refinement LoopClosing runs per candidate (src/LoopClosing.cc:556, :767), one

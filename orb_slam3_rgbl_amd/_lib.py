@@ -103,6 +103,22 @@ class Sim3Output(C.Structure):
                 ("inlier", C.c_void_p), ("counts", C.c_void_p), ("T12_all", C.c_void_p)]
 
 
+class MlpnpInput(C.Structure):
+    """rgbl_mlpnp_input (one MLPnPsolver problem: the frame, the map points, the state of earlier calls and the drawn samples)."""
+    _fields_ = [("n", C.c_int), ("mp_index", C.c_void_p), ("n_points", C.c_int), ("world_pos", C.c_void_p), ("pool", C.c_void_p),
+                ("slot", C.c_void_p), ("kp_xy", C.c_void_p), ("kp_octave", C.c_void_p), ("device", C.c_void_p),
+                ("K", C.c_float * 4), ("level_sigma2", C.c_void_p), ("n_levels", C.c_int), ("th2", C.c_float),
+                ("min_inliers", C.c_int), ("best_inliers", C.c_int), ("best_mask", C.c_void_p), ("best_Tcw", C.c_float * 16),
+                ("n_hyp", C.c_int), ("samples", C.c_void_p)]
+
+
+class MlpnpOutput(C.Structure):
+    _fields_ = [("found", C.c_int), ("no_more", C.c_int), ("n_inliers", C.c_int), ("iterations_run", C.c_int),
+                ("Tcw", C.c_float * 16), ("inlier", C.c_void_p), ("best_inliers", C.c_int), ("best_mask", C.c_void_p),
+                ("best_Tcw", C.c_float * 16), ("refines", C.c_int), ("counts", C.c_void_p), ("Tcw_all", C.c_void_p),
+                ("gn_path", C.c_void_p)]
+
+
 class Sim3OptInput(C.Structure):
     """rgbl_sim3_opt_input (two key frames, the matches and the entry estimate as Optimizer::OptimizeSim3 reads them)."""
     _fields_ = [("n", C.c_int), ("mp1_index", C.c_void_p), ("match_index", C.c_void_p), ("i2", C.c_void_p),
@@ -362,6 +378,9 @@ SYMBOLS = {
     "rgbl_sim3_ransac": (_I, [_V, C.POINTER(Sim3Input), C.POINTER(Sim3Output)]),
     "rgbl_sim3_ransac_batch": (_I, [_V, _I, _V, _V]),
     "rgbl_sim3_ransac_host": (_I, [C.POINTER(Sim3Input), C.POINTER(Sim3Output)]),
+    "rgbl_mlpnp_ransac": (_I, [_V, C.POINTER(MlpnpInput), C.POINTER(MlpnpOutput)]),
+    "rgbl_mlpnp_ransac_batch": (_I, [_V, _I, _V, _V]),
+    "rgbl_mlpnp_ransac_host": (_I, [C.POINTER(MlpnpInput), C.POINTER(MlpnpOutput)]),
     "rgbl_optimize_sim3": (_I, [_V, C.POINTER(Sim3OptInput), C.POINTER(Sim3OptOutput)]),
     "rgbl_optimize_sim3_batch": (_I, [_V, _I, _V, _V]),
     "rgbl_optimize_sim3_host": (_I, [C.POINTER(Sim3OptInput), C.POINTER(Sim3OptOutput)]),

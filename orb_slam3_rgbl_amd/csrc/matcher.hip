@@ -27,6 +27,7 @@
 #include "common.h"
 #include "frustum_math.h"
 #include "logf_glibc.h"
+#include "mlpnp_math.h"
 #include "newpoint_math.h"
 #include "poseopt_math.h"
 #include "sim3_math.h"
@@ -1346,6 +1347,108 @@ __global__ __launch_bounds__(256) void k_sim3_select(Sim3Dev D) {
   if (sel.selected >= 0) {
     const unsigned long long* mask = D.mask + (size_t)pb.word_off + (size_t)sel.selected * (size_t)pb.words;
     for (int i = tid; i < pb.n; i += 256) D.inlier[(size_t)pb.inl_off + i] = (uint8_t)((mask[i >> 6] >> (i & 63)) & 1ull);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// MLPnPsolver (src/MLPnPsolver.cpp): every RANSAC hypothesis of a call at once.  The arithmetic is csrc/mlpnp_math.h.
+//   k_mlpnp_hypotheses  grid (groups of 4 hypotheses, problem), 256 work-items: one wave per hypothesis, no workgroup barrier.
+//                       The wave runs the six-point computePose together (MlWaveX): the rows of A, the 12 x 12 matrix, its
+//                       eigenvectors and the rows of J live in the wave's MlWork in LDS; a lane owns a correspondence, an
+//                       entry of a sum, or a (row, rotation pair) of a Jacobi step; the 3 x 3 algebra and the 6 x 6 solve are
+//                       wave-uniform.  Then CheckInliers over all N: a chunk's count is a ballot and a population count, the
+//                       ballot word the chunk's part of the bit mask.
+//   k_mlpnp_select      one workgroup per problem: ml_scan over the counts - the loop of iterate with Refine as the reference
+//                       compiles it, which returns the current hypothesis (csrc/mlpnp_math.h) -, run identically by every
+//                       work-item; then all work-items expand the masks of the returned hypothesis and of the record into bytes.
+// Both run on the call's stream, one behind the other; no atomics, no workgroup waits for another.  Every loop is bounded.
+constexpr int kMlHypPerGroup = 4;
+struct MlpnpProblem {
+  MlView v;
+  const int32_t* samples;
+  const unsigned long long* best_mask;   // the carried-in mask as bit words (null: none)
+  int n_hyp;                              // 0: the problem is not run
+  int min_inliers, best_inliers;
+  int hyp_off, word_off, words, corr_off, cword_off;
+  float best_Tcw[16];
+};
+struct MlpnpHypOut {
+  double T[12];   // R row-major, t
+  int32_t count, path;
+};
+struct MlpnpResult {
+  MlScan scan;
+  float Tcw[16], best_Tcw[16];
+};
+struct MlpnpDev {
+  const MlpnpProblem* prob;
+  MlpnpHypOut* hyp;
+  unsigned long long* mask;     // per hypothesis `words` 64-bit words
+  MlpnpResult* res;
+  uint8_t* inlier;              // per correspondence: the flags of the returned solution
+  uint8_t* best_out;            // per correspondence: the new mvbBestInliers
+};
+
+struct MlWaveX {
+  int lane, lanes;
+  __device__ void sync() { wave_sync(); }
+  __device__ bool all(bool p) { return __ballot(!p) == 0ull; }
+};
+__global__ __launch_bounds__(256) void k_mlpnp_hypotheses(MlpnpDev D) {
+  __shared__ MlWork s_work[kMlHypPerGroup];
+  const MlpnpProblem& pb = D.prob[blockIdx.y];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = (int)blockIdx.x * kMlHypPerGroup + wave;
+  if (h >= pb.n_hyp) return;   // a whole wave; the kernel has no workgroup barrier
+  MlWaveX x = {lane, 64};
+  MlSixSums Q;
+  const MlSet S = {&pb.v, pb.samples + 6 * (size_t)h, 6};   // checked by the host: inside [0, N), distinct
+  double R[9], t[3];
+  int path;
+  ml_compute_pose(x, s_work[wave], Q, S, R, t, &path);
+  unsigned long long* mask = D.mask + (size_t)pb.word_off + (size_t)h * (size_t)pb.words;
+  int count = 0;
+  for (int c = 0; c < pb.words; ++c) {   // wave-uniform
+    const int i = c * 64 + lane;
+    const bool in = i < pb.v.N && ml_is_inlier(pb.v, R, t, i);
+    const unsigned long long w = __ballot(in);
+    count += __popcll(w);
+    if (lane == 0) mask[c] = w;
+  }
+  if (lane == 0) {
+    MlpnpHypOut& o = D.hyp[(size_t)pb.hyp_off + (size_t)h];
+    for (int k = 0; k < 9; ++k) o.T[k] = R[k];
+    for (int k = 0; k < 3; ++k) o.T[9 + k] = t[k];
+    o.count = count;
+    o.path = path;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mlpnp_select(MlpnpDev D) {
+  const MlpnpProblem& pb = D.prob[blockIdx.x];
+  if (pb.n_hyp == 0) return;   // the whole workgroup
+  const int tid = (int)threadIdx.x, N = pb.v.N, words = pb.words;
+  const MlpnpHypOut* hyp = D.hyp + (size_t)pb.hyp_off;
+  const unsigned long long* masks = D.mask + (size_t)pb.word_off;
+  struct Counts {   // c[k] of ml_scan
+    const MlpnpHypOut* h;
+    __device__ int operator[](int k) const { return h[k].count; }
+  };
+  const MlScan sc = ml_scan(Counts{hyp}, pb.n_hyp, pb.min_inliers, pb.best_inliers);   // wave-uniform loads, the same in every work-item
+  // mvbBestInliers: the record's mask, or the one carried in; what iterate hands out: the stopping hypothesis's, or the best
+  const unsigned long long* bm = sc.record >= 0 ? masks + (size_t)sc.record * (size_t)words : (pb.best_inliers > 0 ? pb.best_mask : nullptr);
+  const unsigned long long* om = sc.selected >= 0 ? masks + (size_t)sc.selected * (size_t)words : bm;
+  for (int i = tid; i < N; i += 256) {
+    if (bm) D.best_out[(size_t)pb.corr_off + i] = (uint8_t)((bm[i >> 6] >> (i & 63)) & 1ull);
+    if (sc.found) D.inlier[(size_t)pb.corr_off + i] = (uint8_t)((om[i >> 6] >> (i & 63)) & 1ull);
+  }
+  if (tid == 0) {
+    MlpnpResult& r = D.res[blockIdx.x];
+    r.scan = sc;
+    if (sc.record >= 0) ml_Tcw(hyp[sc.record].T, hyp[sc.record].T + 9, r.best_Tcw);
+    else for (int k = 0; k < 16; ++k) r.best_Tcw[k] = pb.best_Tcw[k];
+    if (sc.selected >= 0) ml_Tcw(hyp[sc.selected].T, hyp[sc.selected].T + 9, r.Tcw);
+    else for (int k = 0; k < 16; ++k) r.Tcw[k] = r.best_Tcw[k];
   }
 }
 
@@ -4774,6 +4877,267 @@ int rgbl_sim3_ransac_batch(rgbl_matcher* m, int n_problems, const rgbl_sim3_inpu
 int rgbl_sim3_ransac(rgbl_matcher* m, const rgbl_sim3_input* in, rgbl_sim3_output* out) {
   if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
   return rgbl_sim3_ransac_batch(m, 1, in, out);
+}
+
+// ---- MLPnPsolver (src/MLPnPsolver.cpp) ------------------------------------------------------------------------------------
+namespace {
+constexpr int kMlMaxHyp = 1 << 20;
+constexpr int kMlMaxMaskWordsLog2 = 26;   // 512 MB of masks: 2^20 hypotheses of 4096 correspondences, or 65535 correspondences of 65536 hypotheses
+constexpr size_t kMlMaxMaskWords = (size_t)1 << kMlMaxMaskWordsLog2;
+// Everything that can be refused without the pool is refused here, before anything is staged, launched or written.  *n_corr = N.
+int check_mlpnp_input(const rgbl_mlpnp_input* in, int b, bool host_only, int* n_corr) {
+  *n_corr = 0;
+  if (in->n < 0 || in->n > 65535 || in->n_hyp < 0 || in->n_hyp > kMlMaxHyp) { set_error("mlpnp %d: n outside [0, 65535] or n_hyp outside [0, %d]", b, kMlMaxHyp); return RGBL_ERR_INVALID; }
+  if (in->n_points < 0 || (in->n > 0 && !in->mp_index)) { set_error("mlpnp %d: n_points < 0 or no mp_index", b); return RGBL_ERR_INVALID; }
+  if (in->min_inliers < 6) { set_error("mlpnp %d: min_inliers %d < 6, the minimal set", b, in->min_inliers); return RGBL_ERR_INVALID; }
+  if (in->n_levels < 1 || in->n_levels > kProjMaxLevels || !in->level_sigma2) { set_error("mlpnp %d: n_levels outside [1, %d] or no level_sigma2", b, kProjMaxLevels); return RGBL_ERR_INVALID; }
+  bool finite = std::isfinite(in->th2);
+  for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(in->K[i]);
+  for (int i = 0; i < in->n_levels; ++i) finite = finite && std::isfinite(in->level_sigma2[i]);
+  if (!finite) { set_error("mlpnp %d: K, th2 or a sigma2 is not finite", b); return RGBL_ERR_INVALID; }
+  if (host_only && (in->device || in->pool)) { set_error("mlpnp %d: the host build reads host arrays only", b); return RGBL_ERR_INVALID; }
+  if (in->device ? in->device->n != in->n : (in->n > 0 && (!in->kp_xy || !in->kp_octave))) {
+    set_error("mlpnp %d: the frame side is either kp_xy, kp_octave or a resident frame of n features", b);
+    return RGBL_ERR_INVALID;
+  }
+  if (in->n_points > 0 && (in->pool ? !in->slot : !in->world_pos)) { set_error("mlpnp %d: the map side is either world_pos or a pool with slot", b); return RGBL_ERR_INVALID; }
+  int N = 0;
+  for (int i = 0; i < in->n; ++i) {
+    const int p = in->mp_index[i];
+    if (p < -1 || p >= in->n_points) { set_error("mlpnp %d: mp_index[%d] = %d outside [-1, %d)", b, i, p, in->n_points); return RGBL_ERR_INVALID; }
+    if (p < 0) continue;
+    ++N;
+    if (!in->device && (in->kp_octave[i] < 0 || in->kp_octave[i] >= in->n_levels)) { set_error("mlpnp %d: octave %d of feature %d outside [0, %d)", b, in->kp_octave[i], i, in->n_levels); return RGBL_ERR_INVALID; }
+  }
+  if (in->best_inliers < 0) { set_error("mlpnp %d: best_inliers < 0", b); return RGBL_ERR_INVALID; }
+  if (in->best_inliers > 0) {
+    int ones = 0;
+    for (int i = 0; in->best_mask && i < N; ++i) ones += in->best_mask[i] ? 1 : 0;
+    if (!in->best_mask || ones != in->best_inliers || ones < 6) { set_error("mlpnp %d: best_inliers = %d needs a best_mask with as many (>= 6) ones", b, in->best_inliers); return RGBL_ERR_INVALID; }
+  }
+  if (N >= in->min_inliers && in->n_hyp > 0) {
+    if (N < 6) { set_error("mlpnp %d: %d correspondences, a sample needs 6", b, N); return RGBL_ERR_INVALID; }
+    if (!in->samples) { set_error("mlpnp %d: no samples", b); return RGBL_ERR_INVALID; }
+    for (int k = 0; k < in->n_hyp; ++k) {
+      const int32_t* s = in->samples + 6 * (size_t)k;
+      bool ok = true;
+      for (int i = 0; i < 6; ++i) {
+        ok = ok && s[i] >= 0 && s[i] < N;
+        for (int j = 0; j < i; ++j) ok = ok && s[i] != s[j];
+      }
+      if (!ok) { set_error("mlpnp %d: sample %d = (%d, %d, %d, %d, %d, %d) is not six distinct indices in [0, %d)", b, k, s[0], s[1], s[2], s[3], s[4], s[5], N); return RGBL_ERR_INVALID; }
+    }
+  }
+  *n_corr = N;
+  return RGBL_OK;
+}
+// a problem the reference leaves at once (:106-110), or that has nothing to run
+inline bool mlpnp_skipped(const rgbl_mlpnp_input* in, int N) { return N < in->min_inliers || in->n_hyp == 0; }
+void write_mlpnp_skipped(const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out, int N) {
+  out->found = 0; out->no_more = N < in->min_inliers ? 1 : 0; out->n_inliers = 0; out->iterations_run = 0; out->refines = 0;
+  for (int k = 0; k < 16; ++k) out->Tcw[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+  out->best_inliers = in->best_inliers;
+  memcpy(out->best_Tcw, in->best_Tcw, sizeof(out->best_Tcw));
+  if (out->best_mask && in->best_inliers > 0) memcpy(out->best_mask, in->best_mask, (size_t)N);
+}
+// inlier / best: per correspondence
+void write_mlpnp_output(const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out, int N, const MlpnpResult& r, const uint8_t* inlier, const uint8_t* best,
+                        const MlpnpHypOut* hyp) {
+  const MlScan& sc = r.scan;
+  out->found = sc.found; out->no_more = sc.no_more; out->n_inliers = sc.n_inliers; out->iterations_run = sc.iterations; out->refines = sc.refines;
+  if (sc.found) memcpy(out->Tcw, r.Tcw, sizeof(out->Tcw));
+  else for (int k = 0; k < 16; ++k) out->Tcw[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+  if (sc.found && out->inlier) {
+    memset(out->inlier, 0, (size_t)in->n);
+    int k = 0;
+    for (int i = 0; i < in->n; ++i)
+      if (in->mp_index[i] >= 0) out->inlier[i] = inlier[k++];
+  }
+  out->best_inliers = sc.best;
+  memcpy(out->best_Tcw, r.best_Tcw, sizeof(out->best_Tcw));
+  if (out->best_mask && sc.best > 0) memcpy(out->best_mask, best, (size_t)N);
+  for (int k = 0; hyp && k < in->n_hyp; ++k) {
+    if (out->counts) out->counts[k] = hyp[k].count;
+    if (out->gn_path) out->gn_path[k] = hyp[k].path;
+    if (out->Tcw_all) {
+      double* T = out->Tcw_all + 12 * (size_t)k;
+      for (int i = 0; i < 3; ++i) { T[4 * i] = hyp[k].T[3 * i]; T[4 * i + 1] = hyp[k].T[3 * i + 1]; T[4 * i + 2] = hyp[k].T[3 * i + 2]; T[4 * i + 3] = hyp[k].T[9 + i]; }
+    }
+  }
+}
+// the correspondences of a problem: feature and row of the map side
+void mlpnp_correspondences(const rgbl_mlpnp_input* in, int32_t* feat, int32_t* point) {
+  int k = 0;
+  for (int i = 0; i < in->n; ++i) {
+    const int p = in->mp_index[i];
+    if (p < 0) continue;
+    feat[k] = i;
+    point[k] = in->pool ? in->slot[p] : p;
+    ++k;
+  }
+}
+void mlpnp_mask_words(const uint8_t* bytes, int N, unsigned long long* words) {
+  for (int w = 0; w < (N + 63) / 64; ++w) words[w] = 0;
+  for (int i = 0; i < N; ++i)
+    if (bytes[i]) words[i >> 6] |= 1ull << (i & 63);
+}
+}  // namespace
+
+int rgbl_mlpnp_ransac_host(const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out) {
+  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  int N = 0;
+  RGBL_TRY(check_mlpnp_input(in, 0, true, &N));
+  if (mlpnp_skipped(in, N)) { write_mlpnp_skipped(in, out, N); return RGBL_OK; }
+  const int words = (N + 63) / 64;
+  std::vector<int32_t> feat((size_t)N), point((size_t)N);
+  mlpnp_correspondences(in, feat.data(), point.data());
+  MlView v;
+  v.xy = in->kp_xy; v.oct = in->kp_octave; v.wpos = in->world_pos; v.sigma2 = in->level_sigma2; v.feat = feat.data(); v.point = point.data();
+  v.N = N; v.n_levels = in->n_levels; v.th2 = in->th2;
+  memcpy(v.K, in->K, sizeof(v.K));
+  std::vector<MlpnpHypOut> hyp((size_t)in->n_hyp);
+  std::vector<unsigned long long> mask((size_t)in->n_hyp * (size_t)words, 0ull), carried((size_t)words, 0ull);
+  if (in->best_inliers > 0) mlpnp_mask_words(in->best_mask, N, carried.data());
+  std::vector<MlWork> work(1);
+  MlHostX x;
+  auto check = [&](const double* R, const double* t, unsigned long long* m) {
+    int count = 0;
+    for (int w = 0; w < words; ++w) m[w] = 0ull;
+    for (int i = 0; i < N; ++i)
+      if (ml_is_inlier(v, R, t, i)) { m[i >> 6] |= 1ull << (i & 63); ++count; }
+    return count;
+  };
+  for (int h = 0; h < in->n_hyp; ++h) {
+    MlSixSums Q;
+    const MlSet S = {&v, in->samples + 6 * (size_t)h, 6};
+    MlpnpHypOut& o = hyp[(size_t)h];
+    ml_compute_pose(x, work[0], Q, S, o.T, o.T + 9, &o.path);
+    o.count = check(o.T, o.T + 9, mask.data() + (size_t)h * (size_t)words);
+  }
+  struct Counts {
+    const MlpnpHypOut* h;
+    int operator[](int k) const { return h[k].count; }
+  };
+  MlpnpResult r;
+  memset(&r, 0, sizeof(r));
+  r.scan = ml_scan(Counts{hyp.data()}, in->n_hyp, in->min_inliers, in->best_inliers);
+  const MlScan& sc = r.scan;
+  if (sc.record >= 0) ml_Tcw(hyp[(size_t)sc.record].T, hyp[(size_t)sc.record].T + 9, r.best_Tcw);
+  else memcpy(r.best_Tcw, in->best_Tcw, sizeof(r.best_Tcw));
+  if (sc.selected >= 0) ml_Tcw(hyp[(size_t)sc.selected].T, hyp[(size_t)sc.selected].T + 9, r.Tcw);
+  else memcpy(r.Tcw, r.best_Tcw, sizeof(r.Tcw));
+  std::vector<uint8_t> inl((size_t)N, 0), best((size_t)N, 0);
+  const unsigned long long* bm = sc.record >= 0 ? mask.data() + (size_t)sc.record * (size_t)words : carried.data();
+  const unsigned long long* om = sc.selected >= 0 ? mask.data() + (size_t)sc.selected * (size_t)words : bm;
+  for (int i = 0; i < N; ++i) {
+    best[(size_t)i] = (uint8_t)((bm[i >> 6] >> (i & 63)) & 1ull);
+    inl[(size_t)i] = (uint8_t)((om[i >> 6] >> (i & 63)) & 1ull);
+  }
+  write_mlpnp_output(in, out, N, r, inl.data(), best.data(), hyp.data());
+  return RGBL_OK;
+}
+
+int rgbl_mlpnp_ransac_batch(rgbl_matcher* m, int n_problems, const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out) {
+  if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  const int B = n_problems;
+  if (B > 32767) { set_error("mlpnp: more than 32767 problems in one call"); return RGBL_ERR_INVALID; }
+  PoolCall pc(m, "mlpnp", "the frame");
+  // offsets of the problems that run: hypotheses, mask words, correspondences, words of the carried-in mask
+  std::vector<int> Ns((size_t)B, 0), hyp_off((size_t)B + 1, 0), corr_off((size_t)B + 1, 0), cword_off((size_t)B + 1, 0);
+  std::vector<size_t> word_off((size_t)B + 1, 0);
+  int max_hyp = 0;
+  for (int b = 0; b < B; ++b) {
+    RGBL_TRY(check_mlpnp_input(in + b, b, false, &Ns[(size_t)b]));
+    RGBL_TRY(pc.note(in[b].pool, {in[b].device}, b));
+    const bool run = !mlpnp_skipped(in + b, Ns[(size_t)b]);
+    const int nh = run ? in[b].n_hyp : 0, nn = run ? Ns[(size_t)b] : 0;
+    if (hyp_off[(size_t)b] > INT_MAX - nh) { set_error("mlpnp: more than 2^31 hypotheses in one call"); return RGBL_ERR_INVALID; }
+    hyp_off[(size_t)b + 1] = hyp_off[(size_t)b] + nh;
+    corr_off[(size_t)b + 1] = corr_off[(size_t)b] + nn;   // at most 65535 each: B < 2^15 problems fit an int
+    cword_off[(size_t)b + 1] = cword_off[(size_t)b] + (nn + 63) / 64;
+    word_off[(size_t)b + 1] = word_off[(size_t)b] + (size_t)nh * (size_t)((nn + 63) / 64);
+    max_hyp = std::max(max_hyp, nh);
+  }
+  if (word_off[(size_t)B] > (size_t)kMlMaxMaskWords) { set_error("mlpnp: more than 2^%d mask words (n_hyp x ceil(N / 64), all problems) in one call", kMlMaxMaskWordsLog2); return RGBL_ERR_INVALID; }
+  const rgbl_map_points* pool = pc.pool;
+  RGBL_TRY(pc.lock(B, [&](int b) -> int {
+    for (int i = 0; in[b].pool && i < in[b].n_points; ++i)
+      if (!pc.holds(in[b].slot[i])) { set_error("mlpnp %d: slot %d outside [0, %d)", b, in[b].slot[i], pool->cap); return RGBL_ERR_INVALID; }
+    return RGBL_OK;
+  }));
+  const int H = hyp_off[(size_t)B], M = corr_off[(size_t)B];
+  if (H == 0) {   // nothing to run (B == 0 included)
+    for (int b = 0; b < B; ++b) write_mlpnp_skipped(in + b, out + b, Ns[(size_t)b]);
+    return RGBL_OK;
+  }
+  std::vector<int32_t> feat((size_t)M), point((size_t)M);
+  std::vector<unsigned long long> carried((size_t)cword_off[(size_t)B], 0ull);
+  for (int b = 0; b < B; ++b) {
+    if (corr_off[(size_t)b + 1] == corr_off[(size_t)b]) continue;
+    mlpnp_correspondences(in + b, feat.data() + corr_off[(size_t)b], point.data() + corr_off[(size_t)b]);
+    if (in[b].best_inliers > 0) mlpnp_mask_words(in[b].best_mask, Ns[(size_t)b], carried.data() + cword_off[(size_t)b]);
+  }
+  RGBL_HIP(hipSetDevice(m->device));
+  StreamDrain drain(m->stream);  // behind pc (PoolCall)
+  HostCall hc(m);
+  hipStream_t s = hc.s;
+  std::vector<MlpnpProblem> prob((size_t)B);
+  MlpnpDev D;
+  memset(&D, 0, sizeof(D));
+  bool diag = false;
+  for (int b = 0; b < B; ++b) diag = diag || out[b].counts || out[b].Tcw_all || out[b].gn_path;
+  RGBL_TRY(hc.begin([&]() -> int {
+    const int32_t *d_feat = nullptr, *d_point = nullptr;
+    const unsigned long long* d_carried = nullptr;
+    hc.put(&d_feat, feat.data(), (size_t)M);
+    hc.put(&d_point, point.data(), (size_t)M);
+    hc.put(&d_carried, carried.data(), carried.size());
+    for (int b = 0; b < B; ++b) {
+      MlpnpProblem& P = prob[(size_t)b];
+      memset(&P, 0, sizeof(P));
+      const rgbl_mlpnp_input& I = in[b];
+      if (mlpnp_skipped(&I, Ns[(size_t)b])) continue;   // n_hyp = 0: no workgroup touches it
+      RGBL_TRY(put_features(hc, I.device, I.n, nullptr, I.kp_xy, I.kp_octave, nullptr, nullptr, &P.v.xy, &P.v.oct, nullptr));
+      if (I.pool) P.v.wpos = pool->d_wpos; else hc.put(&P.v.wpos, I.world_pos, (size_t)I.n_points * 3);
+      hc.put(&P.v.sigma2, I.level_sigma2, (size_t)I.n_levels);
+      hc.put(&P.samples, I.samples, (size_t)I.n_hyp * 6);
+      P.v.feat = d_feat + corr_off[(size_t)b]; P.v.point = d_point + corr_off[(size_t)b];
+      P.v.N = Ns[(size_t)b]; P.v.n_levels = I.n_levels; P.v.th2 = I.th2;
+      memcpy(P.v.K, I.K, sizeof(P.v.K));
+      P.best_mask = I.best_inliers > 0 ? d_carried + cword_off[(size_t)b] : nullptr;
+      P.n_hyp = I.n_hyp; P.min_inliers = I.min_inliers; P.best_inliers = I.best_inliers;
+      P.hyp_off = hyp_off[(size_t)b]; P.word_off = (int)word_off[(size_t)b]; P.words = (Ns[(size_t)b] + 63) / 64;
+      P.corr_off = corr_off[(size_t)b]; P.cword_off = cword_off[(size_t)b];
+      memcpy(P.best_Tcw, I.best_Tcw, sizeof(P.best_Tcw));
+    }
+    D.prob = hc.stage<MlpnpProblem>((size_t)B, [&](MlpnpProblem* dst) { memcpy(dst, prob.data(), sizeof(MlpnpProblem) * (size_t)B); });
+    D.res = hc.result<MlpnpResult>((size_t)B);   // what comes back, side by side
+    D.inlier = hc.result<uint8_t>((size_t)M);
+    D.best_out = hc.result<uint8_t>((size_t)M);
+    D.hyp = diag ? hc.result<MlpnpHypOut>((size_t)H) : hc.scratch<MlpnpHypOut>((size_t)H);
+    D.mask = hc.scratch<unsigned long long>(word_off[(size_t)B]);
+    return RGBL_OK;
+  }));
+  m->timer.begin("k_mlpnp_hypotheses", s);
+  hipLaunchKernelGGL(k_mlpnp_hypotheses, dim3((unsigned)((max_hyp + kMlHypPerGroup - 1) / kMlHypPerGroup), (unsigned)B), dim3(256), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  m->timer.begin("k_mlpnp_select", s);
+  hipLaunchKernelGGL(k_mlpnp_select, dim3((unsigned)B), dim3(256), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(hc.fetch());
+  for (int b = 0; b < B; ++b) {
+    if (mlpnp_skipped(in + b, Ns[(size_t)b])) { write_mlpnp_skipped(in + b, out + b, Ns[(size_t)b]); continue; }
+    write_mlpnp_output(in + b, out + b, Ns[(size_t)b], hc.host(D.res)[b], hc.host(D.inlier) + corr_off[(size_t)b], hc.host(D.best_out) + corr_off[(size_t)b],
+                       diag ? hc.host(D.hyp) + hyp_off[(size_t)b] : nullptr);
+  }
+  return RGBL_OK;
+}
+
+int rgbl_mlpnp_ransac(rgbl_matcher* m, const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out) {
+  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  return rgbl_mlpnp_ransac_batch(m, 1, in, out);
 }
 
 // ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:2115-2381) --------------------------------------------------------------

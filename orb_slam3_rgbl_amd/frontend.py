@@ -1348,6 +1348,109 @@ class ORBmatcher:
         return self._sim3_result(O, bufs)
 
     @staticmethod
+    def _mlpnp_input(pr, keep, out=None):
+        """rgbl_mlpnp_input of a problem dict: mp_index (per feature, -1 = none), world_pos (points x 3) or pool (MapPointPool) +
+        slot, xy / octave or device (DeviceFrame), K (fx fy cx cy), level_sigma2, th2, min_inliers (after SetRansacParameters),
+        best_inliers / best_mask (N bytes) / best_Tcw (the state of earlier calls; default: a fresh solver), samples (n_hyp x 6)."""
+        P = out if out is not None else L.MlpnpInput()
+
+        def arr(key, dt):
+            if pr.get(key) is None:
+                return None
+            keep.append(np.ascontiguousarray(pr[key], dt))
+            return keep[-1].ctypes.data
+        P.mp_index = arr("mp_index", np.int32)
+        P.n = int(pr["n"]) if pr.get("n") is not None else len(np.asarray(pr["mp_index"]).reshape(-1))
+        pool = pr.get("pool")
+        P.pool = pool.h if pool is not None else None
+        P.world_pos, P.slot = arr("world_pos", np.float32), arr("slot", np.int32)
+        P.n_points = int(pr["n_points"]) if pr.get("n_points") is not None else (
+            len(pr["slot"]) if pool is not None else len(np.asarray(pr["world_pos"]).reshape(-1, 3)))
+        P.kp_xy, P.kp_octave = arr("xy", np.float32), arr("octave", np.int32)
+        P.device = _dev(pr, "device")
+        K = np.asarray(pr["K"], np.float32).reshape(-1)
+        for i in range(4):
+            P.K[i] = K[i]
+        P.level_sigma2 = arr("level_sigma2", np.float32)
+        P.n_levels = int(pr["n_levels"]) if pr.get("n_levels") is not None else len(pr["level_sigma2"])
+        P.th2 = np.float32(pr["th2"])
+        P.min_inliers, P.best_inliers = int(pr["min_inliers"]), int(pr.get("best_inliers", 0))
+        P.best_mask = arr("best_mask", np.uint8)
+        T = np.asarray(pr["best_Tcw"] if pr.get("best_Tcw") is not None else np.eye(4), np.float32).reshape(-1)
+        for i in range(16):
+            P.best_Tcw[i] = T[i]
+        P.samples = arr("samples", np.int32)
+        P.n_hyp = int(pr["n_hyp"]) if pr.get("n_hyp") is not None else (0 if pr.get("samples") is None else len(np.asarray(pr["samples"]).reshape(-1, 6)))
+        return P
+
+    @staticmethod
+    def _mlpnp_buffers(I, O, fill=0, diag=True):
+        """the caller's arrays of one rgbl_mlpnp_output, pre-filled with `fill` so that what a call leaves untouched can be seen"""
+        nh = max(I.n_hyp, 0)
+        inl, best = np.full(max(I.n, 0), fill, np.uint8), np.full(max(I.n, 0), fill, np.uint8)
+        counts = np.full(nh, fill, np.int32) if diag else None
+        T_all = np.full((nh, 3, 4), fill, np.float64) if diag else None
+        path = np.full(nh, fill, np.int32) if diag else None
+        O.inlier, O.best_mask = inl.ctypes.data, best.ctypes.data
+        O.counts = counts.ctypes.data if diag else None
+        O.Tcw_all = T_all.ctypes.data if diag else None
+        O.gn_path = path.ctypes.data if diag else None
+        return inl, best, counts, T_all, path
+
+    @staticmethod
+    def _mlpnp_result(O, bufs):
+        inl, best, counts, T_all, path = bufs
+        return dict(found=int(O.found), no_more=int(O.no_more), n_inliers=int(O.n_inliers), iterations_run=int(O.iterations_run),
+                    Tcw=np.array(O.Tcw, np.float32).reshape(4, 4), inlier=inl, best_inliers=int(O.best_inliers), best_mask=best,
+                    best_Tcw=np.array(O.best_Tcw, np.float32).reshape(4, 4), refines=int(O.refines), counts=counts, Tcw_all=T_all,
+                    gn_path=path)
+
+    def prepare_MLPnPRansacBatch(self, problems, host=False, diag=True, fill=0):
+        """MLPnPsolver::iterate (MLPnPsolver.cpp:100-223) for every problem dict in one upload, one launch pair and one read-back;
+        the call returns one dict per problem: found, no_more, n_inliers, iterations_run, Tcw (4 x 4), inlier (n bytes per
+        feature, written when found), the new state best_inliers / best_mask (the first N of its n bytes, per correspondence) /
+        best_Tcw, refines and, with diag, counts (n_hyp), Tcw_all (n_hyp x 3 x 4, fp64) and gn_path (n_hyp)."""
+        keep = []
+        B = len(problems)
+        I, O = (L.MlpnpInput * max(B, 1))(), (L.MlpnpOutput * max(B, 1))()
+        bufs = []
+        for b, pr in enumerate(problems):
+            self._mlpnp_input(pr, keep, I[b])
+            bufs.append(self._mlpnp_buffers(I[b], O[b], fill, diag))
+        lib, h = self.lib, self.h
+
+        def call(_keep=keep):
+            if host:
+                for b in range(B):
+                    L.check(lib, lib.rgbl_mlpnp_ransac_host(C.byref(I[b]), C.byref(O[b])))
+            else:
+                L.check(lib, lib.rgbl_mlpnp_ransac_batch(h, B, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)))
+            return [self._mlpnp_result(O[b], bufs[b]) for b in range(B)]
+
+        def c_call(_keep=keep):   # the C call alone (what tools/mlpnp_bench.py times): the results stay in the structs
+            L.check(lib, lib.rgbl_mlpnp_ransac_batch(h, B, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)))
+
+        def c_call_host(_keep=keep):
+            for b in range(B):
+                L.check(lib, lib.rgbl_mlpnp_ransac_host(C.byref(I[b]), C.byref(O[b])))
+        call.c_call, call.c_call_host = c_call, c_call_host
+        return call
+
+    def MLPnPRansacBatch(self, problems, host=False, diag=True, fill=0):
+        return self.prepare_MLPnPRansacBatch(problems, host, diag, fill)()
+
+    def MLPnPRansac(self, problem, host=False, diag=True, fill=0):
+        """One problem through rgbl_mlpnp_ransac (host=True: rgbl_mlpnp_ransac_host, the header's host build)."""
+        keep = []
+        I, O = self._mlpnp_input(problem, keep), L.MlpnpOutput()
+        bufs = self._mlpnp_buffers(I, O, fill, diag)
+        if host:
+            L.check(self.lib, self.lib.rgbl_mlpnp_ransac_host(C.byref(I), C.byref(O)))
+        else:
+            L.check(self.lib, self.lib.rgbl_mlpnp_ransac(self.h, C.byref(I), C.byref(O)))
+        return self._mlpnp_result(O, bufs)
+
+    @staticmethod
     def _sim3_opt_input(cs, keep, out=None):
         """rgbl_sim3_opt_input of a case dict: mp1_index, match_index, i2, track_level2 (per feature of key frame 1), bad and
         world_pos (points x 3) or pool (MapPointPool) + slot, Rcw1, tcw1, Rcw2, tcw2, xy1 / octave1 or device1 (DeviceFrame),
@@ -1889,6 +1992,17 @@ def sim3_ransac_host(problem, lib=None, diag=True, fill=0):
     bufs = ORBmatcher._sim3_buffers(I, O, fill, diag)
     L.check(lib, lib.rgbl_sim3_ransac_host(C.byref(I), C.byref(O)))
     return ORBmatcher._sim3_result(O, bufs)
+
+
+def mlpnp_ransac_host(problem, lib=None, diag=True, fill=0):
+    """rgbl_mlpnp_ransac_host: MLPnPsolver by the host build of csrc/mlpnp_math.h (no device, no handle); the result dict of
+    ORBmatcher.MLPnPRansac."""
+    lib = lib or L.load()
+    keep = []
+    I, O = ORBmatcher._mlpnp_input(problem, keep), L.MlpnpOutput()
+    bufs = ORBmatcher._mlpnp_buffers(I, O, fill, diag)
+    L.check(lib, lib.rgbl_mlpnp_ransac_host(C.byref(I), C.byref(O)))
+    return ORBmatcher._mlpnp_result(O, bufs)
 
 
 def quat_from_matrix(R):
