@@ -1175,6 +1175,71 @@ int rgbl_mlpnp_ransac_batch(rgbl_matcher* h, int n_problems, const rgbl_mlpnp_in
  * side must be host arrays (device and pool NULL). */
 int rgbl_mlpnp_ransac_host(const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out);
 
+/* bool TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, T21, vP3D, vbTriangulated) (include/TwoViewReconstruction.h,
+ * src/TwoViewReconstruction.cc:41-129), the step of Tracking::MonocularInitialization (src/Tracking.cc:2538) behind
+ * SearchForInitialization, reached through Pinhole::ReconstructWithTwoViews (src/CameraModels/Pinhole.cpp:83-92): ALL
+ * homography and fundamental hypotheses of a call at once.  One call replaces FindHomography and FindFundamental (:131-230) with
+ * Normalize, ComputeH21, ComputeF21, CheckHomography and CheckFundamental (:232-473, :737-784), the choice of :112-128, and
+ * ReconstructF / ReconstructH with DecomposeE and CheckRT (:475-734, :786-927).  csrc/twoview_math.h restates the arithmetic
+ * and says what is pinned (the plain C++: precisions, orders, the serial score sums, every rule and quirk) and what is not
+ * (what Eigen computes).  The drawing of the sets (:78-98) stays with the caller.  N below = the number of keys of frame 1 with
+ * matches12 >= 0: the matches, in ascending index of frame 1 (mvMatches12). */
+typedef struct {
+  int n1, n2;                   /* vKeys1.size(), vKeys2.size(), 0 .. 65535 each */
+  /* the keys: host arrays, or resident frames (the arrays are then not read) */
+  const float* kp1_xy;          /* vKeys1[i].pt (mvKeysUn), n1 x 2 */
+  const float* kp2_xy;          /* vKeys2[i].pt, n2 x 2 */
+  const rgbl_device_frame* device1;
+  const rgbl_device_frame* device2;
+  const int32_t* matches12;     /* n1 entries: index into frame 2, -1 = none; what rgbl_search_initialization returns */
+  float K[4];                   /* mK: fx, fy, cx, cy */
+  float sigma;                  /* mSigma (1.0 at Pinhole.cpp:87) */
+  int n_hyp;                    /* mMaxIterations (200 there), 0 .. 2^20 */
+  const int32_t* samples;       /* mvSets: n_hyp x 8 indices into the matches 0 .. N-1, distinct in a set, drawn as :83-98 draws them */
+} rgbl_two_view_input;
+typedef struct {
+  int found;                    /* Reconstruct's return value */
+  int model;                    /* 0 = ReconstructH ran, 1 = ReconstructF ran, -1 = the SH + SF == 0 exit (:113) */
+  int exit_code;                /* 0 found; 1 SH + SF == 0 (:113); 2 ReconstructH's d1 / d2, d2 / d3 exit (:597-600); 3 its final
+                                   rule (:725-733); 4 ReconstructF's maxGood < nMinGood || nsimilar > 1 (:520-523); 5 its
+                                   winner lacks parallax (:568) */
+  float SH, SF;                 /* the two scores */
+  int best_h, best_f;           /* the hypotheses that hold them; -1: no score > 0, H21 / F21 stay unset in the reference (zeros here) */
+  float H21[9], F21[9];         /* row-major */
+  float R21[9], t21[3];         /* T21 as the R and t handed to Sophus::SE3f (:533 .. :563, :727); identity and zeros when not found */
+  float* p3d;                   /* n1 x 3: the WINNING motion hypothesis's vP3D, by the index of frame 1 - also on the homography
+                                   path; written when found (NULL: not wanted) */
+  uint8_t* triangulated;        /* vbTriangulated, n1 bytes; written when found (NULL: not wanted) */
+  int p3d_assigned;             /* 1 where the reference assigns vP3D (the fundamental path), 0 where it leaves the caller's vector
+                                   alone: ReconstructH drops bestP3D (:725-731) */
+  int n_inliers;                /* N of ReconstructF / ReconstructH: the ones of the chosen mask (0 for model -1) */
+  int best_motion;              /* the motion hypothesis the rule looked at: 0 .. 3 (F: R1 t, R2 t, R1 -t, R2 -t), 0 .. 7 (H), -1 none */
+  int aux;                      /* nsimilar (F) or secondBestGood (H) */
+  int n_good[8];                /* CheckRT's return value per motion hypothesis (F: the first four), zeros where none ran */
+  float parallax[8];            /* CheckRT's parallax per motion hypothesis, degrees */
+  float* scores;                /* optional diagnostics: currentScore of every hypothesis, n_hyp x 2 (H, F) (NULL: not wanted) */
+  float* models;                /* optional diagnostics: H21i / F21i of every hypothesis, n_hyp x 2 x 9 */
+  uint8_t* inliers_h;           /* optional diagnostics: vbMatchesInliersH, N bytes per MATCH */
+  uint8_t* inliers_f;           /* optional diagnostics: vbMatchesInliersF, N bytes; NOT written when best_f == -1: that mask is
+                                   EMPTY in the reference (FindFundamental sizes it by the empty argument, :185) */
+} rgbl_two_view_output;
+/* One problem.  Host pointers, synchronous, one upload, five launches on one stream, one read-back.  n_hyp == 0 is valid and
+ * launches nothing: both scores stay 0, so model = -1, exit_code = 1, found = 0 (scores / models / masks are not written).
+ * RGBL_ERR_INVALID, before anything is launched and with every output untouched: n1 or n2 outside [0, 65535]; n_hyp outside
+ * [0, 2^20]; N < 8 with n_hyp > 0 (the reference would index an empty vector; Tracking never calls below 100 matches); a
+ * sample outside [0, N) or repeated in its set; a match outside [-1, n2); a K or sigma that is not finite; a frame on another
+ * device than the matcher or whose size is not n1 / n2; a missing array; more than 2^26 mask words in the call, i.e. the sum
+ * over the problems of 2 x n_hyp x ceil(N / 64) (512 MB of device scratch); more than 2^24 keys of frame 1 in the call, summed over the
+ * problems with n_hyp > 0 (CheckRT keeps 8 x 13 bytes per key: 1.7 GB).  Beyond the checks a call can fail with
+ * RGBL_ERR_HIP when the device cannot hold its arena; nothing is written then either. */
+int rgbl_two_view_reconstruct(rgbl_matcher* h, const rgbl_two_view_input* in, rgbl_two_view_output* out);
+/* B independent problems: one upload, one launch sequence, one read-back.  Errors as above, and n_problems outside
+ * [0, 32767] (the problem is a grid dimension): nothing is launched and no problem's output is written. */
+int rgbl_two_view_reconstruct_batch(rgbl_matcher* h, int n_problems, const rgbl_two_view_input* in, rgbl_two_view_output* out);
+/* rgbl_two_view_reconstruct evaluated by the HOST build of csrc/twoview_math.h (no device, no handle): the same bits.  The
+ * keys must be host arrays (device1 and device2 NULL). */
+int rgbl_two_view_reconstruct_host(const rgbl_two_view_input* in, rgbl_two_view_output* out);
+
 /* int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
  * const bool bFixScale, Eigen::Matrix<double,7,7>& mAcumHessian, const bool bAllPoints) (include/Optimizer.h,
  * src/Optimizer.cc:2115-2381): the 7-dof refinement LoopClosing runs per candidate (src/LoopClosing.cc:556, :767), one

@@ -119,6 +119,22 @@ class MlpnpOutput(C.Structure):
                 ("gn_path", C.c_void_p)]
 
 
+class TwoViewInput(C.Structure):
+    """rgbl_two_view_input (one TwoViewReconstruction problem: the keys of both frames, the matches and the drawn sets)."""
+    _fields_ = [("n1", C.c_int), ("n2", C.c_int), ("kp1_xy", C.c_void_p), ("kp2_xy", C.c_void_p), ("device1", C.c_void_p),
+                ("device2", C.c_void_p), ("matches12", C.c_void_p), ("K", C.c_float * 4), ("sigma", C.c_float), ("n_hyp", C.c_int),
+                ("samples", C.c_void_p)]
+
+
+class TwoViewOutput(C.Structure):
+    _fields_ = [("found", C.c_int), ("model", C.c_int), ("exit_code", C.c_int), ("SH", C.c_float), ("SF", C.c_float),
+                ("best_h", C.c_int), ("best_f", C.c_int), ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("R21", C.c_float * 9),
+                ("t21", C.c_float * 3), ("p3d", C.c_void_p), ("triangulated", C.c_void_p), ("p3d_assigned", C.c_int),
+                ("n_inliers", C.c_int), ("best_motion", C.c_int), ("aux", C.c_int), ("n_good", C.c_int * 8),
+                ("parallax", C.c_float * 8), ("scores", C.c_void_p), ("models", C.c_void_p), ("inliers_h", C.c_void_p),
+                ("inliers_f", C.c_void_p)]
+
+
 class Sim3OptInput(C.Structure):
     """rgbl_sim3_opt_input (two key frames, the matches and the entry estimate as Optimizer::OptimizeSim3 reads them)."""
     _fields_ = [("n", C.c_int), ("mp1_index", C.c_void_p), ("match_index", C.c_void_p), ("i2", C.c_void_p),
@@ -381,6 +397,9 @@ SYMBOLS = {
     "rgbl_mlpnp_ransac": (_I, [_V, C.POINTER(MlpnpInput), C.POINTER(MlpnpOutput)]),
     "rgbl_mlpnp_ransac_batch": (_I, [_V, _I, _V, _V]),
     "rgbl_mlpnp_ransac_host": (_I, [C.POINTER(MlpnpInput), C.POINTER(MlpnpOutput)]),
+    "rgbl_two_view_reconstruct": (_I, [_V, C.POINTER(TwoViewInput), C.POINTER(TwoViewOutput)]),
+    "rgbl_two_view_reconstruct_batch": (_I, [_V, _I, _V, _V]),
+    "rgbl_two_view_reconstruct_host": (_I, [C.POINTER(TwoViewInput), C.POINTER(TwoViewOutput)]),
     "rgbl_optimize_sim3": (_I, [_V, C.POINTER(Sim3OptInput), C.POINTER(Sim3OptOutput)]),
     "rgbl_optimize_sim3_batch": (_I, [_V, _I, _V, _V]),
     "rgbl_optimize_sim3_host": (_I, [C.POINTER(Sim3OptInput), C.POINTER(Sim3OptOutput)]),

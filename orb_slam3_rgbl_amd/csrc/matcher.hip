@@ -28,6 +28,7 @@
 #include "frustum_math.h"
 #include "logf_glibc.h"
 #include "mlpnp_math.h"
+#include "twoview_math.h"
 #include "newpoint_math.h"
 #include "poseopt_math.h"
 #include "sim3_math.h"
@@ -1449,6 +1450,273 @@ __global__ __launch_bounds__(256) void k_mlpnp_select(MlpnpDev D) {
     else for (int k = 0; k < 16; ++k) r.best_Tcw[k] = pb.best_Tcw[k];
     if (sc.selected >= 0) ml_Tcw(hyp[sc.selected].T, hyp[sc.selected].T + 9, r.Tcw);
     else for (int k = 0; k < 16; ++k) r.Tcw[k] = r.best_Tcw[k];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// TwoViewReconstruction (src/TwoViewReconstruction.cc): every homography and every fundamental hypothesis of a call at once.
+// The arithmetic is csrc/twoview_math.h.
+//   k_tv_normalize    grid (2 frames, problem), one wave: Normalize over ALL keys of the frame.  The wave stages 64 keys in LDS,
+//                     then every lane adds the two serial chains in index order.
+//   k_tv_hypotheses   grid (groups of 4 hypotheses, 2 models, problem), 256 work-items: one wave per (hypothesis, model), no
+//                     workgroup barrier.  The wave fills A from its eight matches, runs the Jacobi in its TvWork in LDS and forms
+//                     H21i / H12i or F21i wave-uniformly; then walks the matches 64 at a time: a lane computes both terms of
+//                     its match and its inlier bit, the chunk's mask word is a ballot, and the 128 terms go through LDS to be
+//                     added by every lane in the reference's order (two per match, ascending match index): no tree.
+//   k_tv_select       one workgroup per problem: the first strictly greater score per model, Reconstruct's choice, the inlier
+//                     count of the chosen mask, the motion hypotheses (DecomposeE, or Faugeras' eight with the d1 / d2, d2 / d3
+//                     exit); all work-items expand the two winners' masks into bytes.
+//   k_tv_check_rt     grid (8 motion hypotheses, problem), 256 work-items: CheckRT over the inliers of the chosen model.  nGood is
+//                     an integer tree; the min(50, nGood - 1)-th smallest cosParallax comes from at most 51 rounds of "smallest
+//                     value above the last one, and how often" (an order-free min / count tree each).
+//   k_tv_decide       one workgroup per problem: the rules of ReconstructF / ReconstructH, T21, and the winning hypothesis's
+//                     points and flags copied out.
+// All run on the call's stream, one behind the other; no floating-point atomics, no workgroup waits for another, every loop
+// is bounded.
+constexpr int kTvHypPerGroup = 4;
+struct TvProblem {
+  TvView v;                 // T1 / T2 come from k_tv_normalize
+  const int32_t* samples;
+  int n_hyp;                // 0: the problem is not run
+  int words, hyp_off, match_off, key_off;
+  unsigned long long word_off;
+};
+struct TvSelect {
+  float SH, SF;
+  int32_t best_h, best_f, model, n_inliers, exit_code;
+  float H21[9], F21[9];
+  TvMotions mo;
+};
+struct TvResult {
+  int32_t found, model, exit_code, best, aux, n_inliers, best_h, best_f;
+  float SH, SF, H21[9], F21[9], R[9], t[3];
+  int32_t n_good[kTvMaxMotions];
+  float parallax[kTvMaxMotions];
+};
+struct TvDev {
+  const TvProblem* prob;
+  float* norm;                  // per problem 2 x (sX, sY, meanX, meanY)
+  float* score;                 // per hypothesis 2
+  float* model;                 // per hypothesis 2 x 9
+  unsigned long long* mask;     // per hypothesis 2 x `words` 64-bit words
+  TvSelect* sel;
+  int32_t* n_good;              // per problem 8
+  float* parallax;              // per problem 8
+  float* cosv;                  // per problem 8 x N: the vCosParallax entry of a counted match, else NaN
+  float* p3d;                   // per problem 8 x n1 x 3
+  uint8_t* good;                // per problem 8 x n1
+  TvResult* res;
+  float* p3d_out;               // per problem n1 x 3
+  uint8_t* tri_out;             // per problem n1
+  uint8_t *mask_h, *mask_f;     // per match: the winners' inlier flags
+};
+__device__ __forceinline__ TvView tv_view(const TvDev& D, const TvProblem& pb, int b) {
+  TvView v = pb.v;
+  for (int k = 0; k < 4; ++k) { v.T1[k] = D.norm[8 * (size_t)b + k]; v.T2[k] = D.norm[8 * (size_t)b + 4 + k]; }
+  return v;
+}
+
+__global__ __launch_bounds__(64) void k_tv_normalize(TvDev D) {
+  __shared__ float s_buf[2][64];
+  const TvProblem& pb = D.prob[blockIdx.y];
+  if (pb.n_hyp == 0) return;   // the whole wave
+  MlWaveX x = {(int)threadIdx.x, 64};
+  const int f = (int)blockIdx.x;
+  float T[4];
+  tv_normalize(x, s_buf, f ? pb.v.xy2 : pb.v.xy1, f ? pb.v.n2 : pb.v.n1, T);
+  if (threadIdx.x == 0) {   // every lane holds the same T; constant indices keep it in registers (T[threadIdx.x] would put it into scratch)
+    float* out = D.norm + 8 * (size_t)blockIdx.y + 4 * f;
+    out[0] = T[0]; out[1] = T[1]; out[2] = T[2]; out[3] = T[3];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_tv_hypotheses(TvDev D) {
+  __shared__ TvWork s_work[kTvHypPerGroup];
+  const TvProblem& pb = D.prob[blockIdx.z];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = (int)blockIdx.x * kTvHypPerGroup + wave, model = (int)blockIdx.y;
+  if (h >= pb.n_hyp) return;   // a whole wave; the kernel has no workgroup barrier
+  const TvView v = tv_view(D, pb, (int)blockIdx.z);
+  TvWork& W = s_work[wave];
+  MlWaveX x = {lane, 64};
+  float M[9], M2[9];
+  tv_model(x, W, v, pb.samples + 8 * (size_t)h, model, M, M2);   // the sets are checked by the host: inside [0, N), distinct
+  const float invSigmaSquare = tv_inv_sigma2(v.sigma);
+  const size_t hm = 2 * ((size_t)pb.hyp_off + (size_t)h) + (size_t)model;
+  unsigned long long* mask = D.mask + pb.word_off + (2 * (size_t)h + (size_t)model) * (size_t)pb.words;
+  float score = 0.0f;
+  for (int c = 0; c < pb.words; ++c) {   // wave-uniform
+    const int i = c * 64 + lane;
+    float t[2] = {0.0f, 0.0f};
+    bool in = false;
+    if (i < v.N) in = tv_check(model, M, M2, v, i, invSigmaSquare, t);
+    W.terms[2 * lane] = t[0];
+    W.terms[2 * lane + 1] = t[1];
+    wave_sync();
+    score = tv_add_chunk(score, W.terms, 128);   // past N the terms are +0.0f
+    wave_sync();
+    const unsigned long long w = __ballot(in);
+    if (lane == 0) mask[c] = w;
+  }
+  if (lane == 0) {
+    D.score[hm] = score;
+    for (int k = 0; k < 9; ++k) D.model[9 * hm + k] = M[k];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_tv_select(TvDev D) {
+  __shared__ int s_cnt[256];
+  const TvProblem& pb = D.prob[blockIdx.x];
+  if (pb.n_hyp == 0) return;   // the whole workgroup
+  const int tid = (int)threadIdx.x, N = pb.v.N, words = pb.words;
+  const float* scores = D.score + 2 * (size_t)pb.hyp_off;
+  float SH, SF;   // wave-uniform loads, the same in every work-item
+  const int best_h = tv_first_max(scores, pb.n_hyp, 0, &SH), best_f = tv_first_max(scores, pb.n_hyp, 1, &SF);
+  const int model = tv_choose_model(SH, SF);
+  const unsigned long long* mh = best_h >= 0 ? D.mask + pb.word_off + (2 * (size_t)best_h) * (size_t)words : nullptr;
+  const unsigned long long* mf = best_f >= 0 ? D.mask + pb.word_off + (2 * (size_t)best_f + 1) * (size_t)words : nullptr;
+  const unsigned long long* chosen = model == 0 ? mh : mf;   // model >= 0 has a score > 0 on that side: a winner
+  int cnt = 0;
+  for (int c = tid; model >= 0 && c < words; c += 256) cnt += __popcll(chosen[c]);
+  s_cnt[tid] = cnt;
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if (tid < s) s_cnt[tid] += s_cnt[tid + s];
+    __syncthreads();
+  }
+  for (int i = tid; i < N; i += 256) {
+    D.mask_h[(size_t)pb.match_off + i] = mh ? (uint8_t)((mh[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
+    D.mask_f[(size_t)pb.match_off + i] = mf ? (uint8_t)((mf[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
+  }
+  if (tid == 0) {
+    TvSelect& S = D.sel[blockIdx.x];
+    S.SH = SH; S.SF = SF; S.best_h = best_h; S.best_f = best_f; S.model = model; S.n_inliers = s_cnt[0];
+    for (int k = 0; k < 9; ++k) {
+      S.H21[k] = best_h >= 0 ? D.model[9 * (2 * ((size_t)pb.hyp_off + (size_t)best_h)) + k] : 0.0f;
+      S.F21[k] = best_f >= 0 ? D.model[9 * (2 * ((size_t)pb.hyp_off + (size_t)best_f) + 1) + k] : 0.0f;
+    }
+    S.exit_code = kTvFound;
+    if (model < 0) {
+      S.exit_code = kTvNoScore;
+      S.mo.n = 0;
+    } else if (model == 0) {
+      if (!tv_motions_h(S.H21, pb.v.K, S.mo)) S.exit_code = kTvHRatio;
+    } else {
+      tv_motions_f(S.F21, pb.v.K, S.mo);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_tv_check_rt(TvDev D) {
+  __shared__ int s_cnt[256];
+  __shared__ float s_val[256];
+  const int b = (int)blockIdx.y, j = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const TvProblem& pb = D.prob[b];
+  if (pb.n_hyp == 0) return;   // the whole workgroup
+  const TvSelect& S = D.sel[b];
+  const int N = pb.v.N, n1 = pb.v.n1;
+  if (j >= S.mo.n) {           // the whole workgroup
+    if (tid == 0) { D.n_good[8 * (size_t)b + j] = 0; D.parallax[8 * (size_t)b + j] = 0.0f; }
+    return;
+  }
+  TvCam c;
+  tv_cam(pb.v.K, S.mo.R[j], S.mo.t[j], pb.v.sigma, c);
+  float* p3d = D.p3d + 3 * (8 * (size_t)pb.key_off + (size_t)j * (size_t)n1);
+  uint8_t* good = D.good + 8 * (size_t)pb.key_off + (size_t)j * (size_t)n1;
+  float* cosv = D.cosv + 8 * (size_t)pb.match_off + (size_t)j * (size_t)N;
+  for (int i = tid; i < n1; i += 256) { p3d[3 * (size_t)i] = 0.0f; p3d[3 * (size_t)i + 1] = 0.0f; p3d[3 * (size_t)i + 2] = 0.0f; good[i] = 0; }
+  __syncthreads();
+  const unsigned long long* mask = D.mask + pb.word_off + (2 * (size_t)(S.model == 0 ? S.best_h : S.best_f) + (size_t)S.model) * (size_t)pb.words;
+  const float nan = np_float(0x7fc00000u);
+  int cnt = 0;
+  for (int i = tid; i < N; i += 256) {
+    float cv = nan;
+    if ((mask[i >> 6] >> (i & 63)) & 1ull) {
+      const size_t a = (size_t)pb.v.m1[i], q = (size_t)pb.v.m2[i];   // the matches name distinct keys of frame 1
+      float p[3], cp;
+      const int code = tv_rt_point(c, pb.v.xy1[2 * a], pb.v.xy1[2 * a + 1], pb.v.xy2[2 * q], pb.v.xy2[2 * q + 1], p, &cp);
+      if (code) {
+        p3d[3 * a] = p[0]; p3d[3 * a + 1] = p[1]; p3d[3 * a + 2] = p[2];
+        good[a] = code == 2 ? 1 : 0;
+        cv = cp;
+        ++cnt;
+      }
+    }
+    cosv[i] = cv;   // read back by this work-item only
+  }
+  s_cnt[tid] = cnt;
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if (tid < s) s_cnt[tid] += s_cnt[tid + s];
+    __syncthreads();
+  }
+  const int nGood = s_cnt[0];
+  __syncthreads();
+  // sort + vCosParallax[min(50, size - 1)]: the values in ascending order, one distinct value per round
+  const int idx = nGood - 1 < 50 ? nGood - 1 : 50;
+  float last = 0.0f, pick = nan;
+  int rank = 0;
+  for (int round = 0; nGood > 0 && round <= idx; ++round) {   // uniform: at most 51 rounds
+    float lo = nan;
+    int m = 0;
+    for (int i = tid; i < N; i += 256) {
+      const float cv = cosv[i];
+      if (!(cv == cv) || (round > 0 && !(cv > last))) continue;
+      if (m == 0 || cv < lo) { lo = cv; m = 1; }
+      else if (cv == lo) ++m;
+    }
+    s_val[tid] = lo;
+    s_cnt[tid] = m;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+      if (tid < s) {
+        const float a = s_val[tid], o = s_val[tid + s];
+        const int ma = s_cnt[tid], mo = s_cnt[tid + s];
+        if (mo > 0 && (ma == 0 || o < a)) { s_val[tid] = o; s_cnt[tid] = mo; }
+        else if (mo > 0 && o == a) s_cnt[tid] = ma + mo;
+      }
+      __syncthreads();
+    }
+    const float v0 = s_val[0];
+    const int m0 = s_cnt[0];
+    __syncthreads();
+    if (m0 == 0) break;                              // only NaN values are left: pick stays NaN
+    if (rank + m0 > idx) { pick = v0; break; }
+    rank += m0;
+    last = v0;
+  }
+  if (tid == 0) {
+    D.n_good[8 * (size_t)b + j] = nGood;
+    D.parallax[8 * (size_t)b + j] = nGood > 0 ? tv_parallax_deg(pick) : 0.0f;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_tv_decide(TvDev D) {
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const TvProblem& pb = D.prob[b];
+  if (pb.n_hyp == 0) return;   // the whole workgroup
+  const TvSelect& S = D.sel[b];
+  int32_t nGood[kTvMaxMotions];
+  float parallax[kTvMaxMotions];
+  for (int k = 0; k < kTvMaxMotions; ++k) { nGood[k] = D.n_good[8 * (size_t)b + k]; parallax[k] = D.parallax[8 * (size_t)b + k]; }
+  TvDecision d = {0, S.exit_code, -1, 0};   // the same in every work-item
+  if (S.exit_code == kTvFound) d = S.model == 0 ? tv_decide_h(nGood, parallax, S.n_inliers) : tv_decide_f(nGood, parallax, S.n_inliers);
+  const int n1 = pb.v.n1;
+  if (d.found) {
+    const float* p3d = D.p3d + 3 * (8 * (size_t)pb.key_off + (size_t)d.best * (size_t)n1);
+    const uint8_t* good = D.good + 8 * (size_t)pb.key_off + (size_t)d.best * (size_t)n1;
+    for (int i = tid; i < n1; i += 256) {
+      for (int k = 0; k < 3; ++k) D.p3d_out[3 * ((size_t)pb.key_off + i) + k] = p3d[3 * (size_t)i + k];
+      D.tri_out[(size_t)pb.key_off + i] = good[i];
+    }
+  }
+  if (tid == 0) {
+    TvResult& r = D.res[b];
+    r.found = d.found; r.model = S.model; r.exit_code = d.exit_code; r.best = d.best; r.aux = d.aux; r.n_inliers = S.n_inliers;
+    r.best_h = S.best_h; r.best_f = S.best_f; r.SH = S.SH; r.SF = S.SF;
+    for (int k = 0; k < 9; ++k) { r.H21[k] = S.H21[k]; r.F21[k] = S.F21[k]; r.R[k] = d.found ? S.mo.R[d.best][k] : ((k % 4 == 0) ? 1.0f : 0.0f); }
+    for (int k = 0; k < 3; ++k) r.t[k] = d.found ? S.mo.t[d.best][k] : 0.0f;
+    for (int k = 0; k < kTvMaxMotions; ++k) { r.n_good[k] = nGood[k]; r.parallax[k] = parallax[k]; }
   }
 }
 
@@ -5138,6 +5406,285 @@ int rgbl_mlpnp_ransac_batch(rgbl_matcher* m, int n_problems, const rgbl_mlpnp_in
 int rgbl_mlpnp_ransac(rgbl_matcher* m, const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out) {
   if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
   return rgbl_mlpnp_ransac_batch(m, 1, in, out);
+}
+
+// ---- TwoViewReconstruction (src/TwoViewReconstruction.cc) -------------------------------------------------------------------
+namespace {
+constexpr int kTvMaxHyp = 1 << 20;
+constexpr int kTvMaxMaskWordsLog2 = 26;   // 512 MB of masks
+constexpr size_t kTvMaxMaskWords = (size_t)1 << kTvMaxMaskWordsLog2;
+constexpr int kTvMaxKeysLog2 = 24;           // keys of frame 1 over the problems of a call that run: 104 B of CheckRT scratch each, 1.7 GB
+constexpr size_t kTvMaxKeys = (size_t)1 << kTvMaxKeysLog2;
+// Everything that can be refused is refused here, before anything is staged, launched or written.  *n_match = N.
+int check_two_view_input(const rgbl_two_view_input* in, int b, bool host_only, int* n_match) {
+  *n_match = 0;
+  if (in->n1 < 0 || in->n1 > 65535 || in->n2 < 0 || in->n2 > 65535) { set_error("two view %d: n1 or n2 outside [0, 65535]", b); return RGBL_ERR_INVALID; }
+  if (in->n_hyp < 0 || in->n_hyp > kTvMaxHyp) { set_error("two view %d: n_hyp outside [0, %d]", b, kTvMaxHyp); return RGBL_ERR_INVALID; }
+  bool finite = std::isfinite(in->sigma);
+  for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(in->K[i]);
+  if (!finite) { set_error("two view %d: K or sigma is not finite", b); return RGBL_ERR_INVALID; }
+  if (host_only && (in->device1 || in->device2)) { set_error("two view %d: the host build reads host arrays only", b); return RGBL_ERR_INVALID; }
+  if (in->device1 ? in->device1->n != in->n1 : (in->n1 > 0 && !in->kp1_xy)) { set_error("two view %d: frame 1 is either kp1_xy or a resident frame of n1 features", b); return RGBL_ERR_INVALID; }
+  if (in->device2 ? in->device2->n != in->n2 : (in->n2 > 0 && !in->kp2_xy)) { set_error("two view %d: frame 2 is either kp2_xy or a resident frame of n2 features", b); return RGBL_ERR_INVALID; }
+  if (in->n1 > 0 && !in->matches12) { set_error("two view %d: no matches12", b); return RGBL_ERR_INVALID; }
+  int N = 0;
+  for (int i = 0; i < in->n1; ++i) {
+    const int q = in->matches12[i];
+    if (q < -1 || q >= in->n2) { set_error("two view %d: matches12[%d] = %d outside [-1, %d)", b, i, q, in->n2); return RGBL_ERR_INVALID; }
+    N += q >= 0 ? 1 : 0;
+  }
+  if (in->n_hyp > 0) {
+    if (N < 8) { set_error("two view %d: %d matches, a set needs 8", b, N); return RGBL_ERR_INVALID; }
+    if (!in->samples) { set_error("two view %d: no samples", b); return RGBL_ERR_INVALID; }
+    for (int k = 0; k < in->n_hyp; ++k) {
+      const int32_t* s = in->samples + 8 * (size_t)k;
+      bool ok = true;
+      for (int i = 0; i < 8; ++i) {
+        ok = ok && s[i] >= 0 && s[i] < N;
+        for (int j = 0; j < i; ++j) ok = ok && s[i] != s[j];
+      }
+      if (!ok) { set_error("two view %d: set %d is not eight distinct indices in [0, %d)", b, k, N); return RGBL_ERR_INVALID; }
+    }
+  }
+  *n_match = N;
+  return RGBL_OK;
+}
+// mvMatches12 (:55-64)
+void two_view_matches(const rgbl_two_view_input* in, int32_t* m1, int32_t* m2) {
+  int k = 0;
+  for (int i = 0; i < in->n1; ++i)
+    if (in->matches12[i] >= 0) { m1[k] = i; m2[k] = in->matches12[i]; ++k; }
+}
+// n_hyp == 0: both scores stay 0 (:144, :195), the exit of :113
+void write_two_view_skipped(rgbl_two_view_output* out) {
+  out->found = 0; out->model = -1; out->exit_code = kTvNoScore; out->SH = 0.0f; out->SF = 0.0f; out->best_h = -1; out->best_f = -1;
+  for (int k = 0; k < 9; ++k) { out->H21[k] = 0.0f; out->F21[k] = 0.0f; out->R21[k] = (k % 4 == 0) ? 1.0f : 0.0f; }
+  for (int k = 0; k < 3; ++k) out->t21[k] = 0.0f;
+  out->p3d_assigned = 0; out->n_inliers = 0; out->best_motion = -1; out->aux = 0;
+  for (int k = 0; k < 8; ++k) { out->n_good[k] = 0; out->parallax[k] = 0.0f; }
+}
+// p3d / tri: the winning hypothesis's, per key of frame 1; mask_h / mask_f: per match; score / model: per hypothesis (null: not fetched)
+void write_two_view_output(const rgbl_two_view_input* in, rgbl_two_view_output* out, int N, const TvResult& r, const float* p3d, const uint8_t* tri,
+                           const uint8_t* mask_h, const uint8_t* mask_f, const float* score, const float* model) {
+  out->found = r.found; out->model = r.model; out->exit_code = r.exit_code; out->SH = r.SH; out->SF = r.SF; out->best_h = r.best_h; out->best_f = r.best_f;
+  memcpy(out->H21, r.H21, sizeof(out->H21));
+  memcpy(out->F21, r.F21, sizeof(out->F21));
+  memcpy(out->R21, r.R, sizeof(out->R21));
+  memcpy(out->t21, r.t, sizeof(out->t21));
+  if (r.found && out->p3d) memcpy(out->p3d, p3d, sizeof(float) * 3 * (size_t)in->n1);
+  if (r.found && out->triangulated) memcpy(out->triangulated, tri, (size_t)in->n1);
+  out->p3d_assigned = r.found && r.model == 1 ? 1 : 0;
+  out->n_inliers = r.n_inliers; out->best_motion = r.best; out->aux = r.aux;
+  memcpy(out->n_good, r.n_good, sizeof(out->n_good));
+  memcpy(out->parallax, r.parallax, sizeof(out->parallax));
+  if (out->inliers_h) memcpy(out->inliers_h, mask_h, (size_t)N);
+  if (out->inliers_f && r.best_f >= 0) memcpy(out->inliers_f, mask_f, (size_t)N);
+  if (out->scores && score) memcpy(out->scores, score, sizeof(float) * 2 * (size_t)in->n_hyp);
+  if (out->models && model) memcpy(out->models, model, sizeof(float) * 18 * (size_t)in->n_hyp);
+}
+}  // namespace
+
+int rgbl_two_view_reconstruct_host(const rgbl_two_view_input* in, rgbl_two_view_output* out) {
+  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  int N = 0;
+  RGBL_TRY(check_two_view_input(in, 0, true, &N));
+  if (in->n_hyp == 0) { write_two_view_skipped(out); return RGBL_OK; }
+  const int words = (N + 63) / 64, n1 = in->n1, H = in->n_hyp;
+  std::vector<int32_t> m1((size_t)N), m2((size_t)N);
+  two_view_matches(in, m1.data(), m2.data());
+  TvView v;
+  v.xy1 = in->kp1_xy; v.xy2 = in->kp2_xy; v.m1 = m1.data(); v.m2 = m2.data(); v.N = N; v.n1 = n1; v.n2 = in->n2; v.sigma = in->sigma;
+  memcpy(v.K, in->K, sizeof(v.K));
+  TvHostX x;
+  float buf[2][64];
+  tv_normalize(x, buf, v.xy1, v.n1, v.T1);
+  tv_normalize(x, buf, v.xy2, v.n2, v.T2);
+  std::vector<TvWork> work(1);
+  std::vector<float> score(2 * (size_t)H), model(18 * (size_t)H);
+  std::vector<unsigned long long> mask(2 * (size_t)H * (size_t)words, 0ull);
+  const float invSigmaSquare = tv_inv_sigma2(v.sigma);
+  for (int h = 0; h < H; ++h)
+    for (int md = 0; md < 2; ++md) {
+      float M[9], M2[9];
+      tv_model(x, work[0], v, in->samples + 8 * (size_t)h, md, M, M2);
+      unsigned long long* mk = mask.data() + (2 * (size_t)h + (size_t)md) * (size_t)words;
+      float sc = 0.0f;
+      for (int i = 0; i < N; ++i) {
+        float t[2];
+        if (tv_check(md, M, M2, v, i, invSigmaSquare, t)) mk[i >> 6] |= 1ull << (i & 63);
+        sc = tv_add_chunk(sc, t, 2);
+      }
+      score[2 * (size_t)h + md] = sc;
+      memcpy(model.data() + 9 * (2 * (size_t)h + md), M, sizeof(M));
+    }
+  TvResult r;
+  memset(&r, 0, sizeof(r));
+  r.best_h = tv_first_max(score.data(), H, 0, &r.SH);
+  r.best_f = tv_first_max(score.data(), H, 1, &r.SF);
+  r.model = tv_choose_model(r.SH, r.SF);
+  if (r.best_h >= 0) memcpy(r.H21, model.data() + 9 * (2 * (size_t)r.best_h), sizeof(r.H21));
+  if (r.best_f >= 0) memcpy(r.F21, model.data() + 9 * (2 * (size_t)r.best_f + 1), sizeof(r.F21));
+  std::vector<uint8_t> mask_h((size_t)N, 0), mask_f((size_t)N, 0);
+  const unsigned long long* mh = r.best_h >= 0 ? mask.data() + (2 * (size_t)r.best_h) * (size_t)words : nullptr;
+  const unsigned long long* mf = r.best_f >= 0 ? mask.data() + (2 * (size_t)r.best_f + 1) * (size_t)words : nullptr;
+  for (int i = 0; i < N; ++i) {
+    mask_h[(size_t)i] = mh ? (uint8_t)((mh[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
+    mask_f[(size_t)i] = mf ? (uint8_t)((mf[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
+  }
+  TvMotions mo;
+  mo.n = 0;
+  TvDecision d = {0, kTvFound, -1, 0};
+  const uint8_t* chosen = nullptr;
+  if (r.model < 0) d.exit_code = kTvNoScore;
+  else if (r.model == 0) { chosen = mask_h.data(); if (!tv_motions_h(r.H21, v.K, mo)) d.exit_code = kTvHRatio; }
+  else { chosen = mask_f.data(); tv_motions_f(r.F21, v.K, mo); }
+  for (int i = 0; chosen && i < N; ++i) r.n_inliers += chosen[i];
+  std::vector<float> p3d(3 * (size_t)n1 * kTvMaxMotions, 0.0f);
+  std::vector<uint8_t> good((size_t)n1 * kTvMaxMotions, 0);
+  for (int j = 0; j < mo.n; ++j) {
+    TvCam c;
+    tv_cam(v.K, mo.R[j], mo.t[j], v.sigma, c);
+    float* P = p3d.data() + 3 * (size_t)j * (size_t)n1;
+    uint8_t* G = good.data() + (size_t)j * (size_t)n1;
+    std::vector<float> cosv;   // the values that take part in the order (a NaN does not)
+    int nGood = 0;
+    for (int i = 0; i < N; ++i) {
+      if (!chosen[i]) continue;
+      const size_t a = (size_t)m1[(size_t)i], q = (size_t)m2[(size_t)i];
+      float p[3], cp;
+      const int code = tv_rt_point(c, v.xy1[2 * a], v.xy1[2 * a + 1], v.xy2[2 * q], v.xy2[2 * q + 1], p, &cp);
+      if (!code) continue;
+      P[3 * a] = p[0]; P[3 * a + 1] = p[1]; P[3 * a + 2] = p[2];
+      G[a] = code == 2 ? 1 : 0;
+      if (cp == cp) cosv.push_back(cp);
+      ++nGood;
+    }
+    r.n_good[j] = nGood;
+    if (nGood > 0) {
+      std::sort(cosv.begin(), cosv.end());
+      const size_t idx = (size_t)std::min(50, nGood - 1);
+      r.parallax[j] = tv_parallax_deg(idx < cosv.size() ? cosv[idx] : np_float(0x7fc00000u));
+    }
+  }
+  if (d.exit_code == kTvFound) d = r.model == 0 ? tv_decide_h(r.n_good, r.parallax, r.n_inliers) : tv_decide_f(r.n_good, r.parallax, r.n_inliers);
+  r.found = d.found; r.exit_code = d.exit_code; r.best = d.best; r.aux = d.aux;
+  for (int k = 0; k < 9; ++k) r.R[k] = d.found ? mo.R[d.best][k] : ((k % 4 == 0) ? 1.0f : 0.0f);
+  for (int k = 0; k < 3; ++k) r.t[k] = d.found ? mo.t[d.best][k] : 0.0f;
+  const size_t w = d.found ? (size_t)d.best : 0;
+  write_two_view_output(in, out, N, r, p3d.data() + 3 * w * (size_t)n1, good.data() + w * (size_t)n1, mask_h.data(), mask_f.data(), score.data(), model.data());
+  return RGBL_OK;
+}
+
+int rgbl_two_view_reconstruct_batch(rgbl_matcher* m, int n_problems, const rgbl_two_view_input* in, rgbl_two_view_output* out) {
+  if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
+  const int B = n_problems;
+  if (B > 32767) { set_error("two view: more than 32767 problems in one call"); return RGBL_ERR_INVALID; }
+  PoolCall pc(m, "two view", "a frame");
+  // offsets of the problems that run: hypotheses, mask words, matches, keys of frame 1
+  std::vector<int> Ns((size_t)B, 0), hyp_off((size_t)B + 1, 0);
+  std::vector<size_t> word_off((size_t)B + 1, 0), match_off((size_t)B + 1, 0), key_off((size_t)B + 1, 0);
+  int max_hyp = 0;
+  for (int b = 0; b < B; ++b) {
+    RGBL_TRY(check_two_view_input(in + b, b, false, &Ns[(size_t)b]));
+    RGBL_TRY(pc.note(nullptr, {in[b].device1, in[b].device2}, b));
+    const bool run = in[b].n_hyp > 0;
+    const int nh = run ? in[b].n_hyp : 0, nn = run ? Ns[(size_t)b] : 0;
+    if (hyp_off[(size_t)b] > INT_MAX / 2 - nh) { set_error("two view: more than 2^30 hypotheses in one call"); return RGBL_ERR_INVALID; }
+    hyp_off[(size_t)b + 1] = hyp_off[(size_t)b] + nh;
+    match_off[(size_t)b + 1] = match_off[(size_t)b] + (size_t)nn;
+    key_off[(size_t)b + 1] = key_off[(size_t)b] + (size_t)(run ? in[b].n1 : 0);   // at most 65535 each: B < 2^15 problems fit an int
+    word_off[(size_t)b + 1] = word_off[(size_t)b] + 2 * (size_t)nh * (size_t)((nn + 63) / 64);
+    max_hyp = std::max(max_hyp, nh);
+  }
+  if (word_off[(size_t)B] > kTvMaxMaskWords) { set_error("two view: more than 2^%d mask words (2 x n_hyp x ceil(N / 64), all problems) in one call", kTvMaxMaskWordsLog2); return RGBL_ERR_INVALID; }
+  if (key_off[(size_t)B] > kTvMaxKeys) { set_error("two view: more than 2^%d keys of frame 1 (all problems with n_hyp > 0) in one call", kTvMaxKeysLog2); return RGBL_ERR_INVALID; }
+  const int H = hyp_off[(size_t)B];
+  const size_t M = match_off[(size_t)B], Kn = key_off[(size_t)B];
+  if (H == 0) {   // nothing to run (B == 0 included)
+    for (int b = 0; b < B; ++b) write_two_view_skipped(out + b);
+    return RGBL_OK;
+  }
+  std::vector<int32_t> m1(M), m2(M);
+  for (int b = 0; b < B; ++b)
+    if (in[b].n_hyp > 0) two_view_matches(in + b, m1.data() + match_off[(size_t)b], m2.data() + match_off[(size_t)b]);
+  RGBL_HIP(hipSetDevice(m->device));
+  StreamDrain drain(m->stream);
+  HostCall hc(m);
+  hipStream_t s = hc.s;
+  std::vector<TvProblem> prob((size_t)B);
+  TvDev D;
+  memset(&D, 0, sizeof(D));
+  bool diag = false;
+  for (int b = 0; b < B; ++b) diag = diag || out[b].scores || out[b].models;
+  RGBL_TRY(hc.begin([&]() -> int {
+    const int32_t *d_m1 = nullptr, *d_m2 = nullptr;
+    hc.put(&d_m1, m1.data(), M);
+    hc.put(&d_m2, m2.data(), M);
+    for (int b = 0; b < B; ++b) {
+      TvProblem& P = prob[(size_t)b];
+      memset(&P, 0, sizeof(P));
+      const rgbl_two_view_input& I = in[b];
+      if (I.n_hyp == 0) continue;   // no workgroup touches it
+      RGBL_TRY(put_features(hc, I.device1, I.n1, nullptr, I.kp1_xy, nullptr, nullptr, nullptr, &P.v.xy1, nullptr, nullptr));
+      RGBL_TRY(put_features(hc, I.device2, I.n2, nullptr, I.kp2_xy, nullptr, nullptr, nullptr, &P.v.xy2, nullptr, nullptr));
+      hc.put(&P.samples, I.samples, (size_t)I.n_hyp * 8);
+      P.v.m1 = d_m1 + match_off[(size_t)b]; P.v.m2 = d_m2 + match_off[(size_t)b];
+      P.v.N = Ns[(size_t)b]; P.v.n1 = I.n1; P.v.n2 = I.n2; P.v.sigma = I.sigma;
+      memcpy(P.v.K, I.K, sizeof(P.v.K));
+      P.n_hyp = I.n_hyp; P.words = (Ns[(size_t)b] + 63) / 64; P.hyp_off = hyp_off[(size_t)b];
+      P.match_off = (int)match_off[(size_t)b]; P.key_off = (int)key_off[(size_t)b]; P.word_off = (unsigned long long)word_off[(size_t)b];
+    }
+    D.prob = hc.stage<TvProblem>((size_t)B, [&](TvProblem* dst) { memcpy(dst, prob.data(), sizeof(TvProblem) * (size_t)B); });
+    D.res = hc.result<TvResult>((size_t)B);   // what comes back, side by side
+    D.p3d_out = hc.result<float>(3 * Kn);
+    D.tri_out = hc.result<uint8_t>(Kn);
+    D.mask_h = hc.result<uint8_t>(M);
+    D.mask_f = hc.result<uint8_t>(M);
+    D.score = diag ? hc.result<float>(2 * (size_t)H) : hc.scratch<float>(2 * (size_t)H);
+    D.model = diag ? hc.result<float>(18 * (size_t)H) : hc.scratch<float>(18 * (size_t)H);
+    D.norm = hc.scratch<float>(8 * (size_t)B);
+    D.mask = hc.scratch<unsigned long long>(word_off[(size_t)B]);
+    D.sel = hc.scratch<TvSelect>((size_t)B);
+    D.n_good = hc.scratch<int32_t>(8 * (size_t)B);
+    D.parallax = hc.scratch<float>(8 * (size_t)B);
+    D.cosv = hc.scratch<float>(8 * M);
+    D.p3d = hc.scratch<float>(24 * Kn);
+    D.good = hc.scratch<uint8_t>(8 * Kn);
+    return RGBL_OK;
+  }));
+  m->timer.begin("k_tv_normalize", s);
+  hipLaunchKernelGGL(k_tv_normalize, dim3(2, (unsigned)B), dim3(64), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  m->timer.begin("k_tv_hypotheses", s);
+  hipLaunchKernelGGL(k_tv_hypotheses, dim3((unsigned)((max_hyp + kTvHypPerGroup - 1) / kTvHypPerGroup), 2, (unsigned)B), dim3(256), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  m->timer.begin("k_tv_select", s);
+  hipLaunchKernelGGL(k_tv_select, dim3((unsigned)B), dim3(256), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  m->timer.begin("k_tv_check_rt", s);
+  hipLaunchKernelGGL(k_tv_check_rt, dim3(kTvMaxMotions, (unsigned)B), dim3(256), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  m->timer.begin("k_tv_decide", s);
+  hipLaunchKernelGGL(k_tv_decide, dim3((unsigned)B), dim3(256), 0, s, D);
+  m->timer.end(s);
+  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(hc.fetch());
+  for (int b = 0; b < B; ++b) {
+    if (in[b].n_hyp == 0) { write_two_view_skipped(out + b); continue; }
+    write_two_view_output(in + b, out + b, Ns[(size_t)b], hc.host(D.res)[b], hc.host(D.p3d_out) + 3 * key_off[(size_t)b], hc.host(D.tri_out) + key_off[(size_t)b],
+                          hc.host(D.mask_h) + match_off[(size_t)b], hc.host(D.mask_f) + match_off[(size_t)b],
+                          diag ? hc.host(D.score) + 2 * (size_t)hyp_off[(size_t)b] : nullptr, diag ? hc.host(D.model) + 18 * (size_t)hyp_off[(size_t)b] : nullptr);
+  }
+  return RGBL_OK;
+}
+
+int rgbl_two_view_reconstruct(rgbl_matcher* m, const rgbl_two_view_input* in, rgbl_two_view_output* out) {
+  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
+  return rgbl_two_view_reconstruct_batch(m, 1, in, out);
 }
 
 // ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:2115-2381) --------------------------------------------------------------

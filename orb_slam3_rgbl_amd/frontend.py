@@ -1451,6 +1451,102 @@ class ORBmatcher:
         return self._mlpnp_result(O, bufs)
 
     @staticmethod
+    def _two_view_input(pr, keep, out=None):
+        """rgbl_two_view_input of a problem dict: xy1 / xy2 (keys x 2) or device1 / device2 (DeviceFrame) with n1 / n2,
+        matches12 (n1 entries, -1 = none), K (fx fy cx cy), sigma, samples (n_hyp x 8 indices into the matches)."""
+        P = out if out is not None else L.TwoViewInput()
+
+        def arr(key, dt):
+            if pr.get(key) is None:
+                return None
+            keep.append(np.ascontiguousarray(pr[key], dt))
+            return keep[-1].ctypes.data
+        P.matches12 = arr("matches12", np.int32)
+        P.kp1_xy, P.kp2_xy = arr("xy1", np.float32), arr("xy2", np.float32)
+        P.device1, P.device2 = _dev(pr, "device1"), _dev(pr, "device2")
+        P.n1 = int(pr["n1"]) if pr.get("n1") is not None else len(np.asarray(pr["matches12"]).reshape(-1))
+        P.n2 = int(pr["n2"]) if pr.get("n2") is not None else len(np.asarray(pr["xy2"]).reshape(-1, 2))
+        K = np.asarray(pr["K"], np.float32).reshape(-1)
+        for i in range(4):
+            P.K[i] = K[i]
+        P.sigma = np.float32(pr.get("sigma", 1.0))
+        P.samples = arr("samples", np.int32)
+        P.n_hyp = int(pr["n_hyp"]) if pr.get("n_hyp") is not None else (0 if pr.get("samples") is None else len(np.asarray(pr["samples"]).reshape(-1, 8)))
+        return P
+
+    @staticmethod
+    def _two_view_buffers(I, O, fill=0, diag=True):
+        """the caller's arrays of one rgbl_two_view_output, pre-filled with `fill` so that what a call leaves untouched can be seen"""
+        n1, nh = max(I.n1, 0), max(I.n_hyp, 0)
+        p3d, tri = np.full((n1, 3), fill, np.float32), np.full(n1, fill, np.uint8)
+        O.p3d, O.triangulated = p3d.ctypes.data, tri.ctypes.data
+        scores = np.full((nh, 2), fill, np.float32) if diag else None
+        models = np.full((nh, 2, 3, 3), fill, np.float32) if diag else None
+        inl_h = np.full(n1, fill, np.uint8) if diag else None     # N <= n1 bytes are written
+        inl_f = np.full(n1, fill, np.uint8) if diag else None
+        O.scores = scores.ctypes.data if diag else None
+        O.models = models.ctypes.data if diag else None
+        O.inliers_h = inl_h.ctypes.data if diag else None
+        O.inliers_f = inl_f.ctypes.data if diag else None
+        return p3d, tri, scores, models, inl_h, inl_f
+
+    @staticmethod
+    def _two_view_result(O, bufs):
+        p3d, tri, scores, models, inl_h, inl_f = bufs
+        return dict(found=int(O.found), model=int(O.model), exit_code=int(O.exit_code), SH=np.float32(O.SH), SF=np.float32(O.SF),
+                    best_h=int(O.best_h), best_f=int(O.best_f), H21=np.array(O.H21, np.float32).reshape(3, 3),
+                    F21=np.array(O.F21, np.float32).reshape(3, 3), R21=np.array(O.R21, np.float32).reshape(3, 3),
+                    t21=np.array(O.t21, np.float32), p3d=p3d, triangulated=tri, p3d_assigned=int(O.p3d_assigned),
+                    n_inliers=int(O.n_inliers), best_motion=int(O.best_motion), aux=int(O.aux), n_good=np.array(O.n_good, np.int32),
+                    parallax=np.array(O.parallax, np.float32), scores=scores, models=models, inliers_h=inl_h, inliers_f=inl_f)
+
+    def prepare_TwoViewReconstructBatch(self, problems, host=False, diag=True, fill=0):
+        """TwoViewReconstruction::Reconstruct (TwoViewReconstruction.cc:41-129) for every problem dict in one upload, one launch
+        sequence and one read-back; the call returns one dict per problem: found, model (0 H, 1 F, -1 none), exit_code, SH, SF,
+        best_h, best_f, H21, F21, R21, t21, p3d (n1 x 3) and triangulated (n1), both written when found, p3d_assigned, n_inliers,
+        best_motion, aux, n_good (8), parallax (8) and, with diag, scores (n_hyp x 2), models (n_hyp x 2 x 3 x 3), inliers_h and
+        inliers_f (the first N of their n1 bytes, per match)."""
+        keep = []
+        B = len(problems)
+        I, O = (L.TwoViewInput * max(B, 1))(), (L.TwoViewOutput * max(B, 1))()
+        bufs = []
+        for b, pr in enumerate(problems):
+            self._two_view_input(pr, keep, I[b])
+            bufs.append(self._two_view_buffers(I[b], O[b], fill, diag))
+        lib, h = self.lib, self.h
+
+        def call(_keep=keep):
+            if host:
+                for b in range(B):
+                    L.check(lib, lib.rgbl_two_view_reconstruct_host(C.byref(I[b]), C.byref(O[b])))
+            else:
+                L.check(lib, lib.rgbl_two_view_reconstruct_batch(h, B, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)))
+            return [self._two_view_result(O[b], bufs[b]) for b in range(B)]
+
+        def c_call(_keep=keep):   # the C call alone (what tools/two_view_bench.py times): the results stay in the structs
+            L.check(lib, lib.rgbl_two_view_reconstruct_batch(h, B, C.cast(I, C.c_void_p), C.cast(O, C.c_void_p)))
+
+        def c_call_host(_keep=keep):
+            for b in range(B):
+                L.check(lib, lib.rgbl_two_view_reconstruct_host(C.byref(I[b]), C.byref(O[b])))
+        call.c_call, call.c_call_host = c_call, c_call_host
+        return call
+
+    def TwoViewReconstructBatch(self, problems, host=False, diag=True, fill=0):
+        return self.prepare_TwoViewReconstructBatch(problems, host, diag, fill)()
+
+    def TwoViewReconstruct(self, problem, host=False, diag=True, fill=0):
+        """One problem through rgbl_two_view_reconstruct (host=True: rgbl_two_view_reconstruct_host, the header's host build)."""
+        keep = []
+        I, O = self._two_view_input(problem, keep), L.TwoViewOutput()
+        bufs = self._two_view_buffers(I, O, fill, diag)
+        if host:
+            L.check(self.lib, self.lib.rgbl_two_view_reconstruct_host(C.byref(I), C.byref(O)))
+        else:
+            L.check(self.lib, self.lib.rgbl_two_view_reconstruct(self.h, C.byref(I), C.byref(O)))
+        return self._two_view_result(O, bufs)
+
+    @staticmethod
     def _sim3_opt_input(cs, keep, out=None):
         """rgbl_sim3_opt_input of a case dict: mp1_index, match_index, i2, track_level2 (per feature of key frame 1), bad and
         world_pos (points x 3) or pool (MapPointPool) + slot, Rcw1, tcw1, Rcw2, tcw2, xy1 / octave1 or device1 (DeviceFrame),
@@ -2043,3 +2139,14 @@ def optimize_sim3_host(case, lib=None, cleared_fill=0):
     O.cleared = clr.ctypes.data
     L.check(lib, lib.rgbl_optimize_sim3_host(C.byref(I), C.byref(O)))
     return ORBmatcher._sim3_opt_result(O, clr)
+
+
+def two_view_reconstruct_host(problem, lib=None, diag=True, fill=0):
+    """rgbl_two_view_reconstruct_host: TwoViewReconstruction by the host build of csrc/twoview_math.h (no device, no handle); the
+    result dict of ORBmatcher.TwoViewReconstruct."""
+    lib = lib or L.load()
+    keep = []
+    I, O = ORBmatcher._two_view_input(problem, keep), L.TwoViewOutput()
+    bufs = ORBmatcher._two_view_buffers(I, O, fill, diag)
+    L.check(lib, lib.rgbl_two_view_reconstruct_host(C.byref(I), C.byref(O)))
+    return ORBmatcher._two_view_result(O, bufs)
