@@ -1313,6 +1313,68 @@ int rgbl_optimize_sim3_batch(rgbl_matcher* h, int n_problems, const rgbl_sim3_op
  * frames and the map side must be host arrays (device1, device2 and pool NULL). */
 int rgbl_optimize_sim3_host(const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out);
 
+/* Optimizer::LocalBundleAdjustment(KeyFrame*, bool* pbStopFlag, Map*, ...)    src/Optimizer.cc:1116-1498, from :1188 on: the
+ * one optimize(10) of LocalMapping's bundle adjustment, ONE problem spread over the device - linearisation per edge, the Schur
+ * complement one workgroup per block of the reduced camera system, its LDL^T, back-substitution per point -, with Levenberg's
+ * scalar control on the host between launches, where the stop flag is polled exactly where g2o polls it.  Single-camera
+ * pinhole key frames, monocular and stereo / RGB-L edges mixed.  csrc/lba_math.h restates the arithmetic and says what is
+ * pinned (every summation order, g2o's Levenberg with its quirks) and what is not (SimplicialLDLT's elimination order,
+ * Eigen's evaluation order).  The graph walk (:1118-1186), the edge loop (:1282-1403) and the write-back (:1413-1497) stay
+ * with the caller. */
+typedef struct {
+  int n_free;                      /* lLocalKeyFrames, in list order; 0 .. 128 */
+  int n_fixed;                     /* lFixedCameras; 0 .. 1024 */
+  const uint8_t* free_is_fixed;    /* n_free bytes (NULL: none): 1 for the map's initial key frame (:1220) */
+  const float* cam_q;              /* (n_free + n_fixed) x 4, free cameras first: GetPose().unit_quaternion() as x, y, z, w */
+  const float* cam_t;              /* (n_free + n_fixed) x 3: GetPose().translation() */
+  const float* cam_K;              /* (n_free + n_fixed) x 4: fx, fy, cx, cy */
+  const float* cam_bf;             /* n_free + n_fixed: mbf */
+  int n_points;                    /* lLocalMapPoints, in list order; 0 .. 2^18 */
+  const float* world_pos;          /* form 1 (pool == NULL): n_points x 3 */
+  rgbl_map_points* pool;           /* form 2: slots of a pool on the matcher's device, each at most once (the call holds the */
+  const int32_t* slot;             /*   pool's mutex for its duration) */
+  int n_edges;                     /* 0 .. 2^20, in the order the reference creates them */
+  const int32_t* edge_point;       /* non-decreasing */
+  const int32_t* edge_cam;         /* an index into free ++ fixed; a (point, camera) pair at most once */
+  const float* edge_obs;           /* n_edges x 3: kpUn.pt.x, kpUn.pt.y, mvuRight (< 0: a monocular edge) */
+  const float* edge_inv_sigma2;    /* mvInvLevelSigma2[kpUn.octave] */
+  int max_iterations;              /* optimize(10) */
+  double user_lambda_init;         /* > 0 replaces computeLambdaInit (:1197-1198: 100 for an inertial map) */
+  const volatile int32_t* stop;    /* pbStopFlag (NULL: none), read where g2o's terminate() reads it */
+  int stop_after_polls;            /* for tests: N > 0 makes the flag read as set from the N-th poll on (poll 1 is :1406) */
+  const volatile uint8_t* stop_byte; /* the same flag as a one-byte C++ bool (NULL: none), read at the same polls: set when either is */
+} rgbl_lba_input;
+typedef struct {
+  int32_t ran;                     /* 0: returned at :1182-1186 (no fixed camera) or :1406-1408 (stop set); nothing else is written */
+  int32_t iterations, trials;      /* solve() calls, and the Levenberg trials of all of them */
+  int32_t rejected, failed;        /* trials that were popped, and trials whose factorisation failed */
+  int32_t active_cams, active_points;
+  int32_t polls;                   /* how often the stop flag was read */
+  double first_chi2, last_chi2;    /* activeRobustChi2 before the first step and Levenberg's currentChi at the end */
+  double last_lambda;
+  double* cam_q;                   /* optional (NULL: not wanted): the vertex estimates in double, n_free x 4 ... */
+  double* cam_t;                   /* ... n_free x 3 ... */
+  double* point;                   /* ... and n_points x 3 */
+} rgbl_lba_diag;
+typedef struct {
+  float* cam_q;                    /* n_free x 4: what :1483-1485 hands to SetPose, x y z w (the estimate cast to float) */
+  float* cam_t;                    /* n_free x 3 */
+  float* point;                    /* n_points x 3: what :1493 hands to SetWorldPos */
+  double* chi2;                    /* n_edges: e->chi2() as :1425 / :1455 read it (the last TRIED step; 0 if never computed) */
+  uint8_t* flags;                  /* n_edges: bit 0 = erase (:1425 / :1455), bit 1 = the depth is not positive */
+  rgbl_lba_diag diag;
+} rgbl_lba_output;
+/* Host pointers, synchronous; every launch goes on the matcher's stream.  A camera or point without an edge is not active and
+ * comes back as the float -> double -> float round trip of its input; a call without any edge runs no iteration.  No fixed
+ * camera at all (n_fixed == 0 and no free_is_fixed) and a stop flag that is set on entry are valid: diag.ran = 0 and no array,
+ * nor the pool, is written.  With a pool the optimised positions are also written into the slots, only when ran = 1.
+ * RGBL_ERR_INVALID, before anything is launched and with every output untouched: a count outside its range above;
+ * edge_point / edge_cam out of range; edge_point decreasing; a repeated (point, camera) pair; a pose, K or bf that is not
+ * finite; a slot outside the pool or listed twice; a pool on another device than the matcher; a missing array. */
+int rgbl_local_bundle_adjustment(rgbl_matcher* h, const rgbl_lba_input* in, rgbl_lba_output* out);
+/* The same call evaluated by the HOST build of csrc/lba_math.h (no device, no handle): the same bits.  pool must be NULL. */
+int rgbl_local_bundle_adjustment_host(const rgbl_lba_input* in, rgbl_lba_output* out);
+
 /* ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>& vbPrevMatched, vector<int>& vnMatches12,
  * int windowSize)    /root/reference/include/ORBmatcher.h:72, src/ORBmatcher.cc:648-763 (Tracking::MonocularInitialization,
  * src/Tracking.cc:2526; not on the RGB-L / stereo path - built so that every search routine of ORBmatcher has a device form).

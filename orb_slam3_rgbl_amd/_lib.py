@@ -159,6 +159,28 @@ class Sim3OptOutput(C.Structure):
                 ("diag", Sim3OptDiag)]
 
 
+class LbaInput(C.Structure):
+    """rgbl_lba_input (the vertices and edges Optimizer::LocalBundleAdjustment hands to g2o, as flat arrays)."""
+    _fields_ = [("n_free", C.c_int), ("n_fixed", C.c_int), ("free_is_fixed", C.c_void_p), ("cam_q", C.c_void_p),
+                ("cam_t", C.c_void_p), ("cam_K", C.c_void_p), ("cam_bf", C.c_void_p), ("n_points", C.c_int),
+                ("world_pos", C.c_void_p), ("pool", C.c_void_p), ("slot", C.c_void_p), ("n_edges", C.c_int),
+                ("edge_point", C.c_void_p), ("edge_cam", C.c_void_p), ("edge_obs", C.c_void_p),
+                ("edge_inv_sigma2", C.c_void_p), ("max_iterations", C.c_int), ("user_lambda_init", C.c_double),
+                ("stop", C.c_void_p), ("stop_after_polls", C.c_int), ("stop_byte", C.c_void_p)]
+
+
+class LbaDiag(C.Structure):
+    _fields_ = [("ran", C.c_int32), ("iterations", C.c_int32), ("trials", C.c_int32), ("rejected", C.c_int32),
+                ("failed", C.c_int32), ("active_cams", C.c_int32), ("active_points", C.c_int32), ("polls", C.c_int32),
+                ("first_chi2", C.c_double), ("last_chi2", C.c_double), ("last_lambda", C.c_double), ("cam_q", C.c_void_p),
+                ("cam_t", C.c_void_p), ("point", C.c_void_p)]
+
+
+class LbaOutput(C.Structure):
+    _fields_ = [("cam_q", C.c_void_p), ("cam_t", C.c_void_p), ("point", C.c_void_p), ("chi2", C.c_void_p),
+                ("flags", C.c_void_p), ("diag", LbaDiag)]
+
+
 class ProjectionInput(C.Structure):
     """rgbl_projection_input (ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) as flat arrays)."""
     _fields_ = [("n1", C.c_int), ("valid1", C.c_void_p), ("world_pos1", C.c_void_p), ("mp_desc1", C.c_void_p),
@@ -403,6 +425,8 @@ SYMBOLS = {
     "rgbl_optimize_sim3": (_I, [_V, C.POINTER(Sim3OptInput), C.POINTER(Sim3OptOutput)]),
     "rgbl_optimize_sim3_batch": (_I, [_V, _I, _V, _V]),
     "rgbl_optimize_sim3_host": (_I, [C.POINTER(Sim3OptInput), C.POINTER(Sim3OptOutput)]),
+    "rgbl_local_bundle_adjustment": (_I, [_V, C.POINTER(LbaInput), C.POINTER(LbaOutput)]),
+    "rgbl_local_bundle_adjustment_host": (_I, [C.POINTER(LbaInput), C.POINTER(LbaOutput)]),
     "rgbl_search_by_bow": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_rig": (_I, [_V, _V, _V, _I, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_keyframes": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),

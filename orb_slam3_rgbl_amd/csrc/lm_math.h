@@ -3,6 +3,8 @@
 // solve, OptimizationAlgorithmLevenberg::solve and the lanes' summation order, restated from
 //   Thirdparty/g2o/g2o/core/{optimization_algorithm_levenberg,sparse_optimizer}.cpp, solvers/linear_solver_dense.h
 // All arithmetic is fp64, no contraction.  OptimizeSim3 calls lm_levenberg; po_optimize carries that loop written out (it says why).
+// lm_solve_n is lm_solve for a run-time n; csrc/lba_math.h (LocalBundleAdjustment) solves its reduced camera system with it and
+// runs lm_levenberg_loop with its own policy: kernel launches (csrc/lba.hip) or host loops, and the caller's stop flag.
 //
 // What is NOT pinned: Eigen's LDLT with its pivoting, replaced by lm_solve (LDL^T without pivoting).  Deviations that follow
 // from the solver and are kept on purpose, for both optimisers:
@@ -21,6 +23,7 @@
 #pragma once
 #include <float.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #ifndef RGBL_HD
@@ -28,6 +31,14 @@
 #define RGBL_HD __host__ __device__ inline
 #else
 #define RGBL_HD inline
+#endif
+#endif
+// the Levenberg loop and its dense policy dissolve into the kernel that runs them
+#ifndef RGBL_HD_FLAT
+#if defined(__HIPCC__)
+#define RGBL_HD_FLAT __host__ __device__ __forceinline__
+#else
+#define RGBL_HD_FLAT inline
 #endif
 #endif
 
@@ -85,8 +96,112 @@ template <int N> RGBL_HD bool lm_solve(const double* Hu, double lambda, const do
   return true;
 }
 
-// SparseOptimizer::optimize(max_it) (sparse_optimizer.cpp:376-414) with OptimizationAlgorithmLevenberg::solve
-// (optimization_algorithm_levenberg.cpp:61-169) on one vertex of N unknowns.
+// lm_solve for a run-time n (csrc/lba_math.h: the reduced camera system of LocalBundleAdjustment).  A holds the LOWER triangle
+// row by row - element (i, j), j <= i, at i (i + 1) / 2 + j -, the diagonal already with its lambda, and is overwritten with L
+// (the diagonal entries with the pivots).  D and y are scratch of n doubles.  Every element is formed exactly as lm_solve<N>
+// forms it: a - sum_p (L_ip * L_jp) * D_p with p ascending, subtracted one at a time; forward, diagonal and backward
+// substitution in lm_solve's order.  A schedule that computes whole elements in parallel (k_lba_factor) gives the same bits.
+// False, x untouched, when a pivot is not finite and > 0.
+RGBL_HD size_t lm_tri(size_t i, size_t j) { return i * (i + 1) / 2 + j; }
+inline bool lm_solve_n(int n, double* A, const double* b, double* x, double* D, double* y) {
+  for (int j = 0; j < n; ++j) {
+    const double* Lj = A + lm_tri((size_t)j, 0);
+    double d = Lj[j];
+    for (int p = 0; p < j; ++p) d = d - Lj[p] * Lj[p] * D[p];
+    if (!(d > 0.0 && d <= DBL_MAX)) return false;
+    D[j] = d;
+    for (int i = j + 1; i < n; ++i) {
+      double* Li = A + lm_tri((size_t)i, 0);
+      double v = Li[j];
+      for (int p = 0; p < j; ++p) v = v - Li[p] * Lj[p] * D[p];
+      Li[j] = v / d;
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    const double* Li = A + lm_tri((size_t)i, 0);
+    double v = b[i];
+    for (int p = 0; p < i; ++p) v = v - Li[p] * y[p];
+    y[i] = v;
+  }
+  for (int i = 0; i < n; ++i) y[i] = y[i] / D[i];
+  for (int i = n - 1; i >= 0; --i) {
+    double v = y[i];
+    for (int p = i + 1; p < n; ++p) v = v - A[lm_tri((size_t)p, (size_t)i)] * x[p];
+    x[i] = v;
+  }
+  return true;
+}
+
+// ---- Levenberg's scalar control: ONE text for 6, 7 and a run-time number of unknowns -------------------------------------------
+// SparseOptimizer::optimize(max_it) (sparse_optimizer.cpp:354-414) with OptimizationAlgorithmLevenberg::solve
+// (optimization_algorithm_levenberg.cpp:61-169).  The solve and the passes over the edges are a policy P:
+//   P.linearise(first, &chi, &maxdiag)    computeActiveErrors, activeRobustChi2 and buildSystem at the current estimate; for the
+//                                         first iteration also computeLambdaInit's largest |diagonal| (:171-185)
+//   P.trial(lambda, &ok, &chi, &scale)    setLambda, solve (ok: the factorisation held), update, computeActiveErrors,
+//                                         activeRobustChi2 there, and computeScale's sum (:187-194)
+//   P.accept()                            discardTop: the trial estimate becomes the current one
+// Each returns false to end the loop at once (a device error of a host-driven policy); the function then returns false.
+// `stop` is terminate(): polled at the start of every iteration (sparse_optimizer.cpp:376, after i < iterations) and after a
+// trial (:149, only when rho < 0 and trials are left).  LmNoStop never stops.  user_lambda_init > 0 replaces computeLambdaInit.
+// Every loop is bounded: max_it x kLmTrials trials.
+struct LmNoStop { RGBL_HD_FLAT bool poll() { return false; } };
+struct LmCounters { int32_t iterations, trials, rejected, failed; double first_chi2, last_chi2, last_lambda; };
+template <class Passes, class Stop>
+RGBL_HD_FLAT bool lm_levenberg_loop(Passes& P, int max_it, double user_lambda_init, Stop& stop, LmCounters& D) {
+  double lambda = 0.0, ni = 2.0, currentChi = 0.0;
+  int lmBad = 0;
+  D.iterations = D.trials = D.rejected = D.failed = 0;
+  D.first_chi2 = D.last_chi2 = D.last_lambda = 0.0;
+  for (int it = 0; it < max_it; ++it) {
+    if (stop.poll()) break;
+    double maxDiagonal = 0.0;
+    if (!P.linearise(it == 0, &currentChi, &maxDiagonal)) return false;
+    const double iniChi = currentChi;
+    double tempChi = currentChi;
+    if (it == 0) {                  // computeLambdaInit: _tau = 1e-5
+      lambda = user_lambda_init > 0.0 ? user_lambda_init : 1e-5 * maxDiagonal;
+      ni = 2.0;
+      lmBad = 0;
+      D.first_chi2 = currentChi;
+    }
+    double rho = 0.0;
+    int qmax = 0;
+    do {
+      bool ok = false;
+      double scale = 0.0;
+      if (!P.trial(lambda, &ok, &tempChi, &scale)) return false;
+      ++D.trials;
+      if (!ok) { tempChi = DBL_MAX; ++D.failed; }
+      rho = currentChi - tempChi;
+      scale += 1e-3;
+      rho /= scale;
+      if (rho > 0.0 && tempChi >= -DBL_MAX && tempChi <= DBL_MAX) {   // g2o_isfinite
+        const double c = 2.0 * rho - 1.0;
+        double alpha = 1.0 - c * c * c;
+        alpha = (2.0 / 3.0 < alpha) ? 2.0 / 3.0 : alpha;                      // std::min(alpha, _goodStepUpperScale)
+        const double scaleFactor = (1.0 / 3.0 < alpha) ? alpha : 1.0 / 3.0;   // std::max(_goodStepLowerScale, alpha)
+        lambda *= scaleFactor;
+        ni = 2.0;
+        currentChi = tempChi;
+        if (!P.accept()) return false;   // discardTop
+      } else {
+        lambda *= ni;
+        ni *= 2.0;                  // pop: the estimate stays; the edges keep the errors of the rejected step
+        ++D.rejected;
+      }
+      ++qmax;
+    } while (rho < 0.0 && qmax < kLmTrials && !stop.poll());
+    ++D.iterations;
+    D.last_chi2 = currentChi;
+    D.last_lambda = lambda;
+    if (qmax == kLmTrials || rho == 0.0) break;   // Terminate
+    if ((iniChi - currentChi) * 1e3 < iniChi) ++lmBad; else lmBad = 0;   // :157-166
+    if (lmBad >= 3) break;
+  }
+  return true;
+}
+
+// The policy of ONE vertex of N unknowns with the dense solve lm_solve<N>.
 //   G, the lanes, owns the problem's edges and the partial sums (LmSystem<N>::kSums per lane):
 //     G.zero()             every lane's partial sums = 0
 //     G.each(f)            f(Edge&, double* acc) for the caller's edges in ascending k (host: every lane in turn)
@@ -98,62 +213,50 @@ template <int N> RGBL_HD bool lm_solve(const double* Hu, double lambda, const do
 //     M.trial(G, x)        forms the trial estimate from x (and may write x: OptimizeSim3's quirk 8); G.zero() and one pass that adds every active edge's robust chi2
 //                          there to sum 0
 //     M.accept()           the trial estimate becomes the current one
-// On the device every work-item runs this function; the scalar state (lambda, x, ...) is computed redundantly and identically
-// by all of them, so the only synchronisation is inside G.  Every loop is bounded: max_it x kLmTrials trials.
-// *iterations = the solve() calls, *chi = the Levenberg currentChi on return (0 for max_it < 1).
-template <int N, class Lanes, class Model>
-RGBL_HD void lm_levenberg(Lanes& G, Model& M, int max_it, double* x, int* iterations, double* chi) {
+template <int N, class Lanes, class Model> struct LmDensePasses {
   typedef LmSystem<N> Sys;
-  double lambda = 0.0, ni = 2.0, currentChi = 0.0;
-  int lmBad = 0, iters = 0;
+  Lanes& G;
+  Model& M;
+  double* x;
+  const double* S;
   double sums[Sys::kSums];
-  for (int it = 0; it < max_it; ++it) {
+  // S must not start as `sums`: with its own array's address in a member the object stays in memory, and k_sim3_opt, whose
+  // lanes return LDS from reduce_system, goes from 364 to 1 696 bytes of scratch per lane and loses its 256 AGPRs
+  RGBL_HD_FLAT LmDensePasses(Lanes& lanes, Model& model, double* xx) : G(lanes), M(model), x(xx), S(nullptr) {}
+  RGBL_HD_FLAT bool linearise(bool first, double* chi, double* maxdiag) {
     M.linearise(G);
-    const double* S = G.reduce_system(sums);
-    currentChi = S[Sys::kChi];
-    const double iniChi = currentChi;
-    double tempChi = currentChi;
-    if (it == 0) {                  // computeLambdaInit (:171-185): _tau = 1e-5
+    S = G.reduce_system(sums);
+    *chi = S[Sys::kChi];
+    if (first) {
       double maxDiagonal = 0.0;
       for (int j = 0; j < N; ++j) { const double a = fabs(S[Sys::diag(j)]); maxDiagonal = a > maxDiagonal ? a : maxDiagonal; }   // std::max(fabs, max)
-      lambda = 1e-5 * maxDiagonal;
-      ni = 2.0;
-      lmBad = 0;
+      *maxdiag = maxDiagonal;
     }
-    double rho = 0.0;
-    int qmax = 0;
-    do {
-      const bool ok = lm_solve<N>(S, lambda, S + Sys::kB, x);
-      M.trial(G, x);
-      tempChi = G.reduce_one();
-      if (!ok) tempChi = DBL_MAX;
-      rho = currentChi - tempChi;
-      double scale = 0.0;           // computeScale (:187-194)
-      for (int j = 0; j < N; ++j) scale += x[j] * (lambda * x[j] + S[Sys::kB + j]);
-      scale += 1e-3;
-      rho /= scale;
-      if (rho > 0.0 && tempChi >= -DBL_MAX && tempChi <= DBL_MAX) {   // g2o_isfinite
-        const double c = 2.0 * rho - 1.0;
-        double alpha = 1.0 - c * c * c;
-        alpha = (2.0 / 3.0 < alpha) ? 2.0 / 3.0 : alpha;                      // std::min(alpha, _goodStepUpperScale)
-        const double scaleFactor = (1.0 / 3.0 < alpha) ? alpha : 1.0 / 3.0;   // std::max(_goodStepLowerScale, alpha)
-        lambda *= scaleFactor;
-        ni = 2.0;
-        currentChi = tempChi;
-        M.accept();                 // discardTop
-      } else {
-        lambda *= ni;
-        ni *= 2.0;                  // pop: the estimate stays; the edges keep the errors of the rejected step
-      }
-      ++qmax;
-    } while (rho < 0.0 && qmax < kLmTrials);
-    ++iters;
-    if (qmax == kLmTrials || rho == 0.0) break;   // Terminate
-    if ((iniChi - currentChi) * 1e3 < iniChi) ++lmBad; else lmBad = 0;   // :157-166
-    if (lmBad >= 3) break;
+    return true;
   }
-  *iterations = iters;
-  *chi = currentChi;
+  RGBL_HD_FLAT bool trial(double lambda, bool* ok, double* chi, double* scale_sum) {
+    *ok = lm_solve<N>(S, lambda, S + Sys::kB, x);
+    M.trial(G, x);
+    *chi = G.reduce_one();
+    double scale = 0.0;
+    for (int j = 0; j < N; ++j) scale += x[j] * (lambda * x[j] + S[Sys::kB + j]);
+    *scale_sum = scale;
+    return true;
+  }
+  RGBL_HD_FLAT bool accept() { M.accept(); return true; }
+};
+
+// lm_levenberg_loop on one vertex of N unknowns.  On the device every work-item runs this function; the scalar state
+// (lambda, x, ...) is computed redundantly and identically by all of them, so the only synchronisation is inside G.
+// *iterations = the solve() calls, *chi = the Levenberg currentChi on return (0 for max_it < 1).
+template <int N, class Lanes, class Model>
+RGBL_HD_FLAT void lm_levenberg(Lanes& G, Model& M, int max_it, double* x, int* iterations, double* chi) {
+  LmDensePasses<N, Lanes, Model> P(G, M, x);
+  LmNoStop never;
+  LmCounters D;
+  lm_levenberg_loop(P, max_it, 0.0, never, D);
+  *iterations = D.iterations;
+  *chi = D.last_chi2;
 }
 
 // The host's execution of the lanes: the partial sums of all 256 lanes side by side, the tree written out.

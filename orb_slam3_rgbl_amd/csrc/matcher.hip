@@ -4402,6 +4402,21 @@ int pool_resize(rgbl_map_points* p, int cap, int keep) {
 }
 }  // namespace
 
+extern "C++" {   // for csrc/lba.hip (common.h)
+int rgbl_internal_matcher_arena(rgbl_matcher* m, size_t dev_bytes, size_t pin_bytes, int* device, hipStream_t* stream,
+                                uint8_t** d_buf, uint8_t** h_pin, KernelTimer** timer) {
+  RGBL_HIP(hipSetDevice(m->device));
+  RGBL_TRY(ensure_arena(m, dev_bytes));
+  RGBL_TRY(ensure_pin(m, pin_bytes));
+  *device = m->device; *stream = m->stream; *d_buf = m->d_buf; *h_pin = m->h_pin; *timer = &m->timer;
+  return RGBL_OK;
+}
+int rgbl_internal_map_points_view(rgbl_map_points* p, int* device, int* cap, float** d_wpos, std::mutex** mu) {
+  *device = p->device; *cap = p->cap; *d_wpos = p->d_wpos; *mu = &p->mu;
+  return RGBL_OK;
+}
+}  // extern "C++"
+
 int rgbl_map_points_create(int device, int capacity, rgbl_map_points** out) {
   if (!out) { set_error("null argument"); return RGBL_ERR_INVALID; }
   *out = nullptr;

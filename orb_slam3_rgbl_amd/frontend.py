@@ -1644,6 +1644,14 @@ class ORBmatcher:
             L.check(self.lib, self.lib.rgbl_optimize_sim3(self.h, C.byref(I), C.byref(O)))
         return self._sim3_opt_result(O, clr)
 
+    def LocalBundleAdjustment(self, case, host=False, fill=0):
+        """Optimizer::LocalBundleAdjustment from :1188 on through rgbl_local_bundle_adjustment (host=True: the header's host
+        build, no device).  case: an lba_cases.make_lba_case-style dict (local_bundle_adjustment_call lists its keys)."""
+        return local_bundle_adjustment_call(self.lib, None if host else self.h, case, fill)()
+
+    def prepare_LocalBundleAdjustment(self, case, fill=0):
+        return local_bundle_adjustment_call(self.lib, self.h, case, fill)
+
     def CreateNewMapPoints(self, kf1, neighbours, prm, skip=None, cap=None):
         return self.prepare_CreateNewMapPoints(kf1, neighbours, prm, skip, cap)()
 
@@ -2139,6 +2147,65 @@ def optimize_sim3_host(case, lib=None, cleared_fill=0):
     O.cleared = clr.ctypes.data
     L.check(lib, lib.rgbl_optimize_sim3_host(C.byref(I), C.byref(O)))
     return ORBmatcher._sim3_opt_result(O, clr)
+
+
+def local_bundle_adjustment_call(lib, handle, case, fill=0):
+    """The call of rgbl_local_bundle_adjustment (handle None: rgbl_local_bundle_adjustment_host) on a case dict:
+    n_free, n_fixed, free_is_fixed (optional), cam_q, cam_t, cam_K, cam_bf, world_pos (or pool = MapPointPool with slot),
+    edge_point, edge_cam, edge_obs, edge_inv_sigma2; optional max_iterations (10), user_lambda_init (0), stop (an int32 array
+    of one element), stop_byte (a uint8 array of one element) and stop_after_polls (0).  Every output array starts as `fill` bytes, so a test sees what a call left
+    untouched.  Returns a callable that gives dict(cam_q, cam_t, point, chi2, flags, q, t, X (the estimates in double) and
+    the diag's scalars); its .outputs holds the raw arrays."""
+    def arr(key, dt):
+        v = case.get(key)
+        return None if v is None else np.ascontiguousarray(v, dt)
+    nf, nx = int(case["n_free"]), int(case["n_fixed"])
+    a = dict(free_is_fixed=arr("free_is_fixed", np.uint8), cam_q=arr("cam_q", np.float32), cam_t=arr("cam_t", np.float32),
+             cam_K=arr("cam_K", np.float32), cam_bf=arr("cam_bf", np.float32), world_pos=arr("world_pos", np.float32),
+             slot=arr("slot", np.int32), edge_point=arr("edge_point", np.int32), edge_cam=arr("edge_cam", np.int32),
+             edge_obs=arr("edge_obs", np.float32), edge_inv_sigma2=arr("edge_inv_sigma2", np.float32),
+             stop=arr("stop", np.int32), stop_byte=arr("stop_byte", np.uint8))
+    pool = case.get("pool")
+    n_points = int(case["n_points"]) if "n_points" in case else (len(a["slot"]) if pool is not None else a["world_pos"].size // 3)
+    n_edges = int(case["n_edges"]) if "n_edges" in case else (0 if a["edge_point"] is None else len(a["edge_point"]))
+    I = L.LbaInput()
+    I.n_free, I.n_fixed, I.n_points, I.n_edges = nf, nx, n_points, n_edges
+    for k in ("free_is_fixed", "cam_q", "cam_t", "cam_K", "cam_bf", "slot", "edge_point", "edge_cam", "edge_obs",
+              "edge_inv_sigma2", "stop", "stop_byte"):
+        setattr(I, k, L.ptr(a[k]))
+    I.world_pos = L.ptr(a["world_pos"]) if pool is None else None
+    I.pool = pool.h if pool is not None else None
+    I.max_iterations = int(case.get("max_iterations", 10))
+    I.user_lambda_init = float(case.get("user_lambda_init", 0.0))
+    I.stop_after_polls = int(case.get("stop_after_polls", 0))
+    byte = np.uint8(fill)
+    def filled(shape, dt):
+        shape = tuple(max(int(v), 0) for v in shape)   # a negative count is the library's to refuse
+        return np.full(int(np.prod(shape)) * np.dtype(dt).itemsize, byte, np.uint8).view(dt).reshape(shape)
+    o = dict(cam_q=filled((nf, 4), np.float32), cam_t=filled((nf, 3), np.float32), point=filled((n_points, 3), np.float32),
+             chi2=filled((n_edges,), np.float64), flags=filled((n_edges,), np.uint8), q=filled((nf, 4), np.float64),
+             t=filled((nf, 3), np.float64), X=filled((n_points, 3), np.float64))
+    O = L.LbaOutput()
+    C.memset(C.byref(O), int(byte), C.sizeof(O))
+    O.cam_q, O.cam_t, O.point, O.chi2, O.flags = [L.ptr(o[k]) for k in ("cam_q", "cam_t", "point", "chi2", "flags")]
+    O.diag.cam_q, O.diag.cam_t, O.diag.point = L.ptr(o["q"]), L.ptr(o["t"]), L.ptr(o["X"])
+
+    def call(_keep=(a, pool)):
+        if handle is None:
+            L.check(lib, lib.rgbl_local_bundle_adjustment_host(C.byref(I), C.byref(O)))
+        else:
+            L.check(lib, lib.rgbl_local_bundle_adjustment(handle, C.byref(I), C.byref(O)))
+        r = dict(o)
+        for k, _ in L.LbaDiag._fields_[:11]:
+            r[k] = getattr(O.diag, k)
+        return r
+    call.outputs, call.raw = o, O
+    return call
+
+
+def local_bundle_adjustment_host(case, lib=None, fill=0):
+    """rgbl_local_bundle_adjustment_host: the host build of csrc/lba_math.h (no device)."""
+    return local_bundle_adjustment_call(lib or L.load(), None, case, fill)()
 
 
 def two_view_reconstruct_host(problem, lib=None, diag=True, fill=0):
