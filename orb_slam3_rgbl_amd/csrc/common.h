@@ -154,12 +154,6 @@ int rgbl_internal_resize_enqueue(rgbl_resizer* r, hipStream_t s, const uint8_t* 
                                  size_t src_frame, uint8_t* d_dst, int dst_stride, size_t dst_frame);
 int rgbl_internal_resizer_info(const rgbl_resizer* r, int* device, int* src_w, int* src_h, int* dst_w, int* dst_h);
 
-// matcher.hip, for lba.hip: the matcher's device, stream, timer and its grow-only arena with the page-locked mirror grown to
-// at least dev_bytes / pin_bytes; and a pool's device, capacity, positions and the mutex a call holds while it uses them
-int rgbl_internal_matcher_arena(rgbl_matcher* m, size_t dev_bytes, size_t pin_bytes, int* device, hipStream_t* stream,
-                                uint8_t** d_buf, uint8_t** h_pin, rgbl::KernelTimer** timer);
-int rgbl_internal_map_points_view(rgbl_map_points* p, int* device, int* cap, float** d_wpos, std::mutex** mu);
-
 namespace rgbl {
 
 // ---- device helpers ----------------------------------------------------------------------------

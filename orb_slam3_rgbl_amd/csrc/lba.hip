@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "matcher_call.h"
 #include "lba_math.h"
 
 namespace rgbl {
@@ -446,21 +447,19 @@ namespace {
 // the device's execution of the passes: launches on the matcher's stream, one record read back per pass
 struct LbaDeviceBackend {
   LbaView V;
+  rgbl_matcher* m;
   hipStream_t s;
-  KernelTimer* timer;
   LbaRecord* h_rec;   // page-locked
-  int rc = RGBL_OK;
+  int rc = RGBL_OK;   // the first error of a launch or a copy; nothing is launched behind it
   static unsigned blocks(int items) { return (unsigned)((items + kLbaBlock - 1) / kLbaBlock); }
-  template <class... Args, class... Given> void launch(const char* name, void (*k)(Args...), dim3 grid, dim3 block, Given... given) {
-    timer->begin(name, s);
-    hipLaunchKernelGGL(k, grid, block, 0, s, given...);
-    timer->end(s);
+  template <class... Params, class... Args> void launch(const char* name, void (*k)(Params...), dim3 grid, dim3 block, const Args&... args) {
+    if (rc == RGBL_OK) rc = rgbl::launch(m, s, name, k, grid, block, 0, args...);
   }
   int fetch() {
-    RGBL_HIP(hipGetLastError());
+    RGBL_TRY(rc);
     RGBL_HIP(hipMemcpyAsync(h_rec, V.rec, sizeof(LbaRecord), hipMemcpyDeviceToHost, s));
     RGBL_HIP(hipStreamSynchronize(s));
-    timer->collect();
+    m->timer.collect();
     return RGBL_OK;
   }
   bool linearise(bool, double* chi, double* maxdiag) {
@@ -495,23 +494,17 @@ int rgbl_local_bundle_adjustment(rgbl_matcher* m, const rgbl_lba_input* in, rgbl
   if (!m || !in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
   LbaProblem P;
   RGBL_TRY(check_lba_input(in, false, P));
-  std::unique_lock<std::mutex> pool_lock;
-  float* d_wpos = nullptr;
-  if (in->pool) {
-    int pool_device = 0, cap = 0;
-    std::mutex* mu = nullptr;
-    RGBL_TRY(rgbl_internal_map_points_view(in->pool, &pool_device, &cap, &d_wpos, &mu));
-    pool_lock = std::unique_lock<std::mutex>(*mu);
-    RGBL_TRY(rgbl_internal_map_points_view(in->pool, &pool_device, &cap, &d_wpos, &mu));   // under the lock: what holds now
-    int device = 0; hipStream_t s0; uint8_t *b0, *p0; KernelTimer* t0;
-    RGBL_TRY(rgbl_internal_matcher_arena(m, 0, 0, &device, &s0, &b0, &p0, &t0));
-    if (pool_device != device) { set_error("local BA: the pool is on device %d, the matcher on %d", pool_device, device); return RGBL_ERR_INVALID; }
+  PoolCall pc(m, "local BA", "a frame");
+  RGBL_TRY(pc.note(in->pool, {}, -1));
+  RGBL_TRY(pc.lock(1, [&](int) -> int {   // the smallest slot below 0, else the largest beyond the pool, else the first listed twice
     std::vector<int32_t> sorted(in->slot, in->slot + P.nP);
     std::sort(sorted.begin(), sorted.end());
-    if (P.nP > 0 && (sorted.front() < 0 || sorted.back() >= cap)) { set_error("local BA: slot %d outside [0, %d)", sorted.front() < 0 ? sorted.front() : sorted.back(), cap); return RGBL_ERR_INVALID; }
+    if (P.nP > 0 && !(pc.holds(sorted.front()) && pc.holds(sorted.back()))) { set_error("local BA: slot %d outside [0, %d)", sorted.front() < 0 ? sorted.front() : sorted.back(), pc.pool->cap); return RGBL_ERR_INVALID; }
     for (int p = 0; p + 1 < P.nP; ++p)
       if (sorted[(size_t)p] == sorted[(size_t)p + 1]) { set_error("local BA: slot %d is listed twice", sorted[(size_t)p]); return RGBL_ERR_INVALID; }
-  }
+    return RGBL_OK;
+  }));
+  float* d_wpos = pc.pool ? pc.pool->d_wpos : nullptr;
   RGBL_TRY(build_lba_structure(in, P));
   LbaStop stop = {in->stop, in->stop_byte, in->stop_after_polls, 0};
   if (lba_returns_early(P, stop)) { write_lba_early(out, stop); return RGBL_OK; }
@@ -522,11 +515,13 @@ int rgbl_local_bundle_adjustment(rgbl_matcher* m, const rgbl_lba_input* in, rgbl
   const LbaOffsets O = lba_offsets(P);
   // the page-locked side: the record, then what comes back (T | X | e_chi2 | flags)
   const size_t back_begin = O.T, back_end = O.flags + (size_t)P.nE, pin_back = 256;
-  int device = 0;
+  RGBL_HIP(hipSetDevice(m->device));
+  RGBL_TRY(ensure_arena(m, O.total));
+  RGBL_TRY(ensure_pin(m, pin_back + (back_end - back_begin)));
   LbaDeviceBackend B;
-  uint8_t *d_buf = nullptr, *h_pin = nullptr;
-  RGBL_TRY(rgbl_internal_matcher_arena(m, O.total, pin_back + (back_end - back_begin), &device, &B.s, &d_buf, &h_pin, &B.timer));
-  StreamDrain drain(B.s);   // behind pool_lock: the stream is idle before the pool is released
+  B.m = m; B.s = m->stream;
+  uint8_t *d_buf = m->d_buf, *h_pin = m->h_pin;
+  StreamDrain drain(B.s);   // behind pc (PoolCall): the stream is idle before the pool is released
   B.V = lba_view(P, O, d_buf);
   B.h_rec = reinterpret_cast<LbaRecord*>(h_pin);
   RGBL_HIP(hipMemsetAsync(d_buf, 0, O.total, B.s));
@@ -544,10 +539,10 @@ int rgbl_local_bundle_adjustment(rgbl_matcher* m, const rgbl_lba_input* in, rgbl
   if (!done) return B.rc;
   if (P.nE > 0) B.launch("k_lba_flags", k_lba_flags, dim3(B.blocks(P.nE)), dim3(kLbaBlock), B.V);
   if (in->pool && P.nP > 0) B.launch("k_lba_pool_write", k_lba_pool_write, dim3(B.blocks(P.nP)), dim3(kLbaBlock), B.V, d_wpos, d_slot);
-  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(B.rc);
   RGBL_HIP(hipMemcpyAsync(h_pin + pin_back, d_buf + back_begin, back_end - back_begin, hipMemcpyDeviceToHost, B.s));
   RGBL_HIP(hipStreamSynchronize(B.s));
-  B.timer->collect();
+  m->timer.collect();
   const uint8_t* back = h_pin + pin_back - back_begin;
   write_lba_output(in, out, P, reinterpret_cast<const PoPose*>(back + O.T), reinterpret_cast<const double*>(back + O.X),
                    reinterpret_cast<const double*>(back + O.e_chi2), back + O.flags, D, stop);

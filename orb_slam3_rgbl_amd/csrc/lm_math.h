@@ -19,7 +19,7 @@
 // Summation order (host, emulator and GPU agree bit for bit).  Edge k, in ascending feature index, belongs to lane k mod 256;
 // a lane adds its edges in ascending k; the 256 partial sums are combined by the fixed tree v[i] = v[i] + v[i + s] for
 // s = 128, 64, ..., 1.  This holds for every sum of a system and for every single sum.  LmHostLanes below is the host's
-// execution of it, lm_tree_reduce of csrc/matcher.hip the workgroup's.
+// execution of it, lm_tree_reduce of csrc/optimize.hip the workgroup's.
 #pragma once
 #include <float.h>
 #include <math.h>

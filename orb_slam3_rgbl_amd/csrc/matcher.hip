@@ -11,6 +11,14 @@
 //   k_search_triangulation one workgroup per BoW node shared by both key-frames, both buckets staged in LDS, one
 //                         query feature per wave, the candidates over its lanes (ties -> later candidate wins, as
 //                         in the reference) with the eligibility masks and epipolar test.
+//
+// What else lives here, each under its own heading: the matrix-core forms of the scan (k_hamming_mfma, k_hamming_fp4), the
+// projection, fuse, local-map and initialisation searches (k_proj_*, k_fuse_search, k_local_*, k_init_*), SearchByBoW and the
+// vocabulary descent (k_search_by_bow*, k_bow_descend), CreateNewMapPoints (k_new_points), the frustum test, the map-point
+// pool and its refresh (k_frustum, k_map_points_scatter, k_map_refresh_*), and the handles: matcher, matcher pool, resident
+// frames, map points, vocabulary.  The scaffold of a host-pointer call is csrc/matcher_call.h; the geometry solvers that
+// share it are csrc/optimize.hip (PoseOptimization, OptimizeSim3), csrc/ransac.hip (Sim3Solver, MLPnPsolver,
+// TwoViewReconstruction) and csrc/lba.hip (LocalBundleAdjustment).
 #include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,14 +33,10 @@
 #include <vector>
 
 #include "common.h"
+#include "matcher_call.h"
 #include "frustum_math.h"
 #include "logf_glibc.h"
-#include "mlpnp_math.h"
-#include "twoview_math.h"
 #include "newpoint_math.h"
-#include "poseopt_math.h"
-#include "sim3_math.h"
-#include "sim3opt_math.h"
 
 namespace rgbl {
 
@@ -866,861 +870,6 @@ __global__ void k_test_np_cos_parallax(float mb, const float* __restrict__ depth
 }
 
 // ------------------------------------------------------------------------------------------------
-// Optimizer::PoseOptimization (src/Optimizer.cc:814-1114): k_pose_opt, one workgroup of 256 work-items per problem.  The
-// algorithm is po_optimize of csrc/poseopt_math.h, run by every work-item: the scalar state (pose, lambda, the 6 x 6 solve,
-// the update) is computed redundantly and identically, the edges are spread over the lanes (edge k on lane k mod 256).  No
-// communication between workgroups, no atomics; the barriers of lm_tree_reduce are the only synchronisation and every
-// work-item reaches every one of them (all branches around them depend on reduced values only).  Every loop is bounded by
-// 4 rounds x 10 iterations x 10 trials.
-struct PoseOptProblem {
-  const float* xy;       // the frame's mvKeysUn (resident or staged)
-  const int32_t* oct;
-  const float* ur;
-  const float* wpos;     // world positions: the call's staged array or the pool's
-  const float* sigma;    // mvInvLevelSigma2
-  int edge_off, m, n_levels;
-  float q[4], t[3], K[4], bf;
-};
-struct PoseOptDev {
-  const PoseOptProblem* prob;
-  const int32_t* feat;   // per correspondence (all problems back to back): the feature ...
-  const int32_t* point;  // ... and its row of wpos
-  double* chi2;          // the state of the edges beyond 8 per lane
-  uint8_t* level;        // every edge's level: the result, and the state of the edges beyond 8 per lane (starts 0)
-  float* pose;           // 8 floats per problem: q, t
-  int32_t* ret;
-  PoDiag* diag;
-};
-
-__device__ __forceinline__ PoEdge pose_opt_edge(const PoseOptProblem& pb, const PoseOptDev& D, int k) {
-  const int f = D.feat[pb.edge_off + k], p = D.point[pb.edge_off + k];
-  PoEdge e;
-  e.Xw[0] = pb.wpos[3 * (size_t)p]; e.Xw[1] = pb.wpos[3 * (size_t)p + 1]; e.Xw[2] = pb.wpos[3 * (size_t)p + 2];
-  e.obs[0] = pb.xy[2 * f]; e.obs[1] = pb.xy[2 * f + 1]; e.obs[2] = pb.ur[f];
-  const int oc = pb.oct[f], o = oc < 0 ? 0 : (oc >= pb.n_levels ? pb.n_levels - 1 : oc);   // host arrays are checked before the launch
-  e.info = pb.sigma[o];
-  e.stereo = e.obs[2] >= 0.0f ? 1 : 0;   // !(mvuRight[i] < 0) (:866)
-  e.level = 0;
-  e.chi2 = 0.0;
-  return e;
-}
-
-// The workgroup's execution of csrc/lm_math.h's fixed tree v[i] = v[i] + v[i + s] over the first N sums of every lane's acc:
-// lanes 64 .. 255 put their sums into LDS and wave 0 forms (v[i] + v[i + 128]) + (v[i + 64] + v[i + 192]), which is what s = 128
-// and s = 64 leave in lane i < 64; s = 32 .. 1 run inside wave 0 (lane i reads lane i + s; lanes >= s compute values nobody
-// reads), all sums side by side so that the cross-lane reads overlap; lane 0 writes the result to dst (LDS), where every
-// work-item reads it.  Two barriers.
-constexpr int kLmTreeLds = kLmLanes - 64;   // the partial sums of lanes 64 .. 255
-template <int N> __device__ __forceinline__ void lm_tree_reduce(const double* acc, double (*red)[kLmTreeLds], double* dst, int tid) {
-  if (tid >= 64) {
-#pragma unroll
-    for (int c = 0; c < N; ++c) red[c][tid - 64] = acc[c];
-  }
-  __syncthreads();
-  if (tid < 64) {
-    double v[N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) v[c] = (acc[c] + red[c][tid + 64]) + (red[c][tid] + red[c][tid + 128]);
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-      for (int c = 0; c < N; ++c) v[c] = v[c] + __shfl_down(v[c], (unsigned)s);
-    }
-    if (tid == 0) {
-#pragma unroll
-      for (int c = 0; c < N; ++c) dst[c] = v[c];
-    }
-  }
-  __syncthreads();
-}
-
-struct PoDevLanes {
-  PoEdge r[kPoRegEdges];   // edges tid, tid + 256, ... in registers
-  double acc[kPoSums];
-  const PoseOptProblem* pb;
-  const PoseOptDev* D;
-  double (*red)[kLmTreeLds];
-  double* bc;
-  int tid, m;
-  __device__ void zero() {
-#pragma unroll
-    for (int c = 0; c < kPoSums; ++c) acc[c] = 0.0;
-  }
-  template <class F> __device__ void each(F f) {
-#pragma unroll
-    for (int j = 0; j < kPoRegEdges; ++j)
-      if (tid + kPoLanes * j < m) f(r[j], acc);
-    for (int k = tid + kPoLanes * kPoRegEdges; k < m; k += kPoLanes) {   // beyond 2048 correspondences: global memory
-      PoEdge e = pose_opt_edge(*pb, *D, k);
-      e.chi2 = D->chi2[pb->edge_off + k];
-      e.level = D->level[pb->edge_off + k];
-      f(e, acc);
-      D->chi2[pb->edge_off + k] = e.chi2;
-      D->level[pb->edge_off + k] = e.level;
-    }
-  }
-  // every work-item copies the system's 28 sums from bc to registers (the trials' solves read them there: measured against
-  // reading them from LDS, docs/history/r15_measured.md), so the single sum can go through bc[0]
-  __device__ const double* reduce_system(double* S) {
-    lm_tree_reduce<kPoSums>(acc, red, bc, tid);
-#pragma unroll
-    for (int c = 0; c < kPoSums; ++c) S[c] = bc[c];
-    return S;
-  }
-  __device__ double reduce_one() { lm_tree_reduce<1>(acc, red, bc, tid); return bc[0]; }
-};
-
-__global__ __launch_bounds__(kPoLanes) void k_pose_opt(PoseOptDev D) {
-  __shared__ double s_red[kPoSums][kLmTreeLds];   // 42 KB
-  __shared__ double s_bc[kPoSums];
-  const PoseOptProblem& pb = D.prob[blockIdx.x];
-  PoDevLanes G;
-  G.pb = &pb; G.D = &D; G.red = s_red; G.bc = s_bc; G.tid = (int)threadIdx.x; G.m = pb.m;
-#pragma unroll
-  for (int j = 0; j < kPoRegEdges; ++j) {
-    const int k = G.tid + kPoLanes * j;
-    if (k < pb.m) G.r[j] = pose_opt_edge(pb, D, k);
-  }
-  const PoCam C = {(double)pb.K[0], (double)pb.K[1], (double)pb.K[2], (double)pb.K[3], (double)pb.bf};
-  const PoPose entry = po_pose_from_float(pb.q, pb.t);
-  PoPose out;
-  PoDiag diag;
-  const int ret = po_optimize(G, C, entry, pb.m, out, diag);
-#pragma unroll
-  for (int j = 0; j < kPoRegEdges; ++j) {
-    const int k = G.tid + kPoLanes * j;
-    if (k < pb.m) D.level[pb.edge_off + k] = G.r[j].level;
-  }
-  if (threadIdx.x == 0) {
-    float* o = D.pose + 8 * (size_t)blockIdx.x;
-    for (int i = 0; i < 4; ++i) o[i] = (float)out.q[i];
-    for (int i = 0; i < 3; ++i) o[4 + i] = (float)out.t[i];
-    o[7] = 0.0f;
-    D.ret[blockIdx.x] = ret;
-    D.diag[blockIdx.x] = diag;
-  }
-}
-
-// test hook: the header's sin / cos and the fp64 quotient and square root on the device (op 0: sin, 1: cos, 2: x / y, 3: sqrt)
-__global__ void k_test_po_math(int op, const double* __restrict__ x, const double* __restrict__ y, double* __restrict__ z, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  z[i] = op == 0 ? po_sin(x[i]) : op == 1 ? po_cos(x[i]) : op == 2 ? x[i] / y[i] : sqrt(x[i]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Optimizer::OptimizeSim3 (src/Optimizer.cc:2115-2381): k_sim3_opt, one workgroup of 256 work-items per problem, after
-// k_pose_opt.  The algorithm is so_optimize of csrc/sim3opt_math.h, run by every work-item: the scalar state (estimate, lambda,
-// the 7 x 7 solve, the update) is computed redundantly and identically, the edge pairs are spread over the lanes (pair k on
-// lane k mod 256).  The host hands over the CANDIDATES (the features that pass :2169-2233); the workgroup forms P3D2c, applies
-// the float test of :2235 and numbers the survivors in ascending feature index with a ballot scan, 256 candidates at a time
-// (at most 256 chunks).  The 30 transforms of a linearisation are computed by work-items 0 .. 14 and kept in LDS.  No
-// communication between workgroups, no atomics; every work-item reaches every barrier (all branches around them depend on
-// reduced values only).  The optimiser's loops are bounded by (5 + 10) iterations x 10 trials.
-struct Sim3OptProblem {
-  const float *xy1, *xy2;        // mvKeysUn of both key frames (resident or staged)
-  const int32_t *oct1, *oct2;
-  const float* wpos;             // world positions: the call's staged array or the pool's
-  const float *sig1, *sig2;      // mvInvLevelSigma2 of both
-  int cand_off, n_cand, n_levels1, n_levels2, fix_scale;
-  float th2;
-  float Rcw1[9], tcw1[3], Rcw2[9], tcw2[3], K1[4], K2[4];
-  SoSim3 entry;
-  SoDiag diag;                   // the host's counters (n_bad_mps, n_without_mp); the others are the kernel's
-};
-struct Sim3OptOut {
-  SoSim3 est;
-  SoDiag diag;
-  int32_t ret, reserved;
-};
-struct Sim3OptDev {
-  const Sim3OptProblem* prob;
-  const int32_t *feat, *p1, *p2, *i2, *lvl2;   // per candidate (all problems back to back): feature, rows of wpos, i2, mnTrackScaleLevel
-  int32_t* corr;       // per correspondence k of a problem (at cand_off + k): its candidate
-  double* chi;         // the state of the pairs beyond 8 per lane: chi12, chi21 ...
-  uint8_t* state;      // ... and gone | cleared << 1
-  uint8_t* cleared;    // per candidate: the result (2: no edge pair)
-  Sim3OptOut* out;
-};
-
-__device__ __forceinline__ int clamp_level(int o, int n_levels) { return o < 0 ? 0 : (o >= n_levels ? n_levels - 1 : o); }   // host arrays are checked before the launch
-
-__device__ __forceinline__ bool sim3_opt_edge(const Sim3OptProblem& pb, const Sim3OptDev& D, int c, SoEdge& e) {
-  const int g = pb.cand_off + c, f = D.feat[g], i2 = D.i2[g];
-  const float info1 = pb.sig1[clamp_level(pb.oct1[f], pb.n_levels1)];
-  const float info2 = pb.sig2[clamp_level(i2 >= 0 ? pb.oct2[i2] : D.lvl2[g], pb.n_levels2)];
-  return so_make_edge(pb.Rcw1, pb.tcw1, pb.Rcw2, pb.tcw2, pb.wpos + 3 * (size_t)D.p1[g], pb.wpos + 3 * (size_t)D.p2[g], pb.xy1 + 2 * (size_t)f,
-                      info1, i2 >= 0, pb.xy2 + 2 * (size_t)(i2 >= 0 ? i2 : 0), info2, e);
-}
-
-// A pair's twelve floats are used as doubles in every pass over the edges.  Left alone, the compiler converts them once and
-// keeps the doubles for the whole kernel: 24 more registers per pair.  An empty statement the value passes through makes the
-// conversion belong to the pass.
-#ifdef RGBL_EMU
-#define SO_OPAQUE(x) ((void)0)
-#else
-#define SO_OPAQUE(x) asm volatile("" : "+v"(x))
-#endif
-struct SoDevLanes {
-  SoEdge r[kSoRegEdges];   // pairs tid, tid + 256, ... in registers
-  double acc[kSoSums];
-  const Sim3OptProblem* pb;
-  const Sim3OptDev* D;
-  double (*red)[kLmTreeLds];
-  double* bc;
-  SoSim3* T;
-  int tid, m;
-  __device__ void zero() {
-#pragma unroll
-    for (int c = 0; c < kSoSums; ++c) acc[c] = 0.0;
-  }
-  template <class F> __device__ void each(F f) {
-#pragma unroll
-    for (int j = 0; j < kSoRegEdges; ++j) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) { SO_OPAQUE(r[j].X1[c]); SO_OPAQUE(r[j].X2[c]); }
-      SO_OPAQUE(r[j].obs1[0]); SO_OPAQUE(r[j].obs1[1]); SO_OPAQUE(r[j].obs2[0]); SO_OPAQUE(r[j].obs2[1]);
-      SO_OPAQUE(r[j].info1); SO_OPAQUE(r[j].info2);
-      if (tid + kSoLanes * j < m) f(r[j], acc);
-    }
-    for (int k = tid + kSoLanes * kSoRegEdges; k < m; k += kSoLanes) {   // beyond 2048 correspondences: global memory
-      const size_t g = (size_t)pb->cand_off + (size_t)k;
-      SoEdge e;
-      sim3_opt_edge(*pb, *D, D->corr[g], e);
-      e.chi12 = D->chi[2 * g]; e.chi21 = D->chi[2 * g + 1];
-      e.gone = D->state[g] & 1; e.cleared = D->state[g] >> 1;
-      f(e, acc);
-      D->chi[2 * g] = e.chi12; D->chi[2 * g + 1] = e.chi21;
-      D->state[g] = (uint8_t)(e.gone | (e.cleared << 1));
-    }
-  }
-  // the system's 36 sums stay in bc[0 .. 35] for the trials' solves; the single sum goes through bc[36]
-  __device__ const double* reduce_system(double*) { lm_tree_reduce<kSoSums>(acc, red, bc, tid); return bc; }
-  __device__ double reduce_one() { lm_tree_reduce<1>(acc, red, bc + kSoSums, tid); return bc[kSoSums]; }
-  // work-item j < 14 forms perturbed estimate j and its inverse, work-item 14 the estimate's inverse; the readers of the
-  // previous linearisation are behind the barriers of the reductions in between
-  __device__ const SoSim3* transforms(const SoSim3& S, bool fix_scale) {
-    if (tid < 14) {
-      const SoSim3 P = so_perturbed(S, tid, fix_scale);
-      T[2 + tid] = P;
-      T[16 + tid] = so_inverse(P);
-    } else if (tid == 14) {
-      T[0] = S;
-      T[1] = so_inverse(S);
-    }
-    __syncthreads();
-    return T;
-  }
-};
-
-__global__ __launch_bounds__(kSoLanes) void k_sim3_opt(Sim3OptDev D) {
-  __shared__ double s_red[kSoSums][kLmTreeLds];   // 54 KB
-  __shared__ double s_bc[kSoSums + 1];
-  __shared__ SoSim3 s_T[kSoTransforms];           // 1920 B
-  __shared__ int s_cnt[4][2];
-  const Sim3OptProblem& pb = D.prob[blockIdx.x];
-  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  // :2235 and the numbering of the correspondences
-  int m = 0, n_in = 0;
-  for (int c0 = 0; c0 < pb.n_cand; c0 += kSoLanes) {   // uniform
-    const int c = c0 + tid;
-    bool keep = false, in2 = false;
-    if (c < pb.n_cand) {
-      float X2[3];
-      s3_transform(pb.Rcw2, pb.tcw2, pb.wpos + 3 * (size_t)D.p2[pb.cand_off + c], X2);
-      keep = !(X2[2] < 0.0f);
-      in2 = keep && D.i2[pb.cand_off + c] >= 0;
-    }
-    const unsigned long long bk = __ballot(keep), bi = __ballot(in2);
-    if (lane == 0) { s_cnt[wave][0] = __popcll(bk); s_cnt[wave][1] = __popcll(bi); }
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      if (w < wave) before += s_cnt[w][0];
-      total += s_cnt[w][0];
-      n_in += s_cnt[w][1];
-    }
-    if (keep) D.corr[pb.cand_off + m + before + __popcll(bk & ((1ull << lane) - 1ull))] = c;   // < cand_off + n_cand
-    m += total;
-    __syncthreads();
-  }
-  SoDevLanes G;
-  G.pb = &pb; G.D = &D; G.red = s_red; G.bc = s_bc; G.T = s_T; G.tid = tid; G.m = m;
-#pragma unroll
-  for (int j = 0; j < kSoRegEdges; ++j) {
-    const int k = tid + kSoLanes * j;
-    if (k < m) sim3_opt_edge(pb, D, D.corr[pb.cand_off + k], G.r[j]);
-  }
-  for (int k = tid + kSoLanes * kSoRegEdges; k < m; k += kSoLanes) D.state[pb.cand_off + k] = 0;
-  const SoCam C1 = {(double)pb.K1[0], (double)pb.K1[1], (double)pb.K1[2], (double)pb.K1[3]};
-  const SoCam C2 = {(double)pb.K2[0], (double)pb.K2[1], (double)pb.K2[2], (double)pb.K2[3]};
-  SoSim3 est;
-  SoDiag diag = pb.diag;
-  diag.n_correspondences = m; diag.n_in_kf2 = n_in; diag.n_out_kf2 = m - n_in;
-  const int ret = so_optimize(G, C1, C2, pb.entry, m, pb.th2, pb.fix_scale != 0, est, diag);
-#pragma unroll
-  for (int j = 0; j < kSoRegEdges; ++j) {
-    const int k = tid + kSoLanes * j;
-    if (k < m) D.cleared[pb.cand_off + D.corr[pb.cand_off + k]] = G.r[j].cleared;
-  }
-  for (int k = tid + kSoLanes * kSoRegEdges; k < m; k += kSoLanes)
-    D.cleared[pb.cand_off + D.corr[pb.cand_off + k]] = D.state[pb.cand_off + k] >> 1;
-  if (tid == 0) {
-    Sim3OptOut& o = D.out[blockIdx.x];
-    o.est = est;
-    o.diag = diag;
-    o.ret = ret;
-    o.reserved = 0;
-  }
-}
-
-// test hook: the header's exp on the device
-__global__ void k_test_so_exp(const double* __restrict__ x, double* __restrict__ z, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) z[i] = so_exp(x[i]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Sim3Solver (src/Sim3Solver.cc): every hypothesis of a call at once.  The arithmetic is csrc/sim3_math.h.
-//   k_sim3_hypotheses  grid (groups of 4 hypotheses, problem), 256 work-items: one wave per hypothesis.  The workgroup stages
-//                      the problem's correspondences once in LDS (12 floats each: X1c, X2c, both own-image projections, both
-//                      thresholds; problems beyond kS3LdsPoints read global memory and recompute them).  The closed form is
-//                      wave-uniform: every lane computes it, no broadcast, no divergent branch.  A lane then takes every 64th
-//                      correspondence; a chunk's count is a ballot and a population count, the ballot word is the chunk's
-//                      part of the hypothesis's bit mask.  No atomics, no floating-point reduction.
-//   k_sim3_select      one workgroup per problem: wave 0 runs the selection scan 64 hypotheses at a time (a prefix maximum and
-//                      two ballots per chunk), then all work-items expand the selected mask into bytes.
-// Both run on the call's stream, one behind the other; no workgroup waits for another.
-constexpr int kS3LdsPoints = 1024;   // 48 KB of LDS
-constexpr int kS3HypPerGroup = 4;
-struct Sim3Problem {
-  const float *x1, *x2;            // form 1: the staged camera-frame points
-  const float* wpos;               // form 2: the pool's positions ...
-  const int32_t *slot1, *slot2;    // ... and the slots
-  const float *e1, *e2;            // the thresholds
-  const int32_t* samples;
-  int n, n_hyp;                    // n_hyp = 0: the problem is not run
-  int hyp_off, word_off, words, inl_off;
-  int fix_scale, min_inliers, best_inliers, pool_form;
-  float K1[4], K2[4], Rcw1[9], tcw1[3], Rcw2[9], tcw2[3];
-};
-struct Sim3HypOut {
-  int32_t count;
-  float T12[16], R[9], t[3], s;
-};
-struct Sim3Result {
-  S3Selection sel;
-  float T12[16], R[9], t[3], s;
-};
-struct Sim3Dev {
-  const Sim3Problem* prob;
-  Sim3HypOut* hyp;             // all problems' hypotheses back to back
-  unsigned long long* mask;    // per hypothesis `words` 64-bit words
-  Sim3Result* res;
-  uint8_t* inlier;             // all problems' flags back to back
-};
-
-__device__ __forceinline__ S3Point sim3_point(const Sim3Problem& pb, int i) {
-  float a[3], b[3];
-  if (pb.pool_form) {
-    s3_transform(pb.Rcw1, pb.tcw1, pb.wpos + 3 * (size_t)pb.slot1[i], a);   // Sim3Solver.cc:107
-    s3_transform(pb.Rcw2, pb.tcw2, pb.wpos + 3 * (size_t)pb.slot2[i], b);   // :110
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { a[c] = pb.x1[3 * (size_t)i + c]; b[c] = pb.x2[3 * (size_t)i + c]; }
-  }
-  return s3_point(a, b, pb.K1, pb.K2, pb.e1[i], pb.e2[i]);
-}
-
-__global__ __launch_bounds__(256) void k_sim3_hypotheses(Sim3Dev D) {
-  __shared__ float s_pt[12][kS3LdsPoints];
-  const Sim3Problem& pb = D.prob[blockIdx.y];
-  if ((int)blockIdx.x * kS3HypPerGroup >= pb.n_hyp) return;   // the whole workgroup, before the barrier
-  const int tid = (int)threadIdx.x, n = pb.n;
-  const bool lds = n <= kS3LdsPoints;
-  if (lds) {
-    for (int i = tid; i < n; i += 256) {
-      const S3Point p = sim3_point(pb, i);
-      s_pt[0][i] = p.x1[0]; s_pt[1][i] = p.x1[1]; s_pt[2][i] = p.x1[2];
-      s_pt[3][i] = p.x2[0]; s_pt[4][i] = p.x2[1]; s_pt[5][i] = p.x2[2];
-      s_pt[6][i] = p.p1[0]; s_pt[7][i] = p.p1[1]; s_pt[8][i] = p.p2[0]; s_pt[9][i] = p.p2[1];
-      s_pt[10][i] = p.e1; s_pt[11][i] = p.e2;
-    }
-  }
-  __syncthreads();
-  const int lane = tid & 63, h = (int)blockIdx.x * kS3HypPerGroup + (tid >> 6);
-  if (h >= pb.n_hyp) return;   // a whole wave; no barrier follows
-  auto point = [&](int i) {
-    if (!lds) return sim3_point(pb, i);
-    S3Point p;
-    p.x1[0] = s_pt[0][i]; p.x1[1] = s_pt[1][i]; p.x1[2] = s_pt[2][i];
-    p.x2[0] = s_pt[3][i]; p.x2[1] = s_pt[4][i]; p.x2[2] = s_pt[5][i];
-    p.p1[0] = s_pt[6][i]; p.p1[1] = s_pt[7][i]; p.p2[0] = s_pt[8][i]; p.p2[1] = s_pt[9][i];
-    p.e1 = s_pt[10][i]; p.e2 = s_pt[11][i];
-    return p;
-  };
-  float P1[9], P2[9];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const S3Point p = point(pb.samples[3 * (size_t)h + k]);   // checked by the host: inside [0, n)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { P1[3 * k + c] = p.x1[c]; P2[3 * k + c] = p.x2[c]; }
-  }
-  S3Hyp H;
-  s3_compute_sim3(P1, P2, pb.fix_scale, H);
-  unsigned long long* mask = D.mask + (size_t)pb.word_off + (size_t)h * (size_t)pb.words;
-  int count = 0;
-  for (int c = 0; c < pb.words; ++c) {   // wave-uniform
-    const int i = c * 64 + lane;
-    bool in = false;
-    if (i < n) in = s3_is_inlier(H, pb.K1, pb.K2, point(i));
-    const unsigned long long w = __ballot(in);
-    count += __popcll(w);
-    if (lane == 0) mask[c] = w;
-  }
-  if (lane == 0) {
-    Sim3HypOut& o = D.hyp[(size_t)pb.hyp_off + (size_t)h];
-    o.count = count;
-    s3_T12(H, o.T12);
-    for (int k = 0; k < 9; ++k) o.R[k] = H.R[k];
-    for (int k = 0; k < 3; ++k) o.t[k] = H.t[k];
-    o.s = H.s;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_sim3_select(Sim3Dev D) {
-  __shared__ S3Selection s_sel;
-  const Sim3Problem& pb = D.prob[blockIdx.x];
-  if (pb.n_hyp == 0) return;   // the whole workgroup
-  const int tid = (int)threadIdx.x;
-  const Sim3HypOut* hyp = D.hyp + (size_t)pb.hyp_off;
-  if (tid < 64) {
-    // s3_select, 64 hypotheses at a time: before hypothesis k the best is max(b, c[0 .. k-1])
-    int b = pb.best_inliers, held = -1, conv = 0, iters = pb.n_hyp;
-    for (int base = 0; base < pb.n_hyp && !conv; base += 64) {   // wave-uniform
-      const int k = base + tid;
-      const bool valid = k < pb.n_hyp;
-      const int c = valid ? hyp[k].count : -1;
-      int m = c;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(m, (unsigned)d);
-        if (tid >= d && o > m) m = o;
-      }
-      const int ex = __shfl_up(m, 1u);
-      const int before = (tid == 0 || b > ex) ? b : ex;
-      const bool upd = valid && c >= before;
-      const bool stop = upd && c > pb.min_inliers;
-      const unsigned long long su = __ballot(stop);
-      unsigned long long uu = __ballot(upd);
-      if (su) {
-        const int first = __ffsll((long long)su) - 1;
-        uu &= (2ull << first) - 1ull;
-        conv = 1;
-        iters = base + first + 1;
-      }
-      if (uu) {
-        const int last = 63 - __clzll((long long)uu);
-        held = base + last;
-        b = __shfl(c, last);
-      }
-    }
-    if (tid == 0) {
-      S3Selection sel;
-      sel.selected = held; sel.converged = conv; sel.n_inliers = held >= 0 ? b : 0; sel.iterations = iters;
-      s_sel = sel;
-    }
-  }
-  __syncthreads();
-  const S3Selection sel = s_sel;
-  if (tid == 0) {
-    Sim3Result& r = D.res[blockIdx.x];
-    r.sel = sel;
-    if (sel.selected >= 0) {
-      const Sim3HypOut& o = hyp[sel.selected];
-      for (int k = 0; k < 16; ++k) r.T12[k] = o.T12[k];
-      for (int k = 0; k < 9; ++k) r.R[k] = o.R[k];
-      for (int k = 0; k < 3; ++k) r.t[k] = o.t[k];
-      r.s = o.s;
-    }
-  }
-  if (sel.selected >= 0) {
-    const unsigned long long* mask = D.mask + (size_t)pb.word_off + (size_t)sel.selected * (size_t)pb.words;
-    for (int i = tid; i < pb.n; i += 256) D.inlier[(size_t)pb.inl_off + i] = (uint8_t)((mask[i >> 6] >> (i & 63)) & 1ull);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// MLPnPsolver (src/MLPnPsolver.cpp): every RANSAC hypothesis of a call at once.  The arithmetic is csrc/mlpnp_math.h.
-//   k_mlpnp_hypotheses  grid (groups of 4 hypotheses, problem), 256 work-items: one wave per hypothesis, no workgroup barrier.
-//                       The wave runs the six-point computePose together (MlWaveX): the rows of A, the 12 x 12 matrix, its
-//                       eigenvectors and the rows of J live in the wave's MlWork in LDS; a lane owns a correspondence, an
-//                       entry of a sum, or a (row, rotation pair) of a Jacobi step; the 3 x 3 algebra and the 6 x 6 solve are
-//                       wave-uniform.  Then CheckInliers over all N: a chunk's count is a ballot and a population count, the
-//                       ballot word the chunk's part of the bit mask.
-//   k_mlpnp_select      one workgroup per problem: ml_scan over the counts - the loop of iterate with Refine as the reference
-//                       compiles it, which returns the current hypothesis (csrc/mlpnp_math.h) -, run identically by every
-//                       work-item; then all work-items expand the masks of the returned hypothesis and of the record into bytes.
-// Both run on the call's stream, one behind the other; no atomics, no workgroup waits for another.  Every loop is bounded.
-constexpr int kMlHypPerGroup = 4;
-struct MlpnpProblem {
-  MlView v;
-  const int32_t* samples;
-  const unsigned long long* best_mask;   // the carried-in mask as bit words (null: none)
-  int n_hyp;                              // 0: the problem is not run
-  int min_inliers, best_inliers;
-  int hyp_off, word_off, words, corr_off, cword_off;
-  float best_Tcw[16];
-};
-struct MlpnpHypOut {
-  double T[12];   // R row-major, t
-  int32_t count, path;
-};
-struct MlpnpResult {
-  MlScan scan;
-  float Tcw[16], best_Tcw[16];
-};
-struct MlpnpDev {
-  const MlpnpProblem* prob;
-  MlpnpHypOut* hyp;
-  unsigned long long* mask;     // per hypothesis `words` 64-bit words
-  MlpnpResult* res;
-  uint8_t* inlier;              // per correspondence: the flags of the returned solution
-  uint8_t* best_out;            // per correspondence: the new mvbBestInliers
-};
-
-struct MlWaveX {
-  int lane, lanes;
-  __device__ void sync() { wave_sync(); }
-  __device__ bool all(bool p) { return __ballot(!p) == 0ull; }
-};
-__global__ __launch_bounds__(256) void k_mlpnp_hypotheses(MlpnpDev D) {
-  __shared__ MlWork s_work[kMlHypPerGroup];
-  const MlpnpProblem& pb = D.prob[blockIdx.y];
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h = (int)blockIdx.x * kMlHypPerGroup + wave;
-  if (h >= pb.n_hyp) return;   // a whole wave; the kernel has no workgroup barrier
-  MlWaveX x = {lane, 64};
-  MlSixSums Q;
-  const MlSet S = {&pb.v, pb.samples + 6 * (size_t)h, 6};   // checked by the host: inside [0, N), distinct
-  double R[9], t[3];
-  int path;
-  ml_compute_pose(x, s_work[wave], Q, S, R, t, &path);
-  unsigned long long* mask = D.mask + (size_t)pb.word_off + (size_t)h * (size_t)pb.words;
-  int count = 0;
-  for (int c = 0; c < pb.words; ++c) {   // wave-uniform
-    const int i = c * 64 + lane;
-    const bool in = i < pb.v.N && ml_is_inlier(pb.v, R, t, i);
-    const unsigned long long w = __ballot(in);
-    count += __popcll(w);
-    if (lane == 0) mask[c] = w;
-  }
-  if (lane == 0) {
-    MlpnpHypOut& o = D.hyp[(size_t)pb.hyp_off + (size_t)h];
-    for (int k = 0; k < 9; ++k) o.T[k] = R[k];
-    for (int k = 0; k < 3; ++k) o.T[9 + k] = t[k];
-    o.count = count;
-    o.path = path;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_mlpnp_select(MlpnpDev D) {
-  const MlpnpProblem& pb = D.prob[blockIdx.x];
-  if (pb.n_hyp == 0) return;   // the whole workgroup
-  const int tid = (int)threadIdx.x, N = pb.v.N, words = pb.words;
-  const MlpnpHypOut* hyp = D.hyp + (size_t)pb.hyp_off;
-  const unsigned long long* masks = D.mask + (size_t)pb.word_off;
-  struct Counts {   // c[k] of ml_scan
-    const MlpnpHypOut* h;
-    __device__ int operator[](int k) const { return h[k].count; }
-  };
-  const MlScan sc = ml_scan(Counts{hyp}, pb.n_hyp, pb.min_inliers, pb.best_inliers);   // wave-uniform loads, the same in every work-item
-  // mvbBestInliers: the record's mask, or the one carried in; what iterate hands out: the stopping hypothesis's, or the best
-  const unsigned long long* bm = sc.record >= 0 ? masks + (size_t)sc.record * (size_t)words : (pb.best_inliers > 0 ? pb.best_mask : nullptr);
-  const unsigned long long* om = sc.selected >= 0 ? masks + (size_t)sc.selected * (size_t)words : bm;
-  for (int i = tid; i < N; i += 256) {
-    if (bm) D.best_out[(size_t)pb.corr_off + i] = (uint8_t)((bm[i >> 6] >> (i & 63)) & 1ull);
-    if (sc.found) D.inlier[(size_t)pb.corr_off + i] = (uint8_t)((om[i >> 6] >> (i & 63)) & 1ull);
-  }
-  if (tid == 0) {
-    MlpnpResult& r = D.res[blockIdx.x];
-    r.scan = sc;
-    if (sc.record >= 0) ml_Tcw(hyp[sc.record].T, hyp[sc.record].T + 9, r.best_Tcw);
-    else for (int k = 0; k < 16; ++k) r.best_Tcw[k] = pb.best_Tcw[k];
-    if (sc.selected >= 0) ml_Tcw(hyp[sc.selected].T, hyp[sc.selected].T + 9, r.Tcw);
-    else for (int k = 0; k < 16; ++k) r.Tcw[k] = r.best_Tcw[k];
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// TwoViewReconstruction (src/TwoViewReconstruction.cc): every homography and every fundamental hypothesis of a call at once.
-// The arithmetic is csrc/twoview_math.h.
-//   k_tv_normalize    grid (2 frames, problem), one wave: Normalize over ALL keys of the frame.  The wave stages 64 keys in LDS,
-//                     then every lane adds the two serial chains in index order.
-//   k_tv_hypotheses   grid (groups of 4 hypotheses, 2 models, problem), 256 work-items: one wave per (hypothesis, model), no
-//                     workgroup barrier.  The wave fills A from its eight matches, runs the Jacobi in its TvWork in LDS and forms
-//                     H21i / H12i or F21i wave-uniformly; then walks the matches 64 at a time: a lane computes both terms of
-//                     its match and its inlier bit, the chunk's mask word is a ballot, and the 128 terms go through LDS to be
-//                     added by every lane in the reference's order (two per match, ascending match index): no tree.
-//   k_tv_select       one workgroup per problem: the first strictly greater score per model, Reconstruct's choice, the inlier
-//                     count of the chosen mask, the motion hypotheses (DecomposeE, or Faugeras' eight with the d1 / d2, d2 / d3
-//                     exit); all work-items expand the two winners' masks into bytes.
-//   k_tv_check_rt     grid (8 motion hypotheses, problem), 256 work-items: CheckRT over the inliers of the chosen model.  nGood is
-//                     an integer tree; the min(50, nGood - 1)-th smallest cosParallax comes from at most 51 rounds of "smallest
-//                     value above the last one, and how often" (an order-free min / count tree each).
-//   k_tv_decide       one workgroup per problem: the rules of ReconstructF / ReconstructH, T21, and the winning hypothesis's
-//                     points and flags copied out.
-// All run on the call's stream, one behind the other; no floating-point atomics, no workgroup waits for another, every loop
-// is bounded.
-constexpr int kTvHypPerGroup = 4;
-struct TvProblem {
-  TvView v;                 // T1 / T2 come from k_tv_normalize
-  const int32_t* samples;
-  int n_hyp;                // 0: the problem is not run
-  int words, hyp_off, match_off, key_off;
-  unsigned long long word_off;
-};
-struct TvSelect {
-  float SH, SF;
-  int32_t best_h, best_f, model, n_inliers, exit_code;
-  float H21[9], F21[9];
-  TvMotions mo;
-};
-struct TvResult {
-  int32_t found, model, exit_code, best, aux, n_inliers, best_h, best_f;
-  float SH, SF, H21[9], F21[9], R[9], t[3];
-  int32_t n_good[kTvMaxMotions];
-  float parallax[kTvMaxMotions];
-};
-struct TvDev {
-  const TvProblem* prob;
-  float* norm;                  // per problem 2 x (sX, sY, meanX, meanY)
-  float* score;                 // per hypothesis 2
-  float* model;                 // per hypothesis 2 x 9
-  unsigned long long* mask;     // per hypothesis 2 x `words` 64-bit words
-  TvSelect* sel;
-  int32_t* n_good;              // per problem 8
-  float* parallax;              // per problem 8
-  float* cosv;                  // per problem 8 x N: the vCosParallax entry of a counted match, else NaN
-  float* p3d;                   // per problem 8 x n1 x 3
-  uint8_t* good;                // per problem 8 x n1
-  TvResult* res;
-  float* p3d_out;               // per problem n1 x 3
-  uint8_t* tri_out;             // per problem n1
-  uint8_t *mask_h, *mask_f;     // per match: the winners' inlier flags
-};
-__device__ __forceinline__ TvView tv_view(const TvDev& D, const TvProblem& pb, int b) {
-  TvView v = pb.v;
-  for (int k = 0; k < 4; ++k) { v.T1[k] = D.norm[8 * (size_t)b + k]; v.T2[k] = D.norm[8 * (size_t)b + 4 + k]; }
-  return v;
-}
-
-__global__ __launch_bounds__(64) void k_tv_normalize(TvDev D) {
-  __shared__ float s_buf[2][64];
-  const TvProblem& pb = D.prob[blockIdx.y];
-  if (pb.n_hyp == 0) return;   // the whole wave
-  MlWaveX x = {(int)threadIdx.x, 64};
-  const int f = (int)blockIdx.x;
-  float T[4];
-  tv_normalize(x, s_buf, f ? pb.v.xy2 : pb.v.xy1, f ? pb.v.n2 : pb.v.n1, T);
-  if (threadIdx.x == 0) {   // every lane holds the same T; constant indices keep it in registers (T[threadIdx.x] would put it into scratch)
-    float* out = D.norm + 8 * (size_t)blockIdx.y + 4 * f;
-    out[0] = T[0]; out[1] = T[1]; out[2] = T[2]; out[3] = T[3];
-  }
-}
-
-__global__ __launch_bounds__(256) void k_tv_hypotheses(TvDev D) {
-  __shared__ TvWork s_work[kTvHypPerGroup];
-  const TvProblem& pb = D.prob[blockIdx.z];
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h = (int)blockIdx.x * kTvHypPerGroup + wave, model = (int)blockIdx.y;
-  if (h >= pb.n_hyp) return;   // a whole wave; the kernel has no workgroup barrier
-  const TvView v = tv_view(D, pb, (int)blockIdx.z);
-  TvWork& W = s_work[wave];
-  MlWaveX x = {lane, 64};
-  float M[9], M2[9];
-  tv_model(x, W, v, pb.samples + 8 * (size_t)h, model, M, M2);   // the sets are checked by the host: inside [0, N), distinct
-  const float invSigmaSquare = tv_inv_sigma2(v.sigma);
-  const size_t hm = 2 * ((size_t)pb.hyp_off + (size_t)h) + (size_t)model;
-  unsigned long long* mask = D.mask + pb.word_off + (2 * (size_t)h + (size_t)model) * (size_t)pb.words;
-  float score = 0.0f;
-  for (int c = 0; c < pb.words; ++c) {   // wave-uniform
-    const int i = c * 64 + lane;
-    float t[2] = {0.0f, 0.0f};
-    bool in = false;
-    if (i < v.N) in = tv_check(model, M, M2, v, i, invSigmaSquare, t);
-    W.terms[2 * lane] = t[0];
-    W.terms[2 * lane + 1] = t[1];
-    wave_sync();
-    score = tv_add_chunk(score, W.terms, 128);   // past N the terms are +0.0f
-    wave_sync();
-    const unsigned long long w = __ballot(in);
-    if (lane == 0) mask[c] = w;
-  }
-  if (lane == 0) {
-    D.score[hm] = score;
-    for (int k = 0; k < 9; ++k) D.model[9 * hm + k] = M[k];
-  }
-}
-
-__global__ __launch_bounds__(256) void k_tv_select(TvDev D) {
-  __shared__ int s_cnt[256];
-  const TvProblem& pb = D.prob[blockIdx.x];
-  if (pb.n_hyp == 0) return;   // the whole workgroup
-  const int tid = (int)threadIdx.x, N = pb.v.N, words = pb.words;
-  const float* scores = D.score + 2 * (size_t)pb.hyp_off;
-  float SH, SF;   // wave-uniform loads, the same in every work-item
-  const int best_h = tv_first_max(scores, pb.n_hyp, 0, &SH), best_f = tv_first_max(scores, pb.n_hyp, 1, &SF);
-  const int model = tv_choose_model(SH, SF);
-  const unsigned long long* mh = best_h >= 0 ? D.mask + pb.word_off + (2 * (size_t)best_h) * (size_t)words : nullptr;
-  const unsigned long long* mf = best_f >= 0 ? D.mask + pb.word_off + (2 * (size_t)best_f + 1) * (size_t)words : nullptr;
-  const unsigned long long* chosen = model == 0 ? mh : mf;   // model >= 0 has a score > 0 on that side: a winner
-  int cnt = 0;
-  for (int c = tid; model >= 0 && c < words; c += 256) cnt += __popcll(chosen[c]);
-  s_cnt[tid] = cnt;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if (tid < s) s_cnt[tid] += s_cnt[tid + s];
-    __syncthreads();
-  }
-  for (int i = tid; i < N; i += 256) {
-    D.mask_h[(size_t)pb.match_off + i] = mh ? (uint8_t)((mh[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
-    D.mask_f[(size_t)pb.match_off + i] = mf ? (uint8_t)((mf[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
-  }
-  if (tid == 0) {
-    TvSelect& S = D.sel[blockIdx.x];
-    S.SH = SH; S.SF = SF; S.best_h = best_h; S.best_f = best_f; S.model = model; S.n_inliers = s_cnt[0];
-    for (int k = 0; k < 9; ++k) {
-      S.H21[k] = best_h >= 0 ? D.model[9 * (2 * ((size_t)pb.hyp_off + (size_t)best_h)) + k] : 0.0f;
-      S.F21[k] = best_f >= 0 ? D.model[9 * (2 * ((size_t)pb.hyp_off + (size_t)best_f) + 1) + k] : 0.0f;
-    }
-    S.exit_code = kTvFound;
-    if (model < 0) {
-      S.exit_code = kTvNoScore;
-      S.mo.n = 0;
-    } else if (model == 0) {
-      if (!tv_motions_h(S.H21, pb.v.K, S.mo)) S.exit_code = kTvHRatio;
-    } else {
-      tv_motions_f(S.F21, pb.v.K, S.mo);
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void k_tv_check_rt(TvDev D) {
-  __shared__ int s_cnt[256];
-  __shared__ float s_val[256];
-  const int b = (int)blockIdx.y, j = (int)blockIdx.x, tid = (int)threadIdx.x;
-  const TvProblem& pb = D.prob[b];
-  if (pb.n_hyp == 0) return;   // the whole workgroup
-  const TvSelect& S = D.sel[b];
-  const int N = pb.v.N, n1 = pb.v.n1;
-  if (j >= S.mo.n) {           // the whole workgroup
-    if (tid == 0) { D.n_good[8 * (size_t)b + j] = 0; D.parallax[8 * (size_t)b + j] = 0.0f; }
-    return;
-  }
-  TvCam c;
-  tv_cam(pb.v.K, S.mo.R[j], S.mo.t[j], pb.v.sigma, c);
-  float* p3d = D.p3d + 3 * (8 * (size_t)pb.key_off + (size_t)j * (size_t)n1);
-  uint8_t* good = D.good + 8 * (size_t)pb.key_off + (size_t)j * (size_t)n1;
-  float* cosv = D.cosv + 8 * (size_t)pb.match_off + (size_t)j * (size_t)N;
-  for (int i = tid; i < n1; i += 256) { p3d[3 * (size_t)i] = 0.0f; p3d[3 * (size_t)i + 1] = 0.0f; p3d[3 * (size_t)i + 2] = 0.0f; good[i] = 0; }
-  __syncthreads();
-  const unsigned long long* mask = D.mask + pb.word_off + (2 * (size_t)(S.model == 0 ? S.best_h : S.best_f) + (size_t)S.model) * (size_t)pb.words;
-  const float nan = np_float(0x7fc00000u);
-  int cnt = 0;
-  for (int i = tid; i < N; i += 256) {
-    float cv = nan;
-    if ((mask[i >> 6] >> (i & 63)) & 1ull) {
-      const size_t a = (size_t)pb.v.m1[i], q = (size_t)pb.v.m2[i];   // the matches name distinct keys of frame 1
-      float p[3], cp;
-      const int code = tv_rt_point(c, pb.v.xy1[2 * a], pb.v.xy1[2 * a + 1], pb.v.xy2[2 * q], pb.v.xy2[2 * q + 1], p, &cp);
-      if (code) {
-        p3d[3 * a] = p[0]; p3d[3 * a + 1] = p[1]; p3d[3 * a + 2] = p[2];
-        good[a] = code == 2 ? 1 : 0;
-        cv = cp;
-        ++cnt;
-      }
-    }
-    cosv[i] = cv;   // read back by this work-item only
-  }
-  s_cnt[tid] = cnt;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if (tid < s) s_cnt[tid] += s_cnt[tid + s];
-    __syncthreads();
-  }
-  const int nGood = s_cnt[0];
-  __syncthreads();
-  // sort + vCosParallax[min(50, size - 1)]: the values in ascending order, one distinct value per round
-  const int idx = nGood - 1 < 50 ? nGood - 1 : 50;
-  float last = 0.0f, pick = nan;
-  int rank = 0;
-  for (int round = 0; nGood > 0 && round <= idx; ++round) {   // uniform: at most 51 rounds
-    float lo = nan;
-    int m = 0;
-    for (int i = tid; i < N; i += 256) {
-      const float cv = cosv[i];
-      if (!(cv == cv) || (round > 0 && !(cv > last))) continue;
-      if (m == 0 || cv < lo) { lo = cv; m = 1; }
-      else if (cv == lo) ++m;
-    }
-    s_val[tid] = lo;
-    s_cnt[tid] = m;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-      if (tid < s) {
-        const float a = s_val[tid], o = s_val[tid + s];
-        const int ma = s_cnt[tid], mo = s_cnt[tid + s];
-        if (mo > 0 && (ma == 0 || o < a)) { s_val[tid] = o; s_cnt[tid] = mo; }
-        else if (mo > 0 && o == a) s_cnt[tid] = ma + mo;
-      }
-      __syncthreads();
-    }
-    const float v0 = s_val[0];
-    const int m0 = s_cnt[0];
-    __syncthreads();
-    if (m0 == 0) break;                              // only NaN values are left: pick stays NaN
-    if (rank + m0 > idx) { pick = v0; break; }
-    rank += m0;
-    last = v0;
-  }
-  if (tid == 0) {
-    D.n_good[8 * (size_t)b + j] = nGood;
-    D.parallax[8 * (size_t)b + j] = nGood > 0 ? tv_parallax_deg(pick) : 0.0f;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_tv_decide(TvDev D) {
-  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
-  const TvProblem& pb = D.prob[b];
-  if (pb.n_hyp == 0) return;   // the whole workgroup
-  const TvSelect& S = D.sel[b];
-  int32_t nGood[kTvMaxMotions];
-  float parallax[kTvMaxMotions];
-  for (int k = 0; k < kTvMaxMotions; ++k) { nGood[k] = D.n_good[8 * (size_t)b + k]; parallax[k] = D.parallax[8 * (size_t)b + k]; }
-  TvDecision d = {0, S.exit_code, -1, 0};   // the same in every work-item
-  if (S.exit_code == kTvFound) d = S.model == 0 ? tv_decide_h(nGood, parallax, S.n_inliers) : tv_decide_f(nGood, parallax, S.n_inliers);
-  const int n1 = pb.v.n1;
-  if (d.found) {
-    const float* p3d = D.p3d + 3 * (8 * (size_t)pb.key_off + (size_t)d.best * (size_t)n1);
-    const uint8_t* good = D.good + 8 * (size_t)pb.key_off + (size_t)d.best * (size_t)n1;
-    for (int i = tid; i < n1; i += 256) {
-      for (int k = 0; k < 3; ++k) D.p3d_out[3 * ((size_t)pb.key_off + i) + k] = p3d[3 * (size_t)i + k];
-      D.tri_out[(size_t)pb.key_off + i] = good[i];
-    }
-  }
-  if (tid == 0) {
-    TvResult& r = D.res[b];
-    r.found = d.found; r.model = S.model; r.exit_code = d.exit_code; r.best = d.best; r.aux = d.aux; r.n_inliers = S.n_inliers;
-    r.best_h = S.best_h; r.best_f = S.best_f; r.SH = S.SH; r.SF = S.SF;
-    for (int k = 0; k < 9; ++k) { r.H21[k] = S.H21[k]; r.F21[k] = S.F21[k]; r.R[k] = d.found ? S.mo.R[d.best][k] : ((k % 4 == 0) ? 1.0f : 0.0f); }
-    for (int k = 0; k < 3; ++k) r.t[k] = d.found ? S.mo.t[d.best][k] : 0.0f;
-    for (int k = 0; k < kTvMaxMotions; ++k) { r.n_good[k] = nGood[k]; r.parallax[k] = parallax[k]; }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
 // ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)
 // (/root/reference/src/ORBmatcher.cc:1676-1887, single camera) with Frame::AssignFeaturesToGrid,
 // PosInGrid and GetFeaturesInArea (src/Frame.cc:475-506, 815-825, 747-813).
@@ -1736,7 +885,6 @@ __global__ __launch_bounds__(256) void k_tv_decide(TvDev D) {
 //                      blocker still has that feature among its viable candidates (min_unres).  Finals commit, the
 //                      rest try again.  The lowest unresolved index is final in every round, so the loop terminates,
 //                      and induction over the index shows the result is the sequential one.
-constexpr int kProjMaxLevels = 16;
 constexpr int kProjCand = 16;  // viable candidates kept per point; a point with more re-scans its window (kRefOverflow)
 constexpr uint32_t kRefOverflow = 1u << 31;
 __host__ __device__ __forceinline__ int ref_n(uint32_t r) { return (int)((r >> 26) & 31u); }
@@ -3027,131 +2175,11 @@ __global__ __launch_bounds__(64) void k_search_by_bow_rig(BowDev T) {   // a two
 
 using namespace rgbl;
 
-struct rgbl_matcher {
-  int device = 0;
-  hipStream_t stream = nullptr, own_stream = nullptr;
-  KernelTimer timer;
-  uint8_t* d_buf = nullptr;  // grow-only staging arena for the host entry points
-  size_t buf_size = 0;
-  uint8_t* h_pin = nullptr;  // grow-only page-locked mirror of the brute-force scan's inputs / outputs (rgbl_hamming_bf)
-  size_t pin_size = 0;
-  // tuning switches, read ONCE at rgbl_matcher_create (include/rgbl_frontend.h lists them): never on a launch path
-  bool bf_matrix = true;   // RGBL_BF_MFMA=0: the VALU popcount scan (k_hamming_bf)
-  bool bf_fp4 = true;      // RGBL_BF_MFMA=i8: v_mfma_i32_32x32x32_i8 (k_hamming_mfma) instead of the block-scaled FP4 instruction
-  bool bf_split = true;    // RGBL_BF_SPLIT=0: one pair per call without train-set slices
-};
-
 namespace {
-int ensure_arena(rgbl_matcher* m, size_t bytes) {
-  if (bytes <= m->buf_size) return RGBL_OK;
-  if (m->d_buf) { RGBL_HIP(hipStreamSynchronize(m->stream)); RGBL_HIP(hipFree(m->d_buf)); m->d_buf = nullptr; m->buf_size = 0; }
-  const size_t sz = std::max(bytes, (size_t)1 << 20);
-  RGBL_HIP(hipMalloc(&m->d_buf, sz));
-  m->buf_size = sz;
-  return RGBL_OK;
-}
 // RGBL_BF_MFMA=0 selects the VALU popcount scan (k_hamming_bf) instead of the matrix-core one, =i8 the i8 instruction
 // (k_hamming_mfma) instead of the block-scaled FP4 one (k_hamming_fp4, the default): read when the handle is created.
 inline bool bf_on_matrix_cores(const rgbl_matcher* m) { return m->bf_matrix; }
 inline bool bf_on_fp4(const rgbl_matcher* m) { return m->bf_fp4; }
-int ensure_pin(rgbl_matcher* m, size_t bytes) {
-  if (bytes <= m->pin_size) return RGBL_OK;
-  if (m->h_pin) { (void)hipHostFree(m->h_pin); m->h_pin = nullptr; m->pin_size = 0; }
-  const size_t sz = std::max(bytes, (size_t)1 << 20);
-  RGBL_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->h_pin), sz, hipHostMallocDefault));
-  m->pin_size = sz;
-  return RGBL_OK;
-}
-// One call of a host-pointer entry point.  The device arena and its page-locked mirror share ONE layout: what the call
-// uploads is copied into the mirror at the offsets its device copies have and goes up with ONE hipMemcpyAsync (round 5
-// queued one per array, 8 - 17 per call, from pageable memory); the result arrays are taken back to back and come back
-// with one.  Arrays of a frame that is resident on the device (rgbl_device_frame) are not staged at all.
-// begin() runs the call's layout - its put / put_fill / stage / result / scratch calls - twice: a measuring pass that copies,
-// waits for and launches nothing, then, with the arena and mirror grown to that size, the carving pass.
-struct HostCall {
-  rgbl_matcher* m;
-  hipStream_t s;
-  bool carving = false;
-  size_t off = 0, up_end = 0, res_begin = ~(size_t)0, res_end = 0;
-  explicit HostCall(rgbl_matcher* mm) : m(mm), s(mm->stream) {}
-  template <class Layout> int begin(Layout&& layout) {   // ... and the call's ONE upload
-    RGBL_TRY(layout());
-    const size_t measured = off;
-    RGBL_TRY(ensure_arena(m, measured));
-    RGBL_TRY(ensure_pin(m, measured));
-    carving = true;
-    off = up_end = 0;
-    RGBL_TRY(layout());
-    if (off != measured) { set_error("staging layout: %zu bytes measured, %zu carved", measured, off); return RGBL_ERR_INVALID; }
-    if (up_end) RGBL_HIP(hipMemcpyAsync(m->d_buf, m->h_pin, up_end, hipMemcpyHostToDevice, s));
-    return RGBL_OK;
-  }
-  template <class E> E* take(size_t count) {   // every array starts 256-byte aligned; nullptr while measuring
-    off = (off + 255) / 256 * 256;
-    E* p = carving ? reinterpret_cast<E*>(m->d_buf + off) : nullptr;
-    off += count * sizeof(E);
-    return p;
-  }
-  size_t off_of(const void* d) const { return (size_t)(reinterpret_cast<const uint8_t*>(d) - m->d_buf); }
-  template <class E> void put(const E** dst, const E* src, size_t count) {
-    E* p = take<E>(count);
-    *dst = p;
-    if (carving && count) memcpy(m->h_pin + off_of(p), src, count * sizeof(E));
-    up_end = off;
-  }
-  template <class E> E* put_fill(size_t count, int byte) {   // an array the device starts from (e.g. all -1) travels with the upload
-    E* p = take<E>(count);
-    if (carving && count) memset(m->h_pin + off_of(p), byte, count * sizeof(E));
-    up_end = off;
-    return p;
-  }
-  template <class E, class Fill> E* stage(size_t count, Fill fill) {   // fill(mirror) writes the upload itself
-    E* p = take<E>(count);
-    if (carving) fill(reinterpret_cast<E*>(m->h_pin + off_of(p)));
-    up_end = off;
-    return p;
-  }
-  template <class E> E* scratch(size_t count) { return take<E>(count); }
-  template <class E> void mark_result(E* p, size_t count) {
-    if (!carving) return;
-    res_begin = std::min(res_begin, off_of(p));
-    res_end = std::max(res_end, off_of(p) + count * sizeof(E));
-  }
-  template <class E> E* result(size_t count) { E* p = take<E>(count); mark_result(p, count); return p; }
-  int fetch() {   // the call's only wait
-    if (res_end > res_begin) RGBL_HIP(hipMemcpyAsync(m->h_pin + res_begin, m->d_buf + res_begin, res_end - res_begin, hipMemcpyDeviceToHost, s));
-    RGBL_HIP(hipStreamSynchronize(s));
-    m->timer.collect();
-    return RGBL_OK;
-  }
-  template <class E> const E* host(const E* d) const { return reinterpret_cast<const E*>(m->h_pin + off_of(d)); }
-  // a frame's resident arrays: the stream waits for whatever filled them last
-  int use(const rgbl_device_frame* f, int n) {
-    if (f->device != m->device || f->n != n) { set_error("device frame: %d features on device %d, the call says %d on device %d", f->n, f->device, n, m->device); return RGBL_ERR_INVALID; }
-    if (carving) RGBL_HIP(hipStreamWaitEvent(s, f->ready, 0));
-    return RGBL_OK;
-  }
-};
-
-// A frame's per-feature arrays that the call reads (a null destination: not read): the resident copy when the frame has one
-// (dev), else staged with the rest of the call's upload.
-int put_features(HostCall& hc, const rgbl_device_frame* dev, int n, const uint8_t* desc, const float* xy, const int32_t* oct,
-                 const float* ur, const uint8_t** d_desc, const float** d_xy, const int32_t** d_oct, const float** d_ur) {
-  if (dev) {
-    RGBL_TRY(hc.use(dev, n));
-    if (d_desc) *d_desc = dev->d_desc;
-    if (d_xy) *d_xy = dev->d_xy;
-    if (d_oct) *d_oct = dev->d_oct;
-    if (d_ur) *d_ur = dev->d_ur;
-    return RGBL_OK;
-  }
-  if (d_desc) hc.put(d_desc, desc, (size_t)n * 32);
-  if (d_xy) hc.put(d_xy, xy, (size_t)n * 2);
-  if (d_oct) hc.put(d_oct, oct, (size_t)n);
-  if (d_ur) hc.put(d_ur, ur, (size_t)n);
-  return RGBL_OK;
-}
-
 // A key frame's FeatureVector (CSR): the resident copy when its frame holds one of the same shape
 // (rgbl_device_frame_set_feature_vector since the last upload / capture), else staged.
 void put_feature_vector(HostCall& hc, const rgbl_keyframe_view* v, const int32_t** d_off, const int32_t** d_feat) {
@@ -3236,10 +2264,7 @@ int enqueue_triangulation(rgbl_matcher* m, hipStream_t s, TriDev& T, const rgbl_
   T.ep[1] = prm->epipole[1];
   T.only_stereo = prm->only_stereo;
   T.coarse = prm->coarse;
-  m->timer.begin("k_search_triangulation", s);
-  hipLaunchKernelGGL(k_search_triangulation, dim3(npairs), dim3(256), 0, s, T);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(launch(m, s, "k_search_triangulation", k_search_triangulation, dim3(npairs), dim3(256), 0, T));
   return RGBL_OK;
 }
 
@@ -3258,30 +2283,6 @@ void finish_matches12(const SharedNodes& sn, int32_t* matches12, bool check_orie
   *out_nmatches = nmatches;
 }
 
-// The element-wise device test hooks (rgbl_test_*_device): every array of `in` (n elements each) goes to the device,
-// launch(d_in, d_out, grid, block) runs one work-item per element on the null stream, d_out comes back as `out`.  The device
-// arrays are freed on every path.
-template <class T, class Launch> int elementwise_device_hook(std::initializer_list<const T*> in, T* out, int n, Launch launch) {
-  const size_t bytes = sizeof(T) * (size_t)n;
-  std::vector<T*> d(in.size() + 1, nullptr);   // the inputs, then the output
-  hipError_t e = hipSuccess;
-  for (T*& p : d)
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p), bytes);
-  size_t k = 0;
-  for (const T* h : in) {
-    if (e == hipSuccess) e = hipMemcpy(d[k], h, bytes, hipMemcpyHostToDevice);
-    ++k;
-  }
-  if (e == hipSuccess) {
-    launch(d.data(), d.back(), dim3((unsigned)((n + 255) / 256)), dim3(256));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(out, d.back(), bytes, hipMemcpyDeviceToHost);
-  for (T* p : d)
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess) { set_error("device test hook: %s", hipGetErrorString(e)); return RGBL_ERR_HIP; }
-  return RGBL_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -3577,20 +2578,13 @@ int rgbl_hamming_bf_batch_device(rgbl_matcher* m, const uint8_t* d_desc, const i
   }
   if (n_pairs == 0) return RGBL_OK;
   RGBL_HIP(hipSetDevice(m->device));
-  if (bf_on_matrix_cores(m)) {
-    m->timer.begin(bf_on_fp4(m) ? "k_hamming_fp4" : "k_hamming_mfma", m->stream);
-    if (bf_on_fp4(m)) hipLaunchKernelGGL(k_hamming_fp4, xcd_grid(true, (cap + kBfQueriesPerBlock - 1) / kBfQueriesPerBlock, n_pairs), dim3(256), 0, m->stream,
-                       d_desc, d_n, cap, d_pair_a, d_pair_b, d_best_idx, d_best_dist, d_second_dist, 1, (uint32_t*)nullptr);
-    else hipLaunchKernelGGL(k_hamming_mfma, xcd_grid(true, (cap + kBfQueriesPerBlock - 1) / kBfQueriesPerBlock, n_pairs), dim3(256), 0, m->stream,
-                       d_desc, d_n, cap, d_pair_a, d_pair_b, d_best_idx, d_best_dist, d_second_dist);
-  } else {
-    m->timer.begin("k_hamming_bf", m->stream);
-    hipLaunchKernelGGL(k_hamming_bf, dim3((cap + 63) / 64, n_pairs), dim3(256), 0, m->stream, d_desc, d_n, cap, d_pair_a,
-                       d_pair_b, d_best_idx, d_best_dist, d_second_dist);
-  }
-  m->timer.end(m->stream);
-  RGBL_HIP(hipGetLastError());
-  return RGBL_OK;
+  hipStream_t s = m->stream;
+  const dim3 grid = xcd_grid(true, (cap + kBfQueriesPerBlock - 1) / kBfQueriesPerBlock, n_pairs);
+  if (!bf_on_matrix_cores(m))
+    return launch(m, s, "k_hamming_bf", k_hamming_bf, dim3((cap + 63) / 64, n_pairs), dim3(256), 0, d_desc, d_n, cap, d_pair_a, d_pair_b, d_best_idx, d_best_dist, d_second_dist);
+  if (!bf_on_fp4(m))
+    return launch(m, s, "k_hamming_mfma", k_hamming_mfma, grid, dim3(256), 0, d_desc, d_n, cap, d_pair_a, d_pair_b, d_best_idx, d_best_dist, d_second_dist);
+  return launch(m, s, "k_hamming_fp4", k_hamming_fp4, grid, dim3(256), 0, d_desc, d_n, cap, d_pair_a, d_pair_b, d_best_idx, d_best_dist, d_second_dist, 1, (uint32_t*)nullptr);
 }
 
 int rgbl_hamming_bf(rgbl_matcher* m, const uint8_t* desc_a, int na, const uint8_t* desc_b, int nb, int32_t* best_idx,
@@ -3846,10 +2840,7 @@ int rgbl_triangulate_matches(rgbl_matcher* m, const rgbl_new_points_keyframe* kf
   }));
   D.P = new_points_params(kf1, prm);
   D.n = n_pairs; D.n_levels = prm->n_levels; D.report_rejected = 1; D.cap = n_pairs;
-  m->timer.begin("k_new_points", s);
-  hipLaunchKernelGGL(k_new_points, dim3(1), dim3(kNewPointsBS), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(launch(m, s, "k_new_points", k_new_points, dim3(1), dim3(kNewPointsBS), 0, D));
   RGBL_TRY(hc.fetch());
   memcpy(out, hc.host(D.out), sizeof(rgbl_new_point) * (size_t)n_pairs);
   return RGBL_OK;
@@ -3935,10 +2926,7 @@ int rgbl_create_new_map_points(rgbl_matcher* m, const rgbl_new_points_keyframe* 
       d.n = n1; d.n_levels = prm->n_levels;
       d.idx2 = d_m12; d.list = d_list; d.reset = 1; d.report_rejected = prm->report_rejected; d.neighbour = i; d.cap = cap;
       d.mask1 = d_mask; d.out = d_out; d.total = d_cnt; d.per_launch = d_cnt + 1 + 2 * i;
-      m->timer.begin("k_new_points", s);
-      hipLaunchKernelGGL(k_new_points, dim3(1), dim3(kNewPointsBS), 0, s, d);
-      m->timer.end(s);
-      RGBL_HIP(hipGetLastError());
+      RGBL_TRY(launch(m, s, "k_new_points", k_new_points, dim3(1), dim3(kNewPointsBS), 0, d));
     }
     RGBL_TRY(hc.fetch());
     const int32_t* cnt = hc.host(d_cnt);
@@ -4048,15 +3036,9 @@ int scatter_matches(const int32_t* choice, int n1, int32_t* match2) {
 
 int greedy_search(rgbl_matcher* m, hipStream_t s, ProjDev& P, const rgbl_device_frame* dev2, const GreedyKernels& K) {
   grid_for_call(m, s, P, dev2);
-  m->timer.begin(K.candidates_name, s);
-  hipLaunchKernelGGL(K.candidates, dim3((P.n1 + kPointsPerBlock - 1) / kPointsPerBlock), dim3(256), 0, s, P);
-  m->timer.end(s);
-  m->timer.begin(K.resolve_name, s);
+  RGBL_TRY(launch(m, s, K.candidates_name, K.candidates, dim3((P.n1 + kPointsPerBlock - 1) / kPointsPerBlock), dim3(256), 0, P));
   const bool lds = P.n2 <= kResolveLdsN2 && P.n1 <= kResolveLdsN1;
-  hipLaunchKernelGGL(lds ? K.resolve_lds : K.resolve_global, dim3(1), dim3(kResolveBS), 0, s, P);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  return RGBL_OK;
+  return launch(m, s, K.resolve_name, lds ? K.resolve_lds : K.resolve_global, dim3(1), dim3(kResolveBS), 0, P);
 }
 
 int projection_core(rgbl_matcher* m, const ProjHost& in, int32_t* match2, int* out_nmatches) {
@@ -4192,10 +3174,7 @@ int rgbl_distinctive_descriptors(rgbl_matcher* m, const uint8_t* desc, const int
     d_best = hc.result<int32_t>(n_points);
     return RGBL_OK;
   }));
-  m->timer.begin("k_distinctive", s);
-  hipLaunchKernelGGL(k_distinctive, dim3(n_points), dim3(64), 0, s, d_desc, d_off, d_best);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(launch(m, s, "k_distinctive", k_distinctive, dim3(n_points), dim3(64), 0, d_desc, d_off, d_best));
   RGBL_TRY(hc.fetch());
   memcpy(best, hc.host(d_best), sizeof(int32_t) * n_points);
   return RGBL_OK;
@@ -4241,10 +3220,7 @@ static int fuse_core(rgbl_matcher* m, const rgbl_fuse_input* in, int cam_frame, 
   set_scales(P, in->scale_factors, in->n_levels);
   for (int l = 0; l < kProjMaxLevels; ++l) Fz.inv_sigma2[l] = l < in->n_levels ? in->inv_level_sigma2[l] : 1.f;
   grid_for_call(m, s, P, in->device2);
-  m->timer.begin("k_fuse_search", s);
-  hipLaunchKernelGGL(k_fuse_search, dim3((n1 + kPointsPerBlock - 1) / kPointsPerBlock), dim3(256), 0, s, P, Fz);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(launch(m, s, "k_fuse_search", k_fuse_search, dim3((n1 + kPointsPerBlock - 1) / kPointsPerBlock), dim3(256), 0, P, Fz));
   RGBL_TRY(hc.fetch());
   const unsigned long long* keys = hc.host(P.cand);
   for (int i = 0; i < n1; ++i) {
@@ -4350,20 +3326,6 @@ int rgbl_search_local_points(rgbl_matcher* m, const rgbl_local_points_input* in,
   return RGBL_OK;
 }
 
-// ---- rgbl_map_points: map-point data resident on the device ------------------------------------------------------------
-// One allocation: world_pos [cap x 3] | normal [cap x 3] | min [cap] | max [cap] | desc [cap x 32], every array 256-byte
-// aligned (64 bytes per slot).  `mu` is held by every call that reads or writes the arrays until its device work is done.
-struct rgbl_map_points {
-  int device = 0, cap = 0;
-  std::mutex mu;
-  uint8_t* block = nullptr;
-  float *d_wpos = nullptr, *d_normal = nullptr, *d_min = nullptr, *d_max = nullptr;
-  uint8_t* d_desc = nullptr;
-  hipStream_t stream = nullptr;
-  uint8_t *d_stage = nullptr, *h_stage = nullptr;   // one update's packed arrays and their page-locked mirror (grow-only)
-  size_t stage_size = 0;
-};
-
 namespace {
 constexpr int kMaxPoolSlots = 1 << 26;   // 4 GiB of slots: keeps every byte offset far inside size_t / int arithmetic
 struct PoolArrays { size_t wpos, normal, min_d, max_d, desc, total; };
@@ -4401,21 +3363,6 @@ int pool_resize(rgbl_map_points* p, int cap, int keep) {
   return RGBL_OK;
 }
 }  // namespace
-
-extern "C++" {   // for csrc/lba.hip (common.h)
-int rgbl_internal_matcher_arena(rgbl_matcher* m, size_t dev_bytes, size_t pin_bytes, int* device, hipStream_t* stream,
-                                uint8_t** d_buf, uint8_t** h_pin, KernelTimer** timer) {
-  RGBL_HIP(hipSetDevice(m->device));
-  RGBL_TRY(ensure_arena(m, dev_bytes));
-  RGBL_TRY(ensure_pin(m, pin_bytes));
-  *device = m->device; *stream = m->stream; *d_buf = m->d_buf; *h_pin = m->h_pin; *timer = &m->timer;
-  return RGBL_OK;
-}
-int rgbl_internal_map_points_view(rgbl_map_points* p, int* device, int* cap, float** d_wpos, std::mutex** mu) {
-  *device = p->device; *cap = p->cap; *d_wpos = p->d_wpos; *mu = &p->mu;
-  return RGBL_OK;
-}
-}  // extern "C++"
 
 int rgbl_map_points_create(int device, int capacity, rgbl_map_points** out) {
   if (!out) { set_error("null argument"); return RGBL_ERR_INVALID; }
@@ -4639,25 +3586,16 @@ int rgbl_map_points_refresh(rgbl_matcher* m, rgbl_map_points* pool, const rgbl_m
     PoolScatter S{};
     S.n = np; S.slot = R.slot; S.wpos = d_wpos;
     S.p_wpos = pool->d_wpos; S.p_normal = pool->d_normal; S.p_min = pool->d_min; S.p_max = pool->d_max; S.p_desc = pool->d_desc;
-    m->timer.begin("k_map_points_scatter", s);
-    hipLaunchKernelGGL(k_map_points_scatter, dim3((np + 255) / 256), dim3(256), 0, s, S);
-    m->timer.end(s);
-    RGBL_HIP(hipGetLastError());
+    RGBL_TRY(launch(m, s, "k_map_points_scatter", k_map_points_scatter, dim3((np + 255) / 256), dim3(256), 0, S));
   }
   if (run_n) {
     if (do_n) R.top_scale = in->scale_factors[in->n_levels - 1];
     R.compute = do_n; R.o_wrote = wrote_n;
-    m->timer.begin("k_map_refresh_normal", s);
-    hipLaunchKernelGGL(k_map_refresh_normal, dim3(np), dim3(64), 0, s, R);
-    m->timer.end(s);
-    RGBL_HIP(hipGetLastError());
+    RGBL_TRY(launch(m, s, "k_map_refresh_normal", k_map_refresh_normal, dim3(np), dim3(64), 0, R));
   }
   if (run_d) {
     R.compute = do_d; R.o_wrote = wrote_d;
-    m->timer.begin("k_map_refresh_desc", s);
-    hipLaunchKernelGGL(k_map_refresh_desc, dim3(np), dim3(64), 0, s, R);
-    m->timer.end(s);
-    RGBL_HIP(hipGetLastError());
+    RGBL_TRY(launch(m, s, "k_map_refresh_desc", k_map_refresh_desc, dim3(np), dim3(64), 0, R));
   }
   RGBL_TRY(hc.fetch());
   if (out) {
@@ -4760,10 +3698,7 @@ int track_local_core(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t*
   memcpy(F.bounds, in->grid, sizeof(F.bounds));
   F.mbf = in->mbf; F.log_scale = in->log_scale_factor; F.cos_limit = in->viewing_cos_limit;
   F.far_points = in->far_points; F.th_far = in->th_far_points; F.n_levels = in->n_levels;
-  m->timer.begin("k_frustum", s);
-  hipLaunchKernelGGL(k_frustum, dim3((n1 + 255) / 256), dim3(256), 0, s, F);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
+  RGBL_TRY(launch(m, s, "k_frustum", k_frustum, dim3((n1 + 255) / 256), dim3(256), 0, F));
   if (do_search) {
     memcpy(P.grid, in->grid, sizeof(P.grid));
     P.th = in->th;
@@ -4789,1122 +3724,6 @@ int rgbl_frustum_cull(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t
 int rgbl_track_local_points(rgbl_matcher* m, const rgbl_track_local_input* in, uint8_t* in_view, rgbl_frustum_record* rec,
                             int* n_to_match, int32_t* match2, int* out_nmatches) {
   return track_local_core(m, in, in_view, rec, n_to_match, true, match2, out_nmatches);
-}
-
-namespace {
-// The prologue of the batch entry points whose problems read resident frames and a map-point pool: the problems of one call
-// share one pool, pool and frames are on the matcher's device, and the pool is locked while its slots are range-checked and
-// until the call returns.  An entry point declares its PoolCall FIRST, then - after lock() - StreamDrain, then HostCall:
-// destruction runs backwards, so the stream is drained (error returns included) before the pool is released.
-struct PoolCall {
-  const rgbl_matcher* m;
-  const char *what, *frame;   // the entry point and a resident frame as the error texts name them
-  rgbl_map_points* pool = nullptr;
-  std::unique_lock<std::mutex> held;
-  PoolCall(const rgbl_matcher* matcher, const char* name, const char* frame_name) : m(matcher), what(name), frame(frame_name) {}
-  // problem b reads pool `p` and the resident `frames` (null: host arrays)
-  int note(rgbl_map_points* p, std::initializer_list<const rgbl_device_frame*> frames, int b) {
-    for (const rgbl_device_frame* fr : frames)
-      if (fr && fr->device != m->device) {
-        set_error("%s %d: %s is on device %d, the matcher on %d", what, b, frame, fr->device, m->device);
-        return RGBL_ERR_INVALID;
-      }
-    if (!p) return RGBL_OK;
-    if (pool && pool != p) { set_error("%s %d: the problems of one call share one pool", what, b); return RGBL_ERR_INVALID; }
-    pool = p;
-    if (pool->device != m->device) { set_error("%s %d: the pool is on device %d, the matcher on %d", what, b, pool->device, m->device); return RGBL_ERR_INVALID; }
-    return RGBL_OK;
-  }
-  // locks the pool; under the lock, check(b) asks holds() for every slot problem b names (none if it does not read the pool)
-  // and returns RGBL_OK, or sets the error text of the first slot outside and returns RGBL_ERR_INVALID
-  int lock(int B, const std::function<int(int)>& check) {
-    if (!pool) return RGBL_OK;
-    held = std::unique_lock<std::mutex>(pool->mu);
-    for (int b = 0; b < B; ++b) RGBL_TRY(check(b));
-    return RGBL_OK;
-  }
-  bool holds(int slot) const { return slot >= 0 && slot < pool->cap; }
-};
-}  // namespace
-
-// ---- Optimizer::PoseOptimization (src/Optimizer.cc:814-1114) ---------------------------------------------------------
-namespace {
-// everything that can be refused is refused here, before anything is staged, launched or written; counts the correspondences
-int check_pose_opt_input(const rgbl_pose_opt_input* in, int b, bool host_only, int* n_corr) {
-  *n_corr = 0;
-  if (in->n < 0 || in->n > 65535 || in->n_points < 0 || (in->n > 0 && !in->mp_index)) { set_error("pose optimisation %d: n outside [0, 65535], n_points < 0 or no mp_index", b); return RGBL_ERR_INVALID; }
-  if (in->n_levels < 1 || in->n_levels > kProjMaxLevels || !in->inv_level_sigma2) { set_error("pose optimisation %d: n_levels outside [1, %d] or no inv_level_sigma2", b, kProjMaxLevels); return RGBL_ERR_INVALID; }
-  bool finite = std::isfinite(in->bf);
-  for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(in->Tcw_q[i]) && std::isfinite(in->K[i]);
-  for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(in->Tcw_t[i]);
-  if (!finite) { set_error("pose optimisation %d: the pose, K or bf is not finite", b); return RGBL_ERR_INVALID; }
-  if (host_only && (in->device || in->pool)) { set_error("pose optimisation %d: the host build reads host arrays only", b); return RGBL_ERR_INVALID; }
-  if (in->device ? in->device->n != in->n : (in->n > 0 && (!in->kp_xy || !in->kp_octave || !in->uright))) {
-    set_error("pose optimisation %d: the frame side is either kp_xy, kp_octave, uright or a resident frame of n features", b);
-    return RGBL_ERR_INVALID;
-  }
-  if (in->n_points > 0 && (in->pool ? !in->slot : !in->world_pos)) { set_error("pose optimisation %d: the map side is either world_pos or a pool with slot", b); return RGBL_ERR_INVALID; }
-  int m = 0;
-  for (int i = 0; i < in->n; ++i) {
-    const int p = in->mp_index[i];
-    if (p < -1 || p >= in->n_points) { set_error("pose optimisation %d: mp_index[%d] = %d outside [-1, %d)", b, i, p, in->n_points); return RGBL_ERR_INVALID; }
-    if (p < 0) continue;
-    ++m;
-    if (!in->device && (in->kp_octave[i] < 0 || in->kp_octave[i] >= in->n_levels)) { set_error("pose optimisation %d: octave %d of feature %d outside [0, %d)", b, in->kp_octave[i], i, in->n_levels); return RGBL_ERR_INVALID; }
-  }
-  *n_corr = m;
-  return RGBL_OK;
-}
-// what :869 / :897 and :1107-1113 leave in the caller's arrays, from the level of every correspondence
-void write_pose_opt_output(const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out, const float pose[7], const uint8_t* level, int ret,
-                           const PoDiag& diag) {
-  const bool untouched = diag.rounds == 0;   // fewer than 3 correspondences: the pose is not written (:996-997)
-  memcpy(out->Tcw_q, untouched ? in->Tcw_q : pose, sizeof(out->Tcw_q));
-  memcpy(out->Tcw_t, untouched ? in->Tcw_t : pose + 4, sizeof(out->Tcw_t));
-  if (out->outlier) {
-    int k = 0;
-    for (int i = 0; i < in->n; ++i)
-      if (in->mp_index[i] >= 0) out->outlier[i] = level[k++];
-  }
-  out->result = ret;
-  static_assert(sizeof(PoDiag) == sizeof(rgbl_pose_opt_diag), "PoDiag is rgbl_pose_opt_diag");
-  memcpy(&out->diag, &diag, sizeof(diag));
-}
-}  // namespace
-
-int rgbl_pose_optimization_host(const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out) {
-  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  int m = 0;
-  RGBL_TRY(check_pose_opt_input(in, 0, true, &m));
-  std::vector<PoEdge> edges((size_t)m);
-  int k = 0;
-  for (int i = 0; i < in->n; ++i) {
-    const int p = in->mp_index[i];
-    if (p < 0) continue;
-    PoEdge& e = edges[(size_t)k++];
-    for (int c = 0; c < 3; ++c) e.Xw[c] = in->world_pos[3 * (size_t)p + c];
-    e.obs[0] = in->kp_xy[2 * i]; e.obs[1] = in->kp_xy[2 * i + 1]; e.obs[2] = in->uright[i];
-    e.info = in->inv_level_sigma2[in->kp_octave[i]];
-    e.stereo = e.obs[2] >= 0.0f ? 1 : 0;
-    e.level = 0;
-    e.chi2 = 0.0;
-  }
-  std::vector<LmHostLanes<PoEdge, kPoSums>> lanes(1, LmHostLanes<PoEdge, kPoSums>(edges.data(), m));   // 57 KB: not on the stack
-  const PoCam C = {(double)in->K[0], (double)in->K[1], (double)in->K[2], (double)in->K[3], (double)in->bf};
-  PoPose T;
-  PoDiag diag;
-  const int ret = po_optimize(lanes[0], C, po_pose_from_float(in->Tcw_q, in->Tcw_t), m, T, diag);
-  float pose[7];
-  for (int i = 0; i < 4; ++i) pose[i] = (float)T.q[i];
-  for (int i = 0; i < 3; ++i) pose[4 + i] = (float)T.t[i];
-  std::vector<uint8_t> level((size_t)m);
-  for (int i = 0; i < m; ++i) level[(size_t)i] = edges[(size_t)i].level;
-  write_pose_opt_output(in, out, pose, level.data(), ret, diag);
-  return RGBL_OK;
-}
-
-int rgbl_pose_optimization_batch(rgbl_matcher* m, int n_problems, const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out) {
-  if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
-  const int B = n_problems;
-  std::vector<int> off((size_t)B + 1, 0);
-  PoolCall pc(m, "pose optimisation", "the frame");
-  for (int b = 0; b < B; ++b) {
-    int mb = 0;
-    RGBL_TRY(check_pose_opt_input(in + b, b, false, &mb));
-    if (off[(size_t)b] > INT_MAX - mb) { set_error("pose optimisation: more than 2^31 correspondences in one call"); return RGBL_ERR_INVALID; }
-    off[(size_t)b + 1] = off[(size_t)b] + mb;
-    RGBL_TRY(pc.note(in[b].pool, {in[b].device}, b));
-  }
-  if (B == 0) return RGBL_OK;
-  const int M = off[(size_t)B];
-  const rgbl_map_points* pool = pc.pool;
-  RGBL_TRY(pc.lock(B, [&](int b) -> int {
-    for (int i = 0; in[b].pool && i < in[b].n_points; ++i)
-      if (!pc.holds(in[b].slot[i])) { set_error("pose optimisation %d: slot %d outside [0, %d)", b, in[b].slot[i], pool->cap); return RGBL_ERR_INVALID; }
-    return RGBL_OK;
-  }));
-  // the correspondences of all problems back to back: feature, and row of the problem's world positions
-  std::vector<int32_t> feat((size_t)M), point((size_t)M);
-  for (int b = 0; b < B; ++b) {
-    int k = off[(size_t)b];
-    for (int i = 0; i < in[b].n; ++i) {
-      const int p = in[b].mp_index[i];
-      if (p < 0) continue;
-      feat[(size_t)k] = i;
-      point[(size_t)k] = in[b].pool ? in[b].slot[p] : p;
-      ++k;
-    }
-  }
-  RGBL_HIP(hipSetDevice(m->device));
-  StreamDrain drain(m->stream);  // behind pc (PoolCall)
-  HostCall hc(m);
-  hipStream_t s = hc.s;
-  std::vector<PoseOptProblem> prob((size_t)B);
-  PoseOptDev D;
-  memset(&D, 0, sizeof(D));
-  RGBL_TRY(hc.begin([&]() -> int {
-    for (int b = 0; b < B; ++b) {
-      PoseOptProblem& P = prob[(size_t)b];
-      memset(&P, 0, sizeof(P));
-      const rgbl_pose_opt_input& I = in[b];
-      RGBL_TRY(put_features(hc, I.device, I.n, nullptr, I.kp_xy, I.kp_octave, I.uright, nullptr, &P.xy, &P.oct, &P.ur));
-      if (I.pool) P.wpos = pool->d_wpos; else hc.put(&P.wpos, I.world_pos, (size_t)I.n_points * 3);
-      hc.put(&P.sigma, I.inv_level_sigma2, (size_t)I.n_levels);
-      P.edge_off = off[(size_t)b]; P.m = off[(size_t)b + 1] - off[(size_t)b]; P.n_levels = I.n_levels;
-      memcpy(P.q, I.Tcw_q, sizeof(P.q)); memcpy(P.t, I.Tcw_t, sizeof(P.t)); memcpy(P.K, I.K, sizeof(P.K));
-      P.bf = I.bf;
-    }
-    hc.put(&D.feat, feat.data(), (size_t)M);
-    hc.put(&D.point, point.data(), (size_t)M);
-    D.prob = hc.stage<PoseOptProblem>((size_t)B, [&](PoseOptProblem* dst) { memcpy(dst, prob.data(), sizeof(PoseOptProblem) * (size_t)B); });
-    D.level = hc.put_fill<uint8_t>((size_t)M, 0);   // what comes back, side by side
-    hc.mark_result(D.level, (size_t)M);
-    D.pose = hc.result<float>((size_t)B * 8);
-    D.ret = hc.result<int32_t>((size_t)B);
-    D.diag = hc.result<PoDiag>((size_t)B);
-    D.chi2 = hc.scratch<double>((size_t)M);
-    return RGBL_OK;
-  }));
-  m->timer.begin("k_pose_opt", s);
-  hipLaunchKernelGGL(k_pose_opt, dim3((unsigned)B), dim3(kPoLanes), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  RGBL_TRY(hc.fetch());
-  for (int b = 0; b < B; ++b)
-    write_pose_opt_output(in + b, out + b, hc.host(D.pose) + 8 * (size_t)b, hc.host(D.level) + off[(size_t)b], hc.host(D.ret)[b], hc.host(D.diag)[b]);
-  return RGBL_OK;
-}
-
-int rgbl_pose_optimization(rgbl_matcher* m, const rgbl_pose_opt_input* in, rgbl_pose_opt_output* out) {
-  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  return rgbl_pose_optimization_batch(m, 1, in, out);
-}
-
-// ---- Sim3Solver (src/Sim3Solver.cc) ------------------------------------------------------------------------------------
-namespace {
-constexpr int kS3MaxHyp = 1 << 20;
-// a problem the reference leaves at once (:155-159), or that has nothing to run
-inline bool sim3_skipped(const rgbl_sim3_input* in) { return in->n < 3 || in->n < in->min_inliers || in->n_hyp == 0; }
-// everything that can be refused without the pool is refused here, before anything is staged, launched or written
-int check_sim3_input(const rgbl_sim3_input* in, int b, bool host_only) {
-  if (in->n < 0 || in->n > 65535 || in->n_hyp < 0 || in->n_hyp > kS3MaxHyp) { set_error("sim3 %d: n outside [0, 65535] or n_hyp outside [0, %d]", b, kS3MaxHyp); return RGBL_ERR_INVALID; }
-  if (host_only && in->pool) { set_error("sim3 %d: the host build reads host arrays only", b); return RGBL_ERR_INVALID; }
-  if (in->n > 0 && (in->pool ? (!in->slot1 || !in->slot2) : (!in->x1c || !in->x2c))) { set_error("sim3 %d: the points are either x1c, x2c or a pool with slot1, slot2", b); return RGBL_ERR_INVALID; }
-  if (in->n > 0 && (!in->max_err1 || !in->max_err2)) { set_error("sim3 %d: no max_err1 / max_err2", b); return RGBL_ERR_INVALID; }
-  bool finite = true;
-  for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(in->K1[i]) && std::isfinite(in->K2[i]);
-  if (in->pool) {
-    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(in->Rcw1[i]) && std::isfinite(in->Rcw2[i]);
-    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(in->tcw1[i]) && std::isfinite(in->tcw2[i]);
-  }
-  for (int i = 0; i < in->n; ++i) finite = finite && std::isfinite(in->max_err1[i]) && std::isfinite(in->max_err2[i]);
-  if (!finite) { set_error("sim3 %d: K, a pose or a threshold is not finite", b); return RGBL_ERR_INVALID; }
-  if (in->n >= 3 && in->n_hyp > 0) {
-    if (!in->samples) { set_error("sim3 %d: no samples", b); return RGBL_ERR_INVALID; }
-    for (int k = 0; k < in->n_hyp; ++k) {
-      const int32_t* s = in->samples + 3 * (size_t)k;
-      if (s[0] < 0 || s[0] >= in->n || s[1] < 0 || s[1] >= in->n || s[2] < 0 || s[2] >= in->n || s[0] == s[1] || s[0] == s[2] || s[1] == s[2]) {
-        set_error("sim3 %d: sample %d = (%d, %d, %d) is not three distinct indices in [0, %d)", b, k, s[0], s[1], s[2], in->n);
-        return RGBL_ERR_INVALID;
-      }
-    }
-  }
-  return RGBL_OK;
-}
-void write_sim3_output(const rgbl_sim3_input* in, rgbl_sim3_output* out, const Sim3Result& r, const uint8_t* inlier, const Sim3HypOut* hyp) {
-  out->selected = r.sel.selected; out->converged = r.sel.converged; out->n_inliers = r.sel.n_inliers; out->iterations_run = r.sel.iterations;
-  if (r.sel.selected >= 0) {
-    memcpy(out->T12, r.T12, sizeof(out->T12)); memcpy(out->R12, r.R, sizeof(out->R12)); memcpy(out->t12, r.t, sizeof(out->t12));
-    out->s12 = r.s;
-    if (out->inlier && in->n) memcpy(out->inlier, inlier, (size_t)in->n);
-  }
-  for (int k = 0; k < in->n_hyp; ++k) {
-    if (out->counts) out->counts[k] = hyp[k].count;
-    if (out->T12_all) memcpy(out->T12_all + 16 * (size_t)k, hyp[k].T12, sizeof(hyp[k].T12));
-  }
-}
-}  // namespace
-
-int rgbl_sim3_ransac_host(const rgbl_sim3_input* in, rgbl_sim3_output* out) {
-  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  RGBL_TRY(check_sim3_input(in, 0, true));
-  if (sim3_skipped(in)) { out->selected = -1; return RGBL_OK; }
-  const int n = in->n, words = (n + 63) / 64;
-  std::vector<S3Point> pts((size_t)n);
-  for (int i = 0; i < n; ++i) pts[(size_t)i] = s3_point(in->x1c + 3 * (size_t)i, in->x2c + 3 * (size_t)i, in->K1, in->K2, in->max_err1[i], in->max_err2[i]);
-  std::vector<Sim3HypOut> hyp((size_t)in->n_hyp);
-  std::vector<int32_t> counts((size_t)in->n_hyp);
-  std::vector<uint64_t> mask((size_t)in->n_hyp * (size_t)words, 0);
-  for (int h = 0; h < in->n_hyp; ++h) {
-    float P1[9], P2[9];
-    for (int k = 0; k < 3; ++k) {
-      const S3Point& p = pts[(size_t)in->samples[3 * (size_t)h + k]];
-      for (int c = 0; c < 3; ++c) { P1[3 * k + c] = p.x1[c]; P2[3 * k + c] = p.x2[c]; }
-    }
-    S3Hyp H;
-    s3_compute_sim3(P1, P2, in->fix_scale, H);
-    int count = 0;
-    for (int i = 0; i < n; ++i)
-      if (s3_is_inlier(H, in->K1, in->K2, pts[(size_t)i])) { mask[(size_t)h * words + (i >> 6)] |= (uint64_t)1 << (i & 63); ++count; }
-    Sim3HypOut& o = hyp[(size_t)h];
-    o.count = counts[(size_t)h] = count;
-    s3_T12(H, o.T12);
-    memcpy(o.R, H.R, sizeof(o.R)); memcpy(o.t, H.t, sizeof(o.t));
-    o.s = H.s;
-  }
-  Sim3Result r;
-  memset(&r, 0, sizeof(r));
-  r.sel = s3_select(counts.data(), in->n_hyp, in->best_inliers, in->min_inliers);
-  std::vector<uint8_t> inl((size_t)n, 0);
-  if (r.sel.selected >= 0) {
-    const Sim3HypOut& o = hyp[(size_t)r.sel.selected];
-    memcpy(r.T12, o.T12, sizeof(r.T12)); memcpy(r.R, o.R, sizeof(r.R)); memcpy(r.t, o.t, sizeof(r.t));
-    r.s = o.s;
-    for (int i = 0; i < n; ++i) inl[(size_t)i] = (uint8_t)((mask[(size_t)r.sel.selected * words + (i >> 6)] >> (i & 63)) & 1u);
-  }
-  write_sim3_output(in, out, r, inl.data(), hyp.data());
-  return RGBL_OK;
-}
-
-int rgbl_sim3_ransac_batch(rgbl_matcher* m, int n_problems, const rgbl_sim3_input* in, rgbl_sim3_output* out) {
-  if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
-  const int B = n_problems;
-  if (B > 32767) { set_error("sim3: more than 32767 problems in one call"); return RGBL_ERR_INVALID; }
-  PoolCall pc(m, "sim3", "a frame");
-  // offsets of the problems that run: hypotheses, mask words, flags
-  std::vector<int> hyp_off((size_t)B + 1, 0), inl_off((size_t)B + 1, 0);
-  std::vector<size_t> word_off((size_t)B + 1, 0);
-  int max_hyp = 0;
-  for (int b = 0; b < B; ++b) {
-    RGBL_TRY(check_sim3_input(in + b, b, false));
-    RGBL_TRY(pc.note(in[b].pool, {}, b));
-    const bool run = !sim3_skipped(in + b);
-    const int nh = run ? in[b].n_hyp : 0, nn = run ? in[b].n : 0;
-    if (hyp_off[(size_t)b] > INT_MAX - nh) { set_error("sim3: more than 2^31 hypotheses in one call"); return RGBL_ERR_INVALID; }
-    hyp_off[(size_t)b + 1] = hyp_off[(size_t)b] + nh;
-    inl_off[(size_t)b + 1] = inl_off[(size_t)b] + nn;   // at most 65535 each: B < 2^15 problems fit an int
-    word_off[(size_t)b + 1] = word_off[(size_t)b] + (size_t)nh * (size_t)((nn + 63) / 64);
-    max_hyp = std::max(max_hyp, nh);
-  }
-  if (word_off[(size_t)B] > (size_t)INT_MAX) { set_error("sim3: more than 2^31 mask words in one call"); return RGBL_ERR_INVALID; }
-  const rgbl_map_points* pool = pc.pool;
-  RGBL_TRY(pc.lock(B, [&](int b) -> int {
-    for (int i = 0; in[b].pool && i < in[b].n; ++i)
-      if (!pc.holds(in[b].slot1[i]) || !pc.holds(in[b].slot2[i])) {
-        set_error("sim3 %d: slots (%d, %d) of correspondence %d outside [0, %d)", b, in[b].slot1[i], in[b].slot2[i], i, pool->cap);
-        return RGBL_ERR_INVALID;
-      }
-    return RGBL_OK;
-  }));
-  const int H = hyp_off[(size_t)B];
-  if (H == 0) {   // nothing to run (B == 0 included)
-    for (int b = 0; b < B; ++b) out[b].selected = -1;
-    return RGBL_OK;
-  }
-  RGBL_HIP(hipSetDevice(m->device));
-  StreamDrain drain(m->stream);  // behind pc (PoolCall)
-  HostCall hc(m);
-  hipStream_t s = hc.s;
-  std::vector<Sim3Problem> prob((size_t)B);
-  Sim3Dev D;
-  memset(&D, 0, sizeof(D));
-  bool diag = false;
-  for (int b = 0; b < B; ++b) diag = diag || out[b].counts || out[b].T12_all;
-  RGBL_TRY(hc.begin([&]() -> int {
-    for (int b = 0; b < B; ++b) {
-      Sim3Problem& P = prob[(size_t)b];
-      memset(&P, 0, sizeof(P));
-      const rgbl_sim3_input& I = in[b];
-      if (sim3_skipped(&I)) continue;   // n_hyp = 0: no workgroup touches it
-      if (I.pool) {
-        P.pool_form = 1; P.wpos = pool->d_wpos;
-        hc.put(&P.slot1, I.slot1, (size_t)I.n);
-        hc.put(&P.slot2, I.slot2, (size_t)I.n);
-        memcpy(P.Rcw1, I.Rcw1, sizeof(P.Rcw1)); memcpy(P.tcw1, I.tcw1, sizeof(P.tcw1));
-        memcpy(P.Rcw2, I.Rcw2, sizeof(P.Rcw2)); memcpy(P.tcw2, I.tcw2, sizeof(P.tcw2));
-      } else {
-        hc.put(&P.x1, I.x1c, (size_t)I.n * 3);
-        hc.put(&P.x2, I.x2c, (size_t)I.n * 3);
-      }
-      hc.put(&P.e1, I.max_err1, (size_t)I.n);
-      hc.put(&P.e2, I.max_err2, (size_t)I.n);
-      hc.put(&P.samples, I.samples, (size_t)I.n_hyp * 3);
-      P.n = I.n; P.n_hyp = I.n_hyp; P.words = (I.n + 63) / 64;
-      P.hyp_off = hyp_off[(size_t)b]; P.word_off = (int)word_off[(size_t)b]; P.inl_off = inl_off[(size_t)b];
-      P.fix_scale = I.fix_scale ? 1 : 0; P.min_inliers = I.min_inliers; P.best_inliers = I.best_inliers;
-      memcpy(P.K1, I.K1, sizeof(P.K1)); memcpy(P.K2, I.K2, sizeof(P.K2));
-    }
-    D.prob = hc.stage<Sim3Problem>((size_t)B, [&](Sim3Problem* dst) { memcpy(dst, prob.data(), sizeof(Sim3Problem) * (size_t)B); });
-    D.res = hc.result<Sim3Result>((size_t)B);   // what comes back, side by side
-    D.inlier = hc.result<uint8_t>((size_t)inl_off[(size_t)B]);
-    D.hyp = diag ? hc.result<Sim3HypOut>((size_t)H) : hc.scratch<Sim3HypOut>((size_t)H);
-    D.mask = hc.scratch<unsigned long long>(word_off[(size_t)B]);
-    return RGBL_OK;
-  }));
-  m->timer.begin("k_sim3_hypotheses", s);
-  hipLaunchKernelGGL(k_sim3_hypotheses, dim3((unsigned)((max_hyp + kS3HypPerGroup - 1) / kS3HypPerGroup), (unsigned)B), dim3(256), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  m->timer.begin("k_sim3_select", s);
-  hipLaunchKernelGGL(k_sim3_select, dim3((unsigned)B), dim3(256), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  RGBL_TRY(hc.fetch());
-  for (int b = 0; b < B; ++b) {
-    if (sim3_skipped(in + b)) { out[b].selected = -1; continue; }
-    write_sim3_output(in + b, out + b, hc.host(D.res)[b], hc.host(D.inlier) + inl_off[(size_t)b], hc.host(D.hyp) + hyp_off[(size_t)b]);
-  }
-  return RGBL_OK;
-}
-
-int rgbl_sim3_ransac(rgbl_matcher* m, const rgbl_sim3_input* in, rgbl_sim3_output* out) {
-  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  return rgbl_sim3_ransac_batch(m, 1, in, out);
-}
-
-// ---- MLPnPsolver (src/MLPnPsolver.cpp) ------------------------------------------------------------------------------------
-namespace {
-constexpr int kMlMaxHyp = 1 << 20;
-constexpr int kMlMaxMaskWordsLog2 = 26;   // 512 MB of masks: 2^20 hypotheses of 4096 correspondences, or 65535 correspondences of 65536 hypotheses
-constexpr size_t kMlMaxMaskWords = (size_t)1 << kMlMaxMaskWordsLog2;
-// Everything that can be refused without the pool is refused here, before anything is staged, launched or written.  *n_corr = N.
-int check_mlpnp_input(const rgbl_mlpnp_input* in, int b, bool host_only, int* n_corr) {
-  *n_corr = 0;
-  if (in->n < 0 || in->n > 65535 || in->n_hyp < 0 || in->n_hyp > kMlMaxHyp) { set_error("mlpnp %d: n outside [0, 65535] or n_hyp outside [0, %d]", b, kMlMaxHyp); return RGBL_ERR_INVALID; }
-  if (in->n_points < 0 || (in->n > 0 && !in->mp_index)) { set_error("mlpnp %d: n_points < 0 or no mp_index", b); return RGBL_ERR_INVALID; }
-  if (in->min_inliers < 6) { set_error("mlpnp %d: min_inliers %d < 6, the minimal set", b, in->min_inliers); return RGBL_ERR_INVALID; }
-  if (in->n_levels < 1 || in->n_levels > kProjMaxLevels || !in->level_sigma2) { set_error("mlpnp %d: n_levels outside [1, %d] or no level_sigma2", b, kProjMaxLevels); return RGBL_ERR_INVALID; }
-  bool finite = std::isfinite(in->th2);
-  for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(in->K[i]);
-  for (int i = 0; i < in->n_levels; ++i) finite = finite && std::isfinite(in->level_sigma2[i]);
-  if (!finite) { set_error("mlpnp %d: K, th2 or a sigma2 is not finite", b); return RGBL_ERR_INVALID; }
-  if (host_only && (in->device || in->pool)) { set_error("mlpnp %d: the host build reads host arrays only", b); return RGBL_ERR_INVALID; }
-  if (in->device ? in->device->n != in->n : (in->n > 0 && (!in->kp_xy || !in->kp_octave))) {
-    set_error("mlpnp %d: the frame side is either kp_xy, kp_octave or a resident frame of n features", b);
-    return RGBL_ERR_INVALID;
-  }
-  if (in->n_points > 0 && (in->pool ? !in->slot : !in->world_pos)) { set_error("mlpnp %d: the map side is either world_pos or a pool with slot", b); return RGBL_ERR_INVALID; }
-  int N = 0;
-  for (int i = 0; i < in->n; ++i) {
-    const int p = in->mp_index[i];
-    if (p < -1 || p >= in->n_points) { set_error("mlpnp %d: mp_index[%d] = %d outside [-1, %d)", b, i, p, in->n_points); return RGBL_ERR_INVALID; }
-    if (p < 0) continue;
-    ++N;
-    if (!in->device && (in->kp_octave[i] < 0 || in->kp_octave[i] >= in->n_levels)) { set_error("mlpnp %d: octave %d of feature %d outside [0, %d)", b, in->kp_octave[i], i, in->n_levels); return RGBL_ERR_INVALID; }
-  }
-  if (in->best_inliers < 0) { set_error("mlpnp %d: best_inliers < 0", b); return RGBL_ERR_INVALID; }
-  if (in->best_inliers > 0) {
-    int ones = 0;
-    for (int i = 0; in->best_mask && i < N; ++i) ones += in->best_mask[i] ? 1 : 0;
-    if (!in->best_mask || ones != in->best_inliers || ones < 6) { set_error("mlpnp %d: best_inliers = %d needs a best_mask with as many (>= 6) ones", b, in->best_inliers); return RGBL_ERR_INVALID; }
-  }
-  if (N >= in->min_inliers && in->n_hyp > 0) {
-    if (N < 6) { set_error("mlpnp %d: %d correspondences, a sample needs 6", b, N); return RGBL_ERR_INVALID; }
-    if (!in->samples) { set_error("mlpnp %d: no samples", b); return RGBL_ERR_INVALID; }
-    for (int k = 0; k < in->n_hyp; ++k) {
-      const int32_t* s = in->samples + 6 * (size_t)k;
-      bool ok = true;
-      for (int i = 0; i < 6; ++i) {
-        ok = ok && s[i] >= 0 && s[i] < N;
-        for (int j = 0; j < i; ++j) ok = ok && s[i] != s[j];
-      }
-      if (!ok) { set_error("mlpnp %d: sample %d = (%d, %d, %d, %d, %d, %d) is not six distinct indices in [0, %d)", b, k, s[0], s[1], s[2], s[3], s[4], s[5], N); return RGBL_ERR_INVALID; }
-    }
-  }
-  *n_corr = N;
-  return RGBL_OK;
-}
-// a problem the reference leaves at once (:106-110), or that has nothing to run
-inline bool mlpnp_skipped(const rgbl_mlpnp_input* in, int N) { return N < in->min_inliers || in->n_hyp == 0; }
-void write_mlpnp_skipped(const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out, int N) {
-  out->found = 0; out->no_more = N < in->min_inliers ? 1 : 0; out->n_inliers = 0; out->iterations_run = 0; out->refines = 0;
-  for (int k = 0; k < 16; ++k) out->Tcw[k] = (k % 5 == 0) ? 1.0f : 0.0f;
-  out->best_inliers = in->best_inliers;
-  memcpy(out->best_Tcw, in->best_Tcw, sizeof(out->best_Tcw));
-  if (out->best_mask && in->best_inliers > 0) memcpy(out->best_mask, in->best_mask, (size_t)N);
-}
-// inlier / best: per correspondence
-void write_mlpnp_output(const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out, int N, const MlpnpResult& r, const uint8_t* inlier, const uint8_t* best,
-                        const MlpnpHypOut* hyp) {
-  const MlScan& sc = r.scan;
-  out->found = sc.found; out->no_more = sc.no_more; out->n_inliers = sc.n_inliers; out->iterations_run = sc.iterations; out->refines = sc.refines;
-  if (sc.found) memcpy(out->Tcw, r.Tcw, sizeof(out->Tcw));
-  else for (int k = 0; k < 16; ++k) out->Tcw[k] = (k % 5 == 0) ? 1.0f : 0.0f;
-  if (sc.found && out->inlier) {
-    memset(out->inlier, 0, (size_t)in->n);
-    int k = 0;
-    for (int i = 0; i < in->n; ++i)
-      if (in->mp_index[i] >= 0) out->inlier[i] = inlier[k++];
-  }
-  out->best_inliers = sc.best;
-  memcpy(out->best_Tcw, r.best_Tcw, sizeof(out->best_Tcw));
-  if (out->best_mask && sc.best > 0) memcpy(out->best_mask, best, (size_t)N);
-  for (int k = 0; hyp && k < in->n_hyp; ++k) {
-    if (out->counts) out->counts[k] = hyp[k].count;
-    if (out->gn_path) out->gn_path[k] = hyp[k].path;
-    if (out->Tcw_all) {
-      double* T = out->Tcw_all + 12 * (size_t)k;
-      for (int i = 0; i < 3; ++i) { T[4 * i] = hyp[k].T[3 * i]; T[4 * i + 1] = hyp[k].T[3 * i + 1]; T[4 * i + 2] = hyp[k].T[3 * i + 2]; T[4 * i + 3] = hyp[k].T[9 + i]; }
-    }
-  }
-}
-// the correspondences of a problem: feature and row of the map side
-void mlpnp_correspondences(const rgbl_mlpnp_input* in, int32_t* feat, int32_t* point) {
-  int k = 0;
-  for (int i = 0; i < in->n; ++i) {
-    const int p = in->mp_index[i];
-    if (p < 0) continue;
-    feat[k] = i;
-    point[k] = in->pool ? in->slot[p] : p;
-    ++k;
-  }
-}
-void mlpnp_mask_words(const uint8_t* bytes, int N, unsigned long long* words) {
-  for (int w = 0; w < (N + 63) / 64; ++w) words[w] = 0;
-  for (int i = 0; i < N; ++i)
-    if (bytes[i]) words[i >> 6] |= 1ull << (i & 63);
-}
-}  // namespace
-
-int rgbl_mlpnp_ransac_host(const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out) {
-  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  int N = 0;
-  RGBL_TRY(check_mlpnp_input(in, 0, true, &N));
-  if (mlpnp_skipped(in, N)) { write_mlpnp_skipped(in, out, N); return RGBL_OK; }
-  const int words = (N + 63) / 64;
-  std::vector<int32_t> feat((size_t)N), point((size_t)N);
-  mlpnp_correspondences(in, feat.data(), point.data());
-  MlView v;
-  v.xy = in->kp_xy; v.oct = in->kp_octave; v.wpos = in->world_pos; v.sigma2 = in->level_sigma2; v.feat = feat.data(); v.point = point.data();
-  v.N = N; v.n_levels = in->n_levels; v.th2 = in->th2;
-  memcpy(v.K, in->K, sizeof(v.K));
-  std::vector<MlpnpHypOut> hyp((size_t)in->n_hyp);
-  std::vector<unsigned long long> mask((size_t)in->n_hyp * (size_t)words, 0ull), carried((size_t)words, 0ull);
-  if (in->best_inliers > 0) mlpnp_mask_words(in->best_mask, N, carried.data());
-  std::vector<MlWork> work(1);
-  MlHostX x;
-  auto check = [&](const double* R, const double* t, unsigned long long* m) {
-    int count = 0;
-    for (int w = 0; w < words; ++w) m[w] = 0ull;
-    for (int i = 0; i < N; ++i)
-      if (ml_is_inlier(v, R, t, i)) { m[i >> 6] |= 1ull << (i & 63); ++count; }
-    return count;
-  };
-  for (int h = 0; h < in->n_hyp; ++h) {
-    MlSixSums Q;
-    const MlSet S = {&v, in->samples + 6 * (size_t)h, 6};
-    MlpnpHypOut& o = hyp[(size_t)h];
-    ml_compute_pose(x, work[0], Q, S, o.T, o.T + 9, &o.path);
-    o.count = check(o.T, o.T + 9, mask.data() + (size_t)h * (size_t)words);
-  }
-  struct Counts {
-    const MlpnpHypOut* h;
-    int operator[](int k) const { return h[k].count; }
-  };
-  MlpnpResult r;
-  memset(&r, 0, sizeof(r));
-  r.scan = ml_scan(Counts{hyp.data()}, in->n_hyp, in->min_inliers, in->best_inliers);
-  const MlScan& sc = r.scan;
-  if (sc.record >= 0) ml_Tcw(hyp[(size_t)sc.record].T, hyp[(size_t)sc.record].T + 9, r.best_Tcw);
-  else memcpy(r.best_Tcw, in->best_Tcw, sizeof(r.best_Tcw));
-  if (sc.selected >= 0) ml_Tcw(hyp[(size_t)sc.selected].T, hyp[(size_t)sc.selected].T + 9, r.Tcw);
-  else memcpy(r.Tcw, r.best_Tcw, sizeof(r.Tcw));
-  std::vector<uint8_t> inl((size_t)N, 0), best((size_t)N, 0);
-  const unsigned long long* bm = sc.record >= 0 ? mask.data() + (size_t)sc.record * (size_t)words : carried.data();
-  const unsigned long long* om = sc.selected >= 0 ? mask.data() + (size_t)sc.selected * (size_t)words : bm;
-  for (int i = 0; i < N; ++i) {
-    best[(size_t)i] = (uint8_t)((bm[i >> 6] >> (i & 63)) & 1ull);
-    inl[(size_t)i] = (uint8_t)((om[i >> 6] >> (i & 63)) & 1ull);
-  }
-  write_mlpnp_output(in, out, N, r, inl.data(), best.data(), hyp.data());
-  return RGBL_OK;
-}
-
-int rgbl_mlpnp_ransac_batch(rgbl_matcher* m, int n_problems, const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out) {
-  if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
-  const int B = n_problems;
-  if (B > 32767) { set_error("mlpnp: more than 32767 problems in one call"); return RGBL_ERR_INVALID; }
-  PoolCall pc(m, "mlpnp", "the frame");
-  // offsets of the problems that run: hypotheses, mask words, correspondences, words of the carried-in mask
-  std::vector<int> Ns((size_t)B, 0), hyp_off((size_t)B + 1, 0), corr_off((size_t)B + 1, 0), cword_off((size_t)B + 1, 0);
-  std::vector<size_t> word_off((size_t)B + 1, 0);
-  int max_hyp = 0;
-  for (int b = 0; b < B; ++b) {
-    RGBL_TRY(check_mlpnp_input(in + b, b, false, &Ns[(size_t)b]));
-    RGBL_TRY(pc.note(in[b].pool, {in[b].device}, b));
-    const bool run = !mlpnp_skipped(in + b, Ns[(size_t)b]);
-    const int nh = run ? in[b].n_hyp : 0, nn = run ? Ns[(size_t)b] : 0;
-    if (hyp_off[(size_t)b] > INT_MAX - nh) { set_error("mlpnp: more than 2^31 hypotheses in one call"); return RGBL_ERR_INVALID; }
-    hyp_off[(size_t)b + 1] = hyp_off[(size_t)b] + nh;
-    corr_off[(size_t)b + 1] = corr_off[(size_t)b] + nn;   // at most 65535 each: B < 2^15 problems fit an int
-    cword_off[(size_t)b + 1] = cword_off[(size_t)b] + (nn + 63) / 64;
-    word_off[(size_t)b + 1] = word_off[(size_t)b] + (size_t)nh * (size_t)((nn + 63) / 64);
-    max_hyp = std::max(max_hyp, nh);
-  }
-  if (word_off[(size_t)B] > (size_t)kMlMaxMaskWords) { set_error("mlpnp: more than 2^%d mask words (n_hyp x ceil(N / 64), all problems) in one call", kMlMaxMaskWordsLog2); return RGBL_ERR_INVALID; }
-  const rgbl_map_points* pool = pc.pool;
-  RGBL_TRY(pc.lock(B, [&](int b) -> int {
-    for (int i = 0; in[b].pool && i < in[b].n_points; ++i)
-      if (!pc.holds(in[b].slot[i])) { set_error("mlpnp %d: slot %d outside [0, %d)", b, in[b].slot[i], pool->cap); return RGBL_ERR_INVALID; }
-    return RGBL_OK;
-  }));
-  const int H = hyp_off[(size_t)B], M = corr_off[(size_t)B];
-  if (H == 0) {   // nothing to run (B == 0 included)
-    for (int b = 0; b < B; ++b) write_mlpnp_skipped(in + b, out + b, Ns[(size_t)b]);
-    return RGBL_OK;
-  }
-  std::vector<int32_t> feat((size_t)M), point((size_t)M);
-  std::vector<unsigned long long> carried((size_t)cword_off[(size_t)B], 0ull);
-  for (int b = 0; b < B; ++b) {
-    if (corr_off[(size_t)b + 1] == corr_off[(size_t)b]) continue;
-    mlpnp_correspondences(in + b, feat.data() + corr_off[(size_t)b], point.data() + corr_off[(size_t)b]);
-    if (in[b].best_inliers > 0) mlpnp_mask_words(in[b].best_mask, Ns[(size_t)b], carried.data() + cword_off[(size_t)b]);
-  }
-  RGBL_HIP(hipSetDevice(m->device));
-  StreamDrain drain(m->stream);  // behind pc (PoolCall)
-  HostCall hc(m);
-  hipStream_t s = hc.s;
-  std::vector<MlpnpProblem> prob((size_t)B);
-  MlpnpDev D;
-  memset(&D, 0, sizeof(D));
-  bool diag = false;
-  for (int b = 0; b < B; ++b) diag = diag || out[b].counts || out[b].Tcw_all || out[b].gn_path;
-  RGBL_TRY(hc.begin([&]() -> int {
-    const int32_t *d_feat = nullptr, *d_point = nullptr;
-    const unsigned long long* d_carried = nullptr;
-    hc.put(&d_feat, feat.data(), (size_t)M);
-    hc.put(&d_point, point.data(), (size_t)M);
-    hc.put(&d_carried, carried.data(), carried.size());
-    for (int b = 0; b < B; ++b) {
-      MlpnpProblem& P = prob[(size_t)b];
-      memset(&P, 0, sizeof(P));
-      const rgbl_mlpnp_input& I = in[b];
-      if (mlpnp_skipped(&I, Ns[(size_t)b])) continue;   // n_hyp = 0: no workgroup touches it
-      RGBL_TRY(put_features(hc, I.device, I.n, nullptr, I.kp_xy, I.kp_octave, nullptr, nullptr, &P.v.xy, &P.v.oct, nullptr));
-      if (I.pool) P.v.wpos = pool->d_wpos; else hc.put(&P.v.wpos, I.world_pos, (size_t)I.n_points * 3);
-      hc.put(&P.v.sigma2, I.level_sigma2, (size_t)I.n_levels);
-      hc.put(&P.samples, I.samples, (size_t)I.n_hyp * 6);
-      P.v.feat = d_feat + corr_off[(size_t)b]; P.v.point = d_point + corr_off[(size_t)b];
-      P.v.N = Ns[(size_t)b]; P.v.n_levels = I.n_levels; P.v.th2 = I.th2;
-      memcpy(P.v.K, I.K, sizeof(P.v.K));
-      P.best_mask = I.best_inliers > 0 ? d_carried + cword_off[(size_t)b] : nullptr;
-      P.n_hyp = I.n_hyp; P.min_inliers = I.min_inliers; P.best_inliers = I.best_inliers;
-      P.hyp_off = hyp_off[(size_t)b]; P.word_off = (int)word_off[(size_t)b]; P.words = (Ns[(size_t)b] + 63) / 64;
-      P.corr_off = corr_off[(size_t)b]; P.cword_off = cword_off[(size_t)b];
-      memcpy(P.best_Tcw, I.best_Tcw, sizeof(P.best_Tcw));
-    }
-    D.prob = hc.stage<MlpnpProblem>((size_t)B, [&](MlpnpProblem* dst) { memcpy(dst, prob.data(), sizeof(MlpnpProblem) * (size_t)B); });
-    D.res = hc.result<MlpnpResult>((size_t)B);   // what comes back, side by side
-    D.inlier = hc.result<uint8_t>((size_t)M);
-    D.best_out = hc.result<uint8_t>((size_t)M);
-    D.hyp = diag ? hc.result<MlpnpHypOut>((size_t)H) : hc.scratch<MlpnpHypOut>((size_t)H);
-    D.mask = hc.scratch<unsigned long long>(word_off[(size_t)B]);
-    return RGBL_OK;
-  }));
-  m->timer.begin("k_mlpnp_hypotheses", s);
-  hipLaunchKernelGGL(k_mlpnp_hypotheses, dim3((unsigned)((max_hyp + kMlHypPerGroup - 1) / kMlHypPerGroup), (unsigned)B), dim3(256), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  m->timer.begin("k_mlpnp_select", s);
-  hipLaunchKernelGGL(k_mlpnp_select, dim3((unsigned)B), dim3(256), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  RGBL_TRY(hc.fetch());
-  for (int b = 0; b < B; ++b) {
-    if (mlpnp_skipped(in + b, Ns[(size_t)b])) { write_mlpnp_skipped(in + b, out + b, Ns[(size_t)b]); continue; }
-    write_mlpnp_output(in + b, out + b, Ns[(size_t)b], hc.host(D.res)[b], hc.host(D.inlier) + corr_off[(size_t)b], hc.host(D.best_out) + corr_off[(size_t)b],
-                       diag ? hc.host(D.hyp) + hyp_off[(size_t)b] : nullptr);
-  }
-  return RGBL_OK;
-}
-
-int rgbl_mlpnp_ransac(rgbl_matcher* m, const rgbl_mlpnp_input* in, rgbl_mlpnp_output* out) {
-  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  return rgbl_mlpnp_ransac_batch(m, 1, in, out);
-}
-
-// ---- TwoViewReconstruction (src/TwoViewReconstruction.cc) -------------------------------------------------------------------
-namespace {
-constexpr int kTvMaxHyp = 1 << 20;
-constexpr int kTvMaxMaskWordsLog2 = 26;   // 512 MB of masks
-constexpr size_t kTvMaxMaskWords = (size_t)1 << kTvMaxMaskWordsLog2;
-constexpr int kTvMaxKeysLog2 = 24;           // keys of frame 1 over the problems of a call that run: 104 B of CheckRT scratch each, 1.7 GB
-constexpr size_t kTvMaxKeys = (size_t)1 << kTvMaxKeysLog2;
-// Everything that can be refused is refused here, before anything is staged, launched or written.  *n_match = N.
-int check_two_view_input(const rgbl_two_view_input* in, int b, bool host_only, int* n_match) {
-  *n_match = 0;
-  if (in->n1 < 0 || in->n1 > 65535 || in->n2 < 0 || in->n2 > 65535) { set_error("two view %d: n1 or n2 outside [0, 65535]", b); return RGBL_ERR_INVALID; }
-  if (in->n_hyp < 0 || in->n_hyp > kTvMaxHyp) { set_error("two view %d: n_hyp outside [0, %d]", b, kTvMaxHyp); return RGBL_ERR_INVALID; }
-  bool finite = std::isfinite(in->sigma);
-  for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(in->K[i]);
-  if (!finite) { set_error("two view %d: K or sigma is not finite", b); return RGBL_ERR_INVALID; }
-  if (host_only && (in->device1 || in->device2)) { set_error("two view %d: the host build reads host arrays only", b); return RGBL_ERR_INVALID; }
-  if (in->device1 ? in->device1->n != in->n1 : (in->n1 > 0 && !in->kp1_xy)) { set_error("two view %d: frame 1 is either kp1_xy or a resident frame of n1 features", b); return RGBL_ERR_INVALID; }
-  if (in->device2 ? in->device2->n != in->n2 : (in->n2 > 0 && !in->kp2_xy)) { set_error("two view %d: frame 2 is either kp2_xy or a resident frame of n2 features", b); return RGBL_ERR_INVALID; }
-  if (in->n1 > 0 && !in->matches12) { set_error("two view %d: no matches12", b); return RGBL_ERR_INVALID; }
-  int N = 0;
-  for (int i = 0; i < in->n1; ++i) {
-    const int q = in->matches12[i];
-    if (q < -1 || q >= in->n2) { set_error("two view %d: matches12[%d] = %d outside [-1, %d)", b, i, q, in->n2); return RGBL_ERR_INVALID; }
-    N += q >= 0 ? 1 : 0;
-  }
-  if (in->n_hyp > 0) {
-    if (N < 8) { set_error("two view %d: %d matches, a set needs 8", b, N); return RGBL_ERR_INVALID; }
-    if (!in->samples) { set_error("two view %d: no samples", b); return RGBL_ERR_INVALID; }
-    for (int k = 0; k < in->n_hyp; ++k) {
-      const int32_t* s = in->samples + 8 * (size_t)k;
-      bool ok = true;
-      for (int i = 0; i < 8; ++i) {
-        ok = ok && s[i] >= 0 && s[i] < N;
-        for (int j = 0; j < i; ++j) ok = ok && s[i] != s[j];
-      }
-      if (!ok) { set_error("two view %d: set %d is not eight distinct indices in [0, %d)", b, k, N); return RGBL_ERR_INVALID; }
-    }
-  }
-  *n_match = N;
-  return RGBL_OK;
-}
-// mvMatches12 (:55-64)
-void two_view_matches(const rgbl_two_view_input* in, int32_t* m1, int32_t* m2) {
-  int k = 0;
-  for (int i = 0; i < in->n1; ++i)
-    if (in->matches12[i] >= 0) { m1[k] = i; m2[k] = in->matches12[i]; ++k; }
-}
-// n_hyp == 0: both scores stay 0 (:144, :195), the exit of :113
-void write_two_view_skipped(rgbl_two_view_output* out) {
-  out->found = 0; out->model = -1; out->exit_code = kTvNoScore; out->SH = 0.0f; out->SF = 0.0f; out->best_h = -1; out->best_f = -1;
-  for (int k = 0; k < 9; ++k) { out->H21[k] = 0.0f; out->F21[k] = 0.0f; out->R21[k] = (k % 4 == 0) ? 1.0f : 0.0f; }
-  for (int k = 0; k < 3; ++k) out->t21[k] = 0.0f;
-  out->p3d_assigned = 0; out->n_inliers = 0; out->best_motion = -1; out->aux = 0;
-  for (int k = 0; k < 8; ++k) { out->n_good[k] = 0; out->parallax[k] = 0.0f; }
-}
-// p3d / tri: the winning hypothesis's, per key of frame 1; mask_h / mask_f: per match; score / model: per hypothesis (null: not fetched)
-void write_two_view_output(const rgbl_two_view_input* in, rgbl_two_view_output* out, int N, const TvResult& r, const float* p3d, const uint8_t* tri,
-                           const uint8_t* mask_h, const uint8_t* mask_f, const float* score, const float* model) {
-  out->found = r.found; out->model = r.model; out->exit_code = r.exit_code; out->SH = r.SH; out->SF = r.SF; out->best_h = r.best_h; out->best_f = r.best_f;
-  memcpy(out->H21, r.H21, sizeof(out->H21));
-  memcpy(out->F21, r.F21, sizeof(out->F21));
-  memcpy(out->R21, r.R, sizeof(out->R21));
-  memcpy(out->t21, r.t, sizeof(out->t21));
-  if (r.found && out->p3d) memcpy(out->p3d, p3d, sizeof(float) * 3 * (size_t)in->n1);
-  if (r.found && out->triangulated) memcpy(out->triangulated, tri, (size_t)in->n1);
-  out->p3d_assigned = r.found && r.model == 1 ? 1 : 0;
-  out->n_inliers = r.n_inliers; out->best_motion = r.best; out->aux = r.aux;
-  memcpy(out->n_good, r.n_good, sizeof(out->n_good));
-  memcpy(out->parallax, r.parallax, sizeof(out->parallax));
-  if (out->inliers_h) memcpy(out->inliers_h, mask_h, (size_t)N);
-  if (out->inliers_f && r.best_f >= 0) memcpy(out->inliers_f, mask_f, (size_t)N);
-  if (out->scores && score) memcpy(out->scores, score, sizeof(float) * 2 * (size_t)in->n_hyp);
-  if (out->models && model) memcpy(out->models, model, sizeof(float) * 18 * (size_t)in->n_hyp);
-}
-}  // namespace
-
-int rgbl_two_view_reconstruct_host(const rgbl_two_view_input* in, rgbl_two_view_output* out) {
-  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  int N = 0;
-  RGBL_TRY(check_two_view_input(in, 0, true, &N));
-  if (in->n_hyp == 0) { write_two_view_skipped(out); return RGBL_OK; }
-  const int words = (N + 63) / 64, n1 = in->n1, H = in->n_hyp;
-  std::vector<int32_t> m1((size_t)N), m2((size_t)N);
-  two_view_matches(in, m1.data(), m2.data());
-  TvView v;
-  v.xy1 = in->kp1_xy; v.xy2 = in->kp2_xy; v.m1 = m1.data(); v.m2 = m2.data(); v.N = N; v.n1 = n1; v.n2 = in->n2; v.sigma = in->sigma;
-  memcpy(v.K, in->K, sizeof(v.K));
-  TvHostX x;
-  float buf[2][64];
-  tv_normalize(x, buf, v.xy1, v.n1, v.T1);
-  tv_normalize(x, buf, v.xy2, v.n2, v.T2);
-  std::vector<TvWork> work(1);
-  std::vector<float> score(2 * (size_t)H), model(18 * (size_t)H);
-  std::vector<unsigned long long> mask(2 * (size_t)H * (size_t)words, 0ull);
-  const float invSigmaSquare = tv_inv_sigma2(v.sigma);
-  for (int h = 0; h < H; ++h)
-    for (int md = 0; md < 2; ++md) {
-      float M[9], M2[9];
-      tv_model(x, work[0], v, in->samples + 8 * (size_t)h, md, M, M2);
-      unsigned long long* mk = mask.data() + (2 * (size_t)h + (size_t)md) * (size_t)words;
-      float sc = 0.0f;
-      for (int i = 0; i < N; ++i) {
-        float t[2];
-        if (tv_check(md, M, M2, v, i, invSigmaSquare, t)) mk[i >> 6] |= 1ull << (i & 63);
-        sc = tv_add_chunk(sc, t, 2);
-      }
-      score[2 * (size_t)h + md] = sc;
-      memcpy(model.data() + 9 * (2 * (size_t)h + md), M, sizeof(M));
-    }
-  TvResult r;
-  memset(&r, 0, sizeof(r));
-  r.best_h = tv_first_max(score.data(), H, 0, &r.SH);
-  r.best_f = tv_first_max(score.data(), H, 1, &r.SF);
-  r.model = tv_choose_model(r.SH, r.SF);
-  if (r.best_h >= 0) memcpy(r.H21, model.data() + 9 * (2 * (size_t)r.best_h), sizeof(r.H21));
-  if (r.best_f >= 0) memcpy(r.F21, model.data() + 9 * (2 * (size_t)r.best_f + 1), sizeof(r.F21));
-  std::vector<uint8_t> mask_h((size_t)N, 0), mask_f((size_t)N, 0);
-  const unsigned long long* mh = r.best_h >= 0 ? mask.data() + (2 * (size_t)r.best_h) * (size_t)words : nullptr;
-  const unsigned long long* mf = r.best_f >= 0 ? mask.data() + (2 * (size_t)r.best_f + 1) * (size_t)words : nullptr;
-  for (int i = 0; i < N; ++i) {
-    mask_h[(size_t)i] = mh ? (uint8_t)((mh[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
-    mask_f[(size_t)i] = mf ? (uint8_t)((mf[i >> 6] >> (i & 63)) & 1ull) : (uint8_t)0;
-  }
-  TvMotions mo;
-  mo.n = 0;
-  TvDecision d = {0, kTvFound, -1, 0};
-  const uint8_t* chosen = nullptr;
-  if (r.model < 0) d.exit_code = kTvNoScore;
-  else if (r.model == 0) { chosen = mask_h.data(); if (!tv_motions_h(r.H21, v.K, mo)) d.exit_code = kTvHRatio; }
-  else { chosen = mask_f.data(); tv_motions_f(r.F21, v.K, mo); }
-  for (int i = 0; chosen && i < N; ++i) r.n_inliers += chosen[i];
-  std::vector<float> p3d(3 * (size_t)n1 * kTvMaxMotions, 0.0f);
-  std::vector<uint8_t> good((size_t)n1 * kTvMaxMotions, 0);
-  for (int j = 0; j < mo.n; ++j) {
-    TvCam c;
-    tv_cam(v.K, mo.R[j], mo.t[j], v.sigma, c);
-    float* P = p3d.data() + 3 * (size_t)j * (size_t)n1;
-    uint8_t* G = good.data() + (size_t)j * (size_t)n1;
-    std::vector<float> cosv;   // the values that take part in the order (a NaN does not)
-    int nGood = 0;
-    for (int i = 0; i < N; ++i) {
-      if (!chosen[i]) continue;
-      const size_t a = (size_t)m1[(size_t)i], q = (size_t)m2[(size_t)i];
-      float p[3], cp;
-      const int code = tv_rt_point(c, v.xy1[2 * a], v.xy1[2 * a + 1], v.xy2[2 * q], v.xy2[2 * q + 1], p, &cp);
-      if (!code) continue;
-      P[3 * a] = p[0]; P[3 * a + 1] = p[1]; P[3 * a + 2] = p[2];
-      G[a] = code == 2 ? 1 : 0;
-      if (cp == cp) cosv.push_back(cp);
-      ++nGood;
-    }
-    r.n_good[j] = nGood;
-    if (nGood > 0) {
-      std::sort(cosv.begin(), cosv.end());
-      const size_t idx = (size_t)std::min(50, nGood - 1);
-      r.parallax[j] = tv_parallax_deg(idx < cosv.size() ? cosv[idx] : np_float(0x7fc00000u));
-    }
-  }
-  if (d.exit_code == kTvFound) d = r.model == 0 ? tv_decide_h(r.n_good, r.parallax, r.n_inliers) : tv_decide_f(r.n_good, r.parallax, r.n_inliers);
-  r.found = d.found; r.exit_code = d.exit_code; r.best = d.best; r.aux = d.aux;
-  for (int k = 0; k < 9; ++k) r.R[k] = d.found ? mo.R[d.best][k] : ((k % 4 == 0) ? 1.0f : 0.0f);
-  for (int k = 0; k < 3; ++k) r.t[k] = d.found ? mo.t[d.best][k] : 0.0f;
-  const size_t w = d.found ? (size_t)d.best : 0;
-  write_two_view_output(in, out, N, r, p3d.data() + 3 * w * (size_t)n1, good.data() + w * (size_t)n1, mask_h.data(), mask_f.data(), score.data(), model.data());
-  return RGBL_OK;
-}
-
-int rgbl_two_view_reconstruct_batch(rgbl_matcher* m, int n_problems, const rgbl_two_view_input* in, rgbl_two_view_output* out) {
-  if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
-  const int B = n_problems;
-  if (B > 32767) { set_error("two view: more than 32767 problems in one call"); return RGBL_ERR_INVALID; }
-  PoolCall pc(m, "two view", "a frame");
-  // offsets of the problems that run: hypotheses, mask words, matches, keys of frame 1
-  std::vector<int> Ns((size_t)B, 0), hyp_off((size_t)B + 1, 0);
-  std::vector<size_t> word_off((size_t)B + 1, 0), match_off((size_t)B + 1, 0), key_off((size_t)B + 1, 0);
-  int max_hyp = 0;
-  for (int b = 0; b < B; ++b) {
-    RGBL_TRY(check_two_view_input(in + b, b, false, &Ns[(size_t)b]));
-    RGBL_TRY(pc.note(nullptr, {in[b].device1, in[b].device2}, b));
-    const bool run = in[b].n_hyp > 0;
-    const int nh = run ? in[b].n_hyp : 0, nn = run ? Ns[(size_t)b] : 0;
-    if (hyp_off[(size_t)b] > INT_MAX / 2 - nh) { set_error("two view: more than 2^30 hypotheses in one call"); return RGBL_ERR_INVALID; }
-    hyp_off[(size_t)b + 1] = hyp_off[(size_t)b] + nh;
-    match_off[(size_t)b + 1] = match_off[(size_t)b] + (size_t)nn;
-    key_off[(size_t)b + 1] = key_off[(size_t)b] + (size_t)(run ? in[b].n1 : 0);   // at most 65535 each: B < 2^15 problems fit an int
-    word_off[(size_t)b + 1] = word_off[(size_t)b] + 2 * (size_t)nh * (size_t)((nn + 63) / 64);
-    max_hyp = std::max(max_hyp, nh);
-  }
-  if (word_off[(size_t)B] > kTvMaxMaskWords) { set_error("two view: more than 2^%d mask words (2 x n_hyp x ceil(N / 64), all problems) in one call", kTvMaxMaskWordsLog2); return RGBL_ERR_INVALID; }
-  if (key_off[(size_t)B] > kTvMaxKeys) { set_error("two view: more than 2^%d keys of frame 1 (all problems with n_hyp > 0) in one call", kTvMaxKeysLog2); return RGBL_ERR_INVALID; }
-  const int H = hyp_off[(size_t)B];
-  const size_t M = match_off[(size_t)B], Kn = key_off[(size_t)B];
-  if (H == 0) {   // nothing to run (B == 0 included)
-    for (int b = 0; b < B; ++b) write_two_view_skipped(out + b);
-    return RGBL_OK;
-  }
-  std::vector<int32_t> m1(M), m2(M);
-  for (int b = 0; b < B; ++b)
-    if (in[b].n_hyp > 0) two_view_matches(in + b, m1.data() + match_off[(size_t)b], m2.data() + match_off[(size_t)b]);
-  RGBL_HIP(hipSetDevice(m->device));
-  StreamDrain drain(m->stream);
-  HostCall hc(m);
-  hipStream_t s = hc.s;
-  std::vector<TvProblem> prob((size_t)B);
-  TvDev D;
-  memset(&D, 0, sizeof(D));
-  bool diag = false;
-  for (int b = 0; b < B; ++b) diag = diag || out[b].scores || out[b].models;
-  RGBL_TRY(hc.begin([&]() -> int {
-    const int32_t *d_m1 = nullptr, *d_m2 = nullptr;
-    hc.put(&d_m1, m1.data(), M);
-    hc.put(&d_m2, m2.data(), M);
-    for (int b = 0; b < B; ++b) {
-      TvProblem& P = prob[(size_t)b];
-      memset(&P, 0, sizeof(P));
-      const rgbl_two_view_input& I = in[b];
-      if (I.n_hyp == 0) continue;   // no workgroup touches it
-      RGBL_TRY(put_features(hc, I.device1, I.n1, nullptr, I.kp1_xy, nullptr, nullptr, nullptr, &P.v.xy1, nullptr, nullptr));
-      RGBL_TRY(put_features(hc, I.device2, I.n2, nullptr, I.kp2_xy, nullptr, nullptr, nullptr, &P.v.xy2, nullptr, nullptr));
-      hc.put(&P.samples, I.samples, (size_t)I.n_hyp * 8);
-      P.v.m1 = d_m1 + match_off[(size_t)b]; P.v.m2 = d_m2 + match_off[(size_t)b];
-      P.v.N = Ns[(size_t)b]; P.v.n1 = I.n1; P.v.n2 = I.n2; P.v.sigma = I.sigma;
-      memcpy(P.v.K, I.K, sizeof(P.v.K));
-      P.n_hyp = I.n_hyp; P.words = (Ns[(size_t)b] + 63) / 64; P.hyp_off = hyp_off[(size_t)b];
-      P.match_off = (int)match_off[(size_t)b]; P.key_off = (int)key_off[(size_t)b]; P.word_off = (unsigned long long)word_off[(size_t)b];
-    }
-    D.prob = hc.stage<TvProblem>((size_t)B, [&](TvProblem* dst) { memcpy(dst, prob.data(), sizeof(TvProblem) * (size_t)B); });
-    D.res = hc.result<TvResult>((size_t)B);   // what comes back, side by side
-    D.p3d_out = hc.result<float>(3 * Kn);
-    D.tri_out = hc.result<uint8_t>(Kn);
-    D.mask_h = hc.result<uint8_t>(M);
-    D.mask_f = hc.result<uint8_t>(M);
-    D.score = diag ? hc.result<float>(2 * (size_t)H) : hc.scratch<float>(2 * (size_t)H);
-    D.model = diag ? hc.result<float>(18 * (size_t)H) : hc.scratch<float>(18 * (size_t)H);
-    D.norm = hc.scratch<float>(8 * (size_t)B);
-    D.mask = hc.scratch<unsigned long long>(word_off[(size_t)B]);
-    D.sel = hc.scratch<TvSelect>((size_t)B);
-    D.n_good = hc.scratch<int32_t>(8 * (size_t)B);
-    D.parallax = hc.scratch<float>(8 * (size_t)B);
-    D.cosv = hc.scratch<float>(8 * M);
-    D.p3d = hc.scratch<float>(24 * Kn);
-    D.good = hc.scratch<uint8_t>(8 * Kn);
-    return RGBL_OK;
-  }));
-  m->timer.begin("k_tv_normalize", s);
-  hipLaunchKernelGGL(k_tv_normalize, dim3(2, (unsigned)B), dim3(64), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  m->timer.begin("k_tv_hypotheses", s);
-  hipLaunchKernelGGL(k_tv_hypotheses, dim3((unsigned)((max_hyp + kTvHypPerGroup - 1) / kTvHypPerGroup), 2, (unsigned)B), dim3(256), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  m->timer.begin("k_tv_select", s);
-  hipLaunchKernelGGL(k_tv_select, dim3((unsigned)B), dim3(256), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  m->timer.begin("k_tv_check_rt", s);
-  hipLaunchKernelGGL(k_tv_check_rt, dim3(kTvMaxMotions, (unsigned)B), dim3(256), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  m->timer.begin("k_tv_decide", s);
-  hipLaunchKernelGGL(k_tv_decide, dim3((unsigned)B), dim3(256), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  RGBL_TRY(hc.fetch());
-  for (int b = 0; b < B; ++b) {
-    if (in[b].n_hyp == 0) { write_two_view_skipped(out + b); continue; }
-    write_two_view_output(in + b, out + b, Ns[(size_t)b], hc.host(D.res)[b], hc.host(D.p3d_out) + 3 * key_off[(size_t)b], hc.host(D.tri_out) + key_off[(size_t)b],
-                          hc.host(D.mask_h) + match_off[(size_t)b], hc.host(D.mask_f) + match_off[(size_t)b],
-                          diag ? hc.host(D.score) + 2 * (size_t)hyp_off[(size_t)b] : nullptr, diag ? hc.host(D.model) + 18 * (size_t)hyp_off[(size_t)b] : nullptr);
-  }
-  return RGBL_OK;
-}
-
-int rgbl_two_view_reconstruct(rgbl_matcher* m, const rgbl_two_view_input* in, rgbl_two_view_output* out) {
-  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  return rgbl_two_view_reconstruct_batch(m, 1, in, out);
-}
-
-// ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:2115-2381) --------------------------------------------------------------
-namespace {
-struct Sim3OptCand { int32_t feat, p1, p2, i2, lvl2; };
-// Everything that can be refused without the pool is refused here, before anything is staged, launched or written.  Runs
-// :2167-2233: counts nBadMPs and nMatchWithoutMP and lists the candidates, the features that reach the depth test of :2235.
-int check_sim3_opt_input(const rgbl_sim3_opt_input* in, int b, bool host_only, std::vector<Sim3OptCand>* cand, SoDiag* diag) {
-  memset(diag, 0, sizeof(*diag));
-  if (in->n < 0 || in->n > 65535 || in->n2 < 0 || in->n2 > 65535 || in->n_points < 0) { set_error("sim3 optimisation %d: n or n2 outside [0, 65535], or n_points < 0", b); return RGBL_ERR_INVALID; }
-  if (in->n > 0 && (!in->mp1_index || !in->match_index || !in->i2 || !in->track_level2)) { set_error("sim3 optimisation %d: no mp1_index, match_index, i2 or track_level2", b); return RGBL_ERR_INVALID; }
-  if (in->n_levels1 < 1 || in->n_levels1 > kProjMaxLevels || in->n_levels2 < 1 || in->n_levels2 > kProjMaxLevels || !in->inv_level_sigma2_1 || !in->inv_level_sigma2_2) {
-    set_error("sim3 optimisation %d: n_levels outside [1, %d] or no inv_level_sigma2", b, kProjMaxLevels);
-    return RGBL_ERR_INVALID;
-  }
-  bool finite = std::isfinite(in->th2) && std::isfinite(in->s);
-  for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(in->K1[i]) && std::isfinite(in->K2[i]) && std::isfinite(in->q[i]);
-  for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(in->Rcw1[i]) && std::isfinite(in->Rcw2[i]);
-  for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(in->tcw1[i]) && std::isfinite(in->tcw2[i]) && std::isfinite(in->t[i]);
-  if (!finite) { set_error("sim3 optimisation %d: a pose, K, th2 or the estimate is not finite", b); return RGBL_ERR_INVALID; }
-  if (host_only && (in->device1 || in->device2 || in->pool)) { set_error("sim3 optimisation %d: the host build reads host arrays only", b); return RGBL_ERR_INVALID; }
-  if (in->device1 ? in->device1->n != in->n : (in->n > 0 && (!in->kp1_xy || !in->kp1_octave))) {
-    set_error("sim3 optimisation %d: key frame 1 is either kp1_xy, kp1_octave or a resident frame of n features", b);
-    return RGBL_ERR_INVALID;
-  }
-  if (in->device2 ? in->device2->n != in->n2 : (in->n2 > 0 && (!in->kp2_xy || !in->kp2_octave))) {
-    set_error("sim3 optimisation %d: key frame 2 is either kp2_xy, kp2_octave or a resident frame of n2 features", b);
-    return RGBL_ERR_INVALID;
-  }
-  if (in->n_points > 0 && (!in->bad || (in->pool ? !in->slot : !in->world_pos))) { set_error("sim3 optimisation %d: no bad flags, or the map side is neither world_pos nor a pool with slot", b); return RGBL_ERR_INVALID; }
-  for (int i = 0; i < in->n; ++i) {
-    const int p1 = in->mp1_index[i], p2 = in->match_index[i];
-    if (p1 < -1 || p1 >= in->n_points || p2 < -1 || p2 >= in->n_points) { set_error("sim3 optimisation %d: mp1_index / match_index of feature %d = (%d, %d) outside [-1, %d)", b, i, p1, p2, in->n_points); return RGBL_ERR_INVALID; }
-    if (p2 < 0) continue;                                                 // :2169
-    const int i2 = in->i2[i];
-    if (i2 < -1 || i2 >= in->n2) { set_error("sim3 optimisation %d: i2 of feature %d = %d outside [-1, %d)", b, i, i2, in->n2); return RGBL_ERR_INVALID; }
-    if (p1 < 0) { ++diag->n_without_mp; continue; }                       // :2209-2227
-    if (in->bad[p1] || in->bad[p2]) { ++diag->n_bad_mps; continue; }      // :2203-2207
-    if (i2 < 0 && !in->all_points) continue;                              // :2229
-    // the levels are checked on every pair that reaches the depth test
-    if (!in->device1 && (in->kp1_octave[i] < 0 || in->kp1_octave[i] >= in->n_levels1)) { set_error("sim3 optimisation %d: octave %d of feature %d outside [0, %d)", b, in->kp1_octave[i], i, in->n_levels1); return RGBL_ERR_INVALID; }
-    if (i2 < 0 ? (in->track_level2[i] < 0 || in->track_level2[i] >= in->n_levels2)
-               : (!in->device2 && (in->kp2_octave[i2] < 0 || in->kp2_octave[i2] >= in->n_levels2))) {
-      set_error("sim3 optimisation %d: the level of feature %d's match outside [0, %d)", b, i, in->n_levels2);
-      return RGBL_ERR_INVALID;
-    }
-    cand->push_back(Sim3OptCand{i, p1, p2, i2, in->track_level2[i]});
-  }
-  return RGBL_OK;
-}
-inline SoSim3 sim3_opt_entry(const rgbl_sim3_opt_input* in) {
-  SoSim3 S;
-  memcpy(S.q, in->q, sizeof(S.q)); memcpy(S.t, in->t, sizeof(S.t));
-  S.s = in->s;
-  return S;
-}
-// `flag` per candidate: 0 / 1 the pair's cleared flag, 2 no pair
-void write_sim3_opt_output(const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out, const Sim3OptCand* cand, int n_cand, const uint8_t* flag,
-                           const SoSim3& est, int ret, const SoDiag& diag) {
-  out->result = ret;
-  memcpy(out->q, est.q, sizeof(out->q)); memcpy(out->t, est.t, sizeof(out->t));
-  out->s = est.s;
-  if (out->cleared)
-    for (int c = 0; c < n_cand; ++c)
-      if (flag[c] != 2) out->cleared[cand[c].feat] = flag[c];
-  static_assert(sizeof(SoDiag) == sizeof(rgbl_sim3_opt_diag), "SoDiag is rgbl_sim3_opt_diag");
-  memcpy(&out->diag, &diag, sizeof(diag));
-}
-}  // namespace
-
-int rgbl_optimize_sim3_host(const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out) {
-  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  std::vector<Sim3OptCand> cand;
-  SoDiag diag;
-  RGBL_TRY(check_sim3_opt_input(in, 0, true, &cand, &diag));
-  const int nc = (int)cand.size();
-  std::vector<SoEdge> edges;
-  std::vector<int> edge_cand;
-  for (int c = 0; c < nc; ++c) {
-    const Sim3OptCand& k = cand[(size_t)c];
-    SoEdge e;
-    const float info1 = in->inv_level_sigma2_1[in->kp1_octave[k.feat]];
-    const float info2 = in->inv_level_sigma2_2[k.i2 >= 0 ? in->kp2_octave[k.i2] : k.lvl2];
-    if (!so_make_edge(in->Rcw1, in->tcw1, in->Rcw2, in->tcw2, in->world_pos + 3 * (size_t)k.p1, in->world_pos + 3 * (size_t)k.p2,
-                      in->kp1_xy + 2 * (size_t)k.feat, info1, k.i2 >= 0, k.i2 >= 0 ? in->kp2_xy + 2 * (size_t)k.i2 : nullptr, info2, e))
-      continue;
-    edges.push_back(e);
-    edge_cand.push_back(c);
-    if (k.i2 >= 0) ++diag.n_in_kf2; else ++diag.n_out_kf2;
-  }
-  const int m = (int)edges.size();
-  diag.n_correspondences = m;
-  std::vector<SoHostLanes> lanes(1, SoHostLanes(edges.data(), m));   // 75 KB: not on the stack
-  const SoCam C1 = {(double)in->K1[0], (double)in->K1[1], (double)in->K1[2], (double)in->K1[3]};
-  const SoCam C2 = {(double)in->K2[0], (double)in->K2[1], (double)in->K2[2], (double)in->K2[3]};
-  SoSim3 est;
-  const int ret = so_optimize(lanes[0], C1, C2, sim3_opt_entry(in), m, in->th2, in->fix_scale != 0, est, diag);
-  std::vector<uint8_t> flag((size_t)nc, 2);
-  for (int k = 0; k < m; ++k) flag[(size_t)edge_cand[(size_t)k]] = edges[(size_t)k].cleared;
-  write_sim3_opt_output(in, out, cand.data(), nc, flag.data(), est, ret, diag);
-  return RGBL_OK;
-}
-
-int rgbl_optimize_sim3_batch(rgbl_matcher* m, int n_problems, const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out) {
-  if (!m || n_problems < 0 || (n_problems > 0 && (!in || !out))) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
-  const int B = n_problems;
-  if (B > 32767) { set_error("sim3 optimisation: more than 32767 problems in one call"); return RGBL_ERR_INVALID; }
-  std::vector<int> off((size_t)B + 1, 0);   // at most 65535 candidates each: B < 2^15 problems fit an int
-  std::vector<Sim3OptCand> cand;
-  std::vector<SoDiag> diag((size_t)B);
-  PoolCall pc(m, "sim3 optimisation", "a frame");
-  for (int b = 0; b < B; ++b) {
-    RGBL_TRY(check_sim3_opt_input(in + b, b, false, &cand, &diag[(size_t)b]));
-    off[(size_t)b + 1] = (int)cand.size();
-    RGBL_TRY(pc.note(in[b].pool, {in[b].device1, in[b].device2}, b));
-  }
-  if (B == 0) return RGBL_OK;
-  const int M = off[(size_t)B];
-  const rgbl_map_points* pool = pc.pool;
-  RGBL_TRY(pc.lock(B, [&](int b) -> int {
-    for (int i = 0; in[b].pool && i < in[b].n_points; ++i)
-      if (!pc.holds(in[b].slot[i])) { set_error("sim3 optimisation %d: slot %d outside [0, %d)", b, in[b].slot[i], pool->cap); return RGBL_ERR_INVALID; }
-    return RGBL_OK;
-  }));
-  // the candidates of all problems back to back
-  std::vector<int32_t> feat((size_t)M), p1((size_t)M), p2((size_t)M), i2((size_t)M), lvl2((size_t)M);
-  for (int b = 0; b < B; ++b)
-    for (int c = off[(size_t)b]; c < off[(size_t)b + 1]; ++c) {
-      const Sim3OptCand& k = cand[(size_t)c];
-      feat[(size_t)c] = k.feat; i2[(size_t)c] = k.i2; lvl2[(size_t)c] = k.lvl2;
-      p1[(size_t)c] = in[b].pool ? in[b].slot[k.p1] : k.p1;
-      p2[(size_t)c] = in[b].pool ? in[b].slot[k.p2] : k.p2;
-    }
-  RGBL_HIP(hipSetDevice(m->device));
-  StreamDrain drain(m->stream);  // behind pc (PoolCall)
-  HostCall hc(m);
-  hipStream_t s = hc.s;
-  std::vector<Sim3OptProblem> prob((size_t)B);
-  Sim3OptDev D;
-  memset(&D, 0, sizeof(D));
-  RGBL_TRY(hc.begin([&]() -> int {
-    for (int b = 0; b < B; ++b) {
-      Sim3OptProblem& P = prob[(size_t)b];
-      memset(&P, 0, sizeof(P));
-      const rgbl_sim3_opt_input& I = in[b];
-      RGBL_TRY(put_features(hc, I.device1, I.n, nullptr, I.kp1_xy, I.kp1_octave, nullptr, nullptr, &P.xy1, &P.oct1, nullptr));
-      RGBL_TRY(put_features(hc, I.device2, I.n2, nullptr, I.kp2_xy, I.kp2_octave, nullptr, nullptr, &P.xy2, &P.oct2, nullptr));
-      if (I.pool) P.wpos = pool->d_wpos; else hc.put(&P.wpos, I.world_pos, (size_t)I.n_points * 3);
-      hc.put(&P.sig1, I.inv_level_sigma2_1, (size_t)I.n_levels1);
-      hc.put(&P.sig2, I.inv_level_sigma2_2, (size_t)I.n_levels2);
-      P.cand_off = off[(size_t)b]; P.n_cand = off[(size_t)b + 1] - off[(size_t)b];
-      P.n_levels1 = I.n_levels1; P.n_levels2 = I.n_levels2; P.fix_scale = I.fix_scale ? 1 : 0; P.th2 = I.th2;
-      memcpy(P.Rcw1, I.Rcw1, sizeof(P.Rcw1)); memcpy(P.tcw1, I.tcw1, sizeof(P.tcw1));
-      memcpy(P.Rcw2, I.Rcw2, sizeof(P.Rcw2)); memcpy(P.tcw2, I.tcw2, sizeof(P.tcw2));
-      memcpy(P.K1, I.K1, sizeof(P.K1)); memcpy(P.K2, I.K2, sizeof(P.K2));
-      P.entry = sim3_opt_entry(&I);
-      P.diag = diag[(size_t)b];
-    }
-    hc.put(&D.feat, feat.data(), (size_t)M);
-    hc.put(&D.p1, p1.data(), (size_t)M);
-    hc.put(&D.p2, p2.data(), (size_t)M);
-    hc.put(&D.i2, i2.data(), (size_t)M);
-    hc.put(&D.lvl2, lvl2.data(), (size_t)M);
-    D.prob = hc.stage<Sim3OptProblem>((size_t)B, [&](Sim3OptProblem* dst) { memcpy(dst, prob.data(), sizeof(Sim3OptProblem) * (size_t)B); });
-    D.cleared = hc.put_fill<uint8_t>((size_t)M, 2);   // what comes back, side by side
-    hc.mark_result(D.cleared, (size_t)M);
-    D.out = hc.result<Sim3OptOut>((size_t)B);
-    D.corr = hc.scratch<int32_t>((size_t)M);
-    D.chi = hc.scratch<double>((size_t)M * 2);
-    D.state = hc.scratch<uint8_t>((size_t)M);
-    return RGBL_OK;
-  }));
-  m->timer.begin("k_sim3_opt", s);
-  hipLaunchKernelGGL(k_sim3_opt, dim3((unsigned)B), dim3(kSoLanes), 0, s, D);
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
-  RGBL_TRY(hc.fetch());
-  for (int b = 0; b < B; ++b) {
-    const Sim3OptOut& o = hc.host(D.out)[b];
-    write_sim3_opt_output(in + b, out + b, cand.data() + off[(size_t)b], off[(size_t)b + 1] - off[(size_t)b], hc.host(D.cleared) + off[(size_t)b], o.est, o.ret, o.diag);
-  }
-  return RGBL_OK;
-}
-
-int rgbl_optimize_sim3(rgbl_matcher* m, const rgbl_sim3_opt_input* in, rgbl_sim3_opt_output* out) {
-  if (!in || !out) { set_error("null argument"); return RGBL_ERR_INVALID; }
-  return rgbl_optimize_sim3_batch(m, 1, in, out);
-}
-
-// test hooks for csrc/sim3opt_math.h: so_exp on the host, and compiled for the device
-double rgbl_test_so_exp(double x) { return so_exp(x); }
-int rgbl_test_so_exp_device(const double* x, double* z, int n) {
-  if (!x || !z || n < 1) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
-  return elementwise_device_hook<double>({x}, z, n, [&](double* const* d, double* dz, dim3 grid, dim3 block) {
-    hipLaunchKernelGGL(k_test_so_exp, grid, block, 0, 0, (const double*)d[0], dz, n);
-  });
-}
-
-// test hooks for csrc/poseopt_math.h: op 0 sin, 1 cos, 2 x / y, 3 sqrt - on the host, and compiled for the device
-double rgbl_test_po_math(int op, double x, double y) { return op == 0 ? po_sin(x) : op == 1 ? po_cos(x) : op == 2 ? x / y : sqrt(x); }
-int rgbl_test_po_math_device(int op, const double* x, const double* y, double* z, int n) {
-  if (!x || !y || !z || n < 1 || op < 0 || op > 3) { set_error("invalid argument"); return RGBL_ERR_INVALID; }
-  return elementwise_device_hook<double>({x, y}, z, n, [&](double* const* d, double* dz, dim3 grid, dim3 block) {
-    hipLaunchKernelGGL(k_test_po_math, grid, block, 0, 0, op, (const double*)d[0], (const double*)d[1], dz, n);
-  });
 }
 
 // test hooks (tests/test_logf_glibc.py): the restatement on the host, and the same function compiled for the device
@@ -6263,15 +4082,8 @@ static int bow_core(rgbl_matcher* m, const SharedNodes& sn, float nnratio, bool 
   T.nnratio = nnratio;
   T.max_best = max_best;
   T.n_left2 = n_left2;
-  if (n_left2 >= 0) {
-    m->timer.begin("k_search_by_bow_rig", s);
-    hipLaunchKernelGGL(k_search_by_bow_rig, dim3(npairs), dim3(64), 0, s, T);
-  } else {
-    m->timer.begin("k_search_by_bow", s);
-    hipLaunchKernelGGL(k_search_by_bow, dim3(npairs), dim3(64), 0, s, T);
-  }
-  m->timer.end(s);
-  RGBL_HIP(hipGetLastError());
+  if (n_left2 >= 0) RGBL_TRY(launch(m, s, "k_search_by_bow_rig", k_search_by_bow_rig, dim3(npairs), dim3(64), 0, T));
+  else RGBL_TRY(launch(m, s, "k_search_by_bow", k_search_by_bow, dim3(npairs), dim3(64), 0, T));
   RGBL_TRY(hc.fetch());
   if (match1) memcpy(match1, hc.host(T.match1), sizeof(int32_t) * n1);
   if (match2) memcpy(match2, hc.host(T.match2), sizeof(int32_t) * n2);

@@ -1,5 +1,5 @@
 """rgbl_mlpnp_ransac - MLPnPsolver (src/MLPnPsolver.cpp), every hypothesis of a call at once: the checks of tests/mlpnp_checks.py on
-the CPU, with the kernel SOURCE of csrc/matcher.hip (k_mlpnp_hypotheses, k_mlpnp_select) running under the SIMT emulator of
+the CPU, with the kernel SOURCE of csrc/ransac.hip (k_mlpnp_hypotheses, k_mlpnp_select) running under the SIMT emulator of
 tests/emu against the host build of csrc/mlpnp_math.h, bit for bit.  tests/test_mlpnp_gpu.py runs the same checks on the MI355X."""
 import os
 import subprocess

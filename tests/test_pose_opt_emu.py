@@ -1,5 +1,5 @@
 """rgbl_pose_optimization - Optimizer::PoseOptimization (Optimizer.cc:814-1114) in one workgroup per frame: the checks of
-tests/pose_opt_checks.py on the CPU, with the kernel SOURCE of csrc/matcher.hip (k_pose_opt) running under the SIMT emulator of
+tests/pose_opt_checks.py on the CPU, with the kernel SOURCE of csrc/optimize.hip (k_pose_opt) running under the SIMT emulator of
 tests/emu against the host build of csrc/poseopt_math.h, bit for bit: pose, flags, count and diagnostics.
 tests/test_pose_opt_gpu.py runs the same checks on the MI355X."""
 import os

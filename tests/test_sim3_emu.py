@@ -1,5 +1,5 @@
 """rgbl_sim3_ransac - Sim3Solver (src/Sim3Solver.cc), every hypothesis of a call at once: the checks of tests/sim3_checks.py on
-the CPU, with the kernel SOURCE of csrc/matcher.hip (k_sim3_hypotheses, k_sim3_select) running under the SIMT emulator of
+the CPU, with the kernel SOURCE of csrc/ransac.hip (k_sim3_hypotheses, k_sim3_select) running under the SIMT emulator of
 tests/emu against the host build of csrc/sim3_math.h, bit for bit.  tests/test_sim3_gpu.py runs the same checks on the MI355X."""
 import os
 import subprocess

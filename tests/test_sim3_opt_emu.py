@@ -1,5 +1,5 @@
 """rgbl_optimize_sim3 - Optimizer::OptimizeSim3 (Optimizer.cc:2115-2381) in one workgroup per candidate: the checks of
-tests/sim3_opt_checks.py on the CPU, with the kernel SOURCE of csrc/matcher.hip (k_sim3_opt) running under the SIMT emulator of
+tests/sim3_opt_checks.py on the CPU, with the kernel SOURCE of csrc/optimize.hip (k_sim3_opt) running under the SIMT emulator of
 tests/emu against the host build of csrc/sim3opt_math.h, bit for bit: estimate, flags, count, counters and diagnostics; and the
 call's size limits from both sides.  tests/test_sim3_opt_gpu.py runs the same checks on the MI355X."""
 import os

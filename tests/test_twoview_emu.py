@@ -1,5 +1,5 @@
 """rgbl_two_view_reconstruct - TwoViewReconstruction (src/TwoViewReconstruction.cc), every hypothesis of a call at once: the checks
-of tests/twoview_checks.py on the CPU, with the kernel SOURCE of csrc/matcher.hip (k_tv_normalize, k_tv_hypotheses, k_tv_select,
+of tests/twoview_checks.py on the CPU, with the kernel SOURCE of csrc/ransac.hip (k_tv_normalize, k_tv_hypotheses, k_tv_select,
 k_tv_check_rt, k_tv_decide) running under the SIMT emulator of tests/emu against the host build of csrc/twoview_math.h, bit for bit.
 tests/test_twoview_gpu.py runs the same checks on the MI355X."""
 import ctypes

@@ -171,7 +171,7 @@ def test_gpu_kitti(gpu_lib):
 
 
 # ---- window bounds under AddressSanitizer (a stand-alone program, CPU only) ------------------------------------------
-KERNEL_SOURCES = ("extractor.hip", "depth.hip", "matcher.hip", "records.hip", "gather.hip", "feed.hip", "kfdb.hip", "rectify.hip", "resize.hip")
+KERNEL_SOURCES = tuple(sorted(os.path.basename(f) for f in glob.glob(os.path.join(ROOT, "orb_slam3_rgbl_amd", "csrc", "*.hip"))))   # csrc/Makefile's SRCS
 
 
 def build_bounds_exe():
