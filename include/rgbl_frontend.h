@@ -1375,6 +1375,60 @@ int rgbl_local_bundle_adjustment(rgbl_matcher* h, const rgbl_lba_input* in, rgbl
 /* The same call evaluated by the HOST build of csrc/lba_math.h (no device, no handle): the same bits.  pool must be NULL. */
 int rgbl_local_bundle_adjustment_host(const rgbl_lba_input* in, rgbl_lba_output* out);
 
+/* Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust)    src/Optimizer.cc:52-390, the
+ * optimize(nIterations) at :281: the global bundle adjustment behind Optimizer::GlobalBundleAdjustemnt - LoopClosing.cc:2284
+ * (10 iterations, mbStopGBA, not robust) and Tracking.cc:2614 (20 iterations) -, as ONE problem spread over the device.  The
+ * edges, the block solver with the Schur complement and Levenberg are rgbl_local_bundle_adjustment's (csrc/lba_math.h) and so
+ * are their kernels; the reduced camera system, up to 6 144 unknowns, is factorised and solved in panels of columns across the
+ * device (csrc/gba.hip, lm_solve_panel of csrc/lm_math.h: lm_solve_n's L, D and y, the backward substitution in the mirrored
+ * order).  The vertex and edge loops (:116-275) and the write-back (:285-389) stay with the caller. */
+typedef struct {
+  int n_cams;                      /* vpKFs without the bad ones, in list order; 0 .. 2048 */
+  const uint8_t* cam_is_fixed;     /* n_cams bytes (NULL: none): 1 for the map's initial key frame (:125); at most 1024 set */
+  const float* cam_q;              /* n_cams x 4: GetPose().unit_quaternion() as x, y, z, w */
+  const float* cam_t;              /* n_cams x 3 */
+  const float* cam_K;              /* n_cams x 4: fx, fy, cx, cy */
+  const float* cam_bf;             /* n_cams: mbf */
+  int n_points;                    /* vpMP without the bad ones, in list order; 0 .. 2^18 */
+  const float* world_pos;          /* form 1 (pool == NULL): n_points x 3 */
+  rgbl_map_points* pool;           /* form 2: slots of a pool on the matcher's device, each at most once */
+  const int32_t* slot;
+  int n_edges;                     /* 0 .. 2^20, in the order the reference creates them (:160-262) */
+  const int32_t* edge_point;       /* non-decreasing */
+  const int32_t* edge_cam;         /* a (point, camera) pair at most once */
+  const float* edge_obs;           /* n_edges x 3: kpUn.pt.x, kpUn.pt.y, mvuRight (< 0: a monocular edge) */
+  const float* edge_inv_sigma2;    /* mvInvLevelSigma2[kpUn.octave] */
+  int robust;                      /* bRobust (:177, :209): 1 = Huber with sqrt(5.99) / sqrt(7.815); 0 = no kernel */
+  int max_iterations;              /* nIterations: 5, 10 or 20 upstream */
+  const volatile int32_t* stop;    /* pbStopFlag (NULL: none), read where g2o's terminate() reads it */
+  int stop_after_polls;            /* for tests: N > 0 makes the flag read as set from the N-th poll on */
+  const volatile uint8_t* stop_byte; /* the same flag as a one-byte C++ bool (NULL: none) */
+} rgbl_ba_input;
+typedef struct {
+  float* cam_q;                    /* n_cams x 4: what :295 / :299 read, x y z w (the estimate cast to float) */
+  float* cam_t;                    /* n_cams x 3 */
+  float* point;                    /* n_points x 3: what :377 / :382 read */
+  uint8_t* included;               /* n_points: !vbNotIncludedMP (:266-270) - the point has an edge */
+  double* chi2;                    /* n_edges: e->chi2() of the last TRIED step (0 if never computed) */
+  rgbl_lba_diag diag;              /* ran is always 1 */
+} rgbl_ba_output;
+/* Host pointers, synchronous; every launch goes on the matcher's stream.  A camera that is flagged fixed or has no edge, and
+ * a point without an edge, are not active and come back as the float -> double -> float round trip of their input.  A stop
+ * flag that is set on entry is NOT an early return: optimize() runs and ends at its first poll (diag.polls = 1, no
+ * iteration), and every output is written.  No fixed camera at all is valid too: g2o then optimises with the gauge free, and
+ * so does this call (Levenberg's lambda keeps the reduced system positive definite, or the factorisation fails as csrc/lm_math.h
+ * says).  With a pool the optimised positions are also written into the slots.
+ * RGBL_ERR_INVALID, before anything is launched and with every output untouched: n_cams outside [0, 2048]; more than 1024
+ * active cameras (free and with an edge; the reduced system has 6 per camera) or more than 1024 fixed ones; n_points or
+ * n_edges outside their range; more than 2^27 pairs of edges that share a point; edge_point / edge_cam out of range;
+ * edge_point decreasing; a repeated (point, camera) pair; a pose, K or bf that is not finite; a slot outside the pool or
+ * listed twice; a pool on another device than the matcher; a missing array.  RGBL_ERR_HIP when the device cannot hold the
+ * call (the reduced matrix alone is 151 MB at 1024 active cameras): nothing is written. */
+int rgbl_bundle_adjustment(rgbl_matcher* h, const rgbl_ba_input* in, rgbl_ba_output* out);
+/* The same call evaluated by the HOST build (no device, no handle): the same bits.  pool must be NULL.  Its solve is cubic in
+ * the number of active cameras and runs on one core. */
+int rgbl_bundle_adjustment_host(const rgbl_ba_input* in, rgbl_ba_output* out);
+
 /* ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>& vbPrevMatched, vector<int>& vnMatches12,
  * int windowSize)    /root/reference/include/ORBmatcher.h:72, src/ORBmatcher.cc:648-763 (Tracking::MonocularInitialization,
  * src/Tracking.cc:2526; not on the RGB-L / stereo path - built so that every search routine of ORBmatcher has a device form).
@@ -1617,6 +1671,7 @@ int rgbl_kfdb_profile_read(rgbl_kf_database* db, const char** names, double* tot
  *   rgbl_matcher_create
  *     RGBL_BF_MFMA=0|i8     Hamming scan on the VALU (popcount) / on v_mfma_i32_32x32x32_i8 (default: block-scaled FP4 instruction)
  *     RGBL_BF_SPLIT=0       one pair per call without train-set slices
+ *     RGBL_GBA_PANEL=16|64  rgbl_bundle_adjustment: columns per panel of the reduced system's solve (32; the bits do not depend on it)
  *   first rgbl_comm_* call
  *     RGBL_RCCL_LIB=path    librccl to dlopen when none is mapped into the process yet
  * ---------------------------------------------------------------------------------------------- */

@@ -181,6 +181,20 @@ class LbaOutput(C.Structure):
                 ("flags", C.c_void_p), ("diag", LbaDiag)]
 
 
+class BaInput(C.Structure):
+    """rgbl_ba_input (the vertices and edges Optimizer::BundleAdjustment hands to g2o, as flat arrays)."""
+    _fields_ = [("n_cams", C.c_int), ("cam_is_fixed", C.c_void_p), ("cam_q", C.c_void_p), ("cam_t", C.c_void_p),
+                ("cam_K", C.c_void_p), ("cam_bf", C.c_void_p), ("n_points", C.c_int), ("world_pos", C.c_void_p),
+                ("pool", C.c_void_p), ("slot", C.c_void_p), ("n_edges", C.c_int), ("edge_point", C.c_void_p),
+                ("edge_cam", C.c_void_p), ("edge_obs", C.c_void_p), ("edge_inv_sigma2", C.c_void_p), ("robust", C.c_int),
+                ("max_iterations", C.c_int), ("stop", C.c_void_p), ("stop_after_polls", C.c_int), ("stop_byte", C.c_void_p)]
+
+
+class BaOutput(C.Structure):
+    _fields_ = [("cam_q", C.c_void_p), ("cam_t", C.c_void_p), ("point", C.c_void_p), ("included", C.c_void_p),
+                ("chi2", C.c_void_p), ("diag", LbaDiag)]
+
+
 class ProjectionInput(C.Structure):
     """rgbl_projection_input (ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) as flat arrays)."""
     _fields_ = [("n1", C.c_int), ("valid1", C.c_void_p), ("world_pos1", C.c_void_p), ("mp_desc1", C.c_void_p),
@@ -427,6 +441,8 @@ SYMBOLS = {
     "rgbl_optimize_sim3_host": (_I, [C.POINTER(Sim3OptInput), C.POINTER(Sim3OptOutput)]),
     "rgbl_local_bundle_adjustment": (_I, [_V, C.POINTER(LbaInput), C.POINTER(LbaOutput)]),
     "rgbl_local_bundle_adjustment_host": (_I, [C.POINTER(LbaInput), C.POINTER(LbaOutput)]),
+    "rgbl_bundle_adjustment": (_I, [_V, C.POINTER(BaInput), C.POINTER(BaOutput)]),
+    "rgbl_bundle_adjustment_host": (_I, [C.POINTER(BaInput), C.POINTER(BaOutput)]),
     "rgbl_search_by_bow": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_rig": (_I, [_V, _V, _V, _I, _F, _I, _V, C.POINTER(_I)]),
     "rgbl_search_by_bow_keyframes": (_I, [_V, _V, _V, _F, _I, _V, C.POINTER(_I)]),

@@ -57,6 +57,9 @@ struct LbaRecord { double chi, maxdiag, scale; int32_t ok, reserved; };
 
 struct LbaView {
   int nC, nA, nP, nE, nPa, n;
+  int robust;                      // 1: every edge has its Huber kernel (LocalBundleAdjustment); 0: none (BundleAdjustment's bRobust)
+  double delta[2];                 // Huber's delta of a monocular and of a stereo edge, as the float the caller's reference sets:
+                                   // sqrt(5.991), sqrt(7.815) (LocalBundleAdjustment, :1275-1276); sqrt(5.99), sqrt(7.815) (BundleAdjustment, :131-132)
   PoPose* T; PoPose* Tt;           // the cameras' estimates and the trial's (free ++ fixed)
   const PoCam* C;
   const int32_t* col;              // camera -> column, -1: fixed or without an edge
@@ -80,6 +83,11 @@ struct LbaView {
   double* x_pt;                    // 3 per point
   LbaRecord* rec;
   uint8_t* flags;
+  // BundleAdjustment's panel solve (csrc/gba.hip; unused by LocalBundleAdjustment)
+  const int32_t* blk_list; int n_blk_list;   // 2 per upper block that is not empty: (i, j)
+  double* pD; double* py; double* pyf;       // n each: the pivots, the forward sweep's running and final values
+  double* pxw;                               // n: the backward sweep's running values
+  int32_t* pfail;                            // 1: a pivot failed; every later kernel of the solve leaves at once
 };
 
 RGBL_HD bool lba_stereo(const float* obs) { return !(obs[2] < 0.0f); }   // :1305 / :1332
@@ -116,6 +124,14 @@ RGBL_HD void lba_rotation(const double q[4], double R[9]) {
   R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
 }
 
+// rho[0] and rho[1] of an edge: Huber with the edge's delta, or - an edge without a kernel (constructQuadraticForm's plain
+// branch, base_binary_edge.hpp:94-113; SparseOptimizer::activeRobustChi2 adds chi2 itself) - rho = (chi2, 1, 0)
+RGBL_HD void lba_rho(const LbaView& V, double chi2, bool stereo, double* rho0, double* rho1) {
+  if (V.robust) { po_huber(chi2, V.delta[stereo ? 1 : 0], rho0, rho1); return; }
+  *rho0 = chi2;
+  *rho1 = 1.0;
+}
+
 // the chi2 of edge k at the estimates (T, X) of every camera and point, kept with the edge
 RGBL_HD void lba_edge_chi2(const LbaView& V, int k, const PoPose* T, const double* X) {
   const int p = V.e_pt[k], c = V.e_cam[k];
@@ -123,7 +139,7 @@ RGBL_HD void lba_edge_chi2(const LbaView& V, int k, const PoPose* T, const doubl
   const bool stereo = lba_stereo(obs);
   double P[3], err[3], r0, r1;
   const double chi2 = lba_edge_error(obs, (double)V.e_info[k], stereo, V.C[c], T[c], X + 3 * (size_t)p, P, err);
-  po_huber(chi2, po_delta(stereo), &r0, &r1);
+  lba_rho(V, chi2, stereo, &r0, &r1);
   V.e_chi2[k] = chi2;
   V.e_rho[k] = r0;
 }
@@ -139,7 +155,7 @@ RGBL_HD void lba_linearise_edge(const LbaView& V, int k) {
   const double s = (double)V.e_info[k];
   double P[3], err[3], rho0, rho1, R[9], A[3][3], B[3][6];
   const double chi2 = lba_edge_error(obs, s, stereo, C, T, V.X + 3 * (size_t)p, P, err);
-  po_huber(chi2, po_delta(stereo), &rho0, &rho1);
+  lba_rho(V, chi2, stereo, &rho0, &rho1);
   V.e_chi2[k] = chi2;
   V.e_rho[k] = rho0;
   lba_rotation(T.q, R);

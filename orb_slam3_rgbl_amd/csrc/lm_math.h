@@ -5,6 +5,8 @@
 // All arithmetic is fp64, no contraction.  OptimizeSim3 calls lm_levenberg; po_optimize carries that loop written out (it says why).
 // lm_solve_n is lm_solve for a run-time n; csrc/lba_math.h (LocalBundleAdjustment) solves its reduced camera system with it and
 // runs lm_levenberg_loop with its own policy: kernel launches (csrc/lba.hip) or host loops, and the caller's stop flag.
+// lm_solve_panel is lm_solve_n in panels of columns with the backward substitution mirrored: the reduced system of the global
+// bundle adjustment (csrc/gba.hip), which is too large for one workgroup and for lm_solve_n's backward order.
 //
 // What is NOT pinned: Eigen's LDLT with its pivoting, replaced by lm_solve (LDL^T without pivoting).  Deviations that follow
 // from the solver and are kept on purpose, for both optimisers:
@@ -46,6 +48,7 @@ namespace rgbl {
 
 constexpr int kLmLanes = 256;   // work-items of one problem
 constexpr int kLmTrials = 10;   // _maxTrialsAfterFailure (optimization_algorithm_levenberg.cpp:46)
+constexpr int kLmPanel = 32;    // columns of a panel of lm_solve_panel on the device (csrc/gba.hip; DESIGN.md 9 has the measurement)
 
 // A reduced system of N unknowns: H's upper triangle row by row, then b, then the robust chi2.
 template <int N> struct LmSystem {
@@ -128,6 +131,81 @@ inline bool lm_solve_n(int n, double* A, const double* b, double* x, double* D, 
     double v = y[i];
     for (int p = i + 1; p < n; ++p) v = v - A[lm_tri((size_t)p, (size_t)i)] * x[p];
     x[i] = v;
+  }
+  return true;
+}
+
+// lm_solve_n in panels of w columns, with the backward substitution in the MIRRORED order: the solve of the global bundle
+// adjustment (csrc/gba.hip), whose reduced system reaches n = 6 144.  Per element:
+//   factorisation           unchanged: a - sum_p (L_ip * L_jp) * D_p, p ascending, subtracted one at a time; the division by the
+//                           pivot and the pivot test d > 0 && d <= DBL_MAX as in lm_solve_n
+//   forward substitution    unchanged: y_i = b_i - sum_p L_ip y_p, p ascending; then y_i / D_i
+//   backward substitution   x_i = y_i - sum_p L_pi x_p with p DESCENDING from n - 1 to i + 1, the mirror of the forward sweep
+// The backward order is the only difference to lm_solve_n, and it is there for the schedule: with p ascending the first term of
+// x_i needs x_{i+1} final and the last term of x_{i+1} is p = n - 1, n (n - 1) / 2 dependent subtractions whatever the schedule
+// (1.9e7 at n = 6 144; k_lba_factor's work-item 0 runs them alone).  Descending, x_i's terms arrive in the order the x_p become
+// final, and a finished block of w values is applied to every row above it in parallel.  The factorisation and the forward
+// sweep have no such chain: every element is a sum over values that are already final, so the panel schedule below - (a) the
+// panel's columns through every p before the panel, (b) its w x w diagonal block, (c) the rows below, then the substitutions
+// block by block - forms lm_solve_n's L, D and y bit for bit, for every w >= 1.  The kernels of csrc/gba.hip run these loops
+// with an element, or a row, per work-item; they run (a) in slices - behind every finished panel all later columns continue
+// their sums through that panel's w columns and are stored back, which is the same p ascending per element and spreads over
+// the whole trailing matrix instead of one panel's columns.  A as in lm_solve_n, but the diagonal entries end as the pivots.
+// False, x untouched, when a pivot is not finite and > 0.
+inline bool lm_solve_panel(int n, int w, double* A, const double* b, double* x, double* D, double* y) {
+  for (int j0 = 0; j0 < n; j0 += w) {
+    const int j1 = j0 + w < n ? j0 + w : n;
+    for (int i = j0; i < n; ++i) {                       // (a)
+      double* Li = A + lm_tri((size_t)i, 0);
+      for (int j = j0; j < j1 && j <= i; ++j) {
+        const double* Lj = A + lm_tri((size_t)j, 0);
+        double v = Li[j];
+        for (int p = 0; p < j0; ++p) v = v - Li[p] * Lj[p] * D[p];
+        Li[j] = v;
+      }
+    }
+    for (int j = j0; j < j1; ++j) {                      // (b)
+      double* Lj = A + lm_tri((size_t)j, 0);
+      for (int i = j; i < j1; ++i) {
+        double* Li = A + lm_tri((size_t)i, 0);
+        double v = Li[j];
+        for (int p = j0; p < j; ++p) v = v - Li[p] * Lj[p] * D[p];
+        Li[j] = v;
+      }
+      const double d = Lj[j];
+      if (!(d > 0.0 && d <= DBL_MAX)) return false;
+      D[j] = d;
+      for (int i = j + 1; i < j1; ++i) A[lm_tri((size_t)i, (size_t)j)] = A[lm_tri((size_t)i, (size_t)j)] / d;
+    }
+    for (int i = j1; i < n; ++i) {                       // (c)
+      double* Li = A + lm_tri((size_t)i, 0);
+      for (int j = j0; j < j1; ++j) {
+        const double* Lj = A + lm_tri((size_t)j, 0);
+        double v = Li[j];
+        for (int p = j0; p < j; ++p) v = v - Li[p] * Lj[p] * D[p];
+        Li[j] = v / D[j];
+      }
+    }
+  }
+  for (int i = 0; i < n; ++i) y[i] = b[i];
+  for (int j0 = 0; j0 < n; j0 += w) {
+    const int j1 = j0 + w < n ? j0 + w : n;
+    for (int i = j0; i < n; ++i) {                       // the block's triangle (i < j1), then the finished block on the rows below
+      const double* Li = A + lm_tri((size_t)i, 0);
+      double v = y[i];
+      for (int p = j0; p < j1 && p < i; ++p) v = v - Li[p] * y[p];
+      y[i] = v;
+    }
+  }
+  for (int i = 0; i < n; ++i) y[i] = y[i] / D[i];
+  for (int i = 0; i < n; ++i) x[i] = y[i];
+  for (int j0 = n > 0 ? (n - 1) / w * w : 0; j0 >= 0 && n > 0; j0 -= w) {
+    const int j1 = j0 + w < n ? j0 + w : n;
+    for (int i = j1 - 1; i >= 0; --i) {                  // the block's triangle (i >= j0), then the finished block on the rows above
+      double v = x[i];
+      for (int p = j1 - 1; p >= j0 && p > i; --p) v = v - A[lm_tri((size_t)p, (size_t)i)] * x[p];
+      x[i] = v;
+    }
   }
   return true;
 }

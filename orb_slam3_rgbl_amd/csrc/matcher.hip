@@ -2299,6 +2299,7 @@ int rgbl_matcher_create(int device, rgbl_matcher** out) {
   m->device = device;
   if (const char* v = getenv("RGBL_BF_MFMA")) { m->bf_matrix = v[0] != '0'; m->bf_fp4 = v[0] != 'i'; }
   if (const char* v = getenv("RGBL_BF_SPLIT")) m->bf_split = v[0] != '0';
+  if (const char* v = getenv("RGBL_GBA_PANEL")) m->gba_panel = atoi(v) == 16 ? 16 : atoi(v) == 64 ? 64 : 32;
   if (hipStreamCreate(&m->own_stream) != hipSuccess) { delete m; set_error("hipStreamCreate failed"); return RGBL_ERR_HIP; }
   m->stream = m->own_stream;
   *out = m;

@@ -40,6 +40,7 @@ struct rgbl_matcher {
   bool bf_matrix = true;   // RGBL_BF_MFMA=0: the VALU popcount scan (k_hamming_bf)
   bool bf_fp4 = true;      // RGBL_BF_MFMA=i8: v_mfma_i32_32x32x32_i8 (k_hamming_mfma) instead of the block-scaled FP4 instruction
   bool bf_split = true;    // RGBL_BF_SPLIT=0: one pair per call without train-set slices
+  int gba_panel = 32;      // RGBL_GBA_PANEL=16|64: the panel width of the global bundle adjustment's solve (gba.hip); the bits do not depend on it
 };
 
 namespace rgbl {

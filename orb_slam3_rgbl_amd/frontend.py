@@ -1652,6 +1652,14 @@ class ORBmatcher:
     def prepare_LocalBundleAdjustment(self, case, fill=0):
         return local_bundle_adjustment_call(self.lib, self.h, case, fill)
 
+    def BundleAdjustment(self, case, host=False, fill=0):
+        """Optimizer::BundleAdjustment's optimize(nIterations) (Optimizer.cc:281) through rgbl_bundle_adjustment (host=True: the
+        header's host build, no device).  case: an lba_cases.make_ba_case-style dict (bundle_adjustment_call lists its keys)."""
+        return bundle_adjustment_call(self.lib, None if host else self.h, case, fill)()
+
+    def prepare_BundleAdjustment(self, case, fill=0):
+        return bundle_adjustment_call(self.lib, self.h, case, fill)
+
     def CreateNewMapPoints(self, kf1, neighbours, prm, skip=None, cap=None):
         return self.prepare_CreateNewMapPoints(kf1, neighbours, prm, skip, cap)()
 
@@ -2206,6 +2214,64 @@ def local_bundle_adjustment_call(lib, handle, case, fill=0):
 def local_bundle_adjustment_host(case, lib=None, fill=0):
     """rgbl_local_bundle_adjustment_host: the host build of csrc/lba_math.h (no device)."""
     return local_bundle_adjustment_call(lib or L.load(), None, case, fill)()
+
+
+def bundle_adjustment_call(lib, handle, case, fill=0):
+    """The call of rgbl_bundle_adjustment (handle None: rgbl_bundle_adjustment_host) on a case dict: n_cams, cam_is_fixed
+    (optional), cam_q, cam_t, cam_K, cam_bf, world_pos (or pool = MapPointPool with slot), edge_point, edge_cam, edge_obs,
+    edge_inv_sigma2; optional robust (1), max_iterations (10), stop, stop_byte and stop_after_polls (0).  Every output array
+    starts as `fill` bytes.  Returns a callable that gives dict(cam_q, cam_t, point, included, chi2, q, t, X (the estimates in
+    double) and the diag's scalars); its .outputs holds the raw arrays."""
+    def arr(key, dt):
+        v = case.get(key)
+        return None if v is None else np.ascontiguousarray(v, dt)
+    nc = int(case["n_cams"])
+    a = dict(cam_is_fixed=arr("cam_is_fixed", np.uint8), cam_q=arr("cam_q", np.float32), cam_t=arr("cam_t", np.float32),
+             cam_K=arr("cam_K", np.float32), cam_bf=arr("cam_bf", np.float32), world_pos=arr("world_pos", np.float32),
+             slot=arr("slot", np.int32), edge_point=arr("edge_point", np.int32), edge_cam=arr("edge_cam", np.int32),
+             edge_obs=arr("edge_obs", np.float32), edge_inv_sigma2=arr("edge_inv_sigma2", np.float32),
+             stop=arr("stop", np.int32), stop_byte=arr("stop_byte", np.uint8))
+    pool = case.get("pool")
+    n_points = int(case["n_points"]) if "n_points" in case else (len(a["slot"]) if pool is not None else a["world_pos"].size // 3)
+    n_edges = int(case["n_edges"]) if "n_edges" in case else (0 if a["edge_point"] is None else len(a["edge_point"]))
+    I = L.BaInput()
+    I.n_cams, I.n_points, I.n_edges = nc, n_points, n_edges
+    for k in ("cam_is_fixed", "cam_q", "cam_t", "cam_K", "cam_bf", "slot", "edge_point", "edge_cam", "edge_obs",
+              "edge_inv_sigma2", "stop", "stop_byte"):
+        setattr(I, k, L.ptr(a[k]))
+    I.world_pos = L.ptr(a["world_pos"]) if pool is None else None
+    I.pool = pool.h if pool is not None else None
+    I.robust = int(case.get("robust", 1))
+    I.max_iterations = int(case.get("max_iterations", 10))
+    I.stop_after_polls = int(case.get("stop_after_polls", 0))
+    byte = np.uint8(fill)
+    def filled(shape, dt):
+        shape = tuple(max(int(v), 0) for v in shape)   # a negative count is the library's to refuse
+        return np.full(int(np.prod(shape)) * np.dtype(dt).itemsize, byte, np.uint8).view(dt).reshape(shape)
+    o = dict(cam_q=filled((nc, 4), np.float32), cam_t=filled((nc, 3), np.float32), point=filled((n_points, 3), np.float32),
+             included=filled((n_points,), np.uint8), chi2=filled((n_edges,), np.float64), q=filled((nc, 4), np.float64),
+             t=filled((nc, 3), np.float64), X=filled((n_points, 3), np.float64))
+    O = L.BaOutput()
+    C.memset(C.byref(O), int(byte), C.sizeof(O))
+    O.cam_q, O.cam_t, O.point, O.included, O.chi2 = [L.ptr(o[k]) for k in ("cam_q", "cam_t", "point", "included", "chi2")]
+    O.diag.cam_q, O.diag.cam_t, O.diag.point = L.ptr(o["q"]), L.ptr(o["t"]), L.ptr(o["X"])
+
+    def call(_keep=(a, pool)):
+        if handle is None:
+            L.check(lib, lib.rgbl_bundle_adjustment_host(C.byref(I), C.byref(O)))
+        else:
+            L.check(lib, lib.rgbl_bundle_adjustment(handle, C.byref(I), C.byref(O)))
+        r = dict(o)
+        for k, _ in L.LbaDiag._fields_[:11]:
+            r[k] = getattr(O.diag, k)
+        return r
+    call.outputs, call.raw = o, O
+    return call
+
+
+def bundle_adjustment_host(case, lib=None, fill=0):
+    """rgbl_bundle_adjustment_host: the host build of csrc/lba_math.h with lm_solve_panel (no device)."""
+    return bundle_adjustment_call(lib or L.load(), None, case, fill)()
 
 
 def two_view_reconstruct_host(problem, lib=None, diag=True, fill=0):

@@ -74,6 +74,41 @@ def make_lba_case(n_free=3, n_fixed=2, n_points=40, obs_per_point=3, seed=1, ste
                 q_true=q_true, t_true=t_true, X_true=X_true, planted_outlier=np.array(planted, bool))
 
 
+def make_ba_case(n_cams=5, n_fixed=1, robust=1, max_iterations=10, **kw):
+    """make_lba_case's scene as Optimizer::BundleAdjustment sees it (src/Optimizer.cc:52-390): ONE camera list in the order
+    of the road, the first n_fixed of them flagged fixed (the map's initial key frame, :125) and given at the plant, the
+    others free.  kw goes to make_lba_case (n_points, obs_per_point, seed, ...).  Keys: the case dict of
+    frontend.bundle_adjustment_call plus the plant."""
+    c = make_lba_case(n_free=n_cams - n_fixed, n_fixed=n_fixed, max_iterations=max_iterations, **kw)
+    nf = n_cams - n_fixed
+    order = np.concatenate([np.arange(nf, n_cams), np.arange(nf)])      # fixed cameras first
+    new_index = np.empty(n_cams, np.int64)
+    new_index[order] = np.arange(n_cams)
+    out = {k: c[k] for k in ("world_pos", "edge_point", "edge_obs", "edge_inv_sigma2", "max_iterations", "stop_after_polls",
+                             "X_true", "planted_outlier")}
+    for k in ("cam_q", "cam_t", "cam_K", "cam_bf", "q_true", "t_true"):
+        out[k] = c[k][order]
+    # a point's edges stay in ascending camera index (the order the reference walks GetObservations is the caller's)
+    cam = new_index[c["edge_cam"]]
+    key = np.lexsort((cam, c["edge_point"]))
+    for k in ("edge_obs", "edge_inv_sigma2", "planted_outlier"):
+        out[k] = c[k][key]
+    out["edge_point"] = c["edge_point"][key]
+    out["edge_cam"] = cam[key].astype(np.int32)
+    fixed = np.zeros(n_cams, np.uint8)
+    fixed[:n_fixed] = 1
+    out.update(n_cams=n_cams, cam_is_fixed=fixed, robust=robust)
+    return out
+
+
+def as_lba_case(ba):
+    """a make_ba_case dict as the rgbl_local_bundle_adjustment call on the same vertices and edges: every camera in the free
+    list, the fixed ones flagged"""
+    out = {k: v for k, v in ba.items() if k not in ("n_cams", "cam_is_fixed", "robust")}
+    out.update(n_free=ba["n_cams"], n_fixed=0, free_is_fixed=ba["cam_is_fixed"], user_lambda_init=0.0)
+    return out
+
+
 def _quat_of(R):
     """x, y, z, w of a rotation matrix (w >= 0)"""
     w = np.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2.0
