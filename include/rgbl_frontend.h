@@ -1672,6 +1672,10 @@ int rgbl_kfdb_profile_read(rgbl_kf_database* db, const char** names, double* tot
  *     RGBL_BF_MFMA=0|i8     Hamming scan on the VALU (popcount) / on v_mfma_i32_32x32x32_i8 (default: block-scaled FP4 instruction)
  *     RGBL_BF_SPLIT=0       one pair per call without train-set slices
  *     RGBL_GBA_PANEL=16|64  rgbl_bundle_adjustment: columns per panel of the reduced system's solve (32; the bits do not depend on it)
+ *   first allocation of the process (whatever handle makes it)
+ *     RGBL_ALLOC_FILL=0..255   TEST switch: every device and page-locked block the library allocates is filled with that byte before
+ *                           its first use, the grow-only staging blocks (the matcher's arena and mirror, the pool's, vocabulary's and
+ *                           stereo matcher's stages) before every call that reuses them; unset: one cached branch per allocation
  *   first rgbl_comm_* call
  *     RGBL_RCCL_LIB=path    librccl to dlopen when none is mapped into the process yet
  * ---------------------------------------------------------------------------------------------- */

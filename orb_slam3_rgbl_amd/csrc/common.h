@@ -10,6 +10,8 @@
 
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include <mutex>
 #include <string>
@@ -40,6 +42,49 @@ const char* last_error();
 
 // grow-only device staging of the host-pointer ingest paths (extractor.hip): reallocates only when `need` exceeds `*have`
 int grow_staging(void** p, size_t* have, size_t need);
+
+// ---- the library's two allocators: every hipMalloc / hipHostMalloc of csrc goes through them
+// RGBL_ALLOC_FILL=<0..255> (a test switch, read ONCE per process at the first allocation, never on a launch path): every
+// new block is filled with that byte before the caller sees it - and before the memsets the caller does itself - so that a
+// kernel that reads an element nobody wrote reads something other than a fresh page's zeros.  Unset (or anything that is
+// not a number in 0..255): one cached branch, nothing else.  The grow-only staging blocks that calls reuse are refilled where
+// they are reused (HostCall::begin, the pool's, the vocabulary's and the stereo matcher's stages).
+inline int alloc_fill() {   // the byte, or -1
+  static const int byte = [] {
+    const char* v = getenv("RGBL_ALLOC_FILL");
+    if (!v || !*v) return -1;
+    char* end = nullptr;
+    const long x = strtol(v, &end, 0);
+    return (*end == 0 && x >= 0 && x <= 255) ? (int)x : -1;
+  }();
+  return byte;
+}
+template <class T>
+inline hipError_t device_alloc(T** p, size_t bytes) {
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), bytes);
+  const int fill = alloc_fill();
+  if (e == hipSuccess && fill >= 0 && bytes) {
+    e = hipMemset(*p, fill, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  return e;
+}
+template <class T>
+inline hipError_t pinned_alloc(T** p, size_t bytes) {
+  const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(p), bytes, hipHostMallocDefault);
+  const int fill = alloc_fill();
+  if (e == hipSuccess && fill >= 0 && bytes) memset(*p, fill, bytes);
+  return e;
+}
+
+// A grow-only staging block (device side d, page-locked mirror h; either may be null) that a call is about to reuse: with the
+// switch set, the bytes the call will use are refilled - the device side on the call's stream - before the call writes them.
+inline hipError_t refill_staging(void* d, void* h, size_t bytes, hipStream_t s) {
+  const int fill = alloc_fill();
+  if (fill < 0 || !bytes) return hipSuccess;
+  if (h) memset(h, fill, bytes);
+  return d ? hipMemsetAsync(d, fill, bytes, s) : hipSuccess;
+}
 
 constexpr int kWave = 64;  // gfx950 wavefront width; hard-coded on purpose
 

@@ -477,7 +477,7 @@ struct rgbl_depth {
 namespace {
 template <class T>
 int dalloc(rgbl_depth* e, T** p, size_t count) {
-  RGBL_HIP(hipMalloc(p, std::max<size_t>(count, 1) * sizeof(T)));
+  RGBL_HIP(rgbl::device_alloc(p, std::max<size_t>(count, 1) * sizeof(T)));
   e->allocs.push_back((void*)*p);
   return RGBL_OK;
 }
@@ -719,7 +719,7 @@ int rgbl_depth_create(const rgbl_depth_cfg* cfg, int device, rgbl_depth** out) {
     e->d_kpun = e->d_kp + (size_t)2 * cfg->max_keypoints;
     e->d_depth = e->d_kpun + cfg->max_keypoints;
     e->d_uright = e->d_depth + cfg->max_keypoints;
-    if (hipHostMalloc(reinterpret_cast<void**>(&e->h_kio), sizeof(float) * 5 * (size_t)std::max(cfg->max_keypoints, 1), hipHostMallocDefault) != hipSuccess) {
+    if (rgbl::pinned_alloc(&e->h_kio, sizeof(float) * 5 * (size_t)std::max(cfg->max_keypoints, 1)) != hipSuccess) {
       e->h_kio = nullptr;
       (void)hipGetLastError();
     }
@@ -768,7 +768,7 @@ static int depth_prefetch_host(rgbl_depth* e, const float* cloud, int n, int ld,
     // The scan goes through a page-locked block of the handle: the host copies it there (while the GPU extracts), the DMA
     // from there is asynchronous under every HIP runtime - an asynchronous copy straight from pageable memory is staged by
     // the runtime, and the one PyTorch ships (ROCm 7.0) holds it back behind the work of other streams: no overlap at all.
-    if (!e->h_cloud && hipHostMalloc(reinterpret_cast<void**>(&e->h_cloud), sizeof(float) * 4 * (size_t)e->cfg.max_points, hipHostMallocDefault) != hipSuccess) {
+    if (!e->h_cloud && rgbl::pinned_alloc(&e->h_cloud, sizeof(float) * 4 * (size_t)e->cfg.max_points) != hipSuccess) {
       e->h_cloud = nullptr;
       (void)hipGetLastError();
     }

@@ -47,7 +47,7 @@ int grow_staging(void** p, size_t* have, size_t need) {
   if (need <= *have) return RGBL_OK;
   if (*p) RGBL_HIP(hipFree(*p));
   *p = nullptr; *have = 0;
-  RGBL_HIP(hipMalloc(p, need));
+  RGBL_HIP(rgbl::device_alloc(p, need));
   *have = need;
   return RGBL_OK;
 }
@@ -55,6 +55,9 @@ int grow_staging(void** p, size_t* have, size_t need) {
 }  // namespace rgbl
 
 using namespace rgbl;
+
+// test hook (tests/test_alloc_fill.py): the byte of RGBL_ALLOC_FILL as this process cached it, -1 without the switch
+extern "C" int rgbl_test_alloc_fill() { return alloc_fill(); }
 
 // ---- launch plan: WHAT runs WHERE and AFTER WHAT, as data (build_plan writes it down, enqueue_extract executes it) ----
 enum StreamId : uint8_t { kMain = 0, kAux, kLvl, kNumStreams };   // the handle's stream (or the caller's), auxiliary, level
@@ -180,7 +183,7 @@ namespace {
 
 template <class T>
 int dev_alloc(rgbl_extractor* e, T** p, size_t count) {
-  RGBL_HIP(hipMalloc(p, std::max<size_t>(count, 1) * sizeof(T)));
+  RGBL_HIP(rgbl::device_alloc(p, std::max<size_t>(count, 1) * sizeof(T)));
   e->allocs.push_back((void*)*p);
   return RGBL_OK;
 }
@@ -551,7 +554,7 @@ int alloc_scratch(rgbl_extractor* e) {
   RGBL_TRY(dev_alloc(e, &e->d_tmp_desc, B * (size_t)e->out_cap * 32));
   // results of up to 4 frames per call come back through one page-locked block (run_staged)
   e->h_pinned_bytes = stage_layout(e, (int)std::min<size_t>(B, 4)).bytes;
-  if (hipHostMalloc(reinterpret_cast<void**>(&e->h_pinned), e->h_pinned_bytes, hipHostMallocDefault) != hipSuccess) { e->h_pinned = nullptr; e->h_pinned_bytes = 0; (void)hipGetLastError(); }
+  if (rgbl::pinned_alloc(&e->h_pinned, e->h_pinned_bytes) != hipSuccess) { e->h_pinned = nullptr; e->h_pinned_bytes = 0; (void)hipGetLastError(); }
   return RGBL_OK;
 }
 
@@ -1317,7 +1320,7 @@ int rgbl_extract_color(rgbl_extractor* e, const uint8_t* img, int channels, int 
   if (need > e->color_bytes) {  // first colour frame (or a wider stride): grown once, kept
     if (e->d_color) RGBL_HIP(hipFree(e->d_color));
     e->d_color = nullptr; e->color_bytes = 0;
-    RGBL_HIP(hipMalloc(&e->d_color, need));
+    RGBL_HIP(rgbl::device_alloc(&e->d_color, need));
     e->color_bytes = need;
   }
   RGBL_HIP(hipMemcpyAsync(e->d_color, img, (size_t)(h - 1) * stride + (size_t)w * channels, hipMemcpyHostToDevice, s));
@@ -1594,9 +1597,10 @@ static int stereo_enqueue(rgbl_extractor* L, rgbl_extractor* R, int batch, const
     RGBL_HIP(hipStreamSynchronize(L->stream));
     if (L->d_stereo_sad) RGBL_HIP(hipFree(L->d_stereo_sad));
     L->d_stereo_sad = nullptr;
-    RGBL_HIP(hipMalloc(&L->d_stereo_sad, need * sizeof(int32_t)));
+    RGBL_HIP(rgbl::device_alloc(&L->d_stereo_sad, need * sizeof(int32_t)));
     L->stereo_sad_count = need;
   }
+  RGBL_HIP(refill_staging(L->d_stereo_sad, nullptr, need * sizeof(int32_t), L->stream));
   RGBL_TRY(rgbl_stream_wait((void*)L->stream, (void*)R->stream));  // the right pyramid and keypoints must be complete
   ScaleTables st;
   for (int i = 0; i < kMaxLevels; ++i) { st.scale[i] = i < L->L ? L->scale[i] : 1.f; st.inv_scale[i] = i < L->L ? L->inv_scale[i] : 1.f; }
@@ -1657,10 +1661,11 @@ int rgbl_stereo_matches(rgbl_extractor* left, rgbl_extractor* right, const rgbl_
     if (left->d_stereo_stage) RGBL_HIP(hipFree(left->d_stereo_stage));
     if (left->h_stereo_stage) RGBL_HIP(hipHostFree(left->h_stereo_stage));
     left->d_stereo_stage = nullptr; left->h_stereo_stage = nullptr; left->stereo_stage_bytes = 0;
-    RGBL_HIP(hipMalloc(&left->d_stereo_stage, bytes));
-    RGBL_HIP(hipHostMalloc(reinterpret_cast<void**>(&left->h_stereo_stage), bytes, hipHostMallocDefault));
+    RGBL_HIP(rgbl::device_alloc(&left->d_stereo_stage, bytes));
+    RGBL_HIP(rgbl::pinned_alloc(&left->h_stereo_stage, bytes));
     left->stereo_stage_bytes = bytes;
   }
+  RGBL_HIP(refill_staging(left->d_stereo_stage, left->h_stereo_stage, bytes, left->stream));
   uint8_t* base = (uint8_t*)left->d_stereo_stage;
   rgbl_keypoint* d_kpl = (rgbl_keypoint*)base;
   rgbl_keypoint* d_kpr = (rgbl_keypoint*)(base + (size_t)cap * sizeof(rgbl_keypoint));
@@ -1741,9 +1746,9 @@ int rgbl_selftest_wrappers(int device, int n, unsigned seed) {
   std::vector<uint8_t> dma((size_t)16 * n, 0);
   int rc = RGBL_OK;
   auto run = [&]() -> int {
-    RGBL_HIP(hipMalloc(&d_a, sizeof(uint32_t) * n)); RGBL_HIP(hipMalloc(&d_fl, sizeof(uint32_t) * n));
-    RGBL_HIP(hipMalloc(&d_mul, sizeof(uint32_t) * n)); RGBL_HIP(hipMalloc(&d_add, sizeof(int) * n));
-    RGBL_HIP(hipMalloc(&d_src, src.size())); RGBL_HIP(hipMalloc(&d_dma, dma.size()));
+    RGBL_HIP(rgbl::device_alloc(&d_a, sizeof(uint32_t) * n)); RGBL_HIP(rgbl::device_alloc(&d_fl, sizeof(uint32_t) * n));
+    RGBL_HIP(rgbl::device_alloc(&d_mul, sizeof(uint32_t) * n)); RGBL_HIP(rgbl::device_alloc(&d_add, sizeof(int) * n));
+    RGBL_HIP(rgbl::device_alloc(&d_src, src.size())); RGBL_HIP(rgbl::device_alloc(&d_dma, dma.size()));
     RGBL_HIP(hipMemcpy(d_a, a.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     RGBL_HIP(hipMemcpy(d_fl, fl.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     RGBL_HIP(hipMemcpy(d_src, src.data(), src.size(), hipMemcpyHostToDevice));

@@ -2505,14 +2505,4 @@ __global__ __launch_bounds__(256) void k_undistort(UndistortParams U, const floa
   q[1] = oy;
 }
 
-__global__ void k_unpack_keys(const uint32_t* __restrict__ keys, int n, rgbl_keypoint* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t k = keys[i];
-  rgbl_keypoint kp;
-  kp.x = (float)key_x(k); kp.y = (float)key_y(k); kp.size = 7.f; kp.angle = -1.f;
-  kp.response = (float)key_s(k); kp.octave = 0; kp.class_id = -1;
-  out[i] = kp;
-}
-
 }  // namespace rgbl

@@ -132,13 +132,13 @@ int rgbl_feeder_create(const rgbl_feeder_cfg* cfg, rgbl_extractor* ex, rgbl_dept
   int rc = RGBL_OK;
   auto fail = [&](const char* what) { set_error("feeder: %s failed", what); rc = RGBL_ERR_HIP; };
   if (hipStreamCreate(&f->copy) != hipSuccess) fail("hipStreamCreate");
-  if (rc == RGBL_OK && cfg->channels != 1 && hipMalloc(&f->d_gray, B * ew * eh + 64) != hipSuccess) fail("hipMalloc");
+  if (rc == RGBL_OK && cfg->channels != 1 && rgbl::device_alloc(&f->d_gray, B * ew * eh + 64) != hipSuccess) fail("hipMalloc");
   for (auto& s : f->slot) {
     if (rc != RGBL_OK) break;
     const size_t bytes = f->in_bytes + f->out.bytes;
-    if (hipHostMalloc(reinterpret_cast<void**>(&s.h), bytes, hipHostMallocDefault) != hipSuccess) { s.h = nullptr; fail("hipHostMalloc"); break; }
+    if (rgbl::pinned_alloc(&s.h, bytes) != hipSuccess) { s.h = nullptr; fail("hipHostMalloc"); break; }
     f->pinned += (long long)bytes;
-    if (hipMalloc(&s.d, bytes) != hipSuccess) { s.d = nullptr; fail("hipMalloc"); break; }
+    if (rgbl::device_alloc(&s.d, bytes) != hipSuccess) { s.d = nullptr; fail("hipMalloc"); break; }
     for (hipEvent_t* ev : {&s.in, &s.img_free, &s.scan_free, &s.extracted, &s.done})
       if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) { *ev = nullptr; fail("hipEventCreate"); break; }
   }

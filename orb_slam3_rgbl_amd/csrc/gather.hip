@@ -157,14 +157,14 @@ struct rgbl_gather {
 namespace {
 template <class T>
 int galloc(rgbl_gather* g, T** p, size_t count) {
-  RGBL_HIP(hipMalloc(p, std::max<size_t>(count, 1) * sizeof(T)));
+  RGBL_HIP(rgbl::device_alloc(p, std::max<size_t>(count, 1) * sizeof(T)));
   g->dev_allocs.push_back((void*)*p);
   RGBL_HIP(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(T)));
   return RGBL_OK;
 }
 template <class T>
 int halloc(rgbl_gather* g, T** p, size_t count) {
-  RGBL_HIP(hipHostMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+  RGBL_HIP(rgbl::pinned_alloc(p, std::max<size_t>(count, 1) * sizeof(T)));
   g->host_allocs.push_back((void*)*p);
   memset(*p, 0, std::max<size_t>(count, 1) * sizeof(T));
   return RGBL_OK;

@@ -186,8 +186,8 @@ static int kfdb_grow_block(uint8_t** d, uint8_t** h, size_t* cap, size_t need) {
   if (*d) (void)hipFree(*d);
   if (*h) (void)hipHostFree(*h);
   *d = nullptr; *h = nullptr; *cap = 0;
-  RGBL_HIP(hipMalloc(d, n));
-  RGBL_HIP(hipHostMalloc(h, n, hipHostMallocDefault));
+  RGBL_HIP(rgbl::device_alloc(d, n));
+  RGBL_HIP(rgbl::pinned_alloc(h, n));
   *cap = n;
   return RGBL_OK;
 }
@@ -200,8 +200,8 @@ static int kfdb_reserve(rgbl_kf_database* db, long long need) {
   if (n > 0x7fffffffll) { set_error("key-frame database: more than 2^31 words"); return RGBL_ERR_OVERFLOW; }
   uint32_t* nid = nullptr;
   double* nval = nullptr;
-  RGBL_HIP(hipMalloc(&nid, sizeof(uint32_t) * (size_t)n));
-  if (hipMalloc(&nval, sizeof(double) * (size_t)n) != hipSuccess) { (void)hipFree(nid); set_error("hipMalloc of the arena failed"); return RGBL_ERR_HIP; }
+  RGBL_HIP(rgbl::device_alloc(&nid, sizeof(uint32_t) * (size_t)n));
+  if (rgbl::device_alloc(&nval, sizeof(double) * (size_t)n) != hipSuccess) { (void)hipFree(nid); set_error("hipMalloc of the arena failed"); return RGBL_ERR_HIP; }
   if (db->used > 0) {
     (void)hipMemcpyAsync(nid, db->d_id, sizeof(uint32_t) * (size_t)db->used, hipMemcpyDeviceToDevice, db->stream);
     (void)hipMemcpyAsync(nval, db->d_val, sizeof(double) * (size_t)db->used, hipMemcpyDeviceToDevice, db->stream);
@@ -231,8 +231,8 @@ static int kfdb_compact(rgbl_kf_database* db) {
     uint32_t* nid = nullptr;
     double* nval = nullptr;
     KfdbMove* d_moves = nullptr;
-    RGBL_HIP(hipMalloc(&nid, sizeof(uint32_t) * (size_t)db->cap));
-    if (hipMalloc(&nval, sizeof(double) * (size_t)db->cap) != hipSuccess || hipMalloc(&d_moves, sizeof(KfdbMove) * moves.size()) != hipSuccess) {
+    RGBL_HIP(rgbl::device_alloc(&nid, sizeof(uint32_t) * (size_t)db->cap));
+    if (rgbl::device_alloc(&nval, sizeof(double) * (size_t)db->cap) != hipSuccess || rgbl::device_alloc(&d_moves, sizeof(KfdbMove) * moves.size()) != hipSuccess) {
       (void)hipFree(nid);
       if (nval) (void)hipFree(nval);
       set_error("hipMalloc for the compaction failed");
@@ -458,7 +458,7 @@ int rgbl_kfdb_query_batch(rgbl_kf_database* db, int n_queries, const int32_t* wo
         if (db->d_ent) (void)hipFree(db->d_ent);
         db->d_ent = nullptr; db->ent_cap = 0;
         const size_t n = std::max<size_t>(1024, (size_t)E * 2);
-        RGBL_HIP(hipMalloc(&db->d_ent, sizeof(KfdbEntry) * n));
+        RGBL_HIP(rgbl::device_alloc(&db->d_ent, sizeof(KfdbEntry) * n));
         db->ent_cap = n;
       }
       RGBL_HIP(hipMemcpyAsync(db->d_ent, db->ent.data(), sizeof(KfdbEntry) * (size_t)E, hipMemcpyHostToDevice, db->stream));

@@ -2395,7 +2395,7 @@ int rgbl_device_frame_create(int device, int capacity, rgbl_device_frame** out) 
   f->device = device;
   f->cap = (capacity + 63) / 64 * 64;   // every array starts 256-byte aligned
   const size_t cap = (size_t)f->cap;
-  if (hipMalloc(&f->block, cap * 48) != hipSuccess || hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess ||
+  if (rgbl::device_alloc(&f->block, cap * 48) != hipSuccess || hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&f->ready, hipEventDisableTiming) != hipSuccess) {
     (void)hipGetLastError();
     rgbl_device_frame_destroy(f);
@@ -2426,7 +2426,7 @@ void rgbl_device_frame_destroy(rgbl_device_frame* f) {
 static int frame_pin(rgbl_device_frame* f, size_t bytes) {
   if (bytes <= f->pin_size) return RGBL_OK;
   if (f->h_pin) { (void)hipHostFree(f->h_pin); f->h_pin = nullptr; f->pin_size = 0; }
-  RGBL_HIP(hipHostMalloc(reinterpret_cast<void**>(&f->h_pin), bytes, hipHostMallocDefault));
+  RGBL_HIP(rgbl::pinned_alloc(&f->h_pin, bytes));
   f->pin_size = bytes;
   return RGBL_OK;
 }
@@ -2462,7 +2462,7 @@ int rgbl_device_frame_set_feature_vector(rgbl_device_frame* f, int n_nodes, cons
   if (words > f->fv_cap) {
     if (f->d_fv) { RGBL_HIP(hipStreamSynchronize(f->stream)); (void)hipFree(f->d_fv); f->d_fv = nullptr; f->fv_cap = 0; }
     const int cap = std::max(words, 2 * f->cap + 2);
-    RGBL_HIP(hipMalloc(&f->d_fv, sizeof(int32_t) * (size_t)cap));
+    RGBL_HIP(rgbl::device_alloc(&f->d_fv, sizeof(int32_t) * (size_t)cap));
     f->fv_cap = cap;
   }
   RGBL_TRY(frame_pin(f, std::max((size_t)f->cap * 48, sizeof(int32_t) * (size_t)words)));
@@ -2484,7 +2484,7 @@ int rgbl_device_frame_set_grid(rgbl_device_frame* f, const float grid[6]) {
     const size_t items = (sizeof(uint32_t) * (kGridCells + 1) + 255) / 256 * 256;
     const size_t scratch = items + (sizeof(uint16_t) * (size_t)f->cap + 255) / 256 * 256;
     uint8_t* block = nullptr;
-    RGBL_HIP(hipMalloc(&block, scratch + sizeof(int32_t) * (size_t)f->cap));
+    RGBL_HIP(rgbl::device_alloc(&block, scratch + sizeof(int32_t) * (size_t)f->cap));
     f->d_cell_start = reinterpret_cast<uint32_t*>(block);
     f->d_cell_items = reinterpret_cast<uint16_t*>(block + items);
     f->d_grid_scratch = reinterpret_cast<int32_t*>(block + scratch);
@@ -3345,7 +3345,7 @@ PoolArrays pool_arrays(int cap) {
 int pool_resize(rgbl_map_points* p, int cap, int keep) {
   const PoolArrays a = pool_arrays(cap);
   uint8_t* nb = nullptr;
-  RGBL_HIP(hipMalloc(reinterpret_cast<void**>(&nb), a.total));
+  RGBL_HIP(rgbl::device_alloc(reinterpret_cast<void**>(&nb), a.total));
   hipError_t e = hipMemset(nb, 0, a.total);
   if (e == hipSuccess && keep > 0) {
     const struct { size_t off; const void* src; size_t bytes; } part[5] = {
@@ -3426,10 +3426,11 @@ int rgbl_map_points_update(rgbl_map_points* p, int n, const int32_t* slot, const
     if (p->h_stage) { (void)hipHostFree(p->h_stage); p->h_stage = nullptr; }
     p->stage_size = 0;
     const size_t sz = std::max(off, (size_t)1 << 16);
-    RGBL_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_stage), sz));
-    RGBL_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_stage), sz, hipHostMallocDefault));
+    RGBL_HIP(rgbl::device_alloc(reinterpret_cast<void**>(&p->d_stage), sz));
+    RGBL_HIP(rgbl::pinned_alloc(&p->h_stage, sz));
     p->stage_size = sz;
   }
+  RGBL_HIP(refill_staging(p->d_stage, p->h_stage, off, p->stream));
   int32_t* h_slot = reinterpret_cast<int32_t*>(p->h_stage + o_slot);
   memcpy(h_slot, slot, (size_t)n * 4);
   {  // a slot listed more than once keeps its last entry: the earlier ones are struck out, so no two work-items write one slot
@@ -3811,7 +3812,7 @@ static int voc_upload(rgbl_vocabulary* v, int n_nodes, int L, const int32_t* chi
                       const double* weight, const int32_t* word_id) {
   auto up = [&](const void* src, size_t bytes, const void** dst) -> int {
     void* p = nullptr;
-    RGBL_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16)));
+    RGBL_HIP(rgbl::device_alloc(&p, std::max<size_t>(bytes, 16)));
     v->allocs.push_back(p);
     RGBL_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
     *dst = p;
@@ -3955,10 +3956,11 @@ static int bow_transform_core(rgbl_vocabulary* v, const rgbl_device_frame* frame
     if (v->d_stage) { (void)hipFree(v->d_stage); (void)hipHostFree(v->h_stage); }
     v->d_stage = nullptr; v->h_stage = nullptr; v->stage_cap = 0;
     const int cap = std::max(n, 4096);
-    RGBL_HIP(hipMalloc(&v->d_stage, (size_t)cap * 48));
-    RGBL_HIP(hipHostMalloc(reinterpret_cast<void**>(&v->h_stage), (size_t)cap * 48, hipHostMallocDefault));
+    RGBL_HIP(rgbl::device_alloc(&v->d_stage, (size_t)cap * 48));
+    RGBL_HIP(rgbl::pinned_alloc(&v->h_stage, (size_t)cap * 48));
     v->stage_cap = cap;
   }
+  RGBL_HIP(refill_staging(v->d_stage, v->h_stage, (size_t)v->stage_cap * 48, v->stream));
   const size_t cap = (size_t)v->stage_cap;   // results back to back: weight [n] | word [n] | node [n]
   const uint8_t* d_desc = v->d_stage;
   double* d_weight = reinterpret_cast<double*>(v->d_stage + cap * 32);

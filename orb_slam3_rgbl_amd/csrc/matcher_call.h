@@ -51,7 +51,7 @@ inline int ensure_arena(rgbl_matcher* m, size_t bytes) {
   if (bytes <= m->buf_size) return RGBL_OK;
   if (m->d_buf) { RGBL_HIP(hipStreamSynchronize(m->stream)); RGBL_HIP(hipFree(m->d_buf)); m->d_buf = nullptr; m->buf_size = 0; }
   const size_t sz = std::max(bytes, (size_t)1 << 20);
-  RGBL_HIP(hipMalloc(&m->d_buf, sz));
+  RGBL_HIP(rgbl::device_alloc(&m->d_buf, sz));
   m->buf_size = sz;
   return RGBL_OK;
 }
@@ -59,7 +59,7 @@ inline int ensure_pin(rgbl_matcher* m, size_t bytes) {
   if (bytes <= m->pin_size) return RGBL_OK;
   if (m->h_pin) { (void)hipHostFree(m->h_pin); m->h_pin = nullptr; m->pin_size = 0; }
   const size_t sz = std::max(bytes, (size_t)1 << 20);
-  RGBL_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->h_pin), sz, hipHostMallocDefault));
+  RGBL_HIP(rgbl::pinned_alloc(&m->h_pin, sz));
   m->pin_size = sz;
   return RGBL_OK;
 }
@@ -80,6 +80,7 @@ struct HostCall {
     const size_t measured = off;
     RGBL_TRY(ensure_arena(m, measured));
     RGBL_TRY(ensure_pin(m, measured));
+    RGBL_HIP(refill_staging(m->d_buf, m->h_pin, measured, s));   // RGBL_ALLOC_FILL: what the last call left behind is gone
     carving = true;
     off = up_end = 0;
     RGBL_TRY(layout());
@@ -236,7 +237,7 @@ template <class T, class Launch> int elementwise_device_hook(std::initializer_li
   std::vector<T*> d(in.size() + 1, nullptr);   // the inputs, then the output
   hipError_t e = hipSuccess;
   for (T*& p : d)
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p), bytes);
+    if (e == hipSuccess) e = rgbl::device_alloc(reinterpret_cast<void**>(&p), bytes);
   size_t k = 0;
   for (const T* h : in) {
     if (e == hipSuccess) e = hipMemcpy(d[k], h, bytes, hipMemcpyHostToDevice);

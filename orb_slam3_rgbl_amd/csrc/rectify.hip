@@ -346,9 +346,9 @@ int rgbl_rectifier_create(int device, int src_w, int src_h, int dst_w, int dst_h
   const size_t tile_bytes = sizeof(RemapTile) * n_tiles, m4 = sizeof(uint32_t) * map4.size(), m8 = sizeof(RemapFixed) * map8.size();
   r->map_bytes = (long long)(tile_bytes + (n_staged ? m4 : 0) + (n_direct ? m8 : 0));
   const size_t src_bytes = (size_t)src_w * 4 * src_h + 16, dst_bytes = (size_t)dst_w * 4 * dst_h + 16;
-  const bool ok = hipMalloc(&r->d_tiles, tile_bytes) == hipSuccess && hipMalloc(&r->d_map4, m4) == hipSuccess &&
-                  hipMalloc(&r->d_map8, m8) == hipSuccess && hipMalloc(&r->d_src, src_bytes) == hipSuccess &&
-                  hipMalloc(&r->d_dst, dst_bytes) == hipSuccess && hipStreamCreate(&r->stream) == hipSuccess &&
+  const bool ok = rgbl::device_alloc(&r->d_tiles, tile_bytes) == hipSuccess && rgbl::device_alloc(&r->d_map4, m4) == hipSuccess &&
+                  rgbl::device_alloc(&r->d_map8, m8) == hipSuccess && rgbl::device_alloc(&r->d_src, src_bytes) == hipSuccess &&
+                  rgbl::device_alloc(&r->d_dst, dst_bytes) == hipSuccess && hipStreamCreate(&r->stream) == hipSuccess &&
                   hipMemcpy(r->d_tiles, order.data(), tile_bytes, hipMemcpyHostToDevice) == hipSuccess &&
                   hipMemcpy(r->d_map4, map4.data(), m4, hipMemcpyHostToDevice) == hipSuccess &&
                   hipMemcpy(r->d_map8, map8.data(), m8, hipMemcpyHostToDevice) == hipSuccess;

@@ -293,7 +293,7 @@ int rgbl_resizer_create(int device, int src_w, int src_h, int dst_w, int dst_h, 
   memcpy(host.data() + 3 * x_bytes, ytab.data(), y_bytes);
   memcpy(host.data() + 3 * x_bytes + y_bytes, rows.data(), t_bytes);
   r->table_bytes = (long long)host.size();
-  const bool ok = hipMalloc(&r->d_tables, host.size()) == hipSuccess && hipStreamCreate(&r->stream) == hipSuccess &&
+  const bool ok = rgbl::device_alloc(&r->d_tables, host.size()) == hipSuccess && hipStreamCreate(&r->stream) == hipSuccess &&
                   hipMemcpy(r->d_tables, host.data(), host.size(), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
     set_error("resizer: device allocation / upload failed: %s", hipGetErrorString(hipGetLastError()));

@@ -174,29 +174,42 @@ def test_gpu_kitti(gpu_lib):
 KERNEL_SOURCES = tuple(sorted(os.path.basename(f) for f in glob.glob(os.path.join(ROOT, "orb_slam3_rgbl_amd", "csrc", "*.hip"))))   # csrc/Makefile's SRCS
 
 
-def build_bounds_exe():
-    """The program, every kernel source of the library (the extractor's entry points reach into the others) and the emulator,
-    each compiled with -fsanitize=address, linked into one executable with the sanitizer's runtime linked statically."""
-    exe = os.path.join(BUILD, "wide_loads_bounds_asan")
+ASAN_FLAGS = ["-O1", "-g", "-std=c++17", "-pthread", "-ffp-contract=off", "-DRGBL_EMU", "-fsanitize=address", "-fno-sanitize-recover=all",
+              "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "tests", "emu"), "-I" + os.path.join(ROOT, "include"), "-Wno-unknown-pragmas"]
+
+
+def build_asan_objects():
+    """Every kernel source of the library and the emulator, each compiled with -fsanitize=address: the objects the stand-alone
+    programs of the suite (this file's, tests/test_alloc_fill.py's) link.  Built once, rebuilt when a source or header is newer."""
     csrc = os.path.join(ROOT, "orb_slam3_rgbl_amd", "csrc")
     emu = os.path.join(ROOT, "tests", "emu")
-    srcs = [os.path.join(ROOT, "tests", "wide_loads_bounds.cpp")] + [os.path.join(csrc, f) for f in KERNEL_SOURCES] + \
-           [os.path.join(emu, f) for f in ("hip_emu.cpp", "nccl_emu.cpp")]
+    srcs = [os.path.join(csrc, f) for f in KERNEL_SOURCES] + [os.path.join(emu, f) for f in ("hip_emu.cpp", "nccl_emu.cpp")]
     deps = srcs + glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(emu, "*.h")) + [os.path.join(ROOT, "include", "rgbl_frontend.h")]
     os.makedirs(BUILD, exist_ok=True)
+    objs = [os.path.join(BUILD, "emu_asan.%s.o" % os.path.basename(s)) for s in srcs]
+    with open(os.path.join(BUILD, "emu_asan.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        newest = max(os.path.getmtime(d) for d in deps)
+        if not all(os.path.exists(o) and os.path.getmtime(o) >= newest for o in objs):
+            jobs = [subprocess.Popen(["g++"] + ASAN_FLAGS + ["-c", "-x", "c++", s, "-o", o + ".tmp"], cwd=csrc) for s, o in zip(srcs, objs)]
+            assert all(j.wait() == 0 for j in jobs)
+            for o in objs:
+                os.replace(o + ".tmp", o)
+    return objs
+
+
+def build_bounds_exe(program="wide_loads_bounds"):
+    """tests/<program>.cpp, the kernel sources (the extractor's entry points reach into the others) and the emulator, each
+    compiled with -fsanitize=address, linked into one executable with the sanitizer's runtime linked statically."""
+    exe = os.path.join(BUILD, program + "_asan")
+    src = os.path.join(ROOT, "tests", program + ".cpp")
+    objs = build_asan_objects()
     with open(exe + ".lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
-        if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):
+        if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in objs + [src]):
             return exe
-        flags = ["-O1", "-g", "-std=c++17", "-pthread", "-ffp-contract=off", "-DRGBL_EMU", "-fsanitize=address", "-fno-sanitize-recover=all",
-                 "-fno-omit-frame-pointer", "-I" + emu, "-I" + os.path.join(ROOT, "include"), "-Wno-unknown-pragmas"]
-        objs = ["%s.%d.o" % (exe, i) for i in range(len(srcs))]
-        jobs = [subprocess.Popen(["g++"] + flags + ["-c", "-x", "c++", s, "-o", o], cwd=csrc) for s, o in zip(srcs, objs)]
-        assert all(j.wait() == 0 for j in jobs)
         # the sanitizer's runtime inside the executable: it starts whatever the environment preloads, and the environment stays as it is
-        subprocess.check_call(["g++"] + flags + ["-static-libasan"] + objs + ["-o", exe + ".tmp", "-ldl"])
-        for o in objs:
-            os.remove(o)
+        subprocess.check_call(["g++"] + ASAN_FLAGS + ["-static-libasan", "-x", "c++", src, "-x", "none"] + objs + ["-o", exe + ".tmp", "-ldl"])
         os.replace(exe + ".tmp", exe)
     return exe
 
